@@ -13,6 +13,11 @@ independent, so there is no data-path collective -- only the all-gather of the
 stream.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4|C5]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints its line; --full
+adds everything else (see below).  --dump-outputs DIR writes what the timed
+path computed in its last step as DIR/<name>.npy (C2: bench.dump_c2).
 
 --gpus N > 1 without a torch.distributed.run environment: this process starts
 the N ranks itself (one child process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
@@ -26,8 +31,9 @@ Other configs of BASELINE.json, same contract, own rooflines:
   --config C3   complete LM fits of the C2 stamps (lock-step batched driver)
   --config C4   admom + em_run over 32x32 stamps (fp64-VALU bound)
   --config C5   10 epochs x 64x64, 16-gaussian 'bdf' loglike (HBM bound)
-A default (C2, N = 1) run appends a short C4 and C5 measurement under
-"other_configs" so that the driver's record carries them too.
+A --full C2 run appends a short C3, C4 and C5 measurement (and, at N = 1, the
+C3_host / prepsfmom / C3_prior legs and the CPU baselines) under
+"other_configs" so that one record carries them too.
 """
 import argparse
 import json
@@ -404,19 +410,23 @@ def run_c2(args, rank, world, device, backend):
     bad = int((status != 0).sum().item())
     render_ms = _mean_ms(ev_r0, ev_r1)
     loglike_ms = _mean_ms(ev_l0, ev_l1)
-    # outside the timed region: the write-only form of the render (what
-    # GMix.make_image / StampBatch.render(image=None) run: the model is stored
-    # without the image being read -- NGMIX_BATCH_RENDER_OVERWRITE), 20 launches
-    fe0, fe1 = _events(20), _events(20)
-    for k in range(25):
-        if k >= 5:
-            fe0[k - 5].record()
-        fresh, _ = sb.render(gm, image=None, fast_exp=True, status=status, exact=args.exact)
-        if k >= 5:
-            fe1[k - 5].record()
-    torch.cuda.synchronize()
-    fresh_ms = _mean_ms(fe0, fe1)
-    del fresh
+    if args.dump_outputs and rank == 0:
+        dump_c2(args.dump_outputs, image, out, status)
+    fresh_ms = None
+    if args.full:
+        # outside the timed region: the write-only form of the render (what
+        # GMix.make_image / StampBatch.render(image=None) run: the model is stored
+        # without the image being read -- NGMIX_BATCH_RENDER_OVERWRITE), 20 launches
+        fe0, fe1 = _events(20), _events(20)
+        for k in range(25):
+            if k >= 5:
+                fe0[k - 5].record()
+            fresh, _ = sb.render(gm, image=None, fast_exp=True, status=status, exact=args.exact)
+            if k >= 5:
+                fe1[k - 5].record()
+        torch.cuda.synchronize()
+        fresh_ms = _mean_ms(fe0, fe1)
+        del fresh
     if rank != 0:
         return None
 
@@ -471,10 +481,6 @@ def run_c2(args, rank, world, device, backend):
                          else "pixpass_wave_kernel<2, false, 16>"),
         },
         "kernels_ms": {"render": render_ms, "loglike": loglike_ms},
-        # the fresh (write-only) render, not part of `value`: 18,432 B written per stamp
-        "fresh_render": {"ms": fresh_ms, "stamp_renders_per_s_per_gpu": n / (fresh_ms * 1e-3),
-                         "hbm_frac": (RENDER_BYTES / 2) * n / (fresh_ms * 1e-3) / 1e9 /
-                         HBM_PEAK_GBS},
         "loglike_stamp_evals_per_s_per_gpu": n / (loglike_ms * 1e-3),
         "render_stamp_evals_per_s_per_gpu": n / (render_ms * 1e-3),
         "loglike_hbm_frac": LOGLIKE_BYTES * n / (loglike_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
@@ -483,9 +489,50 @@ def run_c2(args, rank, world, device, backend):
         "settle_steps": max(args.settle_steps, 0),
         "kernel_mode": "exact" if args.exact else "fused",
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if fresh_ms is not None:
+        # the fresh (write-only) render, not part of `value`: 18,432 B written per stamp
+        line["fresh_render"] = {"ms": fresh_ms,
+                                "stamp_renders_per_s_per_gpu": n / (fresh_ms * 1e-3),
+                                "hbm_frac": (RENDER_BYTES / 2) * n / (fresh_ms * 1e-3) / 1e9 /
+                                HBM_PEAK_GBS}
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(sb, gm)
     return line
+
+
+# outputs of one run, for comparing two builds output for output: at most
+# 64 MB in all; what is larger is written as a fixed, seeded sample of rows
+DUMP_MAX_ROWS = 1000000       # loglike + status rows (40 B each)
+DUMP_IMAGE_STAMPS = 1024      # model-image stamps (18,432 B each)
+
+
+def _dump_rows(n, k, seed):
+    """the rows of an n-row output that are written: all of them, or a sorted
+    sample of k drawn with a fixed seed"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(seed).choice(n, size=k, replace=False))
+
+
+def dump_c2(path, image, out, status):
+    """C2's last timed step as a caller of render + get_loglike receives it:
+      loglike.npy  (rows, 4) float64: loglike, s2n_numer, s2n_denom, npix
+      status.npy   (rows,) float64: the per-stamp status codes
+      image.npy    (stamps, 48, 48) float64: the model image the steps
+                   accumulate into, for a seeded sample of DUMP_IMAGE_STAMPS
+    rows: every stamp, or a seeded sample of DUMP_MAX_ROWS beyond that"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = out.shape[0]
+    rows = torch.from_numpy(_dump_rows(n, DUMP_MAX_ROWS, 11)).to(out.device)
+    stamps = torch.from_numpy(_dump_rows(n, DUMP_IMAGE_STAMPS, 12)).to(out.device)
+    arrays = {
+        "loglike": out[rows],
+        "status": status[rows].to(torch.float64),
+        "image": image.reshape(n, NROW, NCOL)[stamps],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
 
 
 # --------------------------------------------------------------------------
@@ -1661,8 +1708,15 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="C3: one synchronous LMBatchFitter.go() per step instead of the "
                          "software pipeline over the steps (go_stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="C2: besides the headline, time the write-only render, the CPU "
+                         "baseline (N = 1) and the short legs of the other configs "
+                         "under other_configs (off: only what the headline needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="C2: after the timed steps write what the last step computed "
+                         "as DIR/<name>.npy (dump_c2)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="C2 at N = 1 only: skip the short C4 / C5 legs")
+                    help="C2 with --full: skip the short C3 / C4 / C5 legs")
     ap.add_argument("--cpu-baselines", type=float, nargs="?", const=4.0, default=None,
                     metavar="SECONDS",
                     help="only time the CPU port on configs C1 / C2 / C4 (single core "
@@ -1676,12 +1730,18 @@ def main():
         return 0
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and args.config != "C2":
+        raise SystemExit("bench.py: --dump-outputs is implemented for --config C2")
     if args.settle_steps is None:
         # (~0.45 s of uninterrupted load before the clock starts: what the
         # clock governor needs to reach its steady state)
         args.settle_steps = {"C2": 100, "C3": 70, "C4": 30, "C5": 160}[args.config]
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        return launch_ranks(args, sys.argv[1:])
+        argv = sys.argv[1:]
+        if args.dump_outputs:
+            # (the ranks start in the repository root; the last occurrence wins)
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        return launch_ranks(args, argv)
 
     import torch.distributed as dist
     rank, world, device, backend = init_rank(args)
@@ -1694,8 +1754,8 @@ def main():
         line["backend"] = backend or "none (single process)"
         line["per_rank_ms_per_step"] = list(PER_RANK_MS)
     other = {}
-    if args.config == "C2" and not args.no_other_configs:
-        # a default run carries a short leg of every other config, so that ONE
+    if args.config == "C2" and args.full and not args.no_other_configs:
+        # a --full run carries a short leg of every other config, so that ONE
         # driver record holds C2-C5 -- at N > 1 too: every rank runs the legs
         # (each shards its config as its own --config run does and gathers its
         # records), rank 0 keeps the lines with every rank's own ms per step

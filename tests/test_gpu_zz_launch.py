@@ -31,14 +31,14 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     # bench.py starts its two ranks itself (no torch.distributed.run)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--settle-steps", "2", "--nstamps", "3000"]
+           "--warmup", "1", "--settle-steps", "2", "--nstamps", "3000", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak"
-    # a default (C2) run carries a leg of every other config at N > 1 too, each
+    # a --full (C2) run carries a leg of every other config at N > 1 too, each
     # with every rank's own time per step; no CPU legs beside them
     oc = d["other_configs"]
     for name in ("C3", "C4", "C5"):
@@ -107,7 +107,7 @@ def test_bench_rank_local_failure_in_a_leg_keeps_the_headline(spec, leg):
     env = dict(os.environ, NGMIX_DIST_BACKEND="gloo", NGMIX_BENCH_FAIL=spec)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--settle-steps", "1", "--nstamps", "2000"]
+           "--warmup", "1", "--settle-steps", "1", "--nstamps", "2000", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -124,6 +124,41 @@ def test_bench_rank_local_failure_in_a_leg_keeps_the_headline(spec, leg):
         else:
             assert "error" not in oc[name], oc[name]
             assert oc[name]["value"] > 0 and oc[name]["n_gpus"] == 2
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain run times the steps and prints the headline line, none of the
+    --full extras; --dump-outputs writes the last step's loglike records,
+    statuses and a sample of the model image, identical from run to run"""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+               "--warmup", "1", "--settle-steps", "2", "--nstamps", "3000",
+               "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "pixel-gaussian evals/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["bad_status"] == 0
+        for extra in ("other_configs", "cpu_baseline", "fresh_render"):
+            assert extra not in d, extra
+        got = {name: np.load(str(out / (name + ".npy")))
+               for name in ("loglike", "status", "image")}
+        assert got["loglike"].shape == (3000, 4) and got["loglike"].dtype == np.float64
+        assert np.all(got["loglike"][:, 3] == 48 * 48) and np.isfinite(got["loglike"]).all()
+        assert got["status"].shape == (3000,) and np.all(got["status"] == 0)
+        assert got["image"].shape == (1024, 48, 48) and got["image"].dtype == np.float64
+        assert got["image"].max() > 0
+        dumps.append(got)
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name])
 
 
 def test_bench_refuses_more_ranks_than_gpus():

@@ -34,7 +34,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/team_st
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY --output-format csv -d $OUT/pmc_team -o run -- python3 $ROOT/tools/team_probe.py 20000 9 > $OUT/pmc_team.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_LEVEL_LDS GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_team2 -o run -- python3 $ROOT/tools/team_probe.py 20000 9 > $OUT/pmc_team2.log 2>&1
 cd $ROOT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python bench.py --config C3 --steps 60 > $OUT/bench_c3.json 2>> $OUT/bench.err
 python bench.py --config C4 > $OUT/bench_c4.json 2>> $OUT/bench.err
 python bench.py --config C5 > $OUT/bench_c5.json 2>> $OUT/bench.err

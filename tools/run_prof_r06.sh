@@ -18,7 +18,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lm_stat
 # co-elliptical / multi-band fits: the team step and the precise covariance pass
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/team_stats -o run -- python3 $ROOT/tools/lm_advance_share.py 10000 > $OUT/team.log 2>&1
 cd $ROOT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python bench.py --config C3 --steps 60 > $OUT/bench_c3.json 2>> $OUT/bench.err
 python tools/bench_boot_psf.py > $OUT/boot_psf.log 2>&1
 ls $OUT
