@@ -448,6 +448,32 @@ int ngmix_em_batch(int kind, const ngmix_em_conf *conf, const ngmix_batch *batch
 int ngmix_deriv_images_batch(const ngmix_batch *batch, const double *gpars,
                              const double *dcov, double *out,
                              const int64_t *out_start, void *stream);
+/* noise-power sandwich covariance (noise_cov.py:91-137), two stages.
+   ngmix_noise_cov_blocks_batch: per stamp of a chunk of m stamps of one shape
+   nrow x ncol, the nloc x nloc Gram block
+     B_s[a, b] = sum_q Re(conj K_a(q) K_b(q)) |DFT2(noise)(q)|^2 / npix^2,
+     K_a = DFT2(ierr^2 d_a)
+   dimg: the chunk's derivative images, chunk stamp i at i * nplane * npix:
+   flux == NULL: nplane = nloc planes [shape..., flux]; else nplane = 6, the
+   planes of deriv_images [value, cen1, cen2, g1, g2, T] (nloc = 6; the flux
+   derivative is value / flux[stamp]).  stamp_idx (m,): the batch index of
+   chunk stamp i; pix_off (nstamps,): first pixel of each stamp in ierr and
+   noise (full frames, row-major); out (nstamps, nloc, nloc), rows stamp_idx
+   written.  nloc = 6, 7, 8.
+   ngmix_noise_cov_finish_batch: per object o the blocks of its stamps
+   obj_start[o] .. obj_start[o+1]-1 summed in stamp order into B (npars x
+   npars; local index nloc-1 is column nloc-1 + stamp_band[s]), then
+   cov[o] = C0 B C0 with C0 = cov0 + o * cov0_stride (npars x npars row-major).
+   NaN where obj_ok[o] == 0 (obj_ok may be NULL) or any stamp_bad[s] != 0 */
+int ngmix_noise_cov_blocks_batch(const double *dimg, const int64_t *stamp_idx, int64_t m,
+                                 const int64_t *pix_off, const double *ierr,
+                                 const double *noise, const double *flux, int nloc, int nrow,
+                                 int ncol, double *out, void *stream);
+int ngmix_noise_cov_finish_batch(const double *blocks, const int64_t *obj_start,
+                                 const int32_t *stamp_band, const int32_t *stamp_bad,
+                                 const double *cov0, int64_t cov0_stride,
+                                 const int32_t *obj_ok, int64_t nobj, int npars, int nloc,
+                                 double *cov, void *stream);
 
 /* ======================================================================
  * (3) BATCHED LEVENBERG-MARQUARDT (gauss / exp / dev, analytic jacobian)

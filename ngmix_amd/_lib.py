@@ -243,6 +243,10 @@ SIGNATURES = {
     "ngmix_em_batch": (_i32, [_i32, _vp, _pb, _vp, _i32, _vp, _i32, _vp, _vp,
                               _i32, _vp, _vp, _vp]),
     "ngmix_deriv_images_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
+    "ngmix_noise_cov_blocks_batch": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
+                                            _i32, _vp, _vp]),
+    "ngmix_noise_cov_finish_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32,
+                                            _i32, _vp, _vp]),
     # library-owned stamp store and the RCCL gather of result records
     "ngmix_batch_create": (_i32, [ctypes.POINTER(_pb), _i64, _vp, _vp, _i32, _i32]),
     "ngmix_batch_upload": (_i32, [_pb, _vp, _vp, _vp, _vp]),

@@ -626,6 +626,25 @@ int ngmix_deriv_images_batch(const ngmix_batch *batch, const double *gpars,
     return launch_deriv_grid(batch, gpars, dcov, out, out_start, (hipStream_t)stream);
 }
 
+int ngmix_noise_cov_blocks_batch(const double *dimg, const int64_t *stamp_idx, int64_t m,
+                                 const int64_t *pix_off, const double *ierr,
+                                 const double *noise, const double *flux, int nloc, int nrow,
+                                 int ncol, double *out, void *stream)
+{
+    return launch_noise_cov_blocks(dimg, stamp_idx, m, pix_off, ierr, noise, flux, nloc, nrow,
+                                   ncol, out, (hipStream_t)stream);
+}
+
+int ngmix_noise_cov_finish_batch(const double *blocks, const int64_t *obj_start,
+                                 const int32_t *stamp_band, const int32_t *stamp_bad,
+                                 const double *cov0, int64_t cov0_stride,
+                                 const int32_t *obj_ok, int64_t nobj, int npars, int nloc,
+                                 double *cov, void *stream)
+{
+    return launch_noise_cov_finish(blocks, obj_start, stamp_band, stamp_bad, cov0, cov0_stride,
+                                   obj_ok, nobj, npars, nloc, cov, (hipStream_t)stream);
+}
+
 int ngmix_lm_init(ngmix_lm_state *states, int64_t nobj, int npars, const double *x0,
                   double ftol, double xtol, double gtol, int maxfev, double factor,
                   int mode, const double *lo, const double *hi)

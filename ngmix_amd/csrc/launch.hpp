@@ -36,6 +36,15 @@ int launch_prepsf_sums(const double *kim_re, const double *kim_im, const double 
                        const double *wgt, int64_t nstamps, int M, int64_t stride_n,
                        int64_t stride_r, int R, int C, double df2, double df4, double *out,
                        hipStream_t s);
+// noisecov.hip
+int launch_noise_cov_blocks(const double *dimg, const int64_t *stamp_idx, int64_t m,
+                            const int64_t *pix_off, const double *ierr, const double *noise,
+                            const double *flux, int nloc, int nrow, int ncol, double *out,
+                            hipStream_t s);
+int launch_noise_cov_finish(const double *blocks, const int64_t *obj_start,
+                            const int32_t *stamp_band, const int32_t *stamp_bad,
+                            const double *cov0, int64_t cov0_stride, const int32_t *obj_ok,
+                            int64_t nobj, int npars, int nloc, double *cov, hipStream_t s);
 int launch_first_pixels_fdiff2(const ngmix_batch *b, const int64_t *stamp_of,
                                const ngmix_gauss2d *gm, int ngauss, int64_t nobj, int nskip,
                                double *out, hipStream_t s);

@@ -829,23 +829,32 @@ class Fitter(object):
         Returns a ManyResults: a sequence of per-object result dicts with the
         keys Fitter.go sets (made when an element is read), over the arrays
         of the batch (.arrays: the LMBatchFitter result).
+
+        With use_noise_image every observation needs its noise image
+        (ob.noise); the fits with flags == 0 get the sandwich covariance on
+        the device, before the keys derived from pars_cov are cut
+        (fitters.py:108-109).
         """
         from .lm_batch import LMBatchFitter
         from .batch import flatten_observations
         spec = self._batched_model()
-        if spec is None or self.use_noise_image:
-            raise ValueError("go_many runs the models of LMBatchFitter without the "
-                             "noise-image covariance")
+        if spec is None:
+            raise ValueError("go_many runs the models of LMBatchFitter")
         guess = np.ascontiguousarray(np.atleast_2d(guess), dtype="f8")
+        noise = None
+        if self.use_noise_image:
+            from .noise_cov import noise_of_observations
+            noise = noise_of_observations(obs)
         stamps, sobj, sband, nband, psf = flatten_observations(obs)
         if guess.shape[0] != len(obs):
             raise ValueError("one guess per object")
         fitter = LMBatchFitter(spec[0], fit_pars=self.fit_pars, ngauss=spec[1],
-                               analytic_jacobian=self.analytic_jacobian, prior=self.prior)
+                               analytic_jacobian=self.analytic_jacobian, prior=self.prior,
+                               use_noise_image=self.use_noise_image)
         trivial = stamps.n == len(obs) and nband == 1
         res = fitter.go(stamps, guess, psf=psf,
                         stamp_obj=None if trivial else sobj,
-                        stamp_band=None if trivial else sband)
+                        stamp_band=None if trivial else sband, noise=noise)
         return ManyResults(res, self.model_name, nband)
 
 
@@ -881,6 +890,8 @@ class ManyResults(object):
         flags, ier = int(a["flags"][i]), int(a["ier"][i])
         out = {"model": self.model, "flags": flags, "nfev": int(a["nfev"][i]), "ier": ier,
                "errmsg": "" if flags == 0 else "lmder/lmdif ier %d, flags %d" % (ier, flags)}
+        if "noise_cov_failed" in a and a["noise_cov_failed"][i]:
+            out["errmsg"] = "bad noise covariance matrix"
         for k in ("pars", "pars_err", "pars_cov0", "pars_cov"):
             out[k] = np.array(a[k][i])
         if flags != 0:

@@ -240,10 +240,15 @@ class LMBatchFitter(object):
         form by prior_batch.as_batch_prior), or a batch prior
         (prior_batch.PriorSimpleSepBatch, PriorBatchAdapter, or anything with
         their three members)
+    use_noise_image: every fit that ends with flags == 0 gets the noise-power
+        sandwich covariance (Fitter(use_noise_image=True), fitters.py:108-109)
+        from the noise images given to go(noise=...), computed on the device
+        from the batch's own pars_cov0 (noise_cov.apply_noise_cov_device); not
+        for coellip, as the reference's CoellipFitter has no such switch
     """
 
     def __init__(self, model, fit_pars=None, analytic_jacobian=True, prior=None,
-                 device_prior=True, ngauss=None):
+                 device_prior=True, ngauss=None, use_noise_image=False):
         # host joint priors (joint_prior.py) are put in their batch form
         self.prior = as_batch_prior(prior)
         # evaluate a PriorSimpleSepBatch inside one kernel (False: torch ops)
@@ -264,9 +269,12 @@ class LMBatchFitter(object):
             self.nloc = MODEL_NLOC[model]
         self.fd = not (analytic_jacobian and model in SIMPLE_ANALYTIC_MODELS)
         self.fit_pars = dict(DEFAULT_LM_PARS if fit_pars is None else fit_pars)
+        if use_noise_image and model == "coellip":
+            raise ValueError("use_noise_image is not available for coellip")
+        self.use_noise_image = bool(use_noise_image)
 
     def go(self, stamps, guess, psf=None, stamp_obj=None, stamp_band=None,
-           check_every=1):
+           check_every=1, noise=None):
         """
         one batch, start to finish
 
@@ -281,11 +289,34 @@ class LMBatchFitter(object):
         stamp_band: (nstamps,) band of each stamp; None: band 0
         check_every: (host-driven loop only) read the count of running fits
             every so many rounds
+        noise: with use_noise_image, the stamps' noise images: a flat float64
+            device tensor laid out like stamps.val, or one host array per stamp
 
         returns a dict of arrays indexed by object
         """
+        d_noise = self._noise_images(stamps, noise)
         job = self._enqueue(stamps, guess, psf, stamp_obj, stamp_band, check_every, False)
-        return self._collect(job)
+        return self._apply_noise_cov(job, self._collect(job), d_noise)
+
+    def _noise_images(self, stamps, noise):
+        """the checked noise images of a batch (ValueError before any launch)"""
+        if not self.use_noise_image:
+            return None
+        from .noise_cov import noise_flat
+        return noise_flat(stamps, noise)
+
+    def _apply_noise_cov(self, job, res, d_noise):
+        """the sandwich covariance of the fits with flags == 0, from the
+        solutions and pars_cov0 where the finalize kernel left them"""
+        if d_noise is None:
+            return res
+        from .noise_cov import apply_noise_cov_device
+        stamps, psf, sobj, sband, d_rec, _, n = job.fit_ctx
+        c0 = 4 + 2 * n
+        return apply_noise_cov_device(res, stamps, d_noise, self.model, psf=psf,
+                                      stamp_obj=sobj, stamp_band=sband,
+                                      pars=d_rec[:, 4:4 + n],
+                                      pars_cov0=d_rec[:, c0:c0 + n * n])
 
     # host time of the last batch, by what the host was doing (milliseconds):
     # "enqueue" (set-up and queueing, _enqueue), "wait" (blocked on the batch's
@@ -299,7 +330,7 @@ class LMBatchFitter(object):
         Fit a SEQUENCE of batches as a software pipeline: a generator of result
         dicts, one per batch, in order.  batches: an iterable of (stamps,
         guess, kwargs) with kwargs the keyword arguments of go() (psf=...,
-        stamp_obj=..., stamp_band=...).
+        stamp_obj=..., stamp_band=..., noise=...).
 
         Everything a batch needs on the device -- set-up, the lock-step rounds,
         finalize, pack, the downloads -- is queued without the host waiting for
@@ -314,13 +345,14 @@ class LMBatchFitter(object):
         """
         prev = None
         for stamps, guess, kw in batches:
+            d_noise = self._noise_images(stamps, kw.get("noise"))
             job = self._enqueue(stamps, guess, kw.get("psf"), kw.get("stamp_obj"),
                                 kw.get("stamp_band"), check_every, True)
             if prev is not None:
-                yield self._collect(prev)
-            prev = job
+                yield self._apply_noise_cov(prev[0], self._collect(prev[0]), prev[1])
+            prev = (job, d_noise)
         if prev is not None:
-            yield self._collect(prev)
+            yield self._apply_noise_cov(prev[0], self._collect(prev[0]), prev[1])
 
     # ------------------------------------------------------------------
     # the two halves of a fit: everything the device needs, queued; then the

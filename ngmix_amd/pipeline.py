@@ -329,7 +329,8 @@ def bootstrap_batch(stamps, psf_stamps, model="exp", psf_Tguess=0.3, Tguess=None
                     fit_pars=None, rng=None, psf_ngauss=1, em_pars=None, prior=None,
                     stamp_obj=None, stamp_band=None, ntry=1, psf_fitter=None,
                     psf_ntry=1, guess_admom=None, psf_guess=None, psf_fit_pars=None,
-                    guess=None, guesser="admom", drop_failed_psf=True):
+                    guess=None, guesser="admom", drop_failed_psf=True,
+                    use_noise_image=False, noise=None):
     """
     stamps, psf_stamps: StampBatch of the object images and of their psf images
         (stamp i of one belongs to stamp i of the other)
@@ -369,6 +370,12 @@ def bootstrap_batch(stamps, psf_stamps, model="exp", psf_Tguess=0.3, Tguess=None
     stamp_obj / stamp_band: as for LMBatchFitter.go -- objects with several
         epochs and bands (a MultiBandObsList each).  Every stamp gets its own
         psf fit.
+    use_noise_image: the object fits of every attempt get the noise-power
+        sandwich covariance (LMBatchFitter(use_noise_image=True)); a fit whose
+        sandwich fails carries the covariance flags and is retried like any
+        other failed fit.  noise: the object stamps' noise images, a flat
+        float64 device tensor laid out like stamps.val or one host array per
+        stamp.  The psf fits are not affected.
 
     Returns a dict: the LMBatchFitter result arrays per object (objects that
     were not fitted: flags = BOOT_PSF_FAILURE, nfev 0, NaN), plus per stamp
@@ -377,6 +384,10 @@ def bootstrap_batch(stamps, psf_stamps, model="exp", psf_Tguess=0.3, Tguess=None
     'psf_flux' (guesser='psfflux'), 'ntry', 'rounds'.
     """
     assert stamps.n == psf_stamps.n
+    d_noise = None
+    if use_noise_image:
+        from .noise_cov import noise_flat
+        d_noise = noise_flat(stamps, noise)
     if rng is None:
         rng = np.random.RandomState(0)
     if model not in MODEL_NLOC:
@@ -561,14 +572,17 @@ def bootstrap_batch(stamps, psf_stamps, model="exp", psf_Tguess=0.3, Tguess=None
             return g2_
 
     # ---- 4. the fits, on the stamps that are left
-    fitter = LMBatchFitter(model, fit_pars=fit_pars, prior=prior)
+    fitter = LMBatchFitter(model, fit_pars=fit_pars, prior=prior,
+                           use_noise_image=use_noise_image)
     multi = stamp_obj is not None
+    fnoise = d_noise
     if all_kept:
         fstamps, fpsf, fsobj, fsband = stamps, psf_gm, sobj, sband
         sidx_all = np.arange(n)
     else:
         sidx_all = np.nonzero(keep)[0]
         fstamps, fpsf = stamps.select(sidx_all), psf_gm.select(sidx_all)
+        fnoise = _select_pixels(stamps, d_noise, sidx_all)
         # (objects renumbered without the ones that are not fitted)
         fsobj = np.searchsorted(fit_obj, sobj[sidx_all])
         fsband = sband[sidx_all]
@@ -579,7 +593,8 @@ def bootstrap_batch(stamps, psf_stamps, model="exp", psf_Tguess=0.3, Tguess=None
     if fit_obj.size:
         res = fitter.go(fstamps, first_guess[fit_obj], psf=fpsf,
                         stamp_obj=fsobj.astype(np.int32) if multi else None,
-                        stamp_band=fsband.astype(np.int32) if multi else None)
+                        stamp_band=fsband.astype(np.int32) if multi else None,
+                        noise=fnoise)
         tries[fit_obj] = 1
     for t in range(1, int(ntry)):
         if res is None:
@@ -593,7 +608,8 @@ def bootstrap_batch(stamps, psf_stamps, model="exp", psf_Tguess=0.3, Tguess=None
         sub_obj = np.searchsorted(redo, fsobj[sidx]).astype(np.int32)
         g2_ = np.ascontiguousarray(next_guess(t, fit_obj[redo]))
         sub = fitter.go(fstamps.select(sidx), g2_, psf=fpsf.select(sidx), stamp_obj=sub_obj,
-                        stamp_band=fsband[sidx].astype(np.int32))
+                        stamp_band=fsband[sidx].astype(np.int32),
+                        noise=_select_pixels(fstamps, fnoise, sidx))
         tries[fit_obj[redo]] += 1
         # (items() reads through the keys an LMBatchResult keeps on the
         # device, pars_cov0 among them: the retried objects take every array
@@ -663,6 +679,9 @@ def bootstrap_many(obs, model="exp", set_psf_results=False, **kw):
         if not e.has_psf():
             raise ValueError("bootstrap_many: every observation needs its psf observation")
     psf_stamps = StampBatch.from_observations([e.psf for e in flat])
+    if kw.get("use_noise_image"):
+        from .noise_cov import noise_of_observations
+        kw["noise"] = noise_of_observations(obs)
     res = bootstrap_batch(stamps, psf_stamps, model=model, stamp_obj=sobj, stamp_band=sband, **kw)
     if set_psf_results:
         recs = res["psf_gmix"].to_numpy()
@@ -676,6 +695,19 @@ def bootstrap_many(obs, model="exp", set_psf_results=False, **kw):
                 gm._data[:] = recs[i]
                 e.psf.set_gmix(gm)
     return ManyResults(res, model, nband)
+
+
+def _select_pixels(stamps, flat, index):
+    """the per-pixel array `flat` (laid out like stamps.val) of stamps `index`,
+    laid out like stamps.select(index).val; None stays None"""
+    if flat is None:
+        return None
+    import torch
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    npix = stamps.npix[index]
+    off = np.concatenate([[0], np.cumsum(npix)[:-1]]).astype(np.int64)
+    src = np.repeat(stamps.pix_off[index] - off, npix) + np.arange(int(npix.sum()))
+    return flat[torch.from_numpy(src).to(flat.device)]
 
 
 def _scatter(res, fit_obj, nobj, npars):
