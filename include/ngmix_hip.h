@@ -410,6 +410,20 @@ int ngmix_set_norms_batch(ngmix_gauss2d *gmix, int ngauss, int64_t nstamps,
    (written back) when gmix[gm_off].norm_set == 0, as the reference does. */
 int ngmix_loglike_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                         double *out, int32_t *status, void *stream);
+/* get_loglike per stamp together with its gradient with respect to every
+   gaussian of the stamp's mixture, in deriv_images' convention
+   (ngmix/fitting/derivs_nb.py:41-127):
+     grad[(stamps[i].gm_off + g) * 6 + a] = d loglike_i / d theta_a(g),
+     theta = (p, row, col, irr, irc, icc),
+     d loglike / d theta = sum_pix ivar (val - model) d model / d theta.
+   out (nstamps, 4) as ngmix_loglike_batch.  Norms are computed in-kernel from
+   (p, irr, irc, icc) and never written back: gmix is read only (its det and
+   norm fields are ignored).  A stamp with a gaussian the norms refuse
+   (det < 1e-200, T <= 1e-200) gets that status, loglike NaN and NaN
+   gradients.  Deterministic: fixed-order reductions, no atomics. */
+int ngmix_loglike_grad_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
+                             double *out, double *grad, int32_t *status,
+                             void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

@@ -1,0 +1,445 @@
+"""
+Differentiable log-likelihoods of batched fits, for torch autograd.
+
+The pixel pass is one HIP kernel (csrc/loglike_grad.hip,
+ngmix_loglike_grad_batch): for every stamp it returns get_loglike's value and
+the gradient of that value with respect to the six parameters
+(p, row, col, irr, irc, icc) of every gaussian of the stamp's convolved
+mixture, in the convention of the reference's deriv_images
+(ngmix/fitting/derivs_nb.py:41-127): the derivative of the apodised
+exp5_smooth model the fits minimise.  Everything between the fit parameters
+and those gaussians -- the model mixture (gmix_nb.py:307-558) and the psf
+convolution (gmix_nb.py:609-649) -- is written here in torch ops, so autograd
+carries the chain rule to the parameters and to the psf.
+
+    from ngmix_amd import autodiff
+    pars.requires_grad_(True)
+    lnp = autodiff.lnprob(stamps, pars, "exp", psf=psf, prior=prior)
+    lnp.sum().backward()          # pars.grad: d lnprob / d pars, per object
+
+Objects the reference would refuse (|g| >= 1, a zero Tfactor, a psf of zero
+flux, a convolved gaussian whose determinant or T is not positive) get a NaN
+value, a NaN gradient (with respect to pars and to the psf rows of their
+stamps) and a nonzero flag (return_flags=True); the other objects' values and
+gradients do not depend on them.  First derivatives only: differentiating the
+gradient again (create_graph=True) raises.
+"""
+import ctypes
+import math
+
+import numpy as np
+
+from . import _lib
+from .batch import GMixBatch, _dptr, _on_device, _stream, _torch
+from .gmix import get_model_num, get_model_name
+
+__all__ = ["mixture_from_pars", "convolve", "stamp_loglike_grad", "loglike", "lnprob"]
+
+# the model tables of csrc/common.hpp (gmix_nb.py:243-304): 0-5 exp,
+# 6-15 dev, 16-18 turb, 19 gauss
+_PVALS = (0.00061601229677880041, 0.0079461395724623237, 0.053280454055540001,
+          0.21797364640726541, 0.45496740582554868, 0.26521634184240478,
+          6.5288960012625658e-05, 0.00044199216814302695, 0.0020859587871659754,
+          0.0075913681418996841, 0.02260266219257237, 0.056532254390212859,
+          0.11939049233042602, 0.20969545753234975, 0.29254151133139222,
+          0.28905301416582552, 0.596510042804182, 0.4034898268889178,
+          1.303069003078001e-07, 1.0)
+_FVALS = (0.002467115141477932, 0.018147435573256168, 0.07944063151366336,
+          0.27137669897479122, 0.79782256866993773, 2.1623306025075739,
+          2.9934935706271918e-07, 3.4651596338231207e-06, 2.4807910570562753e-05,
+          1.4307404300535354e-04, 7.2753169298239500e-04, 3.4582464394427260e-03,
+          1.6086645440719100e-02, 7.7006776775654429e-02, 4.1012562102501476e-01,
+          2.9812509778548648e00, 0.5793612389470884, 1.621860687127999,
+          7.019347162356363, 1.0)
+_SIMPLE = {"exp": (0, 6), "dev": (6, 10), "turb": (16, 3), "gauss": (19, 1)}
+_NLOC = {"gauss": 6, "turb": 6, "exp": 6, "dev": 6, "bdf": 7, "bd": 8}
+
+
+def _model_name(model):
+    name = get_model_name(get_model_num(model))
+    if name not in _NLOC and name != "coellip":
+        raise ValueError("autodiff supports %s and 'coellip', got %r"
+                         % (tuple(_NLOC), model))
+    return name
+
+
+def _e1e2(g1, g2):
+    """g1g2_to_e1e2 (gmix_nb.py:652-678) in torch ops; bad marks g >= 1.  At
+    g = 0 the value is the reference's 0 and the slope its limit, 2."""
+    torch = _torch()
+    gsq = g1 * g1 + g2 * g2
+    nz = gsq > 0.0
+    # (sqrt at 0 has an infinite slope: keep it out of the graph)
+    g = torch.sqrt(torch.where(nz, gsq, torch.ones_like(gsq)))
+    bad = nz & (g >= 1)
+    pos = nz & ~bad
+    gs = torch.where(pos, g, torch.full_like(g, 0.5))
+    e = torch.tanh(2 * torch.atanh(gs))
+    e = torch.where(e >= 1.0, torch.full_like(e, 0.99999999), e)
+    fac = torch.where(pos, e / gs, torch.full_like(e, 2.0))
+    return fac * g1, fac * g2, bad
+
+
+def _tfactor(ifracdev, fracdev, TdByTe):
+    """get_cm_Tfactor's sum (gmix_nb.py:561-593), in its order"""
+    tf = 0.0
+    for i in range(6):
+        tf = tf + (_PVALS[i] * ifracdev) * _FVALS[i]
+    for i in range(10):
+        tf = tf + (_PVALS[6 + i] * fracdev) * (_FVALS[6 + i] * TdByTe)
+    return tf
+
+
+def _safe_row(name, npars):
+    """a parameter row every model accepts: what refused rows are evaluated
+    at (their results are then replaced by NaN)"""
+    row = [0.0, 0.0, 0.0, 0.0] + [1.0] * (npars - 4)
+    if name == "bdf":
+        row[5] = 0.5
+    elif name == "bd":
+        row[5], row[6] = 0.0, 0.5
+    return row
+
+
+def _mixture(pars, name, ngauss):
+    """(mixture (n, ngauss, 6), bad (n,)): refused rows are evaluated at a
+    safe row, so that nothing non-finite enters the graph"""
+    torch = _torch()
+    n, npars = pars.shape
+    c1, c2, g1, g2 = pars[:, 0], pars[:, 1], pars[:, 2], pars[:, 3]
+    _, _, bad = _e1e2(g1.detach(), g2.detach())
+    if name in ("bdf", "bd"):
+        fd = pars[:, 5] if name == "bdf" else pars[:, 6]
+        tdbyte = 1.0 if name == "bdf" else torch.pow(10.0, pars[:, 5].detach())
+        bad = bad | (_tfactor(1.0 - fd.detach(), fd.detach(), tdbyte) == 0.0)
+    if bool(bad.any()):
+        safe = torch.tensor(_safe_row(name, npars), dtype=pars.dtype, device=pars.device)
+        pars = torch.where(bad[:, None], safe[None, :], pars)
+        c1, c2, g1, g2 = pars[:, 0], pars[:, 1], pars[:, 2], pars[:, 3]
+    e1, e2, _ = _e1e2(g1, g2)
+    dt = dict(dtype=pars.dtype, device=pars.device)
+    if name == "coellip":
+        T_i_2 = 0.5 * pars[:, 4:4 + ngauss]
+        flux_i = pars[:, 4 + ngauss:4 + 2 * ngauss]
+    elif name in ("bdf", "bd"):
+        if name == "bdf":
+            fracdev, flux, TdByTe = pars[:, 5], pars[:, 6], 1.0
+        else:
+            fracdev, flux = pars[:, 6], pars[:, 7]
+            TdByTe = torch.pow(10.0, pars[:, 5])
+        ifracdev = 1.0 - fracdev
+        T = pars[:, 4] * (1.0 / _tfactor(ifracdev, fracdev, TdByTe))
+        pv = torch.tensor(_PVALS[:16], **dt)
+        fv = torch.tensor(_FVALS[:16], **dt)
+        isdev = torch.arange(16, device=pars.device) >= 6
+        p = torch.where(isdev[None, :], pv[None, :] * fracdev[:, None],
+                        pv[None, :] * ifracdev[:, None])
+        if name == "bdf":
+            f = fv[None, :].expand(n, 16)
+        else:
+            f = torch.where(isdev[None, :], fv[None, :] * TdByTe[:, None],
+                            fv[None, :].expand(n, 16))
+        T_i_2 = (0.5 * T)[:, None] * f
+        flux_i = flux[:, None] * p
+    else:
+        off, ng = _SIMPLE[name]
+        fv = torch.tensor(_FVALS[off:off + ng], **dt)
+        pv = torch.tensor(_PVALS[off:off + ng], **dt)
+        T_i_2 = (0.5 * pars[:, 4])[:, None] * fv[None, :]
+        flux_i = pars[:, 5][:, None] * pv[None, :]
+    ng = T_i_2.shape[1]
+    irr = T_i_2 * (1 - e1)[:, None]
+    irc = T_i_2 * e2[:, None]
+    icc = T_i_2 * (1 + e1)[:, None]
+    mix = torch.stack([flux_i, c1[:, None].expand(n, ng), c2[:, None].expand(n, ng),
+                       irr, irc, icc], dim=2)
+    return mix, bad
+
+
+def _ngauss_of(name, npars, ngauss):
+    if name == "coellip":
+        ng = (npars - 4) // 2 if ngauss is None else int(ngauss)
+        if ng < 1 or npars != 4 + 2 * ng:
+            raise ValueError("coellip needs 4 + 2 * ngauss parameters, got %d" % npars)
+        return ng
+    if npars != _NLOC[name]:
+        raise ValueError("model '%s' needs %d parameters, got %d" % (name, _NLOC[name], npars))
+    return {"gauss": 1, "turb": 3, "exp": 6, "dev": 10, "bdf": 16, "bd": 16}[name]
+
+
+def mixture_from_pars(pars, model, ngauss=None):
+    """
+    The model mixtures of GMixBatch.from_pars / GMixModel (gmix_nb.py:307-558)
+    in differentiable torch ops, on pars' device.  pars: (n, npars) float64
+    tensor of one band's parameters (coellip: [cen1, cen2, g1, g2, T_1..,
+    F_1..] with ngauss pairs).  Returns (mix, bad): mix (n, ngauss, 6) as
+    (p, row, col, irr, irc, icc), bad (n,) bool where the reference refuses
+    the row (|g| >= 1, or a zero Tfactor for bdf / bd); those rows are NaN.
+    """
+    torch = _torch()
+    name = _model_name(model)
+    if pars.ndim == 1:
+        pars = pars[None, :]
+    ng = _ngauss_of(name, pars.shape[1], ngauss)
+    mix, bad = _mixture(pars, name, ng)
+    return torch.where(bad[:, None, None], torch.full_like(mix, math.nan), mix), bad
+
+
+def _psf_tensor(psf, nstamps, device):
+    torch = _torch()
+    if isinstance(psf, GMixBatch):
+        assert psf.n == nstamps, "one psf mixture per stamp"
+        return psf.data[:, :6].reshape(psf.n, psf.ngauss, 6).to(device)
+    psf = torch.as_tensor(psf, dtype=torch.float64, device=device)
+    if psf.ndim != 3 or psf.shape[0] != nstamps or psf.shape[2] != 6:
+        raise ValueError("psf: (nstamps, ngauss_psf, 6) tensor or a GMixBatch")
+    return psf
+
+
+def _convolve(mix, psf):
+    """gmix_convolve_fill per row, in its order of operations; bad marks a
+    psf of zero total flux (evaluated at psum = 1, then replaced)"""
+    torch = _torch()
+    psum = 0.0
+    rsum = 0.0
+    csum = 0.0
+    for j in range(psf.shape[1]):
+        q = psf[:, j]
+        rsum = rsum + q[:, 0] * q[:, 1]
+        csum = csum + q[:, 0] * q[:, 2]
+        psum = psum + q[:, 0]
+    bad = psum == 0.0
+    psum = torch.where(bad, torch.ones_like(psum), psum)
+    rowcen = rsum / psum
+    colcen = csum / psum
+    ipsum = 1.0 / psum
+    o = mix[:, :, None, :]
+    q = psf[:, None, :, :]
+    p = o[..., 0] * q[..., 0] * ipsum[:, None, None]
+    row = o[..., 1] + (q[..., 1] - rowcen[:, None, None])
+    col = o[..., 2] + (q[..., 2] - colcen[:, None, None])
+    cov = o[..., 3:6] + q[..., 3:6]
+    out = torch.cat([torch.stack([p, row, col], dim=3), cov], dim=3)
+    return out.reshape(mix.shape[0], -1, 6), bad
+
+
+def convolve(mix, psf):
+    """
+    GMixBatch.convolve / GMix.convolve (gmix_nb.py:609-649) in differentiable
+    torch ops: mix (n, G, 6), psf (n, P, 6) or a GMixBatch.  Returns
+    (conv (n, G*P, 6), bad (n,)) with bad where the psf's flux sums to zero
+    (the reference's ZeroDivisionError); those rows are NaN.
+    """
+    torch = _torch()
+    psf = _psf_tensor(psf, mix.shape[0], mix.device)
+    out, bad = _convolve(mix, psf)
+    return torch.where(bad[:, None, None], torch.full_like(out, math.nan), out), bad
+
+
+def _make_function():
+    torch = _torch()
+
+    class _LoglikeGrad(torch.autograd.Function):
+        """forward: ngmix_loglike_grad_batch over the stamps, (nstamps,)
+        loglikes (NaN where the stamp's status is not 0); backward:
+        grad_output times the per-gaussian gradients the kernel left"""
+
+        @staticmethod
+        def forward(ctx, gpars, stamps):
+            n, G, _ = gpars.shape
+            dev = stamps.device
+            rec = torch.zeros((n * G, 13), dtype=torch.float64, device=dev)
+            rec[:, :6] = gpars.detach().reshape(n * G, 6)
+            out = torch.empty((n, 4), dtype=torch.float64, device=dev)
+            grad = torch.empty((n * G, 6), dtype=torch.float64, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            b = stamps._batch(G)
+            with _on_device(dev):
+                st = _lib.lib().ngmix_loglike_grad_batch(
+                    ctypes.byref(b), _dptr(rec), _dptr(out), _dptr(grad), _dptr(status),
+                    _stream())
+            _lib.check(st, "ngmix_loglike_grad_batch")
+            ctx.save_for_backward(grad.reshape(n, G, 6), status)
+            ctx.mark_non_differentiable(out, status)
+            return out[:, 0].clone(), out, status
+
+        @staticmethod
+        def backward(ctx, g_ll, g_out, g_status):
+            # First derivatives only.  Grad mode is on here exactly when the
+            # caller asked for a graph of the gradient (create_graph=True, e.g.
+            # a Hessian-vector product): the kernel's second-order terms do not
+            # exist, and the rest of the chain would still be differentiable,
+            # so the result would be silently wrong -- refuse instead.
+            if torch.is_grad_enabled():
+                raise RuntimeError(
+                    "autodiff.loglike gives first derivatives only: create_graph=True "
+                    "(second derivatives through the pixel kernel) is not supported")
+            grad, status = ctx.saved_tensors
+            ok = (status == 0)[:, None, None]
+            grad = torch.where(ok, grad, torch.zeros_like(grad))
+            return g_ll[:, None, None] * grad, None
+
+    return _LoglikeGrad
+
+
+_FUNC = None
+
+
+def _func():
+    global _FUNC
+    if _FUNC is None:
+        _FUNC = _make_function()
+    return _FUNC
+
+
+def stamp_loglike_grad(stamps, gpars):
+    """
+    The raw kernel call: gpars (nstamps, G, 6) device tensor of each stamp's
+    convolved gaussians (p, row, col, irr, irc, icc).  Returns (loglike
+    (nstamps,), record (nstamps, 4) = loglike, s2n_numer, s2n_denom, npix,
+    status (nstamps,) int32); loglike is differentiable with respect to gpars.
+    """
+    if gpars.shape[0] != stamps.n:
+        raise ValueError("one mixture per stamp: %d != %d" % (gpars.shape[0], stamps.n))
+    return _func().apply(gpars, stamps)
+
+
+def _stamp_layout(nstamps, nobj, stamp_obj, stamp_band):
+    """(stamp_obj, stamp_band) as int64 numpy arrays, checked as LMBatchFitter
+    checks them"""
+    if stamp_obj is None:
+        if nstamps != nobj:
+            raise ValueError("stamp_obj is needed when objects have several stamps")
+        sobj = np.arange(nstamps, dtype=np.int64)
+    else:
+        sobj = np.asarray(stamp_obj, dtype=np.int64).reshape(-1)
+        if sobj.shape != (nstamps,):
+            raise ValueError("stamp_obj: one entry per stamp")
+        if nstamps and (np.any(np.diff(sobj) < 0) or sobj[0] < 0 or sobj[-1] >= nobj):
+            raise ValueError("stamp_obj must be non-decreasing object indices")
+        if np.any(np.bincount(sobj, minlength=nobj) == 0):
+            raise ValueError("every object needs at least one stamp")
+    if stamp_band is None:
+        sband = np.zeros(nstamps, dtype=np.int64)
+    else:
+        sband = np.asarray(stamp_band, dtype=np.int64).reshape(-1)
+        if sband.shape != (nstamps,) or np.any(sband < 0):
+            raise ValueError("stamp_band: one non-negative band per stamp")
+    return sobj, sband
+
+
+def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
+            ngauss=None, return_flags=False):
+    """
+    Log-likelihood of every object, summed over its stamps as
+    FitModel.calc_lnprob sums its observations, differentiable with respect
+    to pars and to psf (when a tensor that requires grad).
+
+    stamps: StampBatch of every stamp of every object
+    pars: (nobj, nshape + nband) float64 device tensor, LMBatchFitter.go's
+        layout: the model's shape parameters then one flux per band
+        (coellip: one band, [cen1, cen2, g1, g2, T_1.., F_1..])
+    psf: None, a GMixBatch (one mixture per stamp) or a (nstamps, P, 6)
+        tensor of (p, row, col, irr, irc, icc)
+    stamp_obj / stamp_band: as in LMBatchFitter.go
+
+    Returns (nobj,) loglikes; with return_flags, also (nobj,) int32 flags:
+    0, or the code of the object's first refused stamp (_lib.ERR_*), whose
+    value and gradient (pars, and the psf rows of its stamps) are NaN.
+    """
+    torch = _torch()
+    name = _model_name(model)
+    if pars.ndim == 1:
+        pars = pars[None, :]
+    nobj, npars = pars.shape
+    dev = stamps.device
+    if pars.device != dev:
+        raise ValueError("pars must live on the stamps' device (%s)" % dev)
+    sobj, sband = _stamp_layout(stamps.n, nobj, stamp_obj, stamp_band)
+    nst = stamps.n
+    if name == "coellip":
+        if np.any(sband != 0):
+            raise ValueError("coellip fits one band")
+        bpars = pars[torch.from_numpy(sobj).to(dev)]
+    else:
+        nshape = _NLOC[name] - 1
+        nband = npars - nshape
+        if nband < 1 or (nst and sband.max() >= nband):
+            raise ValueError("pars needs %d shape columns and one flux per band" % nshape)
+        d_obj = torch.from_numpy(sobj).to(dev)
+        d_band = torch.from_numpy(nshape + sband).to(dev)
+        bpars = torch.cat([pars[d_obj, :nshape], pars[d_obj, d_band][:, None]], dim=1)
+    ng = _ngauss_of(name, bpars.shape[1], ngauss)
+    mix, bad = _mixture(bpars, name, ng)
+    code = torch.where(bad, torch.full_like(bad, _lib.ERR_G_RANGE, dtype=torch.int32),
+                       torch.zeros_like(bad, dtype=torch.int32))
+    psf_t = None
+    if psf is not None:
+        psf_t = _psf_tensor(psf, nst, dev)
+        mix, pbad = _convolve(mix, psf_t)
+        code = torch.where((code == 0) & pbad, torch.full_like(code, _lib.ERR_ZERO_DIV), code)
+    ll, _, status = stamp_loglike_grad(stamps, mix)
+    code = torch.where(code == 0, status, code)
+    ll = torch.where(code == 0, ll, torch.zeros_like(ll))
+
+    # fixed-order sum over each object's stamps (stamp order), and its flag
+    counts = np.bincount(sobj, minlength=nobj)
+    start = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    L = int(counts.max()) if nobj else 0
+    tot = None
+    flag = torch.zeros(nobj, dtype=torch.int32, device=dev)
+    ll_pad = torch.cat([ll, ll.new_zeros(1)])
+    code_pad = torch.cat([code, code.new_zeros(1)])
+    for j in range(L):
+        idx = np.where(j < counts, start + j, nst)
+        d_idx = torch.from_numpy(idx).to(dev)
+        term = ll_pad[d_idx]
+        tot = term if tot is None else tot + term
+        cj = code_pad[d_idx]
+        flag = torch.where((flag == 0) & (cj != 0), cj, flag)
+    if tot is None:
+        tot = pars.new_zeros(nobj)
+    bad_obj = flag != 0
+    # a flagged object's value, and its gradient with respect to pars and to
+    # the psf rows of its stamps, are NaN: a term that is 0 * x elsewhere
+    poison = torch.where(bad_obj, torch.full_like(tot, math.nan), torch.zeros_like(tot))
+    nan_term = (pars * poison[:, None]).sum(dim=1)
+    if psf_t is not None and psf_t.requires_grad:
+        d_sobj = torch.from_numpy(sobj).to(dev)
+        ps = (psf_t.reshape(nst, -1) * poison[d_sobj][:, None]).sum(dim=1)
+        ps_pad = torch.cat([ps, ps.new_zeros(1)])
+        for j in range(L):
+            idx = np.where(j < counts, start + j, nst)
+            nan_term = nan_term + ps_pad[torch.from_numpy(idx).to(dev)]
+    out = torch.where(bad_obj, nan_term, tot)
+    if return_flags:
+        return out, flag
+    return out
+
+
+def lnprob(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
+           ngauss=None, prior=None, return_flags=False):
+    """
+    loglike() plus the prior's ln p of every object (prior.get_lnprob_batch:
+    PriorSepBatch / PriorSimpleSepBatch, or a reference joint prior that
+    prior_batch.as_batch_prior turns into one), the objective LMBatchFitter
+    maximises.  A prior that as_batch_prior can only evaluate on the host
+    (PriorBatchAdapter) has no gradient: asking for one is a TypeError.
+    """
+    from .prior_batch import as_batch_prior, PriorBatchAdapter
+    torch = _torch()
+    bp = as_batch_prior(prior)
+    # (refused before any launch)
+    if isinstance(bp, PriorBatchAdapter) and torch.is_grad_enabled() and pars.requires_grad:
+        raise TypeError(
+            "prior %r is evaluated object by object on the host (PriorBatchAdapter) and "
+            "has no gradient: use a PriorSepBatch / PriorSimpleSepBatch, or evaluate "
+            "under torch.no_grad()" % (type(prior).__name__,))
+    res = loglike(stamps, pars, model, psf=psf, stamp_obj=stamp_obj,
+                  stamp_band=stamp_band, ngauss=ngauss, return_flags=return_flags)
+    if bp is None:
+        return res
+    lp = bp.get_lnprob_batch(pars if pars.ndim == 2 else pars[None, :])
+    if return_flags:
+        return res[0] + lp, res[1]
+    return res + lp

@@ -575,6 +575,13 @@ int ngmix_loglike_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
     return launch_loglike_grid(batch, gmix, out, status, stream);
 }
 
+int ngmix_loglike_grad_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
+                             double *out, double *grad, int32_t *status,
+                             void *stream)
+{
+    return launch_loglike_grad(batch, gmix, out, grad, status, (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)
