@@ -424,6 +424,21 @@ int ngmix_loglike_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
 int ngmix_loglike_grad_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
                              double *out, double *grad, int32_t *status,
                              void *stream);
+/* vector-Jacobian product of ngmix_render_batch: for every gaussian of every
+   stamp's mixture,
+     grad[(stamps[i].gm_off + g) * 6 + a] =
+         sum_pix gimage[pix_off + pix] d model[pix] / d theta_a(g),
+     theta = (p, row, col, irr, irc, icc),
+   over every pixel of the frame (weights and ignore_zero_weight play no part;
+   batch->val / ierr may be null).  fast_exp != 0: deriv_images' convention
+   (ngmix/fitting/derivs_nb.py:41-127), as ngmix_loglike_grad_batch;
+   fast_exp == 0: the true derivative of the exp render.  Norms are computed
+   in-kernel and never written back: gmix is read only.  A stamp with a
+   gaussian the norms refuse gets that status and NaN gradients.
+   Deterministic: fixed-order reductions, no atomics. */
+int ngmix_render_vjp_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
+                           const double *gimage, int fast_exp, double *grad,
+                           int32_t *status, void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

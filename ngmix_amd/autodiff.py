@@ -1,5 +1,6 @@
 """
-Differentiable log-likelihoods of batched fits, for torch autograd.
+Differentiable log-likelihoods and model images of batched fits, for torch
+autograd.
 
 The pixel pass is one HIP kernel (csrc/loglike_grad.hip,
 ngmix_loglike_grad_batch): for every stamp it returns get_loglike's value and
@@ -23,6 +24,23 @@ value, a NaN gradient (with respect to pars and to the psf rows of their
 stamps) and a nonzero flag (return_flags=True); the other objects' values and
 gradients do not depend on them.  First derivatives only: differentiating the
 gradient again (create_graph=True) raises.
+
+For objectives of your own, render() returns every stamp's model image (flat,
+in StampBatch.render's layout), differentiable with respect to pars and the
+psf.  Its backward is one HIP kernel (csrc/render_grad.hip,
+ngmix_render_vjp_batch): the vector-Jacobian product over the pixels, with no
+(nstamps, G, npix) intermediate.  stamp_render() does the same for raw
+(nstamps, G, 6) mixtures.  A Poisson loss, and a blend of two objects drawn
+into the same stamps by concatenating their mixtures along G:
+
+    img = autodiff.render(stamps, pars, "exp", psf=psf)
+    loss = (img - counts * torch.log(img)).sum()     # -ln L up to a constant
+    loss.backward()
+
+    ma, _ = autodiff.convolve(autodiff.mixture_from_pars(pars_a, "exp")[0], psf)
+    mb, _ = autodiff.convolve(autodiff.mixture_from_pars(pars_b, "dev")[0], psf)
+    img, status = autodiff.stamp_render(stamps, torch.cat([ma, mb], dim=1))
+    ((img - stamps.val) ** 2 * stamps.ierr ** 2).sum().backward()
 """
 import ctypes
 import math
@@ -33,7 +51,8 @@ from . import _lib
 from .batch import GMixBatch, _dptr, _on_device, _stream, _torch
 from .gmix import get_model_num, get_model_name
 
-__all__ = ["mixture_from_pars", "convolve", "stamp_loglike_grad", "loglike", "lnprob"]
+__all__ = ["mixture_from_pars", "convolve", "stamp_loglike_grad", "loglike", "lnprob",
+           "stamp_render", "render"]
 
 # the model tables of csrc/common.hpp (gmix_nb.py:243-304): 0-5 exp,
 # 6-15 dev, 16-18 turb, 19 gauss
@@ -282,6 +301,74 @@ def _make_function():
     return _LoglikeGrad
 
 
+def _make_render_function():
+    torch = _torch()
+
+    class _RenderVJP(torch.autograd.Function):
+        """forward: ngmix_render_batch over the stamps (as StampBatch.render
+        with image=None); backward: one ngmix_render_vjp_batch call, the
+        upstream image contracted with the derivative of every pixel"""
+
+        @staticmethod
+        def forward(ctx, gpars, stamps, fast_exp, exact):
+            n, G, _ = gpars.shape
+            dev = stamps.device
+            rec = torch.zeros((n * G, 13), dtype=torch.float64, device=dev)
+            g = gpars.detach().reshape(n * G, 6)
+            rec[:, :6] = g
+            rec[:, 6] = g[:, 3] * g[:, 5] - g[:, 4] * g[:, 4]   # det, as the kernels form it
+            extent = int(stamps.total_pix)
+            if stamps.n:
+                extent = max(extent, int((stamps.pix_off + stamps.npix).max()))
+            packed = stamps._packed()
+            if packed:
+                image = torch.empty(extent, dtype=torch.float64, device=dev)
+            else:
+                image = torch.zeros(extent, dtype=torch.float64, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            b = stamps._batch(G, False, exact)
+            if packed:
+                b.flags |= _lib.BATCH_RENDER_OVERWRITE
+            with _on_device(dev):
+                st = _lib.lib().ngmix_render_batch(
+                    ctypes.byref(b), _dptr(rec), _dptr(image), int(bool(fast_exp)),
+                    _dptr(status), _stream())
+            _lib.check(st, "ngmix_render_batch")
+            ctx.stamps = stamps
+            ctx.fast_exp = bool(fast_exp)
+            ctx.shape = (n, G)
+            ctx.save_for_backward(rec, status)
+            ctx.mark_non_differentiable(status)
+            return image, status
+
+        @staticmethod
+        def backward(ctx, g_image, g_status):
+            # first derivatives only (see _LoglikeGrad.backward)
+            if torch.is_grad_enabled():
+                raise RuntimeError(
+                    "autodiff.render gives first derivatives only: create_graph=True "
+                    "(second derivatives through the pixel kernel) is not supported")
+            rec, status = ctx.saved_tensors
+            n, G = ctx.shape
+            stamps = ctx.stamps
+            dev = stamps.device
+            # (image.sum() hands back a stride-0 expanded tensor)
+            gimg = g_image.to(torch.float64).contiguous()
+            grad = torch.empty((n * G, 6), dtype=torch.float64, device=dev)
+            vstatus = torch.empty(n, dtype=torch.int32, device=dev)
+            b = stamps._batch(G)
+            with _on_device(dev):
+                st = _lib.lib().ngmix_render_vjp_batch(
+                    ctypes.byref(b), _dptr(rec), _dptr(gimg), int(ctx.fast_exp),
+                    _dptr(grad), _dptr(vstatus), _stream())
+            _lib.check(st, "ngmix_render_vjp_batch")
+            grad = grad.reshape(n, G, 6)
+            ok = (status == 0)[:, None, None]
+            return torch.where(ok, grad, torch.zeros_like(grad)), None, None, None
+
+    return _RenderVJP
+
+
 _FUNC = None
 
 
@@ -290,6 +377,16 @@ def _func():
     if _FUNC is None:
         _FUNC = _make_function()
     return _FUNC
+
+
+_RENDER_FUNC = None
+
+
+def _render_func():
+    global _RENDER_FUNC
+    if _RENDER_FUNC is None:
+        _RENDER_FUNC = _make_render_function()
+    return _RENDER_FUNC
 
 
 def stamp_loglike_grad(stamps, gpars):
@@ -302,6 +399,27 @@ def stamp_loglike_grad(stamps, gpars):
     if gpars.shape[0] != stamps.n:
         raise ValueError("one mixture per stamp: %d != %d" % (gpars.shape[0], stamps.n))
     return _func().apply(gpars, stamps)
+
+
+def stamp_render(stamps, gpars, fast_exp=True, exact=False):
+    """
+    The raw render: gpars (nstamps, G, 6) device tensor of each stamp's
+    gaussians (p, row, col, irr, irc, icc).  Returns (image, status
+    (nstamps,) int32): the image is StampBatch.render's (flat, the stamps'
+    layout, bit for bit for the same fast_exp / exact) and differentiable with
+    respect to gpars; its backward is one ngmix_render_vjp_batch call
+    (fast_exp: deriv_images' convention, else the true derivative).  A stamp
+    whose status is not 0 renders zeros and gets a zero gradient.
+    """
+    if gpars.ndim != 3 or gpars.shape[2] != 6:
+        raise ValueError("gpars: (nstamps, G, 6) tensor of (p, row, col, irr, irc, icc)")
+    if gpars.shape[0] != stamps.n:
+        raise ValueError("one mixture per stamp: %d != %d" % (gpars.shape[0], stamps.n))
+    if gpars.shape[1] < 1:
+        raise ValueError("gpars: at least one gaussian per stamp")
+    if gpars.device != stamps.device:
+        raise ValueError("gpars must live on the stamps' device (%s)" % stamps.device)
+    return _render_func().apply(gpars, stamps, fast_exp, exact)
 
 
 def _stamp_layout(nstamps, nobj, stamp_obj, stamp_band):
@@ -328,25 +446,11 @@ def _stamp_layout(nstamps, nobj, stamp_obj, stamp_band):
     return sobj, sband
 
 
-def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
-            ngauss=None, return_flags=False):
-    """
-    Log-likelihood of every object, summed over its stamps as
-    FitModel.calc_lnprob sums its observations, differentiable with respect
-    to pars and to psf (when a tensor that requires grad).
-
-    stamps: StampBatch of every stamp of every object
-    pars: (nobj, nshape + nband) float64 device tensor, LMBatchFitter.go's
-        layout: the model's shape parameters then one flux per band
-        (coellip: one band, [cen1, cen2, g1, g2, T_1.., F_1..])
-    psf: None, a GMixBatch (one mixture per stamp) or a (nstamps, P, 6)
-        tensor of (p, row, col, irr, irc, icc)
-    stamp_obj / stamp_band: as in LMBatchFitter.go
-
-    Returns (nobj,) loglikes; with return_flags, also (nobj,) int32 flags:
-    0, or the code of the object's first refused stamp (_lib.ERR_*), whose
-    value and gradient (pars, and the psf rows of its stamps) are NaN.
-    """
+def _stamp_mixtures(stamps, pars, model, psf, stamp_obj, stamp_band, ngauss):
+    """what loglike and render share: the layout checks, every stamp's
+    (convolved) mixture and its code (0, or why the reference refuses it).
+    Returns (pars (nobj, npars), sobj, mix (nstamps, G, 6), code (nstamps,)
+    int32, psf tensor or None)"""
     torch = _torch()
     name = _model_name(model)
     if pars.ndim == 1:
@@ -378,43 +482,139 @@ def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
         psf_t = _psf_tensor(psf, nst, dev)
         mix, pbad = _convolve(mix, psf_t)
         code = torch.where((code == 0) & pbad, torch.full_like(code, _lib.ERR_ZERO_DIV), code)
+    return pars, sobj, mix, code, psf_t
+
+
+def _object_rows(sobj, nobj, dev):
+    """the j-th stamp of every object, j = 0 .. (most stamps) - 1, as device
+    indices into a per-stamp array padded with one entry (index nstamps) that
+    objects with fewer stamps read"""
+    torch = _torch()
+    counts = np.bincount(sobj, minlength=nobj)
+    start = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    L = int(counts.max()) if nobj else 0
+    return [torch.from_numpy(np.where(j < counts, start + j, len(sobj))).to(dev)
+            for j in range(L)]
+
+
+def _first_flag(code, rows, nobj):
+    """each object's flag: the code of its first refused stamp, in stamp order"""
+    torch = _torch()
+    flag = torch.zeros(nobj, dtype=torch.int32, device=code.device)
+    code_pad = torch.cat([code, code.new_zeros(1)])
+    for d_idx in rows:
+        cj = code_pad[d_idx]
+        flag = torch.where((flag == 0) & (cj != 0), cj, flag)
+    return flag
+
+
+def _poison(flag, like):
+    """NaN for a flagged object, else 0: multiplied into a term that is then
+    0 * x for the others, it makes the flagged object's gradients NaN"""
+    torch = _torch()
+    return torch.where(flag != 0, torch.full_like(like, math.nan), torch.zeros_like(like))
+
+
+def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
+            ngauss=None, return_flags=False):
+    """
+    Log-likelihood of every object, summed over its stamps as
+    FitModel.calc_lnprob sums its observations, differentiable with respect
+    to pars and to psf (when a tensor that requires grad).
+
+    stamps: StampBatch of every stamp of every object
+    pars: (nobj, nshape + nband) float64 device tensor, LMBatchFitter.go's
+        layout: the model's shape parameters then one flux per band
+        (coellip: one band, [cen1, cen2, g1, g2, T_1.., F_1..])
+    psf: None, a GMixBatch (one mixture per stamp) or a (nstamps, P, 6)
+        tensor of (p, row, col, irr, irc, icc)
+    stamp_obj / stamp_band: as in LMBatchFitter.go
+
+    Returns (nobj,) loglikes; with return_flags, also (nobj,) int32 flags:
+    0, or the code of the object's first refused stamp (_lib.ERR_*), whose
+    value and gradient (pars, and the psf rows of its stamps) are NaN.
+    """
+    torch = _torch()
+    pars, sobj, mix, code, psf_t = _stamp_mixtures(stamps, pars, model, psf, stamp_obj,
+                                                   stamp_band, ngauss)
+    nobj = pars.shape[0]
+    nst = stamps.n
+    dev = stamps.device
     ll, _, status = stamp_loglike_grad(stamps, mix)
     code = torch.where(code == 0, status, code)
     ll = torch.where(code == 0, ll, torch.zeros_like(ll))
 
     # fixed-order sum over each object's stamps (stamp order), and its flag
-    counts = np.bincount(sobj, minlength=nobj)
-    start = np.concatenate([[0], np.cumsum(counts)[:-1]])
-    L = int(counts.max()) if nobj else 0
+    rows = _object_rows(sobj, nobj, dev)
     tot = None
-    flag = torch.zeros(nobj, dtype=torch.int32, device=dev)
     ll_pad = torch.cat([ll, ll.new_zeros(1)])
-    code_pad = torch.cat([code, code.new_zeros(1)])
-    for j in range(L):
-        idx = np.where(j < counts, start + j, nst)
-        d_idx = torch.from_numpy(idx).to(dev)
+    for d_idx in rows:
         term = ll_pad[d_idx]
         tot = term if tot is None else tot + term
-        cj = code_pad[d_idx]
-        flag = torch.where((flag == 0) & (cj != 0), cj, flag)
+    flag = _first_flag(code, rows, nobj)
     if tot is None:
         tot = pars.new_zeros(nobj)
     bad_obj = flag != 0
     # a flagged object's value, and its gradient with respect to pars and to
     # the psf rows of its stamps, are NaN: a term that is 0 * x elsewhere
-    poison = torch.where(bad_obj, torch.full_like(tot, math.nan), torch.zeros_like(tot))
+    poison = _poison(flag, tot)
     nan_term = (pars * poison[:, None]).sum(dim=1)
     if psf_t is not None and psf_t.requires_grad:
         d_sobj = torch.from_numpy(sobj).to(dev)
         ps = (psf_t.reshape(nst, -1) * poison[d_sobj][:, None]).sum(dim=1)
         ps_pad = torch.cat([ps, ps.new_zeros(1)])
-        for j in range(L):
-            idx = np.where(j < counts, start + j, nst)
-            nan_term = nan_term + ps_pad[torch.from_numpy(idx).to(dev)]
+        for d_idx in rows:
+            nan_term = nan_term + ps_pad[d_idx]
     out = torch.where(bad_obj, nan_term, tot)
     if return_flags:
         return out, flag
     return out
+
+
+def render(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None, ngauss=None,
+           fast_exp=True, exact=False, return_flags=False):
+    """
+    The model image of every stamp of every object (render_nb.py:9-36, as
+    GMix.make_image draws it), flat in the stamps' layout (StampBatch.render's
+    image), differentiable with respect to pars and to psf (when a tensor that
+    requires grad).  Arguments as loglike(); fast_exp / exact as
+    StampBatch.render.  Every pixel of the frame is drawn: weights play no
+    part (masking is the loss's business).
+
+    Returns the image; with return_flags, also (nobj,) int32 flags as
+    loglike's.  Every pixel of a flagged object's stamps is NaN, and so are its
+    gradient with respect to pars and the psf rows of its stamps; the other
+    objects' pixels and gradients do not depend on it.
+    """
+    torch = _torch()
+    pars, sobj, mix, code, psf_t = _stamp_mixtures(stamps, pars, model, psf, stamp_obj,
+                                                   stamp_band, ngauss)
+    nobj = pars.shape[0]
+    nst = stamps.n
+    dev = stamps.device
+    image, status = stamp_render(stamps, mix, fast_exp=fast_exp, exact=exact)
+    code = torch.where(code == 0, status, code)
+    flag = _first_flag(code, _object_rows(sobj, nobj, dev), nobj)
+    if nst and bool((flag != 0).any()):
+        # the NaN term of each stamp (its object's pars, its own psf rows),
+        # put on every pixel of the stamps of flagged objects
+        d_sobj = torch.from_numpy(sobj).to(dev)
+        poison = _poison(flag, pars.new_zeros(nobj))
+        term = (pars * poison[:, None]).sum(dim=1)[d_sobj]
+        if psf_t is not None and psf_t.requires_grad:
+            term = term + (psf_t.reshape(nst, -1) * poison[d_sobj][:, None]).sum(dim=1)
+        npix = torch.from_numpy(stamps.npix).to(dev)
+        start = torch.cumsum(npix, 0) - npix
+        pos = torch.repeat_interleave(torch.from_numpy(stamps.pix_off).to(dev) - start, npix) + \
+            torch.arange(int(stamps.total_pix), device=dev)
+        pix_stamp = torch.full((image.shape[0],), nst, dtype=torch.int64, device=dev)
+        pix_stamp[pos] = torch.repeat_interleave(torch.arange(nst, device=dev), npix)
+        bad_pad = torch.cat([flag[d_sobj] != 0, torch.zeros(1, dtype=torch.bool, device=dev)])
+        term_pad = torch.cat([term, term.new_zeros(1)])
+        image = torch.where(bad_pad[pix_stamp], term_pad[pix_stamp], image)
+    if return_flags:
+        return image, flag
+    return image
 
 
 def lnprob(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,

@@ -582,6 +582,14 @@ int ngmix_loglike_grad_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix
     return launch_loglike_grad(batch, gmix, out, grad, status, (hipStream_t)stream);
 }
 
+int ngmix_render_vjp_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
+                           const double *gimage, int fast_exp, double *grad,
+                           int32_t *status, void *stream)
+{
+    return launch_render_vjp(batch, gmix, gimage, fast_exp, grad, status,
+                             (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)

@@ -27,24 +27,12 @@
 // skipped in both passes (exact: every term there is 0).  No floating-point
 // atomics (one LDS integer atomicMin finds the first refused gaussian), no
 // cross-work-group traffic: two runs give the same bits.
-#include "device_utils.hpp"
+#include "grad_common.hpp"
 #include "launch.hpp"
 
 namespace ngmix {
 
 __constant__ double c_exp_table_g[16] = NGMIX_EXP_TABLE;
-
-// per-gaussian staging: the value form of the loglike kernels (EvalGauss) plus
-// what the derivatives need, and the chi2 < 25 pixel box
-struct GradGauss {
-    EvalGauss e;   // row, col, dcc, drr, drc2, pnorm
-    double norm;   // 1 / (2 pi sqrt(det))
-    double drc;
-    PixBox box;
-};
-static_assert(sizeof(GradGauss) == 80, "GradGauss");
-
-constexpr int LG_R = 9;    // tiles per chunk (48x48: 36 tiles, four chunks)
 
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) void loglike_grad_kernel(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
@@ -194,29 +182,8 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) vo
 #pragma unroll
             for (int k = 0; k < LG_R; k++) {
                 if (!((tmask >> k) & 1ull)) continue;
-                const double chi2 = gauss_chi2(G.e, pv[k], pu[k]);
-                if (chi2 < MAX_CHI2 && chi2 >= 0.0) {
-                    const double dv = pv[k] - G.e.row;
-                    const double du = pu[k] - G.e.col;
-                    const double qv = w11 * dv + w12 * du;
-                    const double qu = w12 * dv + w22 * du;
-                    const double E = fexp(-0.5 * chi2, tab) * area;
-                    double e0 = E, ec = E;
-                    if (chi2 > APOD_CHI2) {
-                        const double w = apod_window(chi2);
-                        ec = E * (w - 2.0 * apod_window_deriv(chi2));
-                        e0 = E * w;
-                    }
-                    const double r = pres[k];
-                    const double rv = r * (G.e.pnorm * e0);     // r * val
-                    const double rc = r * (G.e.pnorm * ec);     // r * valc
-                    a0 += r * (G.norm * e0);
-                    a1 += rc * qv;
-                    a2 += rc * qu;
-                    a3 += 0.5 * (rc * (qv * qv) - rv * w11);
-                    a4 += rc * (qv * qu) - rv * w12;
-                    a5 += 0.5 * (rc * (qu * qu) - rv * w22);
-                }
+                grad_pair<true>(G, w11, w22, w12, pv[k], pu[k], pres[k], area, tab, a0, a1,
+                                a2, a3, a4, a5);
             }
             double z0 = 0.0, z1 = 0.0;
             wave_total4(a0, a1, a2, a3);
