@@ -439,6 +439,25 @@ int ngmix_loglike_grad_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix
 int ngmix_render_vjp_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
                            const double *gimage, int fast_exp, double *grad,
                            int32_t *status, void *stream);
+/* Fisher (Gauss-Newton) matrix of every stamp with respect to K parameters
+   (1 <= K <= 16) of its own:
+     out[i * K * K + k * K + l] = sum_pix w[pix] J_k[pix] J_l[pix],
+     J_k[pix] = sum_g sum_a d model[pix] / d theta_a(g)
+                            * dgpars[((stamps[i].gm_off + g) * 6 + a) * K + k],
+     theta = (p, row, col, irr, irc, icc),
+   i.e. dgpars is d theta / d q per gaussian, (total gaussians, 6, K).
+   weight == NULL: w = ierr^2 of the batch (loglike's weighting, zero-weight
+   pixels drop out); otherwise w is read at weight[pix_off + row * ncol + col]
+   over every pixel of the frame and must be >= 0 (sqrt(w) is taken).
+   fast_exp != 0: deriv_images' convention (ngmix/fitting/derivs_nb.py:41-127),
+   as ngmix_loglike_grad_batch; fast_exp == 0: the true derivative of the exp
+   render.  The matrix is symmetric to the bit.  Norms are computed in-kernel
+   and never written back: gmix is read only.  A stamp with a gaussian the
+   norms refuse gets that status and a NaN matrix.  Deterministic: fixed-order
+   reductions, no atomics. */
+int ngmix_fisher_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
+                       const double *dgpars, int K, const double *weight, int fast_exp,
+                       double *out, int32_t *status, void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

@@ -237,6 +237,7 @@ SIGNATURES = {
     "ngmix_loglike_batch": (_i32, [_pb, _vp, _vp, _vp, _vp]),
     "ngmix_loglike_grad_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
     "ngmix_render_vjp_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ngmix_fisher_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ngmix_fill_fdiff_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
     "ngmix_render_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _vp]),
     "ngmix_model_s2n_sum_batch": (_i32, [_pb, _vp, _vp, _vp, _vp]),

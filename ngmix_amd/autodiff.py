@@ -41,6 +41,14 @@ into the same stamps by concatenating their mixtures along G:
     mb, _ = autodiff.convolve(autodiff.mixture_from_pars(pars_b, "dev")[0], psf)
     img, status = autodiff.stamp_render(stamps, torch.cat([ma, mb], dim=1))
     ((img - stamps.val) ** 2 * stamps.ierr ** 2).sum().backward()
+
+Error bars at any parameters -- after an LBFGS fit over lnprob, a Fisher
+forecast at the truth, a blend -- come from fisher() and covariance(): the
+Gauss-Newton matrix sum_pix w J J^T of every object (and its inverse), from
+one HIP kernel (csrc/fisher.hip, ngmix_fisher_batch) that contracts the same
+first derivatives with d theta / d pars and forms the outer products without
+writing J to memory.  stamp_fisher() is the raw form over (nstamps, G, 6)
+mixtures with a caller's tangents (nstamps, G, 6, K).
 """
 import ctypes
 import math
@@ -52,7 +60,7 @@ from .batch import GMixBatch, _dptr, _on_device, _stream, _torch
 from .gmix import get_model_num, get_model_name
 
 __all__ = ["mixture_from_pars", "convolve", "stamp_loglike_grad", "loglike", "lnprob",
-           "stamp_render", "render"]
+           "stamp_render", "render", "stamp_fisher", "fisher", "covariance"]
 
 # the model tables of csrc/common.hpp (gmix_nb.py:243-304): 0-5 exp,
 # 6-15 dev, 16-18 turb, 19 gauss
@@ -643,3 +651,185 @@ def lnprob(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
     if return_flags:
         return res[0] + lp, res[1]
     return res + lp
+
+
+# ------------------------------------------------------------------ Fisher
+
+FISHER_KMAX = 16   # parameters per stamp: one 16 x 16 MFMA accumulator
+
+
+def stamp_fisher(stamps, gpars, dgpars, weight=None, fast_exp=True):
+    """
+    The raw Fisher kernel (ngmix_fisher_batch): for every stamp,
+        F[k, l] = sum_pix w J_k J_l,
+        J_k = sum_g sum_a d model / d theta_a(g) dgpars[s, g, a, k],
+    theta = (p, row, col, irr, irc, icc).
+
+    gpars: (nstamps, G, 6) device tensor of each stamp's gaussians (for a
+        blend, the objects' mixtures concatenated along G, as stamp_render)
+    dgpars: (nstamps, G, 6, K) d theta / d q, 1 <= K <= 16 (e.g. from
+        torch.func.jacfwd)
+    weight: None for w = ierr^2 of the stamps (loglike's weighting: zero-weight
+        pixels drop out), or a flat float64 device tensor in StampBatch.render's
+        layout (every frame pixel, at pix_off).  Weights must be >= 0: the
+        kernel takes sqrt(w).
+    fast_exp: True for deriv_images' convention (the fits' jacobian, their
+        pars_cov), False for the true derivative of the exp render.
+
+    Returns (F (nstamps, K, K) float64, symmetric to the bit, status
+    (nstamps,) int32).  A stamp whose status is not 0 gets a NaN matrix.  No
+    autograd graph.
+    """
+    torch = _torch()
+    if gpars.ndim != 3 or gpars.shape[2] != 6:
+        raise ValueError("gpars: (nstamps, G, 6) tensor of (p, row, col, irr, irc, icc)")
+    n, G, _ = gpars.shape
+    if n != stamps.n:
+        raise ValueError("one mixture per stamp: %d != %d" % (n, stamps.n))
+    if G < 1:
+        raise ValueError("gpars: at least one gaussian per stamp")
+    if dgpars.ndim != 4 or tuple(dgpars.shape[:3]) != (n, G, 6):
+        raise ValueError("dgpars: (nstamps, G, 6, K) tensor, got %s" % (tuple(dgpars.shape),))
+    K = int(dgpars.shape[3])
+    if K < 1 or K > FISHER_KMAX:
+        raise ValueError("dgpars: K must be 1..%d parameters per stamp, got %d"
+                         % (FISHER_KMAX, K))
+    dev = stamps.device
+    if gpars.device != dev or dgpars.device != dev:
+        raise ValueError("gpars and dgpars must live on the stamps' device (%s)" % dev)
+    wt = None
+    if weight is not None:
+        if weight.ndim != 1 or weight.device != dev:
+            raise ValueError("weight: a flat tensor on the stamps' device, in "
+                             "StampBatch.render's layout")
+        extent = int(stamps.total_pix)
+        if stamps.n:
+            extent = max(extent, int((stamps.pix_off + stamps.npix).max()))
+        if weight.shape[0] < extent:
+            raise ValueError("weight: %d pixels, the stamps span %d"
+                             % (weight.shape[0], extent))
+        wt = weight.detach().to(torch.float64).contiguous()
+    rec = torch.zeros((n * G, 13), dtype=torch.float64, device=dev)
+    rec[:, :6] = gpars.detach().reshape(n * G, 6)
+    dg = dgpars.detach().to(torch.float64).contiguous()
+    out = torch.empty((n, K, K), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    b = stamps._batch(G)
+    with _on_device(dev):
+        st = _lib.lib().ngmix_fisher_batch(
+            ctypes.byref(b), _dptr(rec), _dptr(dg), K,
+            _dptr(wt) if wt is not None else None, int(bool(fast_exp)), _dptr(out),
+            _dptr(status), _stream())
+    _lib.check(st, "ngmix_fisher_batch")
+    return out, status
+
+
+def _mixture_tangents(stamps, pars, model, psf, stamp_obj, stamp_band, ngauss):
+    """_stamp_mixtures at pars, and d mix / d pars (nstamps, G, 6, npars) by
+    forward-mode AD in ONE dual pass: the objects repeated npars times, copy k
+    with tangent e_k (every stamp's mixture depends on its own object only)"""
+    import torch.autograd.forward_ad as fwAD
+    torch = _torch()
+    pars = pars.detach()
+    if pars.ndim == 1:
+        pars = pars[None, :]
+    if isinstance(psf, torch.Tensor):
+        psf = psf.detach()
+    base = _stamp_mixtures(stamps, pars, model, psf, stamp_obj, stamp_band, ngauss)
+    _, sobj, mix, _, psf_t = base
+    nobj, npars = pars.shape
+    nst = stamps.n
+    sband = _stamp_layout(nst, nobj, stamp_obj, stamp_band)[1]
+
+    class _Rows(object):
+        n = npars * nst
+        device = stamps.device
+
+    rep = pars.repeat(npars, 1)
+    tan = torch.eye(npars, dtype=pars.dtype, device=pars.device).repeat_interleave(nobj, 0)
+    sobj_rep = (sobj[None, :] + nobj * np.arange(npars)[:, None]).reshape(-1)
+    psf_rep = psf_t.repeat(npars, 1, 1) if psf_t is not None else None
+    with fwAD.dual_level():
+        m = _stamp_mixtures(_Rows(), fwAD.make_dual(rep, tan), model, psf_rep, sobj_rep,
+                            np.tile(sband, npars), ngauss)[2]
+        dm = fwAD.unpack_dual(m).tangent
+    if dm is None:
+        dm = torch.zeros((npars,) + tuple(mix.shape), dtype=torch.float64, device=mix.device)
+    dmix = dm.reshape((npars,) + tuple(mix.shape)).permute(1, 2, 3, 0).contiguous()
+    return base, dmix
+
+
+def fisher(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None, ngauss=None,
+           prior=None, weight=None, fast_exp=True, return_flags=False):
+    """
+    The Fisher (Gauss-Newton) matrix sum_pix w J J^T of every object at pars,
+    J = d model / d pars, summed over the object's stamps in stamp order:
+    what LMBatchFitter inverts for pars_cov0, at any parameters (a torch fit,
+    a forecast at the truth).  Arguments as loglike(); prior: a batch prior or
+    a reference joint prior (as lnprob), whose rows' J^T J by the reference's
+    differences (prior_batch.prior_normal_sums) is added, as the fitter adds
+    it; weight / fast_exp as stamp_fisher (a caller weight, e.g. 1 / model
+    for a Poisson fit, must be >= 0).
+
+    Returns (nobj, npars, npars) float64; with return_flags, also (nobj,)
+    int32 flags as loglike's: a flagged object's matrix is NaN, and the others
+    do not depend on it.  No autograd graph: the result is a value, not
+    differentiable with respect to pars or the psf.
+    """
+    from .prior_batch import as_batch_prior, prior_normal_sums
+    torch = _torch()
+    if pars.shape[-1] > FISHER_KMAX:
+        raise ValueError("fisher: at most %d parameters per object, got %d"
+                         % (FISHER_KMAX, pars.shape[-1]))
+    bp = as_batch_prior(prior)
+    (pars, sobj, mix, code, _), dmix = _mixture_tangents(
+        stamps, pars, model, psf, stamp_obj, stamp_band, ngauss)
+    nobj, npars = pars.shape
+    dev = stamps.device
+    F, status = stamp_fisher(stamps, mix, dmix, weight=weight, fast_exp=fast_exp)
+    code = torch.where(code == 0, status, code)
+    rows = _object_rows(sobj, nobj, dev)
+    tot = pars.new_zeros((nobj, npars, npars))
+    F_pad = torch.cat([F, F.new_zeros((1, npars, npars))])
+    for d_idx in rows:
+        tot = tot + F_pad[d_idx]
+    if bp is not None:
+        sums, _ = prior_normal_sums(bp, pars)
+        iu = torch.triu_indices(npars, npars, device=dev)
+        tri = sums[:, :iu.shape[1]]
+        P = pars.new_zeros((nobj, npars, npars))
+        P[:, iu[0], iu[1]] = tri
+        P[:, iu[1], iu[0]] = tri
+        tot = tot + P
+    flag = _first_flag(code, rows, nobj)
+    tot = torch.where((flag != 0)[:, None, None], torch.full_like(tot, math.nan), tot)
+    if return_flags:
+        return tot, flag
+    return tot
+
+
+def covariance(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
+               ngauss=None, prior=None, weight=None, fast_exp=True, return_flags=False):
+    """
+    The inverse of fisher() per object, by a batched Cholesky
+    (torch.linalg.cholesky_ex): LMBatchFitter's pars_cov0 convention, NOT
+    rescaled by chi2 / dof.  Arguments and flags as fisher(); a matrix that is
+    not positive definite gives NaN and flags.LM_SINGULAR_MATRIX.  No autograd
+    graph.
+    """
+    from .flags import LM_SINGULAR_MATRIX
+    torch = _torch()
+    F, flag = fisher(stamps, pars, model, psf=psf, stamp_obj=stamp_obj,
+                     stamp_band=stamp_band, ngauss=ngauss, prior=prior, weight=weight,
+                     fast_exp=fast_exp, return_flags=True)
+    n = F.shape[1]
+    bad = flag != 0
+    eye = torch.eye(n, dtype=F.dtype, device=F.device).expand_as(F)
+    L, info = torch.linalg.cholesky_ex(torch.where(bad[:, None, None], eye, F))
+    sing = (info != 0) & ~bad
+    cov = torch.cholesky_inverse(L)
+    cov = torch.where((bad | sing)[:, None, None], torch.full_like(cov, math.nan), cov)
+    flag = torch.where(sing, torch.full_like(flag, LM_SINGULAR_MATRIX), flag)
+    if return_flags:
+        return cov, flag
+    return cov

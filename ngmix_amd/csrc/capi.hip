@@ -590,6 +590,14 @@ int ngmix_render_vjp_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
                              (hipStream_t)stream);
 }
 
+int ngmix_fisher_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
+                       const double *dgpars, int K, const double *weight, int fast_exp,
+                       double *out, int32_t *status, void *stream)
+{
+    return launch_fisher(batch, gmix, dgpars, K, weight, fast_exp, out, status,
+                         (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)

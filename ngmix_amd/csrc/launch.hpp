@@ -42,6 +42,10 @@ int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double 
 // render_grad.hip
 int launch_render_vjp(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double *gimage,
                       int fast_exp, double *grad, int32_t *status, hipStream_t s);
+// fisher.hip
+int launch_fisher(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double *dgpars,
+                  int K, const double *weight, int fast_exp, double *out, int32_t *status,
+                  hipStream_t s);
 // noisecov.hip
 int launch_noise_cov_blocks(const double *dimg, const int64_t *stamp_idx, int64_t m,
                             const int64_t *pix_off, const double *ierr, const double *noise,
