@@ -632,6 +632,13 @@ class StampBatch(object):
         the kernel writes the model without reading the buffer
         (NGMIX_BATCH_RENDER_OVERWRITE), 8 bytes per pixel instead of a memset
         plus a read-modify-write.  Returns (image, status).
+
+        The fused kernel neither reads nor writes the image lines (16 pixels
+        of one row) that no gaussian's chi2 < 25 box reaches: the model is
+        exactly 0.0 there.  One edge: a pixel holding -0.0 in such a line
+        stays -0.0, where the reference's `image += 0.0` (and no_skip=True)
+        makes it +0.0; the two compare equal and no other value differs in
+        any bit.  A fresh image (image=None) is still written everywhere.
         """
         torch = _torch()
         assert gm.n == self.n

@@ -374,6 +374,43 @@ __device__ __forceinline__ void gload_f64_if(double &dst, const void *base,
         : "scc");
 }
 
+// The render's form: a 64-bit lane mask in place of the all-or-nothing word.
+// The mask is uniform over each image line (16 lanes of a 4x16 tile), so the
+// lanes that stay on still ask for whole 128-byte lines.  Lanes that are off
+// keep what dst held: nothing may consume it.
+__device__ __forceinline__ void gload_f64_lanes(double &dst, const void *base,
+                                                unsigned off, unsigned long long lanes)
+{
+    unsigned long long save;
+    asm volatile(
+        "s_mov_b64 %1, exec\n\t"
+        "s_and_b64 exec, exec, %3\n\t"
+        "global_load_dwordx2 %0, %2, %4\n\t"
+        "s_mov_b64 exec, %1"
+        : "+v"(dst), "=&s"(save)
+        : "v"(off), "s"(lanes), "s"(base)
+        : "scc");
+}
+
+// ... and the store of the same lanes (a vector store under a scalar mask: no
+// per-lane predicate, no branch).  Like the loads it is invisible to the
+// compiler -- no "memory" clobber, which would pin every LDS read of the next
+// tile behind it: the FULL render path has no compiler-made access to the image
+// that could be ordered wrongly against it.
+__device__ __forceinline__ void gstore_f64_lanes(void *base, unsigned off, double v,
+                                                 unsigned long long lanes)
+{
+    unsigned long long save;
+    asm volatile(
+        "s_mov_b64 %0, exec\n\t"
+        "s_and_b64 exec, exec, %3\n\t"
+        "global_store_dwordx2 %1, %2, %4\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(save)
+        : "v"(off), "v"(v), "s"(lanes), "s"(base)
+        : "scc");
+}
+
 // two loads (val and ierr of one tile) under one EXEC toggle
 __device__ __forceinline__ void gload2_f64_if(double &d0, const void *base0, double &d1,
                                               const void *base1, unsigned off,
@@ -409,14 +446,16 @@ __device__ __forceinline__ void wait_vm_all(double &a, double &b, double &c, dou
 
 // The tile loop of one stamp.  FAST = every gaussian of the stamp is positive
 // definite and shares one centre.
-template <int OP, bool MASKED, bool FAST, bool FULL, int TW>
+// SKIP (render into an existing image only): the line skip described below.
+// An overwriting render is instantiated without it and runs the plain loop.
+template <int OP, bool MASKED, bool FAST, bool FULL, int TW, bool SKIP>
 __device__ __forceinline__ void wave_tiles(
     const LdsLayout &L, const GaussFused *gf, const TileBox *gbox, const TileEnt *te,
     int ng,
     const ngmix_stamp &st, const double *__restrict__ sval,
     const double *__restrict__ sierr, bool masked, double *out, int64_t out_base,
     const ngmix_jacobian &jac, double (&pv)[FUSED_PF], double (&pe)[FUSED_PF],
-    double &acc_ll, double &acc_sn, double &acc_sd, const int keep = -1)
+    double &acc_ll, double &acc_sn, double &acc_sd, const int keep, const TileBox &ub)
 {
     constexpr bool kNeedsVal = (OP == OP_LOGLIKE || OP == OP_FDIFF);
     constexpr bool kNeedsIerr = (OP != OP_RENDER_FAST);
@@ -425,12 +464,18 @@ __device__ __forceinline__ void wave_tiles(
     // read (the look-ahead loads are issued with EXEC = 0, their registers stay
     // 0.0); keep == -1 otherwise.  A scalar mask, never a select.
     const bool overwrite = keep == 0;
+    // render, LINE SKIP: where no gaussian's chi2 < 25 box reaches, the model is
+    // exactly 0.0 and image += 0.0 moves 16 bytes per pixel for nothing.  ub is
+    // the union of the very boxes the pair skip uses; an image line (the 16
+    // lanes of one row of a 4x16 tile = 128 bytes) outside it is neither read
+    // nor written.  An overwriting render still writes every pixel.
+    static_assert(!SKIP || OP == OP_RENDER_FAST, "the line skip is the render's");
     const int lane = threadIdx.x;
     const int lrow = lane / TW, lcol = lane % TW;
     const int nrow = st.nrow, ncol = st.ncol;
     const int ntx = (ncol + TW - 1) / TW;
     const int nty = (nrow + TH - 1) / TH;
-    const int ntiles = __builtin_amdgcn_readfirstlane(ntx * nty);
+    int ntiles = __builtin_amdgcn_readfirstlane(ntx * nty);
     // FULL: every tile is complete -- no per-lane bounds tests, and every
     // load / store is unconditional so that the compiler can count them:
     // waiting for tile T's data is then s_waitcnt vmcnt(ops issued since),
@@ -450,6 +495,19 @@ __device__ __forceinline__ void wave_tiles(
     const char *bierr = (const char *)sierr;
     char *bimg = (char *)(out + st.pix_off);   // render: the stamp's image
     char *bfd = (char *)(out + out_base);      // fdiff: the stamp's residuals
+
+    // render, line skip: the bands of TH rows above the first and below the last reached
+    // row are whole runs of tiles at either end of the row-major tile order: the
+    // loop walks tiles [T, ntiles) of the reached bands only
+    int T = 0;
+    if (SKIP) {
+        const int rmin = ub.r_lo, rmax = (int)((unsigned)ub.r_lo + ub.r_span);
+        const int b0 = (rmin > 0 ? rmin : 0) / TH;
+        const int b1 = (rmax < nrow - 1 ? rmax : nrow - 1) / TH;
+        const bool some = rmax >= 0 && b0 <= b1;
+        T = __builtin_amdgcn_readfirstlane(some ? b0 * ntx : 0);
+        ntiles = __builtin_amdgcn_readfirstlane(some ? (b1 + 1) * ntx : 0);
+    }
 
     // (tile, gaussian) box tests, CH tiles per ballot: lane = k*ng + g holds
     // gaussian g's box and tests it against tile T + k
@@ -471,7 +529,8 @@ __device__ __forceinline__ void wave_tiles(
 
     // issue the loads of tile Tn (a sentinel past the last tile loads
     // nothing); lanes outside the stamp carry val = ierr = 0
-    auto prefetch = [&](int Tn, bool &inb_n, double &nval, double &nierr) {
+    auto prefetch = [&](int Tn, bool &inb_n, unsigned long long &rm_n, double &nval,
+                        double &nierr) {
         if (full) {
             inb_n = true;
             // past the last tile: issued with EXEC = 0 (te[] has sentinels)
@@ -484,11 +543,31 @@ __device__ __forceinline__ void wave_tiles(
             } else {
                 if (kNeedsVal) gload_f64_if(nval, bval, off2, on);
                 if (kNeedsIerr) gload_f64_if(nierr, bierr, off2, on);
-                if (OP == OP_RENDER_FAST) gload_f64_if(nval, bimg, off2, on & keep);
+                if (OP == OP_RENDER_FAST && !SKIP)
+                    gload_f64_if(nval, bimg, off2, on & keep);
+                if (SKIP) {
+                    // the load is issued on every path (the waits count it); only
+                    // the reached lines of a tile inside the stamp ask for memory.
+                    // Lanes whose image line (row r0 + lrow, columns c0 .. c0 + TW
+                    // - 1) the union box reaches: the compares of tile_hits, the
+                    // box in scalar registers.  EXEC must be the whole wave here
+                    // (prefetch is only called at wave-uniform points).
+                    unsigned long long mr, mc;
+                    asm("v_cmp_le_u32 %0, %1, %2"
+                        : "=s"(mr)
+                        : "v"((unsigned)(te[Tn].r0 + lrow - ub.r_lo)), "s"(ub.r_span));
+                    asm("v_cmp_le_u32 %0, %1, %2"
+                        : "=s"(mc) : "v"((unsigned)(te[Tn].c0 - ub.c_lo)), "s"(ub.c_span));
+                    rm_n = mr & mc;   // the lanes compute() stores
+                    gload_f64_lanes(nval, bimg, off2, rm_n & (unsigned long long)(long long)on);
+                }
             }
         } else {
             const int r0n = te[Tn].r0, c0n = te[Tn].c0;
             inb_n = (r0n < rlim) & (c0n < clim);
+            if (SKIP)
+                inb_n &= ((unsigned)(r0n + lrow - ub.r_lo) <= ub.r_span) &
+                         ((unsigned)(c0n - ub.c_lo) <= ub.c_span);
             nval = 0.0;
             nierr = 0.0;
             if (inb_n) {
@@ -503,7 +582,8 @@ __device__ __forceinline__ void wave_tiles(
     // one tile: evaluate the gaussians that can reach it, accumulate / store
     constexpr int kLoadsPerTile = (kNeedsVal ? 1 : 0) + (kNeedsIerr ? 1 : 0) +
                                   (OP == OP_RENDER_FAST ? 1 : 0);
-    auto compute = [&](auto nyounger, int Tc, bool inb, double &pval, double &pierr) {
+    auto compute = [&](auto nyounger, int Tc, bool inb, unsigned long long rm, double &pval,
+                       double &pierr) {
         const double v = te[Tc].bv + olv, u = te[Tc].bu + olu;
         double dv = v, du = u;
         double v2 = dv * dv, u2 = du * du, vu = dv * du;
@@ -515,7 +595,8 @@ __device__ __forceinline__ void wave_tiles(
                 if (kc == 0) {
                     int Tk;  // = Tc + k_l; asm so that it is not hoisted out
                     asm volatile("v_add_u32 %0, %1, %2" : "=v"(Tk) : "s"(Tc), "v"(k_l));
-                    if (Tk > ntiles) Tk = ntiles;  // a sentinel
+                    if (Tk > ntiles) Tk = ntiles;  // a sentinel (SKIP: or a tile past the last
+                                                   // walked band; its slots are never consumed)
                     const int r0k = te[Tk].r0, c0k = te[Tk].c0;
                     const TileBox mybox = *mybox_p;
                     allmask = tile_hits(mybox, r0k, c0k) & valid_mask;
@@ -595,7 +676,16 @@ __device__ __forceinline__ void wave_tiles(
         } else if (full || inb) {
             const unsigned off = lane_off + (unsigned)te[Tc].off;
             if (OP == OP_RENDER_FAST) {
-                *(double *)(bimg + off) = pval + model;
+                // (the lanes left out hold model == 0.0: a pixel outside every
+                // gaussian's box fails the chi2 < 25 gate of every evaluation.)
+                // One path uses ONE form of store: the masked store is invisible
+                // to the compiler, so a path that used it must make no compiler-
+                // visible access to the image -- FULL && SKIP has none (asm loads,
+                // asm stores); every other path uses plain loads and stores only.
+                if (full && SKIP)
+                    gstore_f64_lanes(bimg, off, pval + model, rm);
+                else
+                    *(double *)(bimg + off) = pval + model;
             } else if (!MASKED || !masked) {
                 *(double *)(bfd + off) = (model - pval) * pierr;
             } else if (pierr > 0.0) {
@@ -611,19 +701,22 @@ __device__ __forceinline__ void wave_tiles(
     // halves had left L2 and were fetched from HBM again), so 2-3 tiles are
     // always in flight behind the one being evaluated.  The sets rotate by
     // unrolling, not by copying.  (FULL stamps: the first four tiles were
-    // requested by the kernel before the gaussians were staged.)
+    // requested by the kernel before the gaussians were staged -- except the
+    // render's, see below.)
     static_assert(FUSED_PF == 4, "the rotation below is written for four register sets");
     using Y3 = std::integral_constant<int, 3>;
     using Y2 = std::integral_constant<int, 2>;
-    int T = 0;
     bool in0 = true, in1 = true, in2 = true, in3 = true;
     double va0 = pv[0], va1 = pv[1], va2 = pv[2], va3 = pv[3];
     double ie0 = pe[0], ie1 = pe[1], ie2 = pe[2], ie3 = pe[3];
-    if (!full) {
-        prefetch(0, in0, va0, ie0);
-        prefetch(1, in1, va1, ie1);
-        prefetch(2, in2, va2, ie2);
-        prefetch(3, in3, va3, ie3);
+    unsigned long long rm0 = ~0ull, rm1 = ~0ull, rm2 = ~0ull, rm3 = ~0ull;
+    // (render: the first four tiles are requested here as well, FULL or not --
+    // which of their lines to ask for is known only once the boxes are staged)
+    if (!full || SKIP) {
+        prefetch(T, in0, rm0, va0, ie0);
+        prefetch(T + 1, in1, rm1, va1, ie1);
+        prefetch(T + 2, in2, rm2, va2, ie2);
+        prefetch(T + 3, in3, rm3, va3, ie3);
     }
     // No exit from the middle of a group of four: the tiles past the last one
     // are SKIPPED (forward branches) while their look-ahead loads are still
@@ -634,14 +727,14 @@ __device__ __forceinline__ void wave_tiles(
     // routed the exits back through the loop header, where no static count
     // holds).
     while (T < ntiles) {
-        compute(Y3{}, T, in0, va0, ie0);
-        if (T + 1 < ntiles) compute(Y2{}, T + 1, in1, va1, ie1);
-        prefetch(T + 4, in0, va0, ie0);
-        prefetch(T + 5, in1, va1, ie1);
-        if (T + 2 < ntiles) compute(Y3{}, T + 2, in2, va2, ie2);
-        if (T + 3 < ntiles) compute(Y2{}, T + 3, in3, va3, ie3);
-        prefetch(T + 6, in2, va2, ie2);
-        prefetch(T + 7, in3, va3, ie3);
+        compute(Y3{}, T, in0, rm0, va0, ie0);
+        if (T + 1 < ntiles) compute(Y2{}, T + 1, in1, rm1, va1, ie1);
+        prefetch(T + 4, in0, rm0, va0, ie0);
+        prefetch(T + 5, in1, rm1, va1, ie1);
+        if (T + 2 < ntiles) compute(Y3{}, T + 2, in2, rm2, va2, ie2);
+        if (T + 3 < ntiles) compute(Y2{}, T + 3, in3, rm3, va3, ie3);
+        prefetch(T + 6, in2, rm2, va2, ie2);
+        prefetch(T + 7, in3, rm3, va3, ie3);
         T += 4;
     }
     // every look-ahead load has landed from here on (those past the last tile
@@ -649,7 +742,12 @@ __device__ __forceinline__ void wave_tiles(
     if (full) wait_vm_all(va0, ie0, va1, ie1, va2, ie2, va3, ie3);
 }
 
-template <int OP, bool MASKED, int TW>
+// LS (render only): the kernel with the line skip, launched for renders into an
+// existing image.  An overwriting render (NGMIX_BATCH_RENDER_OVERWRITE) writes
+// every pixel and is launched as the LS = false kernel: the plain loop, the
+// early request, no union of the boxes -- the launcher picks by that flag, and
+// the LS kernel does not look at it.
+template <int OP, bool MASKED, int TW, bool LS = (OP == OP_RENDER_FAST)>
 __device__ __forceinline__ void pixpass_wave_body(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
@@ -700,11 +798,20 @@ __device__ __forceinline__ void pixpass_wave_body(
         e.pad = 0;
         te[T] = e;
     }
+    // render: the union of the stamp's chi2 < 25 boxes, reduced with LDS min / max
+    // while the gaussians are staged (the reduce scratch is otherwise unused here)
+    int *ubx = (int *)L.red;
+    if (LS && lane == 0) {
+        ubx[0] = 1 << 30;      // rmin
+        ubx[1] = -(1 << 30);   // rmax
+        ubx[2] = 1 << 30;      // cmin
+        ubx[3] = -(1 << 30);   // cmax
+    }
     __syncthreads();  // one wave: orders the LDS writes above, no s_barrier
 
     // 0 when an overwriting render must not read the image, else -1 (integer
     // arithmetic on the kernel argument: stays on the scalar unit)
-    const int keep = (OP == OP_RENDER_FAST) ? (((no_skip >> 2) & 1) - 1) : -1;
+    const int keep = (OP == OP_RENDER_FAST && !LS) ? (((no_skip >> 2) & 1) - 1) : -1;
     // ---- request the first tiles now: they fly while the gaussians are staged
     // (no_skip bit 1 = NGMIX_BATCH_TRACKED_LOADS: the compiler-tracked path)
     const bool full = (nrow % TH) == 0 && (ncol % TW) == 0 && !(no_skip & 2);
@@ -714,7 +821,12 @@ __device__ __forceinline__ void pixpass_wave_body(
         pv[t] = 0.0;
         pe[t] = 0.0;
     }
-    if (full && ng > 0 && ntiles > 0) {
+    // (not the line-skipping render's: it asks only for the lines that the union
+    // of the boxes reaches, which exists after stage 2; wave_tiles requests them.
+    // An overwriting render issues them here with EXEC = 0.  Keeping this
+    // early request unmasked would read the stamp's first four tiles, rows 0-4,
+    // which are the lines most often out of reach)
+    if (full && ng > 0 && ntiles > 0 && !LS) {
         const unsigned lane_off = (unsigned)((lane / TW) * ncol + lane % TW) * 8u;
 #pragma unroll
         for (int t = 0; t < FUSED_PF; t++) {
@@ -728,7 +840,7 @@ __device__ __forceinline__ void pixpass_wave_body(
     }
 
     // ---- stage 2: norms (lazily, as the reference) and gaussian records
-    const bool overwrite = OP == OP_RENDER_FAST && (no_skip & 4);
+    const bool overwrite = OP == OP_RENDER_FAST && !LS && (no_skip & 4);
     const int stcode = lazy_norms<WAVE>(L, gm, ng);
     if (stcode != NGMIX_OK || (overwrite && ng == 0)) {
         // the look-ahead registers are dead on this path and the compiler may
@@ -759,6 +871,13 @@ __device__ __forceinline__ void pixpass_wave_body(
         const TileBox tb = tile_box(pb, TH, TW);
         gbox[g] = tb;
         gf[g] = r;
+        if (LS && pb.rmin <= pb.rmax && pb.cmin <= pb.cmax) {
+            // (a box that holds no pixel adds nothing; full_box() makes it full)
+            atomicMin(&ubx[0], pb.rmin);
+            atomicMax(&ubx[1], pb.rmax);
+            atomicMin(&ubx[2], pb.cmin);
+            atomicMax(&ubx[3], pb.cmax);
+        }
         if (!(t.row == row0 && t.col == col0)) L.ctl[2] = 0;
         const double detq = t.dcc * t.drr - t.drc * t.drc;
         if (!(t.dcc > 0.0 && t.drr > 0.0 && detq > 0.0)) L.ctl[3] = 0;
@@ -770,28 +889,41 @@ __device__ __forceinline__ void pixpass_wave_body(
     // below copies them into the loop's register sets (tools/isa_hazards.py)
     wait_vm_all(pv[0], pe[0], pv[1], pe[1], pv[2], pe[2], pv[3], pe[3]);
     const bool fast = L.ctl[2] != 0 && L.ctl[3] != 0;
+    // the union as a line test reads it (tile_box with one-row tiles; an empty
+    // union becomes the box no line reaches), in scalar registers
+    TileBox ub = {0, 0u, 0, 0u};
+    if (LS) {
+        PixBox un;
+        un.rmin = ubx[0];
+        un.rmax = ubx[1];
+        un.cmin = ubx[2];
+        un.cmax = ubx[3];
+        const TileBox t = tile_box(un, 1, TW);
+        ub.r_lo = __builtin_amdgcn_readfirstlane(t.r_lo);
+        ub.r_span = (unsigned)__builtin_amdgcn_readfirstlane((int)t.r_span);
+        ub.c_lo = __builtin_amdgcn_readfirstlane(t.c_lo);
+        ub.c_span = (unsigned)__builtin_amdgcn_readfirstlane((int)t.c_span);
+    }
     const bool masked = MASKED && izw && st.npix_kept != npix;
     if (OP == OP_FDIFF && masked) build_rank_tables<WAVE>(L.cmask, L.cpre, sierr, npix);
     const int64_t out_base = (OP == OP_FDIFF) ? out_start[s] : 0;
 
     double acc_ll = 0.0, acc_sn = 0.0, acc_sd = 0.0;
     if (ng > 0) {
+        // (render: the line skip when the image is accumulated into; an
+        // overwriting render writes every pixel and runs the plain loop)
         if (fast && full)
-            wave_tiles<OP, MASKED, true, true, TW>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                                               out, out_base, jac, pv, pe, acc_ll,
-                                               acc_sn, acc_sd, keep);
+            wave_tiles<OP, MASKED, true, true, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
         else if (fast)
-            wave_tiles<OP, MASKED, true, false, TW>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                                                out, out_base, jac, pv, pe, acc_ll,
-                                                acc_sn, acc_sd, keep);
+            wave_tiles<OP, MASKED, true, false, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
         else if (full)
-            wave_tiles<OP, MASKED, false, true, TW>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                                                out, out_base, jac, pv, pe, acc_ll,
-                                                acc_sn, acc_sd, keep);
+            wave_tiles<OP, MASKED, false, true, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
         else
-            wave_tiles<OP, MASKED, false, false, TW>(L, gf, gbox, te, ng, st, sval, sierr,
-                                                 masked, out, out_base, jac, pv, pe,
-                                                 acc_ll, acc_sn, acc_sd, keep);
+            wave_tiles<OP, MASKED, false, false, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
     } else if (OP != OP_RENDER_FAST) {
         // an empty mixture: model == 0 everywhere
         for (int p = lane; p < npix; p += WAVE) {
@@ -847,6 +979,18 @@ __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel(
 {
     pixpass_wave_body<OP, MASKED, TW>(stamps, val, ierr, jacs, gmix, out, out_start, status,
                                       max_ngauss, nchunks_cap, no_skip, tile_cap);
+}
+
+// the render that overwrites (writes every pixel, reads none): no line skip
+template <int OP, bool MASKED, int TW>
+__global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_plain(
+    const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
+    const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
+    ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+{
+    pixpass_wave_body<OP, MASKED, TW, false>(stamps, val, ierr, jacs, gmix, out, out_start,
+                                             status, max_ngauss, nchunks_cap, no_skip, tile_cap);
 }
 
 // get_loglike at seven waves per SIMD: its body fits 72 VGPRs without spilling
@@ -934,6 +1078,8 @@ static int launch_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
     const bool mk = b->any_masked && FOP != OP_RENDER_FAST;
     const void *kern = mk ? (const void *)pixpass_wave_kernel<FOP, true, TW>
                           : (const void *)pixpass_wave_kernel<FOP, false, TW>;
+    if (FOP == OP_RENDER_FAST && (no_skip & 4))
+        kern = (const void *)pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16>;
     static const bool six_waves = getenv("NGMIX_LOGLIKE_6WAVES") != nullptr;   // A/B knob
     if (FOP == OP_LOGLIKE && !six_waves)
         kern = mk ? (const void *)pixpass_wave_kernel7<OP_LOGLIKE, true, 8>

@@ -1,6 +1,8 @@
 """the fused loglike / render kernels with every (tile, gaussian) pair skipped
 (mixtures centred far outside the stamps): what the kernel's own load / store
-structure sustains when instruction issue is out of the way.
+structure sustains when instruction issue is out of the way.  (Loglike only:
+the render skips the image lines that no gaussian reaches, so this leg of it
+moves nothing and its figure is printed as void.)
 python tools/memory_only.py [nstamps]"""
 import os
 import sys
@@ -42,5 +44,12 @@ def timeit(fn, reps=200):
 for name, g in (("real mixtures", gm), ("all pairs skipped", gfar)):
     tl = timeit(lambda: sb.loglike(g, out=out, status=status))
     tr = timeit(lambda: sb.render(g, image=img, status=status))
-    print("%-18s loglike %.4f ms (%.2f TB/s)   render %.4f ms (%.2f TB/s)" % (
+    if g is gfar:
+        # the render leaves the lines no gaussian's box reaches unread and unwritten:
+        # with the mixtures outside the stamps it moves no image byte at all, so its
+        # time here is the kernel's prologue and no memory floor
+        print("%-18s loglike %.4f ms (%.2f TB/s)   render %.4f ms (void: no image line is "
+              "reached, nothing is moved)" % (name, tl, bench.LOGLIKE_BYTES * n / tl / 1e9, tr))
+        continue
+    print("%-18s loglike %.4f ms (%.2f TB/s)   render %.4f ms (%.2f TB/s of algorithmic bytes)" % (
         name, tl, bench.LOGLIKE_BYTES * n / tl / 1e9, tr, bench.RENDER_BYTES * n / tr / 1e9))
