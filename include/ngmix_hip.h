@@ -273,6 +273,14 @@ int ngmix_deriv_images(const double *gpars, const double *dcov, int64_t ngauss,
  * ====================================================================== */
 
 #define NGMIX_STAMP_IGNORE_ZERO_WEIGHT 1
+/* every one of the stamp's nrow*ncol ierr values has the bit pattern of the
+   first, ierr[pix_off], and that value is finite and > 0 (so the stamp is not
+   masked).  A fact about the data, never a promise: only
+   ngmix_count_kept_batch sets it, from the ierr array it is given, and clears
+   it otherwise; a table built without that pass leaves it clear.  The fused
+   loglike / fdiff / s2n kernels take ierr[pix_off] for every pixel of such a
+   stamp instead of streaming its weight map (same arithmetic, same bits). */
+#define NGMIX_STAMP_UNIFORM_IERR 2
 
 typedef struct {
     int64_t pix_off; /* first pixel of the stamp in val/ierr/image arrays */
@@ -300,6 +308,14 @@ typedef struct {
  * image costs 8 written bytes per pixel instead of a memset plus a
  * read-modify-write; stamps that fail (and empty mixtures) are zero-filled */
 #define NGMIX_BATCH_RENDER_OVERWRITE 8
+/* fused pixel-pass kernels: read the weight map of every stamp, also of those
+ * flagged NGMIX_STAMP_UNIFORM_IERR (bit-identical results; the A/B lever and
+ * the reference of the tests of that path).  The launch then goes to kernels
+ * instantiated without that path, so whoever builds a batch in which NO stamp
+ * is flagged sets it too.  ngmix_batch_upload does, and it REWRITES the bit on
+ * every upload -- set when no stamp of the upload is flagged, cleared when one
+ * is -- so a caller who wants the diagnostic sets it AFTER the upload */
+#define NGMIX_BATCH_STREAM_IERR 16
 
 /* A batch of stamps: HOST struct holding DEVICE pointers plus the few host
    facts a launch needs (LDS sizing, tile schedule). */
@@ -326,7 +342,10 @@ typedef struct {
    or NULL for unit weights) hold the stamps back to back, row-major; `jac` one
    record per stamp; ierr = sqrt(max(weight,0)) and the kept-pixel counts are
    computed on the device; a stamp without any positive weight is
-   NGMIX_ERR_BAD_ARG (the reference's GMixFatalError).  The returned pointer
+   NGMIX_ERR_BAD_ARG (the reference's GMixFatalError).  The same pass sets
+   NGMIX_STAMP_UNIFORM_IERR per stamp, and upload rewrites the batch's
+   NGMIX_BATCH_STREAM_IERR bit from it (set: no stamp flagged; a value the
+   caller put there before the upload is lost).  The returned pointer
    is what the *_batch entry points take; release it with ngmix_batch_free. */
 int ngmix_batch_create(ngmix_batch **out, int64_t nstamps, const int32_t *nrow,
                        const int32_t *ncol, int32_t ngauss, int ignore_zero_weight);
@@ -375,7 +394,8 @@ int ngmix_weight_to_ierr_batch(const double *weight, double *ierr, int64_t n,
                                void *stream);
 /* count kept pixels per stamp into stamps[i].npix_kept (pixels.py:33-37);
    a stamp with no positive weight gets npix_kept = 0 (the host raises
-   GMixFatalError("no weights > 0") from that) */
+   GMixFatalError("no weights > 0") from that).  The same pass sets or clears
+   NGMIX_STAMP_UNIFORM_IERR in stamps[i].flags */
 int ngmix_count_kept_batch(ngmix_stamp *stamps, int64_t nstamps,
                            const double *ierr, void *stream);
 

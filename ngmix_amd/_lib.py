@@ -39,10 +39,12 @@ _RANGE_MESSAGES = {
 }
 
 STAMP_IGNORE_ZERO_WEIGHT = 1
+STAMP_UNIFORM_IERR = 2
 BATCH_NO_SKIP = 1
 BATCH_EXACT = 2
 BATCH_TRACKED_LOADS = 4
 BATCH_RENDER_OVERWRITE = 8
+BATCH_STREAM_IERR = 16
 
 # ---- record layouts = the reference's numpy dtypes ----
 GAUSS2D_DTYPE = np.dtype([

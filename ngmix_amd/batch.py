@@ -195,6 +195,31 @@ class GMixBatch(object):
         return GMixBatch(rows.reshape(-1, 13).contiguous(), idx.numel(), self.ngauss)
 
 
+def _uniform_weights(w):
+    """
+    per row of the host weights w (n, npix): does ierr = sqrt(max(w, 0)) come
+    out as ONE finite value > 0 with one bit pattern?  True only where every
+    weight has the bit pattern of the first and that weight is finite and > 0
+    (equal bits in, equal bits out of the element-wise sqrt) -- what
+    ngmix_count_kept_batch would find on the device, established here from the
+    weights the caller counts npix_kept from.
+    """
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    n = w.shape[0]
+    if w.shape[1] == 0:
+        return np.zeros(n, dtype=bool)
+    bits = w.view(np.int64)
+    first = w[:, 0]
+    with np.errstate(invalid="ignore"):
+        ok = (first > 0.0) & np.isfinite(first)
+    # in chunks of rows: the comparison's temporary stays a few MB whatever n
+    step = max(1, (1 << 22) // w.shape[1])
+    for a in range(0, n, step):
+        blk = bits[a:a + step]
+        ok[a:a + step] &= np.all(blk == blk[:, :1], axis=1)
+    return ok
+
+
 class StampBatch(object):
     """
     N stamps resident in HBM.
@@ -205,10 +230,21 @@ class StampBatch(object):
 
     The reference's pixel list (Observation.pixels) is implicit: the k-th
     pixel with weight > 0 in row-major order (pixels_nb.py:33-38).
+
+    Two properties of the weight maps are computed ONCE, at construction, by a
+    pass over ierr on the device: npix_kept, and the STAMP_UNIFORM_IERR bit of
+    flags -- set for a stamp whose nrow*ncol ierr values all have the bit
+    pattern of the first, that value being finite and > 0.  The fused loglike /
+    fill_fdiff / model_s2n_sum kernels read ierr[pix_off] once for such a stamp
+    instead of its weight map (same results, bit for bit).  A builder that
+    counts npix_kept from host weights sets the bit from those same weights.
+    Whoever changes ierr IN PLACE afterwards calls rescan_weights().
+    stream_ierr = True makes the kernels read every weight map as if no stamp
+    were flagged (a diagnostic: the A/B lever of that path).
     """
 
     def __init__(self, val, ierr, jac, nrow, ncol, pix_off, ignore_zero_weight,
-                 npix_kept=None):
+                 npix_kept=None, uniform_ierr=None):
         torch = _torch()
         self.val = val
         self.ierr = ierr
@@ -223,6 +259,8 @@ class StampBatch(object):
         self.npix = self.nrow.astype(np.int64) * self.ncol
         # diagnostic: fused kernels through the compiler-tracked load path
         self.tracked_loads = False
+        # diagnostic: stream ierr also for the stamps flagged STAMP_UNIFORM_IERR
+        self.stream_ierr = False
         self.max_npix = int(self.npix.max()) if self.n else 0
         self.total_pix = int(self.npix.sum())
         self._stamp_tables = {}
@@ -231,7 +269,25 @@ class StampBatch(object):
         if npix_kept is not None:
             # (counted by the caller from the host weights: no kernel, no read-back)
             self.npix_kept = np.ascontiguousarray(npix_kept, dtype=np.int32)
-        elif ierr is not None and self.n:
+            # (uniform_ierr: found by the caller from the same host weights;
+            # without it the bit stays clear and every weight map is streamed)
+            if uniform_ierr is not None:
+                self.flags |= np.where(np.asarray(uniform_ierr, dtype=bool),
+                                       _lib.STAMP_UNIFORM_IERR, 0).astype(np.int32)
+            self.any_masked = bool(np.any(self.npix_kept != self.npix))
+            self.any_uniform = bool(np.any(self.flags & _lib.STAMP_UNIFORM_IERR))
+        else:
+            self.rescan_weights()
+
+    def rescan_weights(self):
+        """
+        recompute npix_kept and the STAMP_UNIFORM_IERR bits from ierr as it is
+        now (one pass on the device and one read-back): for a caller that has
+        modified ierr in place.  Cached stamp tables are dropped.
+        """
+        self.flags = self.flags & ~np.int32(_lib.STAMP_UNIFORM_IERR)
+        self.npix_kept = self.npix.astype(np.int32).copy()
+        if self.ierr is not None and self.n:
             tab = self._make_table(self.npix_kept, 0, 0)
             with _on_device(self.device):
                 st = _lib.lib().ngmix_count_kept_batch(
@@ -239,7 +295,12 @@ class StampBatch(object):
             _lib.check(st, "ngmix_count_kept_batch")
             host = tab.cpu().numpy().reshape(-1).view(_lib.STAMP_DTYPE)
             self.npix_kept = host["npix_kept"].copy()
+            self.flags = host["flags"].copy()
         self.any_masked = bool(np.any(self.npix_kept != self.npix))
+        # (a batch without a flagged stamp is launched as the kernels that carry
+        # nothing of the uniform path: BATCH_STREAM_IERR)
+        self.any_uniform = bool(np.any(self.flags & _lib.STAMP_UNIFORM_IERR))
+        self._stamp_tables = {}
 
     # ------------------------------------------------------------ builders
     @classmethod
@@ -319,12 +380,14 @@ class StampBatch(object):
         n = len(imgs)
         host = np.empty(2 * tot + 8 * n + 4 * n)      # ... | stamp table (32 B records)
         kept = np.empty(n, dtype=np.int32)
+        uniform = np.empty(n, dtype=bool)
         for i in range(n):
             a, b = int(off[i]), int(off[i] + npix[i])
             host[a:b] = np.asarray(imgs[i], dtype="f8").ravel()
             w = np.asarray(weights[i], dtype="f8").ravel()
             host[tot + a:tot + b] = w
             kept[i] = np.count_nonzero(w > 0.0) if izw[i] else npix[i]
+            uniform[i] = _uniform_weights(w[None])[0]
             host[2 * tot + 8 * i:2 * tot + 8 * i + 8] = \
                 np.ascontiguousarray(jac_records[i]).view(np.float64).reshape(8)
         # (the stamp table of one-gaussian-per-stamp mixtures -- what the lock-step
@@ -333,7 +396,8 @@ class StampBatch(object):
         tab["pix_off"], tab["nrow"], tab["ncol"] = off, nrow, ncol
         tab["gm_off"] = np.arange(n, dtype=np.int32)
         tab["ngauss"] = 1
-        tab["flags"] = np.where(izw, _lib.STAMP_IGNORE_ZERO_WEIGHT, 0)
+        tab["flags"] = np.where(izw, _lib.STAMP_IGNORE_ZERO_WEIGHT, 0) | \
+            np.where(uniform, _lib.STAMP_UNIFORM_IERR, 0)
         tab["npix_kept"] = kept
         host[2 * tot + 8 * n:] = tab.view(np.float64)
         dev_all = torch.from_numpy(host).to(dev)
@@ -348,7 +412,8 @@ class StampBatch(object):
             st = _lib.lib().ngmix_weight_to_ierr_batch(
                 _dptr(dw), _dptr(dw), dw.numel(), _stream())
         _lib.check(st, "ngmix_weight_to_ierr_batch")
-        sb = cls(dval, dw, djac, nrow, ncol, off, izw, npix_kept=kept)
+        sb = cls(dval, dw, djac, nrow, ncol, off, izw, npix_kept=kept,
+                 uniform_ierr=uniform)
         sb._stamp_tables[1] = dtab
         return sb
 
@@ -413,12 +478,14 @@ class StampBatch(object):
         izw = np.broadcast_to(np.asarray(ignore_zero_weight, dtype=bool), (n,))
         kept = np.where(izw, np.count_nonzero(weights.reshape(n, -1) > 0.0, axis=1),
                         npix).astype(np.int32)
+        uniform = _uniform_weights(weights.reshape(n, -1))
         off = np.arange(n, dtype=np.int64) * npix
         tab = np.zeros(n, dtype=_lib.STAMP_DTYPE)
         tab["pix_off"], tab["nrow"], tab["ncol"] = off, nrow, ncol
         tab["gm_off"] = np.arange(n, dtype=np.int32)
         tab["ngauss"] = 1
-        tab["flags"] = np.where(izw, _lib.STAMP_IGNORE_ZERO_WEIGHT, 0)
+        tab["flags"] = np.where(izw, _lib.STAMP_IGNORE_ZERO_WEIGHT, 0) | \
+            np.where(uniform, _lib.STAMP_UNIFORM_IERR, 0)
         tab["npix_kept"] = kept
         host = np.empty(2 * tot + 8 * n + 4 * n)
         host[:tot] = images.reshape(-1)
@@ -434,7 +501,8 @@ class StampBatch(object):
             st = _lib.lib().ngmix_weight_to_ierr_batch(
                 _dptr(dw), _dptr(dw), dw.numel(), _stream())
         _lib.check(st, "ngmix_weight_to_ierr_batch")
-        sb = cls(dval, dw, djac, np.full(n, nrow), np.full(n, ncol), off, izw, npix_kept=kept)
+        sb = cls(dval, dw, djac, np.full(n, nrow), np.full(n, ncol), off, izw, npix_kept=kept,
+                 uniform_ierr=uniform)
         sb._stamp_tables[1] = dtab
         return sb
 
@@ -528,7 +596,8 @@ class StampBatch(object):
         b.max_ncol = int(self.ncol.max()) if self.n else 0
         b.flags = (_lib.BATCH_NO_SKIP if no_skip else 0) | \
             (_lib.BATCH_EXACT if exact else 0) | \
-            (_lib.BATCH_TRACKED_LOADS if self.tracked_loads else 0)
+            (_lib.BATCH_TRACKED_LOADS if self.tracked_loads else 0) | \
+            (_lib.BATCH_STREAM_IERR if self.stream_ierr or not self.any_uniform else 0)
         return b
 
     def _packed(self):

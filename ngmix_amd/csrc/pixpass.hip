@@ -418,14 +418,37 @@ __device__ __forceinline__ void gload2_f64_if(double &d0, const void *base0, dou
 {
     unsigned long long save;
     asm volatile(
-        "s_mov_b64 %2, exec\n\t"
-        "s_and_b32 exec_lo, exec_lo, %4\n\t"
-        "s_and_b32 exec_hi, exec_hi, %4\n\t"
-        "global_load_dwordx2 %0, %3, %5\n\t"
-        "global_load_dwordx2 %1, %3, %6\n\t"
-        "s_mov_b64 exec, %2"
-        : "+v"(d0), "+v"(d1), "=&s"(save)
-        : "v"(off), "s"(on_mask), "s"(base0), "s"(base1)
+        "s_mov_b64 %[save], exec\n\t"
+        "s_and_b32 exec_lo, exec_lo, %[on]\n\t"
+        "s_and_b32 exec_hi, exec_hi, %[on]\n\t"
+        "global_load_dwordx2 %[d0], %[off], %[b0]\n\t"
+        "global_load_dwordx2 %[d1], %[off], %[b1]\n\t"
+        "s_mov_b64 exec, %[save]"
+        : [d0] "+v"(d0), [d1] "+v"(d1), [save] "=&s"(save)
+        : [off] "v"(off), [on] "s"(on_mask), [b0] "s"(base0), [b1] "s"(base1)
+        : "scc");
+}
+
+// the same two loads; the second is
+// narrowed further by on1_mask (-1 or 0, wave-uniform): a stamp whose weight
+// map is one value issues it with EXEC = 0 whatever the tile
+__device__ __forceinline__ void gload2_f64_if(double &d0, const void *base0, double &d1,
+                                              const void *base1, unsigned off,
+                                              int on_mask, int on1_mask)
+{
+    unsigned long long save;
+    asm volatile(
+        "s_mov_b64 %[save], exec\n\t"
+        "s_and_b32 exec_lo, exec_lo, %[on]\n\t"
+        "s_and_b32 exec_hi, exec_hi, %[on]\n\t"
+        "global_load_dwordx2 %[d0], %[off], %[b0]\n\t"
+        "s_and_b32 exec_lo, exec_lo, %[on1]\n\t"
+        "s_and_b32 exec_hi, exec_hi, %[on1]\n\t"
+        "global_load_dwordx2 %[d1], %[off], %[b1]\n\t"
+        "s_mov_b64 exec, %[save]"
+        : [d0] "+v"(d0), [d1] "+v"(d1), [save] "=&s"(save)
+        : [off] "v"(off), [on] "s"(on_mask), [b0] "s"(base0), [b1] "s"(base1),
+          [on1] "s"(on1_mask)
         : "scc");
 }
 
@@ -448,18 +471,27 @@ __device__ __forceinline__ void wait_vm_all(double &a, double &b, double &c, dou
 // definite and shares one centre.
 // SKIP (render into an existing image only): the line skip described below.
 // An overwriting render is instantiated without it and runs the plain loop.
-template <int OP, bool MASKED, bool FAST, bool FULL, int TW, bool SKIP>
+// UE: the kernel honours NGMIX_STAMP_UNIFORM_IERR (ie_on below); the kernels
+// launched for batches without such a stamp are instantiated without it.
+template <int OP, bool MASKED, bool FAST, bool FULL, int TW, bool SKIP, bool UE>
 __device__ __forceinline__ void wave_tiles(
     const LdsLayout &L, const GaussFused *gf, const TileBox *gbox, const TileEnt *te,
     int ng,
     const ngmix_stamp &st, const double *__restrict__ sval,
     const double *__restrict__ sierr, bool masked, double *out, int64_t out_base,
     const ngmix_jacobian &jac, double (&pv)[FUSED_PF], double (&pe)[FUSED_PF],
-    double &acc_ll, double &acc_sn, double &acc_sd, const int keep, const TileBox &ub)
+    double &acc_ll, double &acc_sn, double &acc_sd, const int keep, const TileBox &ub,
+    const int ie_on)
 {
     constexpr bool kNeedsVal = (OP == OP_LOGLIKE || OP == OP_FDIFF);
     constexpr bool kNeedsIerr = (OP != OP_RENDER_FAST);
     constexpr int TH = WAVE / TW;  // tile = TH rows x TW columns = one wave
+    // ie_on == 0: the stamp's weight map is one value (NGMIX_STAMP_UNIFORM_IERR)
+    // and is not read -- the look-ahead loads of ierr are issued with EXEC = 0,
+    // so that every path still issues the same loads in the same order and the
+    // hand-counted waits hold; their registers keep that value, which the
+    // kernel's early request put into pe[].  ie_on == -1 otherwise.  A scalar
+    // mask like `keep`.
     // keep == 0: render with NGMIX_BATCH_RENDER_OVERWRITE -- the image is not
     // read (the look-ahead loads are issued with EXEC = 0, their registers stay
     // 0.0); keep == -1 otherwise.  A scalar mask, never a select.
@@ -539,10 +571,11 @@ __device__ __forceinline__ void wave_tiles(
                 : "=s"(on) : "s"(Tn), "s"(ntiles) : "scc");
             const unsigned off2 = lane_off + (unsigned)te[Tn].off;
             if (kNeedsVal && kNeedsIerr) {
-                gload2_f64_if(nval, bval, nierr, bierr, off2, on);
+                if (UE) gload2_f64_if(nval, bval, nierr, bierr, off2, on, ie_on);
+                else gload2_f64_if(nval, bval, nierr, bierr, off2, on);
             } else {
                 if (kNeedsVal) gload_f64_if(nval, bval, off2, on);
-                if (kNeedsIerr) gload_f64_if(nierr, bierr, off2, on);
+                if (kNeedsIerr) gload_f64_if(nierr, bierr, off2, on & ie_on);
                 if (OP == OP_RENDER_FAST && !SKIP)
                     gload_f64_if(nval, bimg, off2, on & keep);
                 if (SKIP) {
@@ -573,7 +606,10 @@ __device__ __forceinline__ void wave_tiles(
             if (inb_n) {
                 const unsigned off2 = lane_off + (unsigned)te[Tn].off;
                 if (kNeedsVal) nval = *(const double *)(bval + off2);
-                if (kNeedsIerr) nierr = *(const double *)(bierr + off2);
+                // (a uniform weight map: every lane inside the stamp reads its first
+                // value, one cached 8-byte request per tile; lanes outside the stamp
+                // still carry ierr == 0)
+                if (kNeedsIerr) nierr = *(const double *)(bierr + (off2 & (unsigned)ie_on));
                 if (OP == OP_RENDER_FAST && !overwrite) nval = *(const double *)(bimg + off2);
             }
         }
@@ -747,7 +783,7 @@ __device__ __forceinline__ void wave_tiles(
 // every pixel and is launched as the LS = false kernel: the plain loop, the
 // early request, no union of the boxes -- the launcher picks by that flag, and
 // the LS kernel does not look at it.
-template <int OP, bool MASKED, int TW, bool LS = (OP == OP_RENDER_FAST)>
+template <int OP, bool MASKED, int TW, bool LS = (OP == OP_RENDER_FAST), bool UE = true>
 __device__ __forceinline__ void pixpass_wave_body(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
@@ -772,6 +808,19 @@ __device__ __forceinline__ void pixpass_wave_body(
     constexpr bool kNeedsVal = (OP == OP_LOGLIKE || OP == OP_FDIFF);
     const double area = jac.scale * jac.scale;
     const int lane = threadIdx.x;
+    // A stamp whose weight map is ONE value (NGMIX_STAMP_UNIFORM_IERR, found from
+    // the data by count_kept_kernel): that value is ierr[pix_off], one
+    // address for all lanes, and the map is not streamed -- half of get_loglike's
+    // bytes.  The arithmetic per pixel is what it was, on the same numbers.
+    // ie_on: 0 for such a stamp, else -1 (integer arithmetic on a scalar value, like
+    // `keep` below: a select on a condition that also feeds vector selects would
+    // be made in a VGPR, and the mask has to reach EXEC from an SGPR).
+    // UE = false: the kernels of batches without such a stamp and of
+    // NGMIX_BATCH_STREAM_IERR (the launcher picks them) -- the constant folds
+    // every use away.
+    static_assert(NGMIX_STAMP_UNIFORM_IERR == 2, "the shift below");
+    constexpr bool ue = UE && OP != OP_RENDER_FAST;
+    const int ie_on = ue ? ((__builtin_amdgcn_readfirstlane(st.flags) >> 1) & 1) - 1 : -1;
 
     // ---- stage 1: tile records (need only the stamp shape and jacobian)
     constexpr int TH = WAVE / TW;
@@ -833,7 +882,11 @@ __device__ __forceinline__ void pixpass_wave_body(
             const int on = __builtin_amdgcn_readfirstlane(-(int)(t < ntiles));
             const unsigned off = lane_off + (unsigned)te[t].off;
             if (kNeedsVal) gload_f64_if(pv[t], (const char *)sval, off, on);
-            if (OP != OP_RENDER_FAST) gload_f64_if(pe[t], (const char *)sierr, off, on);
+            // (a uniform weight map: all lanes ask for ierr[pix_off], so that each
+            // of the four register sets holds the stamp's value -- the loop's own
+            // ierr loads are then issued with EXEC = 0 and never replace it)
+            if (OP != OP_RENDER_FAST)
+                gload_f64_if(pe[t], (const char *)sierr, off & (unsigned)ie_on, on);
             if (OP == OP_RENDER_FAST)
                 gload_f64_if(pv[t], (const char *)(out + st.pix_off), off, on & keep);
         }
@@ -913,17 +966,17 @@ __device__ __forceinline__ void pixpass_wave_body(
         // (render: the line skip when the image is accumulated into; an
         // overwriting render writes every pixel and runs the plain loop)
         if (fast && full)
-            wave_tiles<OP, MASKED, true, true, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
+            wave_tiles<OP, MASKED, true, true, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
         else if (fast)
-            wave_tiles<OP, MASKED, true, false, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
+            wave_tiles<OP, MASKED, true, false, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
         else if (full)
-            wave_tiles<OP, MASKED, false, true, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
+            wave_tiles<OP, MASKED, false, true, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
         else
-            wave_tiles<OP, MASKED, false, false, TW, LS>(L, gf, gbox, te, ng, st, sval, sierr, masked,
-                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub);
+            wave_tiles<OP, MASKED, false, false, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+                out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
     } else if (OP != OP_RENDER_FAST) {
         // an empty mixture: model == 0 everywhere
         for (int p = lane; p < npix; p += WAVE) {
@@ -1009,6 +1062,34 @@ void pixpass_wave_kernel7(
                                       max_ngauss, nchunks_cap, no_skip, tile_cap);
 }
 
+// loglike / fdiff / s2n of a batch in which no stamp is flagged
+// NGMIX_STAMP_UNIFORM_IERR (or with NGMIX_BATCH_STREAM_IERR): every weight map
+// is streamed, and the kernel carries nothing of the other path
+template <int OP, bool MASKED, int TW>
+__global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_stream(
+    const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
+    const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
+    ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+{
+    pixpass_wave_body<OP, MASKED, TW, false, false>(stamps, val, ierr, jacs, gmix, out,
+                                                    out_start, status, max_ngauss,
+                                                    nchunks_cap, no_skip, tile_cap);
+}
+
+template <int OP, bool MASKED, int TW>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7)))
+void pixpass_wave_kernel7_stream(
+    const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
+    const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
+    ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+{
+    pixpass_wave_body<OP, MASKED, TW, false, false>(stamps, val, ierr, jacs, gmix, out,
+                                                    out_start, status, max_ngauss,
+                                                    nchunks_cap, no_skip, tile_cap);
+}
+
 // ---------------------------------------------------------------- launchers
 
 // fused kernels keep one 32-byte record per 8x8 tile in LDS; batches with a
@@ -1084,6 +1165,21 @@ static int launch_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
     if (FOP == OP_LOGLIKE && !six_waves)
         kern = mk ? (const void *)pixpass_wave_kernel7<OP_LOGLIKE, true, 8>
                   : (const void *)pixpass_wave_kernel7<OP_LOGLIKE, false, 8>;
+    // no stamp of the batch has a uniform weight map (the caller says so with
+    // NGMIX_BATCH_STREAM_IERR, which is also the diagnostic): the kernels that
+    // stream every map
+    // (the launch census counts them under the names of the kernels they stand
+    // in for: the form of the loop is the same, and what a census asserts is
+    // that no generic kernel served the workload)
+    if constexpr (FOP != OP_RENDER_FAST) {
+        if (b->flags & NGMIX_BATCH_STREAM_IERR) {
+            kern = mk ? (const void *)pixpass_wave_kernel_stream<FOP, true, TW>
+                      : (const void *)pixpass_wave_kernel_stream<FOP, false, TW>;
+            if (FOP == OP_LOGLIKE && !six_waves)
+                kern = mk ? (const void *)pixpass_wave_kernel7_stream<OP_LOGLIKE, true, 8>
+                          : (const void *)pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8>;
+        }
+    }
     const size_t flds = lds_bytes(max_ng, nchunks_cap, a_tc);
     if (flds > 160 * 1024) {
         set_last_error_msg("stamp needs more than 160 KiB of LDS");
@@ -1391,12 +1487,25 @@ __global__ __launch_bounds__(BLOCK) void count_kept_kernel(ngmix_stamp *stamps,
     ngmix_stamp st = stamps[blockIdx.x];
     const int npix = st.nrow * st.ncol;
     const bool izw = (st.flags & NGMIX_STAMP_IGNORE_ZERO_WEIGHT) != 0;
-    double cnt = 0.0;
-    for (int p = threadIdx.x; p < npix; p += BLOCK)
-        if (!izw || ierr[st.pix_off + p] > 0.0) cnt += 1.0;
-    double v[1] = {cnt};
-    block_sum<1>(v, red);
-    if (threadIdx.x == 0) stamps[blockIdx.x].npix_kept = (int)v[0];
+    // the same pass finds out whether the weight map is ONE value: every bit
+    // pattern equal to the first's (so -0.0 / +0.0 and NaNs cannot pass for
+    // each other), and that value finite and > 0
+    const long long first = npix > 0 ? __double_as_longlong(ierr[st.pix_off]) : 0ll;
+    double cnt = 0.0, ndiff = 0.0;
+    for (int p = threadIdx.x; p < npix; p += BLOCK) {
+        const double e = ierr[st.pix_off + p];
+        if (!izw || e > 0.0) cnt += 1.0;
+        if (__double_as_longlong(e) != first) ndiff += 1.0;
+    }
+    double v[2] = {cnt, ndiff};
+    block_sum<2>(v, red);
+    if (threadIdx.x == 0) {
+        const double f = __longlong_as_double(first);
+        const bool uniform = npix > 0 && v[1] == 0.0 && f > 0.0 && f < HUGE_VAL;
+        stamps[blockIdx.x].npix_kept = (int)v[0];
+        stamps[blockIdx.x].flags = (st.flags & ~NGMIX_STAMP_UNIFORM_IERR) |
+                                   (uniform ? NGMIX_STAMP_UNIFORM_IERR : 0);
+    }
 }
 
 // fexp / apod_window / apod_window_deriv over an array: the innermost

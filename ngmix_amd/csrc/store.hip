@@ -193,8 +193,11 @@ int ngmix_batch_upload(ngmix_batch *b, const double *images, const double *weigh
     NGMIX_HIP_CHECK(hipMemcpyAsync(s->d_val, images, pixbytes, hipMemcpyHostToDevice, q));
     NGMIX_HIP_CHECK(hipMemcpyAsync(s->d_jac, jac, n * sizeof(ngmix_jacobian),
                                    hipMemcpyHostToDevice, q));
-    for (size_t i = 0; i < n; i++)
+    for (size_t i = 0; i < n; i++) {
         s->host_stamps[i].npix_kept = s->host_stamps[i].nrow * s->host_stamps[i].ncol;
+        // (a fact about the ierr of THIS upload: the pass below establishes it)
+        s->host_stamps[i].flags &= ~NGMIX_STAMP_UNIFORM_IERR;
+    }
     NGMIX_HIP_CHECK(hipMemcpyAsync(s->d_stamps, s->host_stamps.data(),
                                    n * sizeof(ngmix_stamp), hipMemcpyHostToDevice, q));
     if (weights) {
@@ -212,12 +215,18 @@ int ngmix_batch_upload(ngmix_batch *b, const double *images, const double *weigh
         // unit ierr, filled on the device on the caller's stream
         int st = launch_weight_to_ierr(nullptr, s->d_ierr, s->total_pix, q);
         if (st) return st;
+        // (the same pass over what was written: it flags the uniform weight maps)
+        st = launch_count_kept(s->d_stamps, b->nstamps, s->d_ierr, q);
+        if (st) return st;
+        NGMIX_HIP_CHECK(hipMemcpyAsync(s->host_stamps.data(), s->d_stamps,
+                                       n * sizeof(ngmix_stamp), hipMemcpyDeviceToHost, q));
     }
     NGMIX_HIP_CHECK(hipStreamSynchronize(q));
-    int32_t masked = 0;
+    int32_t masked = 0, uniform = 0;
     for (size_t i = 0; i < n; i++) {
         const ngmix_stamp &st = s->host_stamps[i];
         if (st.npix_kept != st.nrow * st.ncol) masked = 1;
+        if (st.flags & NGMIX_STAMP_UNIFORM_IERR) uniform = 1;
         if ((st.flags & NGMIX_STAMP_IGNORE_ZERO_WEIGHT) && st.npix_kept == 0) {
             // GMixFatalError("no weights > 0") in the reference (pixels.py:35-37)
             set_last_error_msg("ngmix_batch_upload: a stamp has no positive weight");
@@ -225,6 +234,10 @@ int ngmix_batch_upload(ngmix_batch *b, const double *images, const double *weigh
         }
     }
     b->any_masked = masked;
+    // no stamp with a uniform weight map: the kernels that carry nothing of that
+    // path serve the batch (a caller's own NGMIX_BATCH_STREAM_IERR is set after
+    // the upload, like the other diagnostics)
+    b->flags = (b->flags & ~NGMIX_BATCH_STREAM_IERR) | (uniform ? 0 : NGMIX_BATCH_STREAM_IERR);
     return NGMIX_OK;
 }
 
