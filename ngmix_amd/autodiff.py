@@ -263,7 +263,39 @@ def convolve(mix, psf):
     return torch.where(bad[:, None, None], torch.full_like(out, math.nan), out), bad
 
 
-def _make_function():
+def _gauss_records(gpars, with_det):
+    """the kernels' (n * G, 13) gaussian records of gpars (n, G, 6): the six
+    parameters, (with_det) det as the kernels form it, the rest zero"""
+    torch = _torch()
+    g = gpars.detach().reshape(-1, 6)
+    rec = torch.zeros((g.shape[0], 13), dtype=torch.float64, device=g.device)
+    rec[:, :6] = g
+    if with_det:
+        rec[:, 6] = g[:, 3] * g[:, 5] - g[:, 4] * g[:, 4]
+    return rec
+
+
+def _pix_extent(stamps):
+    """the length of a flat pixel array that holds every frame of the batch"""
+    extent = int(stamps.total_pix)
+    if stamps.n:
+        extent = max(extent, int((stamps.pix_off + stamps.npix).max()))
+    return extent
+
+
+def _first_order_only(name):
+    """called by the backward passes.  First derivatives only.  Grad mode is on
+    there exactly when the caller asked for a graph of the gradient
+    (create_graph=True, e.g. a Hessian-vector product): the kernel's
+    second-order terms do not exist, and the rest of the chain would still be
+    differentiable, so the result would be silently wrong -- refuse instead."""
+    if _torch().is_grad_enabled():
+        raise RuntimeError(
+            "autodiff.%s gives first derivatives only: create_graph=True "
+            "(second derivatives through the pixel kernel) is not supported" % name)
+
+
+def _make_functions():
     torch = _torch()
 
     class _LoglikeGrad(torch.autograd.Function):
@@ -275,8 +307,8 @@ def _make_function():
         def forward(ctx, gpars, stamps):
             n, G, _ = gpars.shape
             dev = stamps.device
-            rec = torch.zeros((n * G, 13), dtype=torch.float64, device=dev)
-            rec[:, :6] = gpars.detach().reshape(n * G, 6)
+            # (stamp_loglike_grad does not check gpars' device: copied, as ever)
+            rec = _gauss_records(gpars.to(dev), False)
             out = torch.empty((n, 4), dtype=torch.float64, device=dev)
             grad = torch.empty((n * G, 6), dtype=torch.float64, device=dev)
             status = torch.empty(n, dtype=torch.int32, device=dev)
@@ -292,25 +324,11 @@ def _make_function():
 
         @staticmethod
         def backward(ctx, g_ll, g_out, g_status):
-            # First derivatives only.  Grad mode is on here exactly when the
-            # caller asked for a graph of the gradient (create_graph=True, e.g.
-            # a Hessian-vector product): the kernel's second-order terms do not
-            # exist, and the rest of the chain would still be differentiable,
-            # so the result would be silently wrong -- refuse instead.
-            if torch.is_grad_enabled():
-                raise RuntimeError(
-                    "autodiff.loglike gives first derivatives only: create_graph=True "
-                    "(second derivatives through the pixel kernel) is not supported")
+            _first_order_only("loglike")
             grad, status = ctx.saved_tensors
             ok = (status == 0)[:, None, None]
             grad = torch.where(ok, grad, torch.zeros_like(grad))
             return g_ll[:, None, None] * grad, None
-
-    return _LoglikeGrad
-
-
-def _make_render_function():
-    torch = _torch()
 
     class _RenderVJP(torch.autograd.Function):
         """forward: ngmix_render_batch over the stamps (as StampBatch.render
@@ -321,13 +339,8 @@ def _make_render_function():
         def forward(ctx, gpars, stamps, fast_exp, exact):
             n, G, _ = gpars.shape
             dev = stamps.device
-            rec = torch.zeros((n * G, 13), dtype=torch.float64, device=dev)
-            g = gpars.detach().reshape(n * G, 6)
-            rec[:, :6] = g
-            rec[:, 6] = g[:, 3] * g[:, 5] - g[:, 4] * g[:, 4]   # det, as the kernels form it
-            extent = int(stamps.total_pix)
-            if stamps.n:
-                extent = max(extent, int((stamps.pix_off + stamps.npix).max()))
+            rec = _gauss_records(gpars, True)
+            extent = _pix_extent(stamps)
             packed = stamps._packed()
             if packed:
                 image = torch.empty(extent, dtype=torch.float64, device=dev)
@@ -351,11 +364,7 @@ def _make_render_function():
 
         @staticmethod
         def backward(ctx, g_image, g_status):
-            # first derivatives only (see _LoglikeGrad.backward)
-            if torch.is_grad_enabled():
-                raise RuntimeError(
-                    "autodiff.render gives first derivatives only: create_graph=True "
-                    "(second derivatives through the pixel kernel) is not supported")
+            _first_order_only("render")
             rec, status = ctx.saved_tensors
             n, G = ctx.shape
             stamps = ctx.stamps
@@ -374,27 +383,18 @@ def _make_render_function():
             ok = (status == 0)[:, None, None]
             return torch.where(ok, grad, torch.zeros_like(grad)), None, None, None
 
-    return _RenderVJP
+    return _LoglikeGrad, _RenderVJP
 
 
-_FUNC = None
+_FUNCS = None
 
 
-def _func():
-    global _FUNC
-    if _FUNC is None:
-        _FUNC = _make_function()
-    return _FUNC
-
-
-_RENDER_FUNC = None
-
-
-def _render_func():
-    global _RENDER_FUNC
-    if _RENDER_FUNC is None:
-        _RENDER_FUNC = _make_render_function()
-    return _RENDER_FUNC
+def _functions():
+    """(_LoglikeGrad, _RenderVJP), made at first use: torch is imported lazily"""
+    global _FUNCS
+    if _FUNCS is None:
+        _FUNCS = _make_functions()
+    return _FUNCS
 
 
 def stamp_loglike_grad(stamps, gpars):
@@ -406,7 +406,7 @@ def stamp_loglike_grad(stamps, gpars):
     """
     if gpars.shape[0] != stamps.n:
         raise ValueError("one mixture per stamp: %d != %d" % (gpars.shape[0], stamps.n))
-    return _func().apply(gpars, stamps)
+    return _functions()[0].apply(gpars, stamps)
 
 
 def stamp_render(stamps, gpars, fast_exp=True, exact=False):
@@ -427,7 +427,7 @@ def stamp_render(stamps, gpars, fast_exp=True, exact=False):
         raise ValueError("gpars: at least one gaussian per stamp")
     if gpars.device != stamps.device:
         raise ValueError("gpars must live on the stamps' device (%s)" % stamps.device)
-    return _render_func().apply(gpars, stamps, fast_exp, exact)
+    return _functions()[1].apply(gpars, stamps, fast_exp, exact)
 
 
 def _stamp_layout(nstamps, nobj, stamp_obj, stamp_band):
@@ -516,11 +516,30 @@ def _first_flag(code, rows, nobj):
     return flag
 
 
-def _poison(flag, like):
-    """NaN for a flagged object, else 0: multiplied into a term that is then
-    0 * x for the others, it makes the flagged object's gradients NaN"""
+def _sum_over_stamps(values, rows, tot=None):
+    """tot plus every object's sum of the per-stamp values, added in stamp
+    order (a fixed order: the same bits every time); tot None starts from the
+    first stamp's term, and stays None when there is no stamp at all"""
     torch = _torch()
-    return torch.where(flag != 0, torch.full_like(like, math.nan), torch.zeros_like(like))
+    pad = torch.cat([values, values.new_zeros((1,) + tuple(values.shape[1:]))])
+    for d_idx in rows:
+        tot = pad[d_idx] if tot is None else tot + pad[d_idx]
+    return tot
+
+
+def _poison_term(pars, psf_t, flag, sobj):
+    """what makes a flagged object's gradients NaN: per object (nobj,) NaN *
+    its pars, and per stamp (nstamps,) NaN * its psf rows (None unless the psf
+    requires grad); both are 0 * x for the objects that are not flagged.
+    sobj: device indices"""
+    torch = _torch()
+    zero = pars.new_zeros(pars.shape[0])
+    poison = torch.where(flag != 0, torch.full_like(zero, math.nan), zero)
+    obj_term = (pars * poison[:, None]).sum(dim=1)
+    psf_term = None
+    if psf_t is not None and psf_t.requires_grad:
+        psf_term = (psf_t.reshape(sobj.shape[0], -1) * poison[sobj][:, None]).sum(dim=1)
+    return obj_term, psf_term
 
 
 def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
@@ -546,7 +565,6 @@ def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
     pars, sobj, mix, code, psf_t = _stamp_mixtures(stamps, pars, model, psf, stamp_obj,
                                                    stamp_band, ngauss)
     nobj = pars.shape[0]
-    nst = stamps.n
     dev = stamps.device
     ll, _, status = stamp_loglike_grad(stamps, mix)
     code = torch.where(code == 0, status, code)
@@ -554,26 +572,16 @@ def loglike(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
 
     # fixed-order sum over each object's stamps (stamp order), and its flag
     rows = _object_rows(sobj, nobj, dev)
-    tot = None
-    ll_pad = torch.cat([ll, ll.new_zeros(1)])
-    for d_idx in rows:
-        term = ll_pad[d_idx]
-        tot = term if tot is None else tot + term
+    tot = _sum_over_stamps(ll, rows)
     flag = _first_flag(code, rows, nobj)
     if tot is None:
         tot = pars.new_zeros(nobj)
-    bad_obj = flag != 0
     # a flagged object's value, and its gradient with respect to pars and to
     # the psf rows of its stamps, are NaN: a term that is 0 * x elsewhere
-    poison = _poison(flag, tot)
-    nan_term = (pars * poison[:, None]).sum(dim=1)
-    if psf_t is not None and psf_t.requires_grad:
-        d_sobj = torch.from_numpy(sobj).to(dev)
-        ps = (psf_t.reshape(nst, -1) * poison[d_sobj][:, None]).sum(dim=1)
-        ps_pad = torch.cat([ps, ps.new_zeros(1)])
-        for d_idx in rows:
-            nan_term = nan_term + ps_pad[d_idx]
-    out = torch.where(bad_obj, nan_term, tot)
+    nan_term, psf_term = _poison_term(pars, psf_t, flag, torch.from_numpy(sobj).to(dev))
+    if psf_term is not None:
+        nan_term = _sum_over_stamps(psf_term, rows, nan_term)
+    out = torch.where(flag != 0, nan_term, tot)
     if return_flags:
         return out, flag
     return out
@@ -607,10 +615,10 @@ def render(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None, ngaus
         # the NaN term of each stamp (its object's pars, its own psf rows),
         # put on every pixel of the stamps of flagged objects
         d_sobj = torch.from_numpy(sobj).to(dev)
-        poison = _poison(flag, pars.new_zeros(nobj))
-        term = (pars * poison[:, None]).sum(dim=1)[d_sobj]
-        if psf_t is not None and psf_t.requires_grad:
-            term = term + (psf_t.reshape(nst, -1) * poison[d_sobj][:, None]).sum(dim=1)
+        obj_term, psf_term = _poison_term(pars, psf_t, flag, d_sobj)
+        term = obj_term[d_sobj]
+        if psf_term is not None:
+            term = term + psf_term
         npix = torch.from_numpy(stamps.npix).to(dev)
         start = torch.cumsum(npix, 0) - npix
         pos = torch.repeat_interleave(torch.from_numpy(stamps.pix_off).to(dev) - start, npix) + \
@@ -702,15 +710,12 @@ def stamp_fisher(stamps, gpars, dgpars, weight=None, fast_exp=True):
         if weight.ndim != 1 or weight.device != dev:
             raise ValueError("weight: a flat tensor on the stamps' device, in "
                              "StampBatch.render's layout")
-        extent = int(stamps.total_pix)
-        if stamps.n:
-            extent = max(extent, int((stamps.pix_off + stamps.npix).max()))
+        extent = _pix_extent(stamps)
         if weight.shape[0] < extent:
             raise ValueError("weight: %d pixels, the stamps span %d"
                              % (weight.shape[0], extent))
         wt = weight.detach().to(torch.float64).contiguous()
-    rec = torch.zeros((n * G, 13), dtype=torch.float64, device=dev)
-    rec[:, :6] = gpars.detach().reshape(n * G, 6)
+    rec = _gauss_records(gpars, False)
     dg = dgpars.detach().to(torch.float64).contiguous()
     out = torch.empty((n, K, K), dtype=torch.float64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
@@ -789,10 +794,7 @@ def fisher(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None, ngaus
     F, status = stamp_fisher(stamps, mix, dmix, weight=weight, fast_exp=fast_exp)
     code = torch.where(code == 0, status, code)
     rows = _object_rows(sobj, nobj, dev)
-    tot = pars.new_zeros((nobj, npars, npars))
-    F_pad = torch.cat([F, F.new_zeros((1, npars, npars))])
-    for d_idx in rows:
-        tot = tot + F_pad[d_idx]
+    tot = _sum_over_stamps(F, rows, pars.new_zeros((nobj, npars, npars)))
     if bp is not None:
         sums, _ = prior_normal_sums(bp, pars)
         iu = torch.triu_indices(npars, npars, device=dev)

@@ -32,8 +32,6 @@
 
 namespace ngmix {
 
-__constant__ double c_exp_table_f[16] = NGMIX_EXP_TABLE;
-
 constexpr int FI_JS = 17;   // LDS row stride of X (doubles): 16 columns + 1
 
 template <bool FAST, int KT>
@@ -59,7 +57,7 @@ __global__ __launch_bounds__(WAVE) void fisher_kernel(
     double *sout = out + (int64_t)s * K * K;
     const double *sw_src = weight != nullptr ? weight + st.pix_off : ierr + st.pix_off;
 
-    if (lane < 16) tab[lane] = c_exp_table_f[lane];
+    if (lane < 16) tab[lane] = c_exp_table_grad[lane];
     if (lane == 0) ctl[0] = 1 << 30;   // first gaussian whose norm fails
     // columns KT..16 of X stay 0
     for (int i = lane; i < WAVE * FI_JS; i += WAVE) xbuf[i] = 0.0;
@@ -174,11 +172,6 @@ __global__ __launch_bounds__(WAVE) void fisher_kernel(
     if (lane == 0) status[s] = NGMIX_OK;
 }
 
-size_t fisher_lds_bytes(int max_ngauss)
-{
-    return (size_t)WAVE * FI_JS * 8 + 16 * 8 + (size_t)max_ngauss * sizeof(GradGauss) + 16;
-}
-
 template <bool FAST>
 static void launch_fisher_k(const ngmix_batch *b, const ngmix_gauss2d *gmix,
                             const double *dgpars, int K, const double *weight, double *out,
@@ -214,12 +207,10 @@ int launch_fisher(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double 
         set_last_error_msg("fisher: the batch needs ierr when no weight is given");
         return NGMIX_ERR_BAD_ARG;
     }
-    const int max_ng = b->max_ngauss > 0 ? b->max_ngauss : 1;
-    const size_t lds = fisher_lds_bytes(max_ng);
-    if (lds > 64 * 1024) {
-        set_last_error_msg("fisher: too many gaussians for the LDS budget");
+    int max_ng;
+    size_t lds;
+    if (!grad_launch_sizes(b, "fisher", false, (size_t)WAVE * FI_JS * 8, max_ng, lds))
         return NGMIX_ERR_BAD_ARG;
-    }
     if (fast_exp)
         launch_fisher_k<true>(b, gmix, dgpars, K, weight, out, status, max_ng, lds, s);
     else

@@ -1,6 +1,9 @@
-// grad_common.hpp -- what the per-gaussian gradient kernels share
-// (loglike_grad.hip, render_grad.hip): the LDS record of a gaussian and the six derivative terms of one
-// (pixel, gaussian) pair in deriv_images' convention (derivs_nb.py:41-127).
+// grad_common.hpp -- what the one-wave-per-stamp gradient kernels share
+// (loglike_grad.hip, render_grad.hip, fisher.hip): the exp table, the LDS
+// record of a gaussian, the six derivative terms of one (pixel, gaussian) pair
+// in deriv_images' convention (derivs_nb.py:41-127) and the launchers' LDS
+// budget.  The staging prologue and the gaussian passes stay written out in the
+// kernels: DESIGN.md section 3.12, "Tried".
 //
 // With, per gaussian, E = exp(-chi2/2) area, W the window above chi2 = 20,
 //   val  = pnorm E W,  valc = pnorm E (W - 2W'),  Q delta = (qv, qu):
@@ -13,9 +16,13 @@
 // the true derivative of gauss2d_eval_pixel (gmix_nb.py:66-92).
 #pragma once
 
+#include <string>
+
 #include "device_utils.hpp"
 
 namespace ngmix {
+
+static __constant__ double c_exp_table_grad[16] = NGMIX_EXP_TABLE;
 
 // per-gaussian staging: the value form of the loglike kernels (EvalGauss) plus
 // what the derivatives need, and the chi2 < 25 pixel box
@@ -67,6 +74,19 @@ __device__ __forceinline__ void grad_pair(const GradGauss &G, double w11, double
         a4 += rc * (qv * qu) - rv * w12;
         a5 += 0.5 * (rc * (qu * qu) - rv * w22);
     }
+}
+
+// max_ng and the LDS bytes of the batch's launch (extra bytes of the kernel's
+// own, the exp table, the records, with_gacc: six sums per gaussian, ctl);
+// false, with who's error set, when that passes the 64 KiB of a work-group
+inline bool grad_launch_sizes(const ngmix_batch *b, const char *who, bool with_gacc,
+                              size_t extra, int &max_ng, size_t &lds)
+{
+    max_ng = b->max_ngauss > 0 ? b->max_ngauss : 1;
+    lds = extra + 16 * 8 + (size_t)max_ng * (sizeof(GradGauss) + (with_gacc ? 6 * 8 : 0)) + 16;
+    if (lds <= 64 * 1024) return true;
+    set_last_error_msg((std::string(who) + ": too many gaussians for the LDS budget").c_str());
+    return false;
 }
 
 }  // namespace ngmix

@@ -32,8 +32,6 @@
 
 namespace ngmix {
 
-__constant__ double c_exp_table_g[16] = NGMIX_EXP_TABLE;
-
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) void loglike_grad_kernel(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) vo
     const double *sierr = ierr + st.pix_off;
     const bool izw = (st.flags & NGMIX_STAMP_IGNORE_ZERO_WEIGHT) != 0;
 
-    if (lane < 16) tab[lane] = c_exp_table_g[lane];
+    if (lane < 16) tab[lane] = c_exp_table_grad[lane];
     if (lane == 0) {
         ctl[0] = 1 << 30;   // first gaussian whose norm fails
         ctl[1] = 0;         // its code
@@ -207,11 +205,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) vo
     }
 }
 
-size_t loglike_grad_lds_bytes(int max_ngauss)
-{
-    return 16 * 8 + (size_t)max_ngauss * (sizeof(GradGauss) + 6 * 8) + 16;
-}
-
 int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double *out,
                         double *grad, int32_t *status, hipStream_t s)
 {
@@ -220,12 +213,9 @@ int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double 
         set_last_error_msg("loglike_grad: the batch needs val and ierr");
         return NGMIX_ERR_BAD_ARG;
     }
-    const int max_ng = b->max_ngauss > 0 ? b->max_ngauss : 1;
-    const size_t lds = loglike_grad_lds_bytes(max_ng);
-    if (lds > 64 * 1024) {
-        set_last_error_msg("loglike_grad: too many gaussians for the LDS budget");
-        return NGMIX_ERR_BAD_ARG;
-    }
+    int max_ng;
+    size_t lds;
+    if (!grad_launch_sizes(b, "loglike_grad", true, 0, max_ng, lds)) return NGMIX_ERR_BAD_ARG;
     census("loglike_grad_kernel");
     hipLaunchKernelGGL(loglike_grad_kernel, dim3((unsigned)b->nstamps), dim3(WAVE), lds, s,
                        b->stamps, b->val, b->ierr, b->jac, gmix, out, grad, status, max_ng);

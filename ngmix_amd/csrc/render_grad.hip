@@ -31,8 +31,6 @@
 
 namespace ngmix {
 
-__constant__ double c_exp_table_r[16] = NGMIX_EXP_TABLE;
-
 template <bool FAST>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) void render_vjp_kernel(
     const ngmix_stamp *__restrict__ stamps, const ngmix_jacobian *__restrict__ jacs,
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) vo
     double *gout = grad + 6 * (int64_t)st.gm_off;
     const double *sg = gimg + st.pix_off;
 
-    if (lane < 16) tab[lane] = c_exp_table_r[lane];
+    if (lane < 16) tab[lane] = c_exp_table_grad[lane];
     if (lane == 0) ctl[0] = 1 << 30;   // first gaussian whose norm fails
     __syncthreads();
     // norms as gauss_set_norm (gmix_nb.py:190-218) from (p, irr, irc, icc):
@@ -147,11 +145,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 8))) vo
     if (lane == 0) status[s] = NGMIX_OK;
 }
 
-size_t render_vjp_lds_bytes(int max_ngauss)
-{
-    return 16 * 8 + (size_t)max_ngauss * (sizeof(GradGauss) + 6 * 8) + 16;
-}
-
 int launch_render_vjp(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double *gimage,
                       int fast_exp, double *grad, int32_t *status, hipStream_t s)
 {
@@ -160,12 +153,9 @@ int launch_render_vjp(const ngmix_batch *b, const ngmix_gauss2d *gmix, const dou
         set_last_error_msg("render_vjp: gimage, grad and status are required");
         return NGMIX_ERR_BAD_ARG;
     }
-    const int max_ng = b->max_ngauss > 0 ? b->max_ngauss : 1;
-    const size_t lds = render_vjp_lds_bytes(max_ng);
-    if (lds > 64 * 1024) {
-        set_last_error_msg("render_vjp: too many gaussians for the LDS budget");
-        return NGMIX_ERR_BAD_ARG;
-    }
+    int max_ng;
+    size_t lds;
+    if (!grad_launch_sizes(b, "render_vjp", true, 0, max_ng, lds)) return NGMIX_ERR_BAD_ARG;
     if (fast_exp) {
         census("render_vjp_kernel<fast>");
         hipLaunchKernelGGL(render_vjp_kernel<true>, dim3((unsigned)b->nstamps), dim3(WAVE), lds,

@@ -14,7 +14,7 @@ import ngmix_amd as ngmix
 from ngmix_amd import _lib
 from ngmix_amd.batch import StampBatch
 
-from test_gpu_autodiff import (GC_CASES, _gm_records, _jacrec, _make, _psf,
+from test_gpu_autodiff import (GC_CASES, SCALE, _gm_records, _jacrec, _make, _psf,
                                _stamp_mixtures)
 from test_gpu_pixpass import assert_pixels
 
@@ -238,6 +238,52 @@ def test_gradcheck(model, ngauss, nband, nep, fast_exp):
     atol = FAST_FD_RTOL if fast_exp else 1e-7
     assert torch.autograd.gradcheck(lambda pp, qq: f(pp, qq) / d_scale, (p, q), eps=1e-6,
                                     atol=atol, rtol=0.0, raise_exception=True)
+
+
+PASS2_CASES = {"13x11": (13, 11), "25x25": (25, 25), "off_frame": (25, 25)}
+
+
+@pytest.mark.parametrize("case", sorted(PASS2_CASES))
+def test_vjp_of_the_loglike_residual_is_the_loglike_gradient(case):
+    """the fast VJP kernel's gaussian pass is loglike_grad_kernel's pass 2, the
+    same text in both files: fed the residual the loglike kernel
+    forms -- (val - model) (ierr ierr) with the exact=True fast render as
+    model, all weights positive -- the VJP gives the loglike gradient bit for
+    bit.  13x11: ragged tiles, one chunk; 25x25: two chunks, the second short;
+    off_frame: a gaussian centred above the frame that reaches the first rows
+    only (its second chunk is skipped) and one that reaches no tile at all"""
+    torch = _torch()
+    ad = _autodiff()
+    rng = np.random.RandomState(29)
+    dims = PASS2_CASES[case]
+    # (no shear in the off-frame case: v = SCALE (row - row0) exactly)
+    sb, pars, psf, sobj, sband = _make(rng, "exp", 3, dims=dims, npsf=2,
+                                       shear=0.0 if case == "off_frame" else 0.05)
+    mix = _stamp_mixtures(pars, "exp", psf, sobj, sband)
+    if case == "off_frame":
+        row0 = sb.jac.cpu().numpy()[:, 0]
+        mix[:, 0, 1] = SCALE * (-6.0 - row0)       # 5 sigma = 7.5 pixels: rows 0, 1
+        mix[:, 1, 1] = SCALE * (-30.0 - row0)
+        mix[:, 0:2, 3] = mix[:, 0:2, 5] = (1.5 * SCALE) ** 2
+        mix[:, 0:2, 4] = 0.0
+    assert bool((sb.ierr > 0).all())
+
+    g1 = torch.from_numpy(mix).cuda().requires_grad_(True)
+    ll, _, st = ad.stamp_loglike_grad(sb, g1)
+    assert int(st.abs().sum()) == 0
+    want, = torch.autograd.grad(ll.sum(), g1)
+
+    g2 = torch.from_numpy(mix).cuda().requires_grad_(True)
+    model, st = ad.stamp_render(sb, g2, fast_exp=True, exact=True)
+    assert int(st.abs().sum()) == 0
+    r = (sb.val - model.detach()) * (sb.ierr * sb.ierr)
+    got, = torch.autograd.grad(model, g2, grad_outputs=r)
+
+    want, got = want.cpu().numpy(), got.cpu().numpy()
+    print("%s: largest |vjp - loglike gradient| / largest entry = %.3e"
+          % (case, np.abs(got - want).max() / np.abs(want).max()))
+    assert np.abs(want).max() > 0
+    np.testing.assert_array_equal(got, want)
 
 
 # ------------------------------------------------------------------ blends
