@@ -16,6 +16,7 @@
 
 #include "em_common.hpp"
 #include "launch_iter.hpp"
+#include "launch_util.hpp"
 
 namespace ngmix {
 
@@ -336,21 +337,10 @@ __global__ __launch_bounds__(BLOCK) void em_list_kernel(
                             sh, dyn);
 }
 
-template <int NT, int PPT, int NG>
-static void em_grid_launch(int kind, const ngmix_em_conf *conf, const ngmix_batch *b,
-                           ngmix_gauss2d *gmix, int ngauss, ngmix_gauss2d *psf,
-                           int npsf, ngmix_gauss2d *conv, const double *sky_in,
-                           int fzw, double *out, int32_t *status, hipStream_t s)
+// the generic kernels are built for 1, 2, 3, 4, 6 and 10 object gaussians
+static int em_built_ngauss(int ngauss)
 {
-    {
-        char name[64];
-        snprintf(name, sizeof(name), "em_grid_kernel<%d, %d, %d>", NT, PPT, NG);
-        census(name);
-    }
-    hipLaunchKernelGGL((em_grid_kernel<NT, PPT, NG>), dim3((unsigned)b->nstamps),
-                       dim3(NT), em_dyn_lds(ngauss, npsf), s, kind, *conf,
-                       b->stamps, b->val, b->ierr, b->jac, gmix, ngauss, psf, npsf,
-                       conv, sky_in, fzw, out, status);
+    return ngauss <= 4 ? ngauss : ngauss <= 6 ? 6 : 10;
 }
 
 template <int NT, int PPT>
@@ -360,22 +350,17 @@ static int em_grid_dispatch_ng(int kind, const ngmix_em_conf *conf,
                                const double *sky_in, int fzw, double *out,
                                int32_t *status, hipStream_t s)
 {
-#define NGMIX_EM_CASE(N)                                                          \
-    em_grid_launch<NT, PPT, N>(kind, conf, b, gmix, ngauss, psf, npsf, conv,    \
-                               sky_in, fzw, out, status, s)
-    if (ngauss <= 1) NGMIX_EM_CASE(1);
-    else if (ngauss <= 2) NGMIX_EM_CASE(2);
-    else if (ngauss <= 3) NGMIX_EM_CASE(3);
-    else if (ngauss <= 4) NGMIX_EM_CASE(4);
-    else if (ngauss <= 6) NGMIX_EM_CASE(6);
-    else if (ngauss <= 10) NGMIX_EM_CASE(10);
-    else {
+    if (ngauss > 10) {
         set_last_error_msg("em: more than 10 object gaussians not supported");
         return NGMIX_ERR_BAD_ARG;
     }
-#undef NGMIX_EM_CASE
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    return for_int<1, 2, 3, 4, 6, 10>(em_built_ngauss(ngauss), [&](auto NG) {
+        static const CensusName name("em_grid_kernel", {NT, PPT, decltype(NG)::value});
+        return launch(kernel(em_grid_kernel<NT, PPT, decltype(NG)::value>, name.s),
+                      dim3((unsigned)b->nstamps), dim3(NT), em_dyn_lds(ngauss, npsf), NO_OPTIN,
+                      s, kind, *conf, b->stamps, b->val, b->ierr, b->jac, gmix, ngauss, psf,
+                      npsf, conv, sky_in, fzw, out, status);
+    });
 }
 
 int launch_em_grid(int kind, const ngmix_em_conf *conf, const ngmix_batch *b,
@@ -416,24 +401,15 @@ int launch_em_list(int kind, const ngmix_em_conf *conf, ngmix_pixel *pixels,
                    double *out3, int32_t *status, hipStream_t s)
 {
     if (kind < 0 || kind > 3 || ngauss < 1 || npsf < 1) return NGMIX_ERR_BAD_ARG;
-    const size_t lds = em_dyn_lds(ngauss, npsf);
-#define NGMIX_EM_CASE(N)                                                         \
-    hipLaunchKernelGGL((em_list_kernel<N>), dim3(1), dim3(BLOCK), lds, s, kind,  \
-                       *conf, pixels, (int)n, sums, gmix, ngauss, psf, npsf,     \
-                       conv, fzw, out3, status)
-    if (ngauss <= 1) NGMIX_EM_CASE(1);
-    else if (ngauss <= 2) NGMIX_EM_CASE(2);
-    else if (ngauss <= 3) NGMIX_EM_CASE(3);
-    else if (ngauss <= 4) NGMIX_EM_CASE(4);
-    else if (ngauss <= 6) NGMIX_EM_CASE(6);
-    else if (ngauss <= 10) NGMIX_EM_CASE(10);
-    else {
+    if (ngauss > 10) {
         set_last_error_msg("em: more than 10 object gaussians not supported");
         return NGMIX_ERR_BAD_ARG;
     }
-#undef NGMIX_EM_CASE
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    return for_int<1, 2, 3, 4, 6, 10>(em_built_ngauss(ngauss), [&](auto NG) {
+        return launch(em_list_kernel<decltype(NG)::value>, dim3(1), dim3(BLOCK),
+                      em_dyn_lds(ngauss, npsf), s, kind, *conf, pixels, (int)n, sums, gmix,
+                      ngauss, psf, npsf, conv, fzw, out3, status);
+    });
 }
 
 }  // namespace ngmix

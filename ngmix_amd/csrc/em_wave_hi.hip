@@ -10,20 +10,6 @@
 
 namespace ngmix {
 
-template <int KIND>
-static void em_wave_launch_ng_hi(const ngmix_em_conf *conf, const ngmix_batch *b,
-                                 ngmix_gauss2d *gmix, int ngauss, ngmix_gauss2d *psf,
-                                 int npsf, ngmix_gauss2d *conv, const double *sky_in,
-                                 int fzw, double *out, int32_t *status, hipStream_t s)
-{
-    if (ngauss == 4)
-        em_wave_launch<KIND, 4>(conf, b, gmix, psf, npsf, conv, sky_in, fzw, out, status, s);
-    else if (ngauss == 5)
-        em_wave_launch<KIND, 5>(conf, b, gmix, psf, npsf, conv, sky_in, fzw, out, status, s);
-    else
-        em_wave_launch<KIND, 6>(conf, b, gmix, psf, npsf, conv, sky_in, fzw, out, status, s);
-}
-
 int launch_em_wave_hi(int kind, const ngmix_em_conf *conf, const ngmix_batch *b,
                       ngmix_gauss2d *gmix, int ngauss, ngmix_gauss2d *psf, int npsf,
                       ngmix_gauss2d *conv, const double *sky_in, int fzw, double *out,
@@ -36,26 +22,8 @@ int launch_em_wave_hi(int kind, const ngmix_em_conf *conf, const ngmix_batch *b,
         set_last_error_msg("launch_em_wave_hi: 4..6 gaussians on stamps of <= 4096 pixels");
         return NGMIX_ERR_BAD_ARG;
     }
-    switch (kind) {
-    case NGMIX_EM_FULL:
-        em_wave_launch_ng_hi<NGMIX_EM_FULL>(conf, b, gmix, ngauss, psf, npsf, conv, sky_in,
-                                            fzw, out, status, s);
-        break;
-    case NGMIX_EM_FIXCEN:
-        em_wave_launch_ng_hi<NGMIX_EM_FIXCEN>(conf, b, gmix, ngauss, psf, npsf, conv,
-                                              sky_in, fzw, out, status, s);
-        break;
-    case NGMIX_EM_FIXCOV:
-        em_wave_launch_ng_hi<NGMIX_EM_FIXCOV>(conf, b, gmix, ngauss, psf, npsf, conv,
-                                              sky_in, fzw, out, status, s);
-        break;
-    default:
-        em_wave_launch_ng_hi<NGMIX_EM_FLUXONLY>(conf, b, gmix, ngauss, psf, npsf, conv,
-                                                sky_in, fzw, out, status, s);
-        break;
-    }
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    return em_wave_dispatch<4, 5, 6>(kind, conf, b, gmix, ngauss, psf, npsf, conv, sky_in, fzw,
+                                     out, status, s);
 }
 
 }  // namespace ngmix

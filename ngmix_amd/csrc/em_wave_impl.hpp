@@ -12,6 +12,7 @@
 
 #include "em_common.hpp"
 #include "launch_iter.hpp"
+#include "launch_util.hpp"
 
 namespace ngmix {
 
@@ -665,72 +666,84 @@ void em_wave_kernel(
         status ? status + s : nullptr, sh, dyn, c_fexp_coef_e);
 }
 
+// an instantiation and its census name (made once, at the first launch)
+template <int NT, int PPT, int KIND, int NG, int NPSF>
+static auto em_wave_pick()
+{
+    static const CensusName name("em_wave_kernel", {NT, PPT, KIND, NG, NPSF});
+    return kernel(em_wave_kernel<NT, PPT, KIND, NG, NPSF>, name.s);
+}
+
 template <int NT, int PPT, int KIND, int NG>
-static void em_wave_launch_nt(const ngmix_em_conf *conf, const ngmix_batch *b,
-                              ngmix_gauss2d *gmix, ngmix_gauss2d *psf, int npsf,
-                              ngmix_gauss2d *conv, const double *sky_in, int fzw,
-                              double *out, int32_t *status, hipStream_t s)
+static int em_wave_launch_nt(const ngmix_em_conf *conf, const ngmix_batch *b,
+                             ngmix_gauss2d *gmix, ngmix_gauss2d *psf, int npsf,
+                             ngmix_gauss2d *conv, const double *sky_in, int fzw,
+                             double *out, int32_t *status, hipStream_t s)
 {
     const size_t nconv = (size_t)NG * npsf;
     const size_t lds = (NG + npsf + nconv) * sizeof(ngmix_gauss2d) +
                        nconv * sizeof(EmConvF) + 64;
-    {
-        char name[80];
-        snprintf(name, sizeof(name), "em_wave_kernel<%d, %d, %d, %d, %d>", NT, PPT, KIND, NG,
-                 npsf == 1 ? 1 : (npsf == 3 && NG <= 3 && NT == WAVE) ? 3 : 0);
-        census(name);
-    }
+    // (the 'turb' / coellip-3 psf of a galaxy fit on stamps of <= 32 x 32:
+    // the component loop unrolled)
+    constexpr int NPSF3 = (NG <= 3 && NT == WAVE) ? 3 : 0;
+    const auto k = npsf == 1              ? em_wave_pick<NT, PPT, KIND, NG, 1>()
+                   : (npsf == 3 && NPSF3) ? em_wave_pick<NT, PPT, KIND, NG, NPSF3>()
+                                          : em_wave_pick<NT, PPT, KIND, NG, 0>();
     static const bool no_full = getenv("NGMIX_EM_NO_FULL") != nullptr;
     if (no_full) fzw |= 2;
-    if (npsf == 1)
-        hipLaunchKernelGGL((em_wave_kernel<NT, PPT, KIND, NG, 1>),
-                           dim3((unsigned)b->nstamps), dim3(NT), lds, s, *conf,
-                           b->stamps, b->val, b->ierr, b->jac, gmix, psf, npsf, conv,
-                           sky_in, fzw, out, status);
-    else if (npsf == 3 && NG <= 3 && NT == WAVE)
-        // (the 'turb' / coellip-3 psf of a galaxy fit on stamps of <= 32 x 32:
-        // the component loop unrolled)
-        hipLaunchKernelGGL((em_wave_kernel<NT, PPT, KIND, NG, (NG <= 3 && NT == WAVE) ? 3 : 0>),
-                           dim3((unsigned)b->nstamps), dim3(NT), lds, s, *conf,
-                           b->stamps, b->val, b->ierr, b->jac, gmix, psf, npsf, conv,
-                           sky_in, fzw, out, status);
-    else
-        hipLaunchKernelGGL((em_wave_kernel<NT, PPT, KIND, NG, 0>),
-                           dim3((unsigned)b->nstamps), dim3(NT), lds, s, *conf,
-                           b->stamps, b->val, b->ierr, b->jac, gmix, psf, npsf, conv,
-                           sky_in, fzw, out, status);
+    return launch(k, dim3((unsigned)b->nstamps), dim3(NT), lds, NO_OPTIN, s, *conf, b->stamps,
+                  b->val, b->ierr, b->jac, gmix, psf, npsf, conv, sky_in, fzw, out, status);
 }
 
 // one wave up to 32x32 pixels, two up to 45x45, four up to 64x64
 template <int KIND, int NG>
-static void em_wave_launch(const ngmix_em_conf *conf, const ngmix_batch *b,
-                           ngmix_gauss2d *gmix, ngmix_gauss2d *psf, int npsf,
-                           ngmix_gauss2d *conv, const double *sky_in, int fzw,
-                           double *out, int32_t *status, hipStream_t s)
+static int em_wave_launch(const ngmix_em_conf *conf, const ngmix_batch *b,
+                          ngmix_gauss2d *gmix, ngmix_gauss2d *psf, int npsf,
+                          ngmix_gauss2d *conv, const double *sky_in, int fzw,
+                          double *out, int32_t *status, hipStream_t s)
 {
     const int np = b->max_npix;
     if (np <= 16 * WAVE)
-        em_wave_launch_nt<WAVE, 16, KIND, NG>(conf, b, gmix, psf, npsf, conv, sky_in, fzw,
-                                              out, status, s);
-    else if (KIND == NGMIX_EM_FULL && np > 16 * 2 * WAVE && np <= 18 * 2 * WAVE)
+        return em_wave_launch_nt<WAVE, 16, KIND, NG>(conf, b, gmix, psf, npsf, conv, sky_in,
+                                                     fzw, out, status, s);
+    if (KIND == NGMIX_EM_FULL && np > 16 * 2 * WAVE && np <= 18 * 2 * WAVE)
         // 48 x 48 = 18 x 128: two waves, 18 register slots per lane, like the
         // two-wave kernel of <= 2048 pixels (9.6 ms per 50k 45 x 45 stamps) instead
         // of four waves with 16 (20 ms per 50k).  One wave with 36 slots was
         // measured too: 18 ms -- its 270-340 registers leave one wave per SIMD to
         // a serial per-pixel chain.  (The full run only: every (kind, ngauss,
         // psf) combination is a kernel of its own.)
-        em_wave_launch_nt<2 * WAVE, (KIND == NGMIX_EM_FULL ? 18 : 16), KIND, NG>(
+        return em_wave_launch_nt<2 * WAVE, (KIND == NGMIX_EM_FULL ? 18 : 16), KIND, NG>(
             conf, b, gmix, psf, npsf, conv, sky_in, fzw, out, status, s);
-    else if (np <= 16 * 2 * WAVE)
-        em_wave_launch_nt<2 * WAVE, 16, KIND, NG>(conf, b, gmix, psf, npsf, conv, sky_in,
-                                                  fzw, out, status, s);
-    else if constexpr (NG <= 6)
+    if (np <= 16 * 2 * WAVE)
+        return em_wave_launch_nt<2 * WAVE, 16, KIND, NG>(conf, b, gmix, psf, npsf, conv,
+                                                         sky_in, fzw, out, status, s);
+    if constexpr (NG <= 6)
         // (four to six object gaussians: the 26 .. 38 sums go through the
         // reduction tile in two passes, em_reduce_chunk)
-        em_wave_launch_nt<BLOCK, 16, KIND, NG>(conf, b, gmix, psf, npsf, conv, sky_in,
-                                               fzw, out, status, s);
-    // (seven and eight object gaussians: one or two waves, em_wave_8.hip; em.hip
-    // sends larger stamps to the generic kernel)
+        return em_wave_launch_nt<BLOCK, 16, KIND, NG>(conf, b, gmix, psf, npsf, conv, sky_in,
+                                                      fzw, out, status, s);
+    // (seven and eight object gaussians: one or two waves; launch_em_wave_8
+    // admits no larger stamp, em.hip sends those to the generic kernel)
+    set_last_error_msg("em_wave: the stamp is too large for this count of gaussians");
+    return NGMIX_ERR_BAD_ARG;
+}
+
+// the (kind x ngauss) dispatch of one translation unit, NGS its gaussian
+// counts (the caller has checked that ngauss is one of them)
+template <int... NGS>
+static int em_wave_dispatch(int kind, const ngmix_em_conf *conf, const ngmix_batch *b,
+                            ngmix_gauss2d *gmix, int ngauss, ngmix_gauss2d *psf, int npsf,
+                            ngmix_gauss2d *conv, const double *sky_in, int fzw, double *out,
+                            int32_t *status, hipStream_t s)
+{
+    return for_int<NGMIX_EM_FULL, NGMIX_EM_FIXCEN, NGMIX_EM_FIXCOV, NGMIX_EM_FLUXONLY>(
+        kind, [&](auto K) {
+            return for_int<NGS...>(ngauss, [&](auto NG) {
+                return em_wave_launch<decltype(K)::value, decltype(NG)::value>(
+                    conf, b, gmix, psf, npsf, conv, sky_in, fzw, out, status, s);
+            });
+        });
 }
 
 }  // namespace ngmix

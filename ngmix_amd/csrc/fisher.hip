@@ -29,6 +29,7 @@
 // traffic: two runs give the same bits.
 #include "grad_common.hpp"
 #include "launch.hpp"
+#include "launch_util.hpp"
 
 namespace ngmix {
 
@@ -173,21 +174,17 @@ __global__ __launch_bounds__(WAVE) void fisher_kernel(
 }
 
 template <bool FAST>
-static void launch_fisher_k(const ngmix_batch *b, const ngmix_gauss2d *gmix,
-                            const double *dgpars, int K, const double *weight, double *out,
-                            int32_t *status, int max_ng, size_t lds, hipStream_t s)
+static int launch_fisher_k(const ngmix_batch *b, const ngmix_gauss2d *gmix,
+                           const double *dgpars, int K, const double *weight, double *out,
+                           int32_t *status, int max_ng, size_t lds, hipStream_t s)
 {
-    if (K <= 8) {
-        census(FAST ? "fisher_kernel<fast, 8>" : "fisher_kernel<exact, 8>");
-        hipLaunchKernelGGL((fisher_kernel<FAST, 8>), dim3((unsigned)b->nstamps), dim3(WAVE),
-                           lds, s, b->stamps, b->jac, b->ierr, weight, gmix, dgpars, K, out,
-                           status, max_ng);
-    } else {
-        census(FAST ? "fisher_kernel<fast, 16>" : "fisher_kernel<exact, 16>");
-        hipLaunchKernelGGL((fisher_kernel<FAST, 16>), dim3((unsigned)b->nstamps), dim3(WAVE),
-                           lds, s, b->stamps, b->jac, b->ierr, weight, gmix, dgpars, K, out,
-                           status, max_ng);
-    }
+    const auto k =
+        K <= 8 ? kernel(fisher_kernel<FAST, 8>,
+                        FAST ? "fisher_kernel<fast, 8>" : "fisher_kernel<exact, 8>")
+               : kernel(fisher_kernel<FAST, 16>,
+                        FAST ? "fisher_kernel<fast, 16>" : "fisher_kernel<exact, 16>");
+    return launch(k, dim3((unsigned)b->nstamps), dim3(WAVE), lds, NO_OPTIN, s, b->stamps, b->jac,
+                  b->ierr, weight, gmix, dgpars, K, out, status, max_ng);
 }
 
 int launch_fisher(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double *dgpars,
@@ -212,11 +209,8 @@ int launch_fisher(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double 
     if (!grad_launch_sizes(b, "fisher", false, (size_t)WAVE * FI_JS * 8, max_ng, lds))
         return NGMIX_ERR_BAD_ARG;
     if (fast_exp)
-        launch_fisher_k<true>(b, gmix, dgpars, K, weight, out, status, max_ng, lds, s);
-    else
-        launch_fisher_k<false>(b, gmix, dgpars, K, weight, out, status, max_ng, lds, s);
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+        return launch_fisher_k<true>(b, gmix, dgpars, K, weight, out, status, max_ng, lds, s);
+    return launch_fisher_k<false>(b, gmix, dgpars, K, weight, out, status, max_ng, lds, s);
 }
 
 }  // namespace ngmix

@@ -81,6 +81,12 @@ int launch_lm_eval(const ngmix_batch *b, int model, int fd, const ngmix_lm_state
                    const ngmix_gauss2d *psf, int npsf, double *sums, int32_t *status,
                    double *stamp_stats, hipStream_t s, double *jac_point = nullptr,
                    bool precise = false);
+// the NLOC the forward-difference kernel serving `nloc` local parameters is
+// built for: its sums are laid out for that count
+inline int lm_fd_nloc(int nloc)
+{
+    return nloc >= 6 && nloc <= 8 ? nloc : nloc <= 10 ? 10 : nloc <= 12 ? 12 : 14;
+}
 // lm_precise.hip: the covariance factor of the ill-conditioned forward-difference
 // fits from double-double normal equations
 int launch_lm_precise_cov(const ngmix_lm_problem *p, double *psums, hipStream_t s);

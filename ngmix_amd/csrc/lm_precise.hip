@@ -35,6 +35,7 @@
 
 #include "device_utils.hpp"
 #include "launch.hpp"
+#include "launch_util.hpp"
 #include "lm_core.hpp"
 
 namespace ngmix {
@@ -293,11 +294,9 @@ int launch_lm_precise_cov(const ngmix_lm_problem *p, double *psums, hipStream_t 
     int rc = launch_lm_eval(p->batch, p->model, 1, p->states, p->stamp_obj, p->stamp_band,
                             p->psf, p->npsf, psums, nullptr, nullptr, s, p->jac_point, true);
     if (rc != NGMIX_OK) return rc;
-    census("lm_factor_dd_kernel");
-    hipLaunchKernelGGL(lm_factor_dd_kernel, dim3((unsigned)p->nobj), dim3(WAVE), 0, s,
-                       p->states, p->nobj, p->obj_start, p->stamp_band, psums, nloc);
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    return launch(kernel(lm_factor_dd_kernel, "lm_factor_dd_kernel"), dim3((unsigned)p->nobj),
+                  dim3(WAVE), 0, NO_OPTIN, s, p->states, p->nobj, p->obj_start, p->stamp_band,
+                  psums, nloc);
 }
 
 }  // namespace ngmix

@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "launch.hpp"
+#include "launch_util.hpp"
 #include "lm_core_team.hpp"
 
 namespace ngmix {
@@ -271,6 +272,18 @@ __global__ __launch_bounds__(TEAMS * lmteam::TEAM) void lm_advance_team_kernel(
     }
 }
 
+// a row of launch_lm_advance_team's table: the instantiation for (fits per
+// wave, parameters built for) and its census name
+struct TeamRow {
+    int teams, np;
+    decltype(kernel(lm_advance_team_kernel<1, 8>, "")) k;
+};
+template <int T, int N>
+constexpr TeamRow team_row(const char *name)
+{
+    return {T, N, kernel(lm_advance_team_kernel<T, N>, name)};
+}
+
 int launch_lm_advance_team(lm_state *states, int64_t nobj, const int64_t *obj_start,
                            const int32_t *stamp_band, const double *sums, int nloc, int npars,
                            const double *obj_sums, int32_t *nactive,
@@ -280,29 +293,27 @@ int launch_lm_advance_team(lm_state *states, int64_t nobj, const int64_t *obj_st
     const int np = npars <= 8 ? 8 : npars <= 10 ? 10 : npars <= 12 ? 12 : LM_NPMAX;
     // (fits per wave: 1, 2 or 4 -- anything else an A/B knob says is the default)
     if (teams != 1 && teams != 2) teams = 4;
-    char name[64];
-    snprintf(name, sizeof(name), "lm_advance_team_kernel<%d, %d>", teams, np);
-    census(name);
-#define NGMIX_TEAM_LAUNCH(T, N)                                                                 \
-    hipLaunchKernelGGL((lm_advance_team_kernel<T, N>), dim3((unsigned)((nobj + T - 1) / T)),      \
-                       dim3(T * lmteam::TEAM),                                                    \
-                       T * (size_t)lmteam::team_lds_doubles(N) * sizeof(double), s, states, nobj, \
-                       obj_start, stamp_band, sums, nloc, obj_sums, nactive, stamp_stats,         \
-                       obj_stats)
-#define NGMIX_TEAM_NP(T)                                                                         \
-    do {                                                                                          \
-        if (np == 8) NGMIX_TEAM_LAUNCH(T, 8);                                                     \
-        else if (np == 10) NGMIX_TEAM_LAUNCH(T, 10);                                              \
-        else if (np == 12) NGMIX_TEAM_LAUNCH(T, 12);                                              \
-        else NGMIX_TEAM_LAUNCH(T, LM_NPMAX);                                                      \
-    } while (0)
-    if (teams == 1) NGMIX_TEAM_NP(1);
-    else if (teams == 2) NGMIX_TEAM_NP(2);
-    else NGMIX_TEAM_NP(4);
-#undef NGMIX_TEAM_NP
-#undef NGMIX_TEAM_LAUNCH
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    static constexpr TeamRow rows[] = {
+        team_row<1, 8>("lm_advance_team_kernel<1, 8>"),
+        team_row<1, 10>("lm_advance_team_kernel<1, 10>"),
+        team_row<1, 12>("lm_advance_team_kernel<1, 12>"),
+        team_row<1, 14>("lm_advance_team_kernel<1, 14>"),
+        team_row<2, 8>("lm_advance_team_kernel<2, 8>"),
+        team_row<2, 10>("lm_advance_team_kernel<2, 10>"),
+        team_row<2, 12>("lm_advance_team_kernel<2, 12>"),
+        team_row<2, 14>("lm_advance_team_kernel<2, 14>"),
+        team_row<4, 8>("lm_advance_team_kernel<4, 8>"),
+        team_row<4, 10>("lm_advance_team_kernel<4, 10>"),
+        team_row<4, 12>("lm_advance_team_kernel<4, 12>"),
+        team_row<4, 14>("lm_advance_team_kernel<4, 14>"),
+    };
+    static_assert(LM_NPMAX == 14, "the rows built for 14 parameters serve every fit");
+    const auto k =
+        find_kernel(rows, [&](const TeamRow &q) { return q.teams == teams && q.np == np; });
+    const size_t lds = teams * (size_t)lmteam::team_lds_doubles(np) * sizeof(double);
+    return launch(k, dim3((unsigned)((nobj + teams - 1) / teams)), dim3(teams * lmteam::TEAM),
+                  lds, NO_OPTIN, s, states, nobj, obj_start, stamp_band, sums, nloc, obj_sums,
+                  nactive, stamp_stats, obj_stats);
 }
 
 }  // namespace ngmix

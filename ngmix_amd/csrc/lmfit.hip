@@ -23,6 +23,7 @@
 
 #include "device_utils.hpp"
 #include "launch.hpp"
+#include "launch_util.hpp"
 #include "lm_core.hpp"
 #include "lm_core_reg.hpp"
 
@@ -1789,6 +1790,19 @@ static int model_ngauss_npars(int model, int &ng0, int &nloc)
     return -1;
 }
 
+// a row of launch_lm_eval's forward-difference table: the instantiation for
+// (lm_fd_nloc(nloc), row-major tiles, the precise pass) and its census name
+struct FdRow {
+    int n;
+    bool linear, precise;
+    decltype(kernel(lm_eval_fd_kernel<6, false, false>, "")) k;
+};
+template <int N, bool LINEAR, bool PRECISE>
+constexpr FdRow fd_row(const char *name)
+{
+    return {N, LINEAR, PRECISE, kernel(lm_eval_fd_kernel<N, LINEAR, PRECISE>, name)};
+}
+
 int launch_lm_eval(const ngmix_batch *b, int model, int fd, const lm_state *states,
                    const int32_t *stamp_obj, const int32_t *stamp_band,
                    const ngmix_gauss2d *psf, int npsf, double *sums, int32_t *status,
@@ -1835,25 +1849,21 @@ int launch_lm_eval(const ngmix_batch *b, int model, int fd, const lm_state *stat
             set_last_error_msg("lm_eval: NGMIX_LM_JBASIS carries no statistics");
             return NGMIX_ERR_BAD_ARG;
         }
-        const void *kern =
-            jbasis ? (lds_tiles ? (const void *)lm_eval_kernel<true, false>
-                                : (const void *)lm_eval_kernel<false, false>)
-                   : (lds_tiles ? (const void *)lm_eval_kernel<true, true>
-                                : (const void *)lm_eval_kernel<false, true>);
-        if (lds > 48 * 1024)
-            NGMIX_HIP_CHECK(hipFuncSetAttribute(
-                kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const ngmix_stamp *a_stamps = b->stamps;
-        const double *a_val = b->val, *a_ierr = b->ierr;
-        const ngmix_jacobian *a_jac = b->jac;
-        int a_model = model, a_ng0 = ng0, a_npsf = npsf, a_ns = no_skip;
-        void *args[] = {&a_stamps, &a_val, &a_ierr, &a_jac, &a_model, &a_ng0, &states,
-                        &stamp_obj, &stamp_band, &psf, &a_npsf, &sums, &status, &a_ns,
-                        &tile_cap, &stamp_stats};
-        census(jbasis ? (lds_tiles ? "lm_eval_kernel<true, false>" : "lm_eval_kernel<false, false>")
-                      : (lds_tiles ? "lm_eval_kernel<true, true>" : "lm_eval_kernel<false, true>"));
-        NGMIX_HIP_CHECK(hipLaunchKernel(kern, grid, block, args, lds, s));
-        return NGMIX_OK;
+        struct Row {
+            bool lds_tiles, jbasis;
+            decltype(kernel(lm_eval_kernel<true, true>, "")) k;
+        };
+        static constexpr Row rows[] = {
+            {true, true, kernel(lm_eval_kernel<true, false>, "lm_eval_kernel<true, false>")},
+            {false, true, kernel(lm_eval_kernel<false, false>, "lm_eval_kernel<false, false>")},
+            {true, false, kernel(lm_eval_kernel<true, true>, "lm_eval_kernel<true, true>")},
+            {false, false, kernel(lm_eval_kernel<false, true>, "lm_eval_kernel<false, true>")},
+        };
+        const auto k = find_kernel(
+            rows, [&](const Row &q) { return q.lds_tiles == lds_tiles && q.jbasis == jbasis; });
+        return launch(k, grid, block, lds, 48 * 1024, s, b->stamps, b->val, b->ierr, b->jac,
+                      model, ng0, states, stamp_obj, stamp_band, psf, npsf, sums, status,
+                      no_skip, tile_cap, stamp_stats);
     }
     if (stamp_stats) {
         set_last_error_msg("lm_eval: the loglike statistics come with the analytic "
@@ -1875,54 +1885,38 @@ int launch_lm_eval(const ngmix_batch *b, int model, int fd, const lm_state *stat
         const char *e = getenv("NGMIX_LM_FD_TILES");
         if (e) linear = e[0] == 'l';
     }
-#define NGMIX_FD_LAUNCH2(N, L, P, NAME)                                                 \
-    do {                                                                                \
-        census(NAME);                                                                   \
-        if (lds > 48 * 1024)                                                            \
-            NGMIX_HIP_CHECK(hipFuncSetAttribute(                                        \
-                (const void *)lm_eval_fd_kernel<N, L, P>,                               \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
-        hipLaunchKernelGGL((lm_eval_fd_kernel<N, L, P>), grid, block, lds, s, b->stamps, \
-                           b->val, b->ierr, b->jac, model, ng0, states, stamp_obj,      \
-                           stamp_band, psf, npsf, sums, status, no_skip, jac_point);    \
-    } while (0)
-#define NGMIX_FD_LAUNCH1(N, L)                                                          \
-    NGMIX_FD_LAUNCH2(N, L, false,                                                       \
-                     L ? "lm_eval_fd_kernel<" #N ", linear>" : "lm_eval_fd_kernel<" #N ">")
-    if (precise) {
+    if (precise && nloc < NGMIX_LM_PRECISE_MIN_NLOC) {
         // (built for the fits it serves: nine local parameters and up)
-        if (nloc < NGMIX_LM_PRECISE_MIN_NLOC) {
-            set_last_error_msg("lm_eval: the precise pass serves nloc >= 9");
-            return NGMIX_ERR_BAD_ARG;
-        }
-#define NGMIX_FD_PRECISE(N)                                                                  \
-    do {                                                                                     \
-        if (linear) NGMIX_FD_LAUNCH2(N, true, true, "lm_eval_fd_kernel<" #N ", linear, precise>"); \
-        else NGMIX_FD_LAUNCH2(N, false, true, "lm_eval_fd_kernel<" #N ", precise>");        \
-    } while (0)
-        if (nloc <= 10) NGMIX_FD_PRECISE(10);
-        else if (nloc <= 12) NGMIX_FD_PRECISE(12);
-        else NGMIX_FD_PRECISE(14);
-#undef NGMIX_FD_PRECISE
-        NGMIX_HIP_CHECK(hipGetLastError());
-        return NGMIX_OK;
+        set_last_error_msg("lm_eval: the precise pass serves nloc >= 9");
+        return NGMIX_ERR_BAD_ARG;
     }
-#define NGMIX_FD_LAUNCH(N)                                                              \
-    do {                                                                                \
-        if (linear) NGMIX_FD_LAUNCH1(N, true);                                          \
-        else NGMIX_FD_LAUNCH1(N, false);                                                \
-    } while (0)
-    if (nloc == 6) NGMIX_FD_LAUNCH(6);
-    else if (nloc == 7) NGMIX_FD_LAUNCH(7);
-    else if (nloc == 8) NGMIX_FD_LAUNCH(8);
-    else if (nloc <= 10) NGMIX_FD_LAUNCH(10);
-    else if (nloc <= 12) NGMIX_FD_LAUNCH(12);
-    else NGMIX_FD_LAUNCH(14);
-#undef NGMIX_FD_LAUNCH2
-#undef NGMIX_FD_LAUNCH1
-#undef NGMIX_FD_LAUNCH
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    static constexpr FdRow rows[] = {
+        fd_row<6, false, false>("lm_eval_fd_kernel<6>"),
+        fd_row<6, true, false>("lm_eval_fd_kernel<6, linear>"),
+        fd_row<7, false, false>("lm_eval_fd_kernel<7>"),
+        fd_row<7, true, false>("lm_eval_fd_kernel<7, linear>"),
+        fd_row<8, false, false>("lm_eval_fd_kernel<8>"),
+        fd_row<8, true, false>("lm_eval_fd_kernel<8, linear>"),
+        fd_row<10, false, false>("lm_eval_fd_kernel<10>"),
+        fd_row<10, true, false>("lm_eval_fd_kernel<10, linear>"),
+        fd_row<12, false, false>("lm_eval_fd_kernel<12>"),
+        fd_row<12, true, false>("lm_eval_fd_kernel<12, linear>"),
+        fd_row<14, false, false>("lm_eval_fd_kernel<14>"),
+        fd_row<14, true, false>("lm_eval_fd_kernel<14, linear>"),
+        fd_row<10, false, true>("lm_eval_fd_kernel<10, precise>"),
+        fd_row<10, true, true>("lm_eval_fd_kernel<10, linear, precise>"),
+        fd_row<12, false, true>("lm_eval_fd_kernel<12, precise>"),
+        fd_row<12, true, true>("lm_eval_fd_kernel<12, linear, precise>"),
+        fd_row<14, false, true>("lm_eval_fd_kernel<14, precise>"),
+        fd_row<14, true, true>("lm_eval_fd_kernel<14, linear, precise>"),
+    };
+    const int n = lm_fd_nloc(nloc);
+    const auto k = find_kernel(rows, [&](const FdRow &q) {
+        return q.n == n && q.linear == linear && q.precise == precise;
+    });
+    return launch(k, grid, block, lds, 48 * 1024, s, b->stamps, b->val, b->ierr, b->jac, model,
+                  ng0, states, stamp_obj, stamp_band, psf, npsf, sums, status, no_skip,
+                  jac_point);
 }
 
 int launch_lm_advance(lm_state *states, int64_t nobj, const int64_t *obj_start,
@@ -1974,40 +1968,24 @@ int launch_lm_advance(lm_state *states, int64_t nobj, const int64_t *obj_start,
         return launch_lm_advance_team(states, nobj, obj_start, stamp_band, sums, nloc, npars,
                                       obj_sums, nactive, stamp_stats, obj_stats,
                                       teams == 1 || teams == 2 ? teams : 4, s);
-    {
-        char name[64];
-        if (npars >= 6 && npars <= 10 && !generic)
-            snprintf(name, sizeof(name), "lm_advance_kernel<%d, true>", npars);
-        else
-            snprintf(name, sizeof(name), "lm_advance_kernel<%d, false>", LM_NPMAX);
-        census(name);
-    }
-    if (npars == 6 && !generic)
-        hipLaunchKernelGGL((lm_advance_kernel<6, true>), grid, block, 0, s, states, nobj,
-                           obj_start, stamp_band, sums, nloc, obj_sums, nactive, stamp_stats,
-                           obj_stats);
-    else if (npars == 7 && !generic)
-        hipLaunchKernelGGL((lm_advance_kernel<7, true>), grid, block, 0, s, states, nobj,
-                           obj_start, stamp_band, sums, nloc, obj_sums, nactive, stamp_stats,
-                           obj_stats);
-    else if (npars == 8 && !generic)
-        hipLaunchKernelGGL((lm_advance_kernel<8, true>), grid, block, 0, s, states, nobj,
-                           obj_start, stamp_band, sums, nloc, obj_sums, nactive, stamp_stats,
-                           obj_stats);
-    else if (npars == 9 && !generic)
-        hipLaunchKernelGGL((lm_advance_kernel<9, true>), grid, block, 0, s, states, nobj,
-                           obj_start, stamp_band, sums, nloc, obj_sums, nactive, stamp_stats,
-                           obj_stats);
-    else if (npars == 10 && !generic)
-        hipLaunchKernelGGL((lm_advance_kernel<10, true>), grid, block, 0, s, states, nobj,
-                           obj_start, stamp_band, sums, nloc, obj_sums, nactive, stamp_stats,
-                           obj_stats);
-    else
-        hipLaunchKernelGGL((lm_advance_kernel<LM_NPMAX, false>), grid, block, 0, s, states,
-                           nobj, obj_start, stamp_band, sums, nloc, obj_sums, nactive,
-                           stamp_stats, obj_stats);
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    struct Row {
+        int npars;
+        decltype(kernel(lm_advance_kernel<6, true>, "")) k;
+    };
+    static constexpr Row rows[] = {
+        {6, kernel(lm_advance_kernel<6, true>, "lm_advance_kernel<6, true>")},
+        {7, kernel(lm_advance_kernel<7, true>, "lm_advance_kernel<7, true>")},
+        {8, kernel(lm_advance_kernel<8, true>, "lm_advance_kernel<8, true>")},
+        {9, kernel(lm_advance_kernel<9, true>, "lm_advance_kernel<9, true>")},
+        {10, kernel(lm_advance_kernel<10, true>, "lm_advance_kernel<10, true>")},
+        {0, kernel(lm_advance_kernel<LM_NPMAX, false>, "lm_advance_kernel<14, false>")},
+    };
+    static_assert(LM_NPMAX == 14, "the census name of the generic form");
+    // (row 0: the generic form, for every count the register form is not built for)
+    const int reg = npars >= 6 && npars <= 10 && !generic ? npars : 0;
+    const auto k = find_kernel(rows, [&](const Row &q) { return q.npars == reg; });
+    return launch(k, grid, block, 0, NO_OPTIN, s, states, nobj, obj_start, stamp_band, sums,
+                  nloc, obj_sums, nactive, stamp_stats, obj_stats);
 }
 
 // nrounds x {pixel pass, prior rows, lmder step} queued by one host call

@@ -29,6 +29,7 @@
 // cross-work-group traffic: two runs give the same bits.
 #include "grad_common.hpp"
 #include "launch.hpp"
+#include "launch_util.hpp"
 
 namespace ngmix {
 
@@ -216,11 +217,9 @@ int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double 
     int max_ng;
     size_t lds;
     if (!grad_launch_sizes(b, "loglike_grad", true, 0, max_ng, lds)) return NGMIX_ERR_BAD_ARG;
-    census("loglike_grad_kernel");
-    hipLaunchKernelGGL(loglike_grad_kernel, dim3((unsigned)b->nstamps), dim3(WAVE), lds, s,
-                       b->stamps, b->val, b->ierr, b->jac, gmix, out, grad, status, max_ng);
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    return launch(kernel(loglike_grad_kernel, "loglike_grad_kernel"), dim3((unsigned)b->nstamps),
+                  dim3(WAVE), lds, NO_OPTIN, s, b->stamps, b->val, b->ierr, b->jac, gmix, out,
+                  grad, status, max_ng);
 }
 
 }  // namespace ngmix

@@ -11,6 +11,7 @@
 
 #include "iter_common.hpp"
 #include "launch_iter.hpp"
+#include "launch_util.hpp"
 
 #include <stdlib.h>
 
@@ -651,24 +652,14 @@ int launch_weighted_sums_grid(const ngmix_batch *b, const ngmix_gauss2d *gmix,
     const int ng = b->max_ngauss > 0 ? b->max_ngauss : 1;
     if (!(b->flags & NGMIX_BATCH_EXACT)) {
         const size_t lds = (size_t)ng * sizeof(EvalGauss) + 16;
-        census(nmom == 6 ? "wsums_wave_kernel<6>" : "wsums_wave_kernel<17>");
-        if (nmom == 6)
-            hipLaunchKernelGGL(wsums_wave_kernel<6>, dim3((unsigned)b->nstamps),
-                               dim3(WAVE), lds, s, b->stamps, b->val, b->ierr, b->jac,
-                               gmix, (char *)res, maxrad, status);
-        else
-            hipLaunchKernelGGL(wsums_wave_kernel<17>, dim3((unsigned)b->nstamps),
-                               dim3(WAVE), lds, s, b->stamps, b->val, b->ierr, b->jac,
-                               gmix, (char *)res, maxrad, status);
-        NGMIX_HIP_CHECK(hipGetLastError());
-        return NGMIX_OK;
+        const auto k = nmom == 6 ? kernel(wsums_wave_kernel<6>, "wsums_wave_kernel<6>")
+                                 : kernel(wsums_wave_kernel<17>, "wsums_wave_kernel<17>");
+        return launch(k, dim3((unsigned)b->nstamps), dim3(WAVE), lds, NO_OPTIN, s, b->stamps,
+                      b->val, b->ierr, b->jac, gmix, (char *)res, maxrad, status);
     }
-    census("weighted_sums_grid_kernel");
-    hipLaunchKernelGGL(weighted_sums_grid_kernel, dim3((unsigned)b->nstamps),
-                       dim3(BLOCK), wsums_lds(nmom, ng), s, b->stamps, b->val,
-                       b->ierr, b->jac, gmix, (char *)res, nmom, maxrad, status);
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    return launch(kernel(weighted_sums_grid_kernel, "weighted_sums_grid_kernel"),
+                  dim3((unsigned)b->nstamps), dim3(BLOCK), wsums_lds(nmom, ng), NO_OPTIN, s,
+                  b->stamps, b->val, b->ierr, b->jac, gmix, (char *)res, nmom, maxrad, status);
 }
 
 int launch_weighted_sums_list(const ngmix_gauss2d *wt, int ng,
@@ -1509,18 +1500,14 @@ __global__ __launch_bounds__(BLOCK) void admom_list_kernel(
 }
 
 template <int NT, int PPT>
-static void admom_launch(const ngmix_admom_conf *conf, const ngmix_batch *b,
-                         ngmix_gauss2d *wt, ngmix_admom_result *res, int32_t *status,
-                         hipStream_t s)
+static int admom_launch(const ngmix_admom_conf *conf, const ngmix_batch *b,
+                        ngmix_gauss2d *wt, ngmix_admom_result *res, int32_t *status,
+                        hipStream_t s)
 {
-    {
-        char name[64];
-        snprintf(name, sizeof(name), "admom_grid_kernel<%d, %d>", NT, PPT);
-        census(name);
-    }
-    hipLaunchKernelGGL((admom_grid_kernel<NT, PPT>), dim3((unsigned)b->nstamps),
-                       dim3(NT), 0, s, *conf, b->stamps, b->val, b->ierr, b->jac, wt,
-                       res, status);
+    static const CensusName name("admom_grid_kernel", {NT, PPT});
+    return launch(kernel(admom_grid_kernel<NT, PPT>, name.s), dim3((unsigned)b->nstamps),
+                  dim3(NT), 0, NO_OPTIN, s, *conf, b->stamps, b->val, b->ierr, b->jac, wt, res,
+                  status);
 }
 
 int launch_admom_grid(const ngmix_admom_conf *conf, const ngmix_batch *b,
@@ -1538,18 +1525,16 @@ int launch_admom_grid(const ngmix_admom_conf *conf, const ngmix_batch *b,
     if (nt == 0)
         nt = np <= 16 * 64 ? 64
              : (np <= 16 * 128 ? 128 : (np <= 36 * 64 ? 64 : (np <= 32 * 128 ? 128 : 256)));
-    if (nt == 64 && np <= 8 * 64) admom_launch<64, 8>(conf, b, wt, res, status, s);
-    else if (nt == 64 && np <= 16 * 64) admom_launch<64, 16>(conf, b, wt, res, status, s);
-    else if (nt <= 128 && np <= 8 * 128) admom_launch<128, 8>(conf, b, wt, res, status, s);
-    else if (nt <= 128 && np <= 16 * 128) admom_launch<128, 16>(conf, b, wt, res, status, s);
-    else if (nt == 64 && np <= 36 * 64) admom_launch<64, 36>(conf, b, wt, res, status, s);
-    else if (nt == 128 && np <= 32 * 128) admom_launch<128, 32>(conf, b, wt, res, status, s);
-    else if (np <= 4 * BLOCK) admom_launch<BLOCK, 4>(conf, b, wt, res, status, s);
-    else if (np <= 8 * BLOCK) admom_launch<BLOCK, 8>(conf, b, wt, res, status, s);
-    else if (np <= 16 * BLOCK) admom_launch<BLOCK, 16>(conf, b, wt, res, status, s);
-    else admom_launch<BLOCK, 0>(conf, b, wt, res, status, s);
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    if (nt == 64 && np <= 8 * 64) return admom_launch<64, 8>(conf, b, wt, res, status, s);
+    if (nt == 64 && np <= 16 * 64) return admom_launch<64, 16>(conf, b, wt, res, status, s);
+    if (nt <= 128 && np <= 8 * 128) return admom_launch<128, 8>(conf, b, wt, res, status, s);
+    if (nt <= 128 && np <= 16 * 128) return admom_launch<128, 16>(conf, b, wt, res, status, s);
+    if (nt == 64 && np <= 36 * 64) return admom_launch<64, 36>(conf, b, wt, res, status, s);
+    if (nt == 128 && np <= 32 * 128) return admom_launch<128, 32>(conf, b, wt, res, status, s);
+    if (np <= 4 * BLOCK) return admom_launch<BLOCK, 4>(conf, b, wt, res, status, s);
+    if (np <= 8 * BLOCK) return admom_launch<BLOCK, 8>(conf, b, wt, res, status, s);
+    if (np <= 16 * BLOCK) return admom_launch<BLOCK, 16>(conf, b, wt, res, status, s);
+    return admom_launch<BLOCK, 0>(conf, b, wt, res, status, s);
 }
 
 int launch_admom_list(const ngmix_admom_conf *conf, const ngmix_pixel *pixels,

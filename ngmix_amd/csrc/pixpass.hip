@@ -20,6 +20,7 @@
 
 #include "device_utils.hpp"
 #include "launch.hpp"
+#include "launch_util.hpp"
 
 namespace ngmix {
 
@@ -1103,6 +1104,53 @@ static int pick_k(int max_npix)
     return 9;
 }
 
+// The one place that says which kernel serves a grid pass and under which
+// name the launch census counts it.  The exact kernels: K = 4 or 9 tiles per
+// wave per round (pick_k).
+template <int OP>
+static auto pick_grid_kernel(bool k4)
+{
+    constexpr const char *name = OP == OP_LOGLIKE ? "pixpass_grid_kernel<loglike>"
+                                 : OP == OP_FDIFF ? "pixpass_grid_kernel<fdiff>"
+                                 : OP == OP_S2N   ? "pixpass_grid_kernel<s2n>"
+                                                  : "pixpass_grid_kernel<render>";
+    return kernel(k4 ? pixpass_grid_kernel<OP, 4> : pixpass_grid_kernel<OP, 9>, name);
+}
+
+// The fused kernels.  seven: seven waves per SIMD (get_loglike); stream: every
+// weight map is streamed; overwrite: the render into a fresh image.
+// (The census counts the streaming kernels under the names of the kernels they
+// stand in for: the form of the loop is the same, and what a census asserts is
+// that no generic kernel served the workload.)
+using WaveKernel = decltype(kernel(pixpass_wave_kernel<OP_LOGLIKE, false, 8>, ""));
+
+template <int FOP, int TW>
+static WaveKernel pick_wave_kernel(bool masked, bool seven, bool stream, bool overwrite)
+{
+    if constexpr (FOP == OP_LOGLIKE) {
+        constexpr const char *n7 = "pixpass_wave_kernel7<loglike>";
+        if (seven && stream)
+            return masked ? kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, true, 8>, n7)
+                          : kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8>, n7);
+        if (seven)
+            return masked ? kernel(pixpass_wave_kernel7<OP_LOGLIKE, true, 8>, n7)
+                          : kernel(pixpass_wave_kernel7<OP_LOGLIKE, false, 8>, n7);
+    }
+    constexpr const char *n = FOP == OP_LOGLIKE ? "pixpass_wave_kernel<loglike>"
+                              : FOP == OP_FDIFF ? "pixpass_wave_kernel<fdiff>"
+                              : FOP == OP_S2N   ? "pixpass_wave_kernel<s2n>"
+                                                : "pixpass_wave_kernel<render>";
+    if constexpr (FOP == OP_RENDER_FAST) {
+        if (overwrite) return kernel(pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16>, n);
+    } else {
+        if (stream)
+            return masked ? kernel(pixpass_wave_kernel_stream<FOP, true, TW>, n)
+                          : kernel(pixpass_wave_kernel_stream<FOP, false, TW>, n);
+    }
+    return masked ? kernel(pixpass_wave_kernel<FOP, true, TW>, n)
+                  : kernel(pixpass_wave_kernel<FOP, false, TW>, n);
+}
+
 template <int OP>
 static int launch_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
                        const int64_t *out_start, int32_t *status, void *stream)
@@ -1132,72 +1180,26 @@ static int launch_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
     const bool exact = (b->flags & NGMIX_BATCH_EXACT) || OP == OP_RENDER_EXACT ||
                        a_tc > FUSED_TILE_CAP;
     hipStream_t s = (hipStream_t)stream;
-    const ngmix_stamp *a_stamps = b->stamps;
-    const double *a_val = b->val, *a_ierr = b->ierr;
-    const ngmix_jacobian *a_jac = b->jac;
-    int a_ng = max_ng, a_nc = nchunks_cap, a_ns = no_skip;
-    if (exact) {
-        a_ns = no_skip & 5;
-        dim3 grid((unsigned)b->nstamps), block(BLOCK);
-        const bool k4 = pick_k(b->max_npix) == 4;
-        const void *kern = k4 ? (const void *)pixpass_grid_kernel<OP, 4>
-                              : (const void *)pixpass_grid_kernel<OP, 9>;
-        if (lds > 64 * 1024)
-            NGMIX_HIP_CHECK(hipFuncSetAttribute(
-                kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        void *args[] = {&a_stamps, &a_val, &a_ierr, &a_jac, &gmix, &out, &out_start,
-                        &status, &a_ng, &a_nc, &a_ns};
-        census(OP == OP_LOGLIKE ? "pixpass_grid_kernel<loglike>"
-               : OP == OP_FDIFF ? "pixpass_grid_kernel<fdiff>"
-               : OP == OP_S2N   ? "pixpass_grid_kernel<s2n>"
-                                : "pixpass_grid_kernel<render>");
-        NGMIX_HIP_CHECK(hipLaunchKernel(kern, grid, block, args, lds, s));
-        return NGMIX_OK;
-    }
+    const dim3 grid((unsigned)b->nstamps);
+    if (exact)
+        return launch(pick_grid_kernel<OP>(pick_k(b->max_npix) == 4), grid, dim3(BLOCK), lds,
+                      64 * 1024, s, b->stamps, b->val, b->ierr, b->jac, gmix, out, out_start,
+                      status, max_ng, nchunks_cap, no_skip & 5);
     constexpr int FOP = (OP == OP_RENDER_EXACT) ? OP_RENDER_FAST : OP;
-    // zero-weight pixels only matter to the kernels that read ierr
-    const bool mk = b->any_masked && FOP != OP_RENDER_FAST;
-    const void *kern = mk ? (const void *)pixpass_wave_kernel<FOP, true, TW>
-                          : (const void *)pixpass_wave_kernel<FOP, false, TW>;
-    if (FOP == OP_RENDER_FAST && (no_skip & 4))
-        kern = (const void *)pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16>;
     static const bool six_waves = getenv("NGMIX_LOGLIKE_6WAVES") != nullptr;   // A/B knob
-    if (FOP == OP_LOGLIKE && !six_waves)
-        kern = mk ? (const void *)pixpass_wave_kernel7<OP_LOGLIKE, true, 8>
-                  : (const void *)pixpass_wave_kernel7<OP_LOGLIKE, false, 8>;
-    // no stamp of the batch has a uniform weight map (the caller says so with
-    // NGMIX_BATCH_STREAM_IERR, which is also the diagnostic): the kernels that
-    // stream every map
-    // (the launch census counts them under the names of the kernels they stand
-    // in for: the form of the loop is the same, and what a census asserts is
-    // that no generic kernel served the workload)
-    if constexpr (FOP != OP_RENDER_FAST) {
-        if (b->flags & NGMIX_BATCH_STREAM_IERR) {
-            kern = mk ? (const void *)pixpass_wave_kernel_stream<FOP, true, TW>
-                      : (const void *)pixpass_wave_kernel_stream<FOP, false, TW>;
-            if (FOP == OP_LOGLIKE && !six_waves)
-                kern = mk ? (const void *)pixpass_wave_kernel7_stream<OP_LOGLIKE, true, 8>
-                          : (const void *)pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8>;
-        }
-    }
+    // zero-weight pixels only matter to the kernels that read ierr; every map is
+    // streamed when no stamp of the batch has a uniform weight map (the caller
+    // says so with NGMIX_BATCH_STREAM_IERR, which is also the diagnostic)
+    const WaveKernel k = pick_wave_kernel<FOP, TW>(
+        b->any_masked && FOP != OP_RENDER_FAST, !six_waves,
+        (b->flags & NGMIX_BATCH_STREAM_IERR) != 0, (no_skip & 4) != 0);
     const size_t flds = lds_bytes(max_ng, nchunks_cap, a_tc);
     if (flds > 160 * 1024) {
         set_last_error_msg("stamp needs more than 160 KiB of LDS");
         return NGMIX_ERR_BAD_ARG;
     }
-    if (flds > 64 * 1024)
-        NGMIX_HIP_CHECK(hipFuncSetAttribute(
-            kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-    dim3 grid((unsigned)b->nstamps), block(WAVE);
-    void *args[] = {&a_stamps, &a_val, &a_ierr, &a_jac, &gmix, &out, &out_start,
-                    &status, &a_ng, &a_nc, &a_ns, &a_tc};
-    census(FOP == OP_LOGLIKE ? (six_waves ? "pixpass_wave_kernel<loglike>"
-                                          : "pixpass_wave_kernel7<loglike>")
-           : FOP == OP_FDIFF ? "pixpass_wave_kernel<fdiff>"
-           : FOP == OP_S2N   ? "pixpass_wave_kernel<s2n>"
-                             : "pixpass_wave_kernel<render>");
-    NGMIX_HIP_CHECK(hipLaunchKernel(kern, grid, block, args, flds, s));
-    return NGMIX_OK;
+    return launch(k, grid, dim3(WAVE), flds, 64 * 1024, s, b->stamps, b->val, b->ierr, b->jac,
+                  gmix, out, out_start, status, max_ng, nchunks_cap, no_skip, a_tc);
 }
 
 int launch_loglike_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,

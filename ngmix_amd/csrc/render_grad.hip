@@ -28,6 +28,7 @@
 // same bits.
 #include "grad_common.hpp"
 #include "launch.hpp"
+#include "launch_util.hpp"
 
 namespace ngmix {
 
@@ -156,17 +157,10 @@ int launch_render_vjp(const ngmix_batch *b, const ngmix_gauss2d *gmix, const dou
     int max_ng;
     size_t lds;
     if (!grad_launch_sizes(b, "render_vjp", true, 0, max_ng, lds)) return NGMIX_ERR_BAD_ARG;
-    if (fast_exp) {
-        census("render_vjp_kernel<fast>");
-        hipLaunchKernelGGL(render_vjp_kernel<true>, dim3((unsigned)b->nstamps), dim3(WAVE), lds,
-                           s, b->stamps, b->jac, gmix, gimage, grad, status, max_ng);
-    } else {
-        census("render_vjp_kernel<exact>");
-        hipLaunchKernelGGL(render_vjp_kernel<false>, dim3((unsigned)b->nstamps), dim3(WAVE),
-                           lds, s, b->stamps, b->jac, gmix, gimage, grad, status, max_ng);
-    }
-    NGMIX_HIP_CHECK(hipGetLastError());
-    return NGMIX_OK;
+    const auto k = fast_exp ? kernel(render_vjp_kernel<true>, "render_vjp_kernel<fast>")
+                            : kernel(render_vjp_kernel<false>, "render_vjp_kernel<exact>");
+    return launch(k, dim3((unsigned)b->nstamps), dim3(WAVE), lds, NO_OPTIN, s, b->stamps, b->jac,
+                  gmix, gimage, grad, status, max_ng);
 }
 
 }  // namespace ngmix

@@ -1,0 +1,132 @@
+// launcher_early_returns.hip -- a stand-alone host program: every launcher on
+// the paths that return before a launch (empty batch, bad model, bad nloc, LDS
+// too large, statistics pointers not paired, keys outside a dispatch table).
+// Built host-only under AddressSanitizer + UBSan by `make -C ngmix_amd/csrc
+// asan-launchers` and run on the CPU; it launches nothing and needs no GPU.
+#include <stdio.h>
+#include <string.h>
+
+#include "../ngmix_amd/csrc/launch.hpp"
+#include "../ngmix_amd/csrc/launch_iter.hpp"
+#include "../ngmix_amd/csrc/launch_util.hpp"
+
+using namespace ngmix;
+
+static int failures = 0;
+
+static void expect(const char *what, int got, int want, const char *msg_part = nullptr)
+{
+    const bool ok = got == want && (!msg_part || strstr(ngmix_last_error(), msg_part));
+    if (!ok) {
+        failures++;
+        printf("FAIL %s: returned %d (want %d), last error '%s'\n", what, got, want,
+               ngmix_last_error());
+    }
+}
+
+static void dummy_kernel_stub(int) {}
+
+int main()
+{
+    hipStream_t s = nullptr;
+    ngmix_batch empty;
+    memset(&empty, 0, sizeof(empty));
+    ngmix_batch b = empty;
+    b.nstamps = 2;
+    b.max_npix = 81;
+    b.max_nrow = b.max_ncol = 9;
+    b.max_ngauss = 1;
+    double x[64] = {0};
+    int32_t st[4] = {0};
+    const int BAD = NGMIX_ERR_BAD_ARG;
+
+    // lm_eval, in the order its checks fail
+    expect("lm_eval empty", launch_lm_eval(&empty, NGMIX_MODEL_EXP, 0, nullptr, nullptr, nullptr, nullptr, 1, x, st, nullptr, s), NGMIX_OK);
+    expect("lm_eval precise without fd", launch_lm_eval(&b, NGMIX_MODEL_EXP, 0, nullptr, nullptr, nullptr, nullptr, 1, x, st, nullptr, s, nullptr, true), BAD, "precise pass is a forward-difference");
+    expect("lm_eval bad model", launch_lm_eval(&b, 99, 0, nullptr, nullptr, nullptr, nullptr, 1, x, st, nullptr, s), BAD, "model must be");
+    expect("lm_eval coellip 6", launch_lm_eval(&b, NGMIX_MODEL_COELLIP + 256 * 6, 1, nullptr, nullptr, nullptr, nullptr, 1, x, st, nullptr, s), BAD, "model must be");
+    expect("lm_eval analytic bdf", launch_lm_eval(&b, NGMIX_MODEL_BDF, 0, nullptr, nullptr, nullptr, nullptr, 1, x, st, nullptr, s), BAD, "analytic jacobian exists");
+    expect("lm_eval analytic lds", launch_lm_eval(&b, NGMIX_MODEL_DEV, 0, nullptr, nullptr, nullptr, nullptr, 4000, x, st, nullptr, s), BAD, "too many composed gaussians");
+    expect("lm_eval fd stats", launch_lm_eval(&b, NGMIX_MODEL_EXP, 1, nullptr, nullptr, nullptr, nullptr, 1, x, st, x, s, x), BAD, "stamp_stats must be NULL");
+    expect("lm_eval fd lds", launch_lm_eval(&b, NGMIX_MODEL_DEV, 1, nullptr, nullptr, nullptr, nullptr, 4000, x, st, nullptr, s, x), BAD, "too many composed gaussians");
+    expect("lm_eval precise nloc 6", launch_lm_eval(&b, NGMIX_MODEL_EXP, 1, nullptr, nullptr, nullptr, nullptr, 1, x, st, nullptr, s, x, true), BAD, "precise pass serves");
+    for (int nloc = 0; nloc <= 20; nloc++) {
+        const int n = lm_fd_nloc(nloc);
+        if (!(n == 6 || n == 7 || n == 8 || n == 10 || n == 12 || n == 14) || (nloc >= 6 && nloc <= 14 && n < nloc)) {
+            failures++;
+            printf("FAIL lm_fd_nloc(%d) = %d\n", nloc, n);
+        }
+    }
+
+    // lm_advance / lm_precise_cov / lm_rounds
+    expect("lm_advance empty", launch_lm_advance(nullptr, 0, nullptr, nullptr, x, 6, nullptr, nullptr, nullptr, nullptr, s), NGMIX_OK);
+    expect("lm_advance nloc 1", launch_lm_advance(nullptr, 5, nullptr, nullptr, x, 1, nullptr, nullptr, nullptr, nullptr, s), BAD);
+    expect("lm_advance nloc 15", launch_lm_advance(nullptr, 5, nullptr, nullptr, x, 15, nullptr, nullptr, nullptr, nullptr, s), BAD);
+    expect("lm_advance npars 15", launch_lm_advance(nullptr, 5, nullptr, nullptr, x, 6 + 256 * 15, nullptr, nullptr, nullptr, nullptr, s), BAD);
+    expect("lm_advance npars < nloc", launch_lm_advance(nullptr, 5, nullptr, nullptr, x, 8 + 256 * 6, nullptr, nullptr, nullptr, nullptr, s), BAD);
+    expect("lm_advance stats not paired", launch_lm_advance(nullptr, 5, nullptr, nullptr, x, 6 + 256 * 6, nullptr, nullptr, x, nullptr, s), BAD, "go together");
+    expect("lm_advance stats not paired 2", launch_lm_advance(nullptr, 5, nullptr, nullptr, x, 6 + 256 * 6, nullptr, nullptr, nullptr, x, s), BAD, "go together");
+    expect("lm_precise_cov null", launch_lm_precise_cov(nullptr, x, s), BAD, "lm_precise_cov");
+    expect("lm_rounds null", launch_lm_rounds(nullptr, 1, nullptr, nullptr, nullptr, s), BAD, "lm_rounds");
+
+    // the pixel pass
+    expect("loglike empty", launch_loglike_grid(&empty, nullptr, x, st, nullptr), NGMIX_OK);
+    expect("fdiff empty", launch_fdiff_grid(&empty, nullptr, x, nullptr, st, nullptr), NGMIX_OK);
+    expect("render empty", launch_render_grid(&empty, nullptr, x, 1, st, nullptr), NGMIX_OK);
+    expect("s2n empty", launch_s2n_grid(&empty, nullptr, x, st, nullptr), NGMIX_OK);
+    ngmix_batch big = b;
+    big.max_ngauss = 100000;
+    expect("loglike lds", launch_loglike_grid(&big, nullptr, x, st, nullptr), BAD, "160 KiB");
+    expect("render exact lds", launch_render_grid(&big, nullptr, x, 0, st, nullptr), BAD, "160 KiB");
+
+    // EM and moments
+    ngmix_em_conf ec;
+    memset(&ec, 0, sizeof(ec));
+    expect("em_grid empty", launch_em_grid(0, &ec, &empty, nullptr, 1, nullptr, 1, nullptr, x, 0, x, st, s), NGMIX_OK);
+    expect("em_grid kind", launch_em_grid(4, &ec, &b, nullptr, 1, nullptr, 1, nullptr, x, 0, x, st, s), BAD);
+    expect("em_grid ngauss 11", launch_em_grid(0, &ec, &b, nullptr, 11, nullptr, 1, nullptr, x, 0, x, st, s), BAD, "more than 10");
+    expect("em_list ngauss 11", launch_em_list(0, &ec, nullptr, 10, x, nullptr, 11, nullptr, 1, nullptr, 0, x, st, s), BAD, "more than 10");
+    expect("em_list npsf 0", launch_em_list(0, &ec, nullptr, 10, x, nullptr, 1, nullptr, 0, nullptr, 0, x, st, s), BAD);
+    ngmix_batch wide = b;
+    wide.max_npix = 5000;
+    expect("em_wave_hi range", launch_em_wave_hi(0, &ec, &wide, nullptr, 5, nullptr, 1, nullptr, x, 0, x, st, s), BAD, "launch_em_wave_hi");
+    expect("em_wave_8 range", launch_em_wave_8(1, &ec, &wide, nullptr, 8, nullptr, 1, nullptr, x, 0, x, st, s), BAD, "launch_em_wave_8");
+    expect("em_wave_8 ngauss", launch_em_wave_8(0, &ec, &b, nullptr, 9, nullptr, 1, nullptr, x, 0, x, st, s), BAD, "launch_em_wave_8");
+    expect("em_wave to 8 range", launch_em_wave(0, &ec, &wide, nullptr, 7, nullptr, 1, nullptr, x, 0, x, st, s), BAD, "launch_em_wave_8");
+    expect("wsums empty", launch_weighted_sums_grid(&empty, nullptr, x, 6, x, st, s), NGMIX_OK);
+    expect("wsums nmom", launch_weighted_sums_grid(&b, nullptr, x, 7, x, st, s), BAD);
+    expect("wsums list nmom", launch_weighted_sums_list(nullptr, 1, nullptr, 4, x, 7, 1.0, st, s), BAD);
+    expect("admom empty", launch_admom_grid(nullptr, &empty, nullptr, nullptr, st, s), NGMIX_OK);
+    expect("deriv_grid empty", launch_deriv_grid(&empty, x, x, x, nullptr, s), NGMIX_OK);
+
+    // the gradient kernels
+    expect("loglike_grad empty", launch_loglike_grad(&empty, nullptr, x, x, st, s), NGMIX_OK);
+    expect("loglike_grad no val", launch_loglike_grad(&b, nullptr, x, x, st, s), BAD, "val and ierr");
+    expect("render_vjp empty", launch_render_vjp(&empty, nullptr, x, 1, x, st, s), NGMIX_OK);
+    expect("render_vjp null", launch_render_vjp(&b, nullptr, nullptr, 1, x, st, s), BAD, "are required");
+    expect("fisher K", launch_fisher(&b, nullptr, x, 17, x, 1, x, st, s), BAD, "K must be");
+    expect("fisher empty", launch_fisher(&empty, nullptr, x, 4, x, 1, x, st, s), NGMIX_OK);
+    expect("fisher null", launch_fisher(&b, nullptr, nullptr, 4, x, 1, x, st, s), BAD, "are required");
+    expect("fisher no weight", launch_fisher(&b, nullptr, x, 4, nullptr, 1, x, st, s), BAD, "needs ierr");
+
+    // keys outside a dispatch table: no kernel, and launch() refuses
+    struct Row {
+        int key;
+        Kernel<int> k;
+    };
+    static const Row rows[] = {{1, {dummy_kernel_stub, "one"}}, {2, {dummy_kernel_stub, "two"}}};
+    const auto hit = find_kernel(rows, [](const Row &q) { return q.key == 2; });
+    const auto miss = find_kernel(rows, [](const Row &q) { return q.key == 3; });
+    if (!hit.fn || strcmp(hit.name, "two") != 0 || miss.fn) {
+        failures++;
+        printf("FAIL find_kernel\n");
+    }
+    expect("launch of no kernel", launch(miss, dim3(1), dim3(1), 0, NO_OPTIN, s, 0), BAD, "no kernel is built");
+    const CensusName name("k", {1, 22, 333});
+    if (strcmp(name.s, "k<1, 22, 333>") != 0) {
+        failures++;
+        printf("FAIL CensusName '%s'\n", name.s);
+    }
+    printf("launcher_early_returns: %d failure(s)\n", failures);
+    return failures != 0;
+}
