@@ -478,6 +478,43 @@ int ngmix_render_vjp_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
 int ngmix_fisher_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
                        const double *dgpars, int K, const double *weight, int fast_exp,
                        double *out, int32_t *status, void *stream);
+/* ---- many objects, one frame (csrc/scene.hip).  The frame is nrow x ncol
+   doubles, row-major, cut into tiles of 4 rows x 16 columns: tile
+   (ty, tx) = ty * ceil(ncol / 16) + tx.  Fast-exp semantics only
+   (gauss2d_eval_pixel_fast): the chi2 < 25 gate is what makes binning exact. */
+#define NGMIX_SCENE_GAUSS_BYTES 64
+/* per object i (ngauss gaussians at gmix[i * ngauss], jacobian jac[i] with
+   row0 / col0 in FRAME pixel coordinates): norms as ngmix_render_batch sets
+   them (lazily, written back), status[i] = 0 or the code of the first gaussian
+   the norms refuse; gev[i * ngauss + g] (NGMIX_SCENE_GAUSS_BYTES each) = the
+   evaluation record and chi2 < 25 pixel box of gaussian g, for
+   ngmix_scene_render; boxes[8 * i ..] = rmin, rmax, cmin, cmax of the union of
+   the boxes clipped to the frame (inclusive), then the inclusive tile ranges
+   ty_lo, ty_hi, tx_lo, tx_hi.  A refused object, or one that misses the frame,
+   covers nothing: 0, -1 in every pair. */
+int ngmix_scene_boxes(ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac, int64_t n,
+                      int nrow, int ncol, void *gev, int32_t *boxes, int32_t *status,
+                      void *stream);
+/* one wave per tile: tile T adds the objects pair_obj[tile_start[T] ..
+   tile_start[T + 1]) (ascending object index; tile_start has ntiles + 1
+   entries, the last npairs) to its pixels.  Per object m = sum_g value_g in
+   gaussian order from 0.0, then pixel = pixel + m; the pixel starts from the
+   frame's value, or (fresh != 0) from 0.0 and the whole frame is written
+   without being read.  fresh == 0: a tile without objects is neither read nor
+   written.  The bits of ngmix_render_batch (NGMIX_BATCH_EXACT, fast_exp) over
+   the objects one after the other; no atomics. */
+int ngmix_scene_render(const void *gev, int ngauss, const ngmix_jacobian *jac,
+                       const int64_t *pair_obj, int64_t npairs, const int64_t *tile_start,
+                       int nrow, int ncol, double *frame, int fresh, void *stream);
+/* n windows of the frame into a packed layout: win[4 * i ..] = r_lo, c_lo,
+   nrow_i, ncol_i (frame pixel indices, any part may lie outside the frame),
+   window i row-major at out[pix_off[i]].  mode 0: the values; mode 1:
+   ierr = sqrt(max(w, 0)) of a weight frame (pixels_nb.py:49-52).  Outside the
+   frame: 0.0.  win_host: NULL, or the caller's host copy of win, checked before
+   the launch (a window with a non-positive shape is refused). */
+int ngmix_frame_gather(const double *frame, int nrow, int ncol, const int32_t *win,
+                       const int32_t *win_host, const int64_t *pix_off, int64_t n, int mode,
+                       double *out, void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

@@ -52,6 +52,7 @@ from .gaussmom import GaussMom, GaussMomBatch  # noqa: F401
 from . import psfflux  # noqa: F401
 from .psfflux import PSFFluxFitter, PSFFluxBatch  # noqa: F401
 from . import batch  # noqa: F401
+from . import scene  # noqa: F401
 from . import prior_batch  # noqa: F401
 from . import lm_batch  # noqa: F401
 from .lm_batch import LMBatchFitter  # noqa: F401

@@ -49,6 +49,13 @@ one HIP kernel (csrc/fisher.hip, ngmix_fisher_batch) that contracts the same
 first derivatives with d theta / d pars and forms the outer products without
 writing J to memory.  stamp_fisher() is the raw form over (nstamps, G, 6)
 mixtures with a caller's tangents (nstamps, G, 6, K).
+
+A whole frame: scene_render() draws a catalogue into ONE image (every object
+with a jacobian of its own, in frame coordinates; csrc/scene.hip), so any torch
+loss on the frame gets gradients with respect to every object's parameters:
+
+    frame = autodiff.scene_render((4096, 4096), jacobians, pars, "exp", psf=psf)
+    ((frame - data) ** 2 * weight).sum().backward()
 """
 import ctypes
 import math
@@ -60,7 +67,7 @@ from .batch import GMixBatch, _dptr, _on_device, _stream, _torch
 from .gmix import get_model_num, get_model_name
 
 __all__ = ["mixture_from_pars", "convolve", "stamp_loglike_grad", "loglike", "lnprob",
-           "stamp_render", "render", "stamp_fisher", "fisher", "covariance"]
+           "stamp_render", "render", "stamp_fisher", "fisher", "covariance", "scene_render"]
 
 # the model tables of csrc/common.hpp (gmix_nb.py:243-304): 0-5 exp,
 # 6-15 dev, 16-18 turb, 19 gauss
@@ -835,3 +842,166 @@ def covariance(stamps, pars, model, psf=None, stamp_obj=None, stamp_band=None,
     if return_flags:
         return cov, flag
     return cov
+
+
+class _SceneGeometry(object):
+    """what _stamp_mixtures asks of its stamps: one "stamp" per object"""
+
+    def __init__(self, n, device):
+        self.n = int(n)
+        self.device = device
+
+
+def _make_scene_functions():
+    torch = _torch()
+    from . import scene as _scene
+    from .batch import StampBatch
+
+    class _PoisonRows(torch.autograd.Function):
+        """forward: x itself; backward: the gradient with NaN in the rows of
+        the objects that holder["flag"] marks by then (the flags come out of
+        the forward pass that follows)"""
+
+        @staticmethod
+        def forward(ctx, x, holder):
+            ctx.holder = holder
+            return x.view_as(x)
+
+        @staticmethod
+        def backward(ctx, g):
+            flag = ctx.holder.get("flag")
+            if flag is None:
+                return g, None
+            bad = (flag != 0).reshape((-1,) + (1,) * (g.ndim - 1))
+            return torch.where(bad, torch.full_like(g, math.nan), g), None
+
+    class _SceneRender(torch.autograd.Function):
+        """forward: the scene kernels (scene.render_scene's bits); backward:
+        every object's clipped union box cut out of the upstream frame
+        (ngmix_frame_gather), then one ngmix_render_vjp_batch call (fast) on
+        those ragged windows"""
+
+        @staticmethod
+        def forward(ctx, gpars, image, jac, shape, code):
+            n, G, _ = gpars.shape
+            nrow, ncol = shape
+            rec = _gauss_records(gpars, True)
+            # an object refused before the kernels (|g| >= 1, a zero-flux psf)
+            # is left out: all-zero records, which the norms refuse
+            rec = torch.where((code != 0).repeat_interleave(G)[:, None],
+                              torch.zeros_like(rec), rec)
+            frame = None if image is None else image.detach().clone().contiguous()
+            frame, status, boxes = _scene._render_records(nrow, ncol, rec, G, n, jac, frame,
+                                                          None, boxes_to_host=True)
+            ctx.boxes = boxes
+            ctx.shape = (n, G, nrow, ncol)
+            ctx.has_image = image is not None
+            ctx.save_for_backward(rec, status, jac)
+            ctx.mark_non_differentiable(status)
+            return frame, status
+
+        @staticmethod
+        def backward(ctx, g_frame, g_status):
+            _first_order_only("scene_render")
+            rec, status, jac = ctx.saved_tensors
+            n, G, nrow, ncol = ctx.shape
+            dev = rec.device
+            U = g_frame.to(torch.float64).contiguous()
+            g_image = U if ctx.has_image else None
+            if n == 0:
+                return rec.new_zeros((0, G, 6)), g_image, None, None, None
+            hb = ctx.boxes.astype(np.int64)
+            hit = hb[:, 1] >= hb[:, 0]
+            # (an object that misses the frame: a 1 x 1 window, gradient zeroed)
+            r_lo = np.where(hit, hb[:, 0], 0)
+            c_lo = np.where(hit, hb[:, 2], 0)
+            wr = np.where(hit, hb[:, 1] - hb[:, 0] + 1, 1)
+            wc = np.where(hit, hb[:, 3] - hb[:, 2] + 1, 1)
+            npix = wr * wc
+            off = np.concatenate([[0], np.cumsum(npix)[:-1]]).astype(np.int64)
+            gimg = _scene._gather(U, np.stack([r_lo, c_lo, wr, wc], axis=1), off,
+                                  int(npix.sum()), 0)
+            wjac = jac.clone()
+            wjac[:, 0] -= torch.from_numpy(r_lo.astype(np.float64)).to(dev)
+            wjac[:, 1] -= torch.from_numpy(c_lo.astype(np.float64)).to(dev)
+            stamps = StampBatch(None, None, wjac, wr, wc, off, False)
+            grad = torch.empty((n * G, 6), dtype=torch.float64, device=dev)
+            vstatus = torch.empty(n, dtype=torch.int32, device=dev)
+            b = stamps._batch(G)
+            with _on_device(dev):
+                st = _lib.lib().ngmix_render_vjp_batch(
+                    ctypes.byref(b), _dptr(rec), _dptr(gimg), 1, _dptr(grad), _dptr(vstatus),
+                    _stream())
+            _lib.check(st, "ngmix_render_vjp_batch")
+            grad = grad.reshape(n, G, 6)
+            ok = ((status == 0) & torch.from_numpy(hit).to(dev))[:, None, None]
+            return torch.where(ok, grad, torch.zeros_like(grad)), g_image, None, None, None
+
+    return _PoisonRows, _SceneRender
+
+
+_SCENE_FUNCS = None
+
+
+def scene_render(shape, jacobians, pars, model, psf=None, ngauss=None, image=None,
+                 return_flags=False, fast_exp=True):
+    """
+    A catalogue drawn into ONE frame: the (nrow, ncol) image of the nobj
+    objects pars (nobj, npars: the model's parameters with one flux), object i
+    with jacobians[i] (row0 / col0 in FRAME pixel coordinates; centres may lie
+    outside the frame) and, with psf, its own psf mixture (a GMixBatch or a
+    (nobj, P, 6) tensor).  Differentiable with respect to pars, to a psf tensor
+    and to image (an (nrow, ncol) tensor the objects are added to; it is not
+    modified).  The values are scene.render_scene's, bit for bit: objects
+    added in ascending index (fast exp; fast_exp=False is refused).
+
+    Backward: each object's chi2 < 25 box, clipped to the frame, is cut out of
+    the upstream gradient frame and one ngmix_render_vjp_batch call (deriv_
+    images' convention, as render(fast_exp=True)) runs over those windows; a
+    gaussian contributes nothing outside its box, so the window loses nothing.
+    An object that misses the frame gets a zero gradient.  The gradient with
+    respect to image is the upstream frame.  First derivatives only.
+
+    With return_flags, also (nobj,) int32 flags (_lib.ERR_*).  An object the
+    reference would refuse (|g| >= 1, a zero-flux psf, a refused gaussian) is
+    LEFT OUT of the frame and reported in flags; its gradient rows, and its psf
+    rows' gradient rows, are NaN, and every other object's pixels and gradients
+    are bit-identical with or without it.  Deliberately not render()'s
+    NaN-on-every-pixel of a flagged object's stamps: here the objects share
+    their pixels, and one bad catalogue row must not erase a frame.
+    """
+    global _SCENE_FUNCS
+    torch = _torch()
+    from . import scene as _scene
+    nrow, ncol = _scene._frame_shape(shape)
+    if not fast_exp:
+        raise ValueError("scene_render: only fast_exp=True is built: the chi2 < 25 gate of "
+                         "the fast exp is what makes the tile binning exact")
+    if not isinstance(pars, torch.Tensor) or pars.ndim != 2:
+        raise ValueError("scene_render: pars must be an (nobj, npars) tensor")
+    nobj = int(pars.shape[0])
+    _scene._check_jacobians(jacobians, nobj, "scene_render")
+    _scene._check_image(image, nrow, ncol, "scene_render")
+    from .batch import _require_cuda
+    dev = _require_cuda(pars.device)
+    if image is not None and image.device != dev:
+        raise ValueError("scene_render: image must live on pars' device (%s)" % dev)
+    if _SCENE_FUNCS is None:
+        _SCENE_FUNCS = _make_scene_functions()
+    poison, render_fn = _SCENE_FUNCS
+    holder = {}
+    pars_in = poison.apply(pars, holder) if pars.requires_grad else pars
+    psf_in = psf
+    if psf is not None and not isinstance(psf, GMixBatch):
+        psf_in = _psf_tensor(psf, nobj, dev)
+        if psf_in.requires_grad:
+            psf_in = poison.apply(psf_in, holder)
+    _, _, mix, code, _ = _stamp_mixtures(_SceneGeometry(nobj, dev), pars_in, model, psf_in,
+                                         None, None, ngauss)
+    jac = _scene._jacobian_tensor(jacobians, nobj, dev)
+    frame, status = render_fn.apply(mix, image, jac, (nrow, ncol), code)
+    flag = torch.where(code == 0, status, code)
+    holder["flag"] = flag
+    if return_flags:
+        return frame, flag
+    return frame

@@ -598,6 +598,30 @@ int ngmix_fisher_batch(const ngmix_batch *batch, const ngmix_gauss2d *gmix,
                          (hipStream_t)stream);
 }
 
+int ngmix_scene_boxes(ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac, int64_t n,
+                      int nrow, int ncol, void *gev, int32_t *boxes, int32_t *status,
+                      void *stream)
+{
+    return launch_scene_boxes(gmix, ngauss, jac, n, nrow, ncol, gev, boxes, status,
+                              (hipStream_t)stream);
+}
+
+int ngmix_scene_render(const void *gev, int ngauss, const ngmix_jacobian *jac,
+                       const int64_t *pair_obj, int64_t npairs, const int64_t *tile_start,
+                       int nrow, int ncol, double *frame, int fresh, void *stream)
+{
+    return launch_scene_render(gev, ngauss, jac, pair_obj, npairs, tile_start, nrow, ncol,
+                               frame, fresh, (hipStream_t)stream);
+}
+
+int ngmix_frame_gather(const double *frame, int nrow, int ncol, const int32_t *win,
+                       const int32_t *win_host, const int64_t *pix_off, int64_t n, int mode,
+                       double *out, void *stream)
+{
+    return launch_frame_gather(frame, nrow, ncol, win, win_host, pix_off, n, mode, out,
+                               (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)

@@ -46,6 +46,16 @@ int launch_render_vjp(const ngmix_batch *b, const ngmix_gauss2d *gmix, const dou
 int launch_fisher(const ngmix_batch *b, const ngmix_gauss2d *gmix, const double *dgpars,
                   int K, const double *weight, int fast_exp, double *out, int32_t *status,
                   hipStream_t s);
+// scene.hip
+int launch_scene_boxes(ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac, int64_t n,
+                       int nrow, int ncol, void *gev, int32_t *boxes, int32_t *status,
+                       hipStream_t s);
+int launch_scene_render(const void *gev, int ngauss, const ngmix_jacobian *jac,
+                        const int64_t *pair_obj, int64_t npairs, const int64_t *tile_start,
+                        int nrow, int ncol, double *frame, int fresh, hipStream_t s);
+int launch_frame_gather(const double *frame, int nrow, int ncol, const int32_t *win,
+                        const int32_t *win_host, const int64_t *pix_off, int64_t n, int mode,
+                        double *out, hipStream_t s);
 // noisecov.hip
 int launch_noise_cov_blocks(const double *dimg, const int64_t *stamp_idx, int64_t m,
                             const int64_t *pix_off, const double *ierr, const double *noise,

@@ -1,0 +1,193 @@
+"""
+The scene renderer on a crowded frame: N 'exp' (x)
+3-gaussian psf objects of the benchmark's parameter draws at uniform positions
+of a SIZE x SIZE frame.  Reports the three stages by HIP events, the pair
+count, render_scene end to end against the long way (per-object windows
+rendered as a ragged StampBatch with the fused render, then
+index_put_(accumulate=True) into the frame), alternating, median of 5, the
+largest difference of the two frames, and one forward + backward of
+autodiff.scene_render under a squared-residual loss.
+
+    python tools/bench_scene.py [--n 30000] [--size 4096] [--out profiles/scene_bench.txt]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SCALE = 0.263
+
+
+def draws(n, size, seed):
+    rng = np.random.RandomState(seed)
+    pars = np.zeros((n, 6))
+    pars[:, 0:2] = rng.uniform(-0.5, 0.5, size=(n, 2)) * SCALE
+    g = rng.normal(scale=0.1, size=(n, 2))
+    gmag = np.sqrt((g ** 2).sum(axis=1))
+    g *= np.where(gmag > 0.7, 0.7 / np.maximum(gmag, 1e-30), 1.0)[:, None]
+    pars[:, 2:4] = g
+    pars[:, 4] = rng.uniform(0.3, 1.5, size=n)
+    pars[:, 5] = rng.uniform(50.0, 500.0, size=n)
+    pos = rng.uniform(-20.0, size + 20.0, size=(n, 2))
+    jac = np.zeros((n, 8))
+    jac[:, 0:2] = pos
+    jac[:, 2] = jac[:, 5] = jac[:, 7] = SCALE
+    jac[:, 6] = SCALE ** 2
+    psf = np.zeros((n, 3, 6))
+    psf[:, :, 0] = (0.6, 0.3, 0.1)
+    psf[:, :, 3] = psf[:, :, 5] = (0.10, 0.18, 0.40)
+    return pars, jac, psf
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=30000)
+    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.txt"))
+    ap.add_argument("--no-backward", action="store_true")
+    args = ap.parse_args()
+
+    import torch
+    from ngmix_amd import _lib, autodiff, scene
+    from ngmix_amd.batch import GMixBatch, StampBatch, _dptr, _stream
+
+    n, size = args.n, args.size
+    shape = (size, size)
+    pars, jac, psf = draws(n, size, 4242)
+    d_pars = torch.from_numpy(pars).cuda()
+    d_psf = torch.from_numpy(psf).cuda()
+    d_jac = torch.from_numpy(jac).cuda()
+    mix, _ = autodiff.convolve(autodiff.mixture_from_pars(d_pars, "exp")[0], d_psf)
+    G = mix.shape[1]
+    rec = torch.zeros((n * G, 13), dtype=torch.float64, device="cuda")
+    rec[:, :6] = mix.reshape(-1, 6)
+    rec[:, 6] = rec[:, 3] * rec[:, 5] - rec[:, 4] * rec[:, 4]
+    gm = GMixBatch(rec, n, G)
+    assert int(gm.set_norms().abs().sum()) == 0
+    L = _lib.lib()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    say("scene bench: %d x %d frame, %d objects, G = %d" % (size, size, n, G))
+
+    # ---- the stages, by events
+    ntx = (size + scene.TILE_W - 1) // scene.TILE_W
+    nty = (size + scene.TILE_H - 1) // scene.TILE_H
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    stage = []
+    for rep in range(args.reps + 1):
+        boxes = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        gev = torch.empty((n * G, 8), dtype=torch.float64, device="cuda")
+        status = torch.empty(n, dtype=torch.int32, device="cuda")
+        frame = torch.empty(shape, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        ev[0].record()
+        _lib.check(L.ngmix_scene_boxes(_dptr(gm.data), G, _dptr(d_jac), n, size, size, _dptr(gev),
+                                       _dptr(boxes), _dptr(status), _stream()), "scene_boxes")
+        ev[1].record()
+        b = boxes.to(torch.int64)
+        pair_obj, tile_start = scene._tile_pairs(b[:, 4], b[:, 5], b[:, 6], b[:, 7], ntx, nty)
+        ev[2].record()
+        _lib.check(L.ngmix_scene_render(_dptr(gev), G, _dptr(d_jac), _dptr(pair_obj),
+                                        int(pair_obj.shape[0]), _dptr(tile_start), size, size,
+                                        _dptr(frame), 1, _stream()), "scene_render")
+        ev[3].record()
+        torch.cuda.synchronize()
+        if rep:
+            stage.append([ev[i].elapsed_time(ev[i + 1]) for i in range(3)])
+    stage = np.median(np.array(stage), axis=0)
+    npairs = int(pair_obj.shape[0])
+    per_tile = np.diff(tile_start.cpu().numpy())
+    say("pairs %d, objects per tile: mean %.3f, max %d, empty tiles %.1f%%"
+        % (npairs, npairs / (ntx * nty), per_tile.max(), 100.0 * (per_tile == 0).mean()))
+    say("stages (ms, median of %d): scene_boxes %.3f, binning %.3f, scene_render %.3f"
+        % (args.reps, stage[0], stage[1], stage[2]))
+
+    # ---- end to end against the long way, alternating
+    hb = boxes.cpu().numpy().astype(np.int64)
+    hit = hb[:, 1] >= hb[:, 0]
+    idx = np.nonzero(hit)[0]
+    r_lo, c_lo = hb[idx, 0], hb[idx, 2]
+    wr, wc = hb[idx, 1] - hb[idx, 0] + 1, hb[idx, 3] - hb[idx, 2] + 1
+    npix = wr * wc
+    off = np.concatenate([[0], np.cumsum(npix)[:-1]]).astype(np.int64)
+    wjac = jac[idx].copy()
+    wjac[:, 0] -= r_lo
+    wjac[:, 1] -= c_lo
+    sb = StampBatch(None, None, torch.from_numpy(wjac).cuda(), wr, wc, off, False)
+    gms = gm.select(idx)
+    d_npix = torch.from_numpy(npix).cuda()
+    d_off = torch.from_numpy(off).cuda()
+    d_rlo, d_clo = torch.from_numpy(r_lo).cuda(), torch.from_numpy(c_lo).cuda()
+    d_wc = torch.from_numpy(wc).cuda()
+    total = int(npix.sum())
+    say("long way: %d windows, %d pixels (%.2f x the frame)" % (len(idx), total,
+                                                               total / float(size * size)))
+
+    def long_way():
+        img, _ = sb.render(gms, fast_exp=True)
+        stamp = torch.repeat_interleave(torch.arange(len(idx), device="cuda"), d_npix,
+                                        output_size=total)
+        p = torch.arange(total, device="cuda") - d_off[stamp]
+        r = torch.div(p, d_wc[stamp], rounding_mode="floor")
+        c = p - r * d_wc[stamp]
+        flat = (d_rlo[stamp] + r) * size + (d_clo[stamp] + c)
+        out = torch.zeros(size * size, dtype=torch.float64, device="cuda")
+        out.index_put_((flat,), img, accumulate=True)
+        return out.reshape(shape)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, (time.perf_counter() - t0) * 1e3
+
+    timed(lambda: scene.render_scene(shape, gm, d_jac))
+    timed(long_way)
+    t_scene, t_long = [], []
+    for rep in range(args.reps):
+        (f_scene, _), t = timed(lambda: scene.render_scene(shape, gm, d_jac))
+        t_scene.append(t)
+        f_long, t = timed(long_way)
+        t_long.append(t)
+    say("render_scene end to end (ms): median %.3f, min %.3f, max %.3f"
+        % (np.median(t_scene), min(t_scene), max(t_scene)))
+    say("long way end to end (ms):     median %.3f, min %.3f, max %.3f"
+        % (np.median(t_long), min(t_long), max(t_long)))
+    peak = float(f_scene.abs().max())
+    say("largest |scene - long way| / peak: %.3g (peak %.6g)"
+        % (float((f_scene - f_long).abs().max()) / peak, peak))
+    del f_long
+
+    # ---- forward + backward of a squared-residual loss, one run
+    if not args.no_backward:
+        data = f_scene + 0.01 * torch.randn(shape, dtype=torch.float64, device="cuda")
+        p = d_pars.clone().requires_grad_(True)
+
+        def fwd_bwd():
+            frame = autodiff.scene_render(shape, d_jac, p, "exp", psf=d_psf)
+            ((frame - data) ** 2).sum().backward()
+            return frame
+
+        frame, t = timed(fwd_bwd)
+        say("scene_render forward + backward (ms, one run): %.3f; |grad| max %.6g, finite %s"
+            % (t, float(p.grad.abs().max()), bool(torch.isfinite(p.grad).all())))
+        assert bool((frame == f_scene).all())
+
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -109,6 +109,27 @@ int main()
     expect("fisher null", launch_fisher(&b, nullptr, nullptr, 4, x, 1, x, st, s), BAD, "are required");
     expect("fisher no weight", launch_fisher(&b, nullptr, x, 4, nullptr, 1, x, st, s), BAD, "needs ierr");
 
+    // the scene kernels
+    int32_t win[8] = {0, 0, 9, 9, 3, 3, 0, 5};
+    int64_t off[2] = {0, 81};
+    expect("scene_boxes n < 0", launch_scene_boxes(nullptr, 1, nullptr, -1, 8, 8, x, st, st, s), BAD, "must not be negative");
+    expect("scene_boxes G", launch_scene_boxes(nullptr, 0, nullptr, 2, 8, 8, x, st, st, s), BAD, "ngauss >= 1");
+    expect("scene_boxes frame", launch_scene_boxes(nullptr, 1, nullptr, 2, 0, 8, x, st, st, s), BAD, "nrow * ncol > 0");
+    expect("scene_boxes empty", launch_scene_boxes(nullptr, 1, nullptr, 0, 8, 8, nullptr, nullptr, nullptr, s), NGMIX_OK);
+    expect("scene_boxes null", launch_scene_boxes(nullptr, 1, nullptr, 2, 8, 8, x, st, st, s), BAD, "are required");
+    expect("scene_render npairs < 0", launch_scene_render(x, 1, nullptr, off, -1, off, 8, 8, x, 0, s), BAD, "must not be negative");
+    expect("scene_render G", launch_scene_render(x, 0, nullptr, off, 1, off, 8, 8, x, 0, s), BAD, "ngauss >= 1");
+    expect("scene_render frame", launch_scene_render(x, 1, nullptr, off, 1, off, 8, 0, x, 0, s), BAD, "nrow * ncol > 0");
+    expect("scene_render null frame", launch_scene_render(x, 1, nullptr, off, 0, off, 8, 8, nullptr, 1, s), BAD, "are required");
+    expect("scene_render null jac", launch_scene_render(x, 1, nullptr, off, 1, off, 8, 8, x, 0, s), BAD, "are required");
+    expect("scene_render nothing to add", launch_scene_render(nullptr, 1, nullptr, nullptr, 0, off, 8, 8, x, 0, s), NGMIX_OK);
+    expect("frame_gather n < 0", launch_frame_gather(x, 8, 8, win, nullptr, off, -1, 0, x, s), BAD, "must not be negative");
+    expect("frame_gather mode", launch_frame_gather(x, 8, 8, win, nullptr, off, 2, 2, x, s), BAD, "mode must be");
+    expect("frame_gather frame", launch_frame_gather(x, 0, 0, win, nullptr, off, 2, 0, x, s), BAD, "nrow * ncol > 0");
+    expect("frame_gather empty", launch_frame_gather(x, 8, 8, nullptr, nullptr, nullptr, 0, 0, nullptr, s), NGMIX_OK);
+    expect("frame_gather null", launch_frame_gather(nullptr, 8, 8, win, nullptr, off, 2, 0, x, s), BAD, "are required");
+    expect("frame_gather window shape", launch_frame_gather(x, 8, 8, win, win, off, 2, 0, x, s), BAD, "window 1 has a non-positive shape");
+
     // keys outside a dispatch table: no kernel, and launch() refuses
     struct Row {
         int key;
