@@ -515,6 +515,29 @@ int ngmix_scene_render(const void *gev, int ngauss, const ngmix_jacobian *jac,
 int ngmix_frame_gather(const double *frame, int nrow, int ncol, const int32_t *win,
                        const int32_t *win_host, const int64_t *pix_off, int64_t n, int mode,
                        double *out, void *stream);
+/* the windows of ngmix_frame_gather (mode 0) with the models of every object
+   but the window's owner subtracted.  gev, jac (nobj records), pair_obj,
+   tile_start: ngmix_scene_boxes' records and the (tile -> object) lists of
+   ngmix_scene_render, as they are.  owner[i] in [-1, nobj): the object that
+   window i keeps (-1: none, a residual stamp); several windows may share one.
+   items[2 * k ..] = window, frame tile: every (window, tile) pair that
+   overlaps inside the frame, nitems of them, in any order; one wave each.
+   A pixel p of window i inside the frame gets frame[p] - nbr, with nbr = 0.0
+   and then nbr = nbr + m_j(p) over the objects j != owner[i] of p's tile in
+   ascending index, m_j = sum_g value_g in gaussian order from 0.0 as in
+   ngmix_scene_render: bit for bit the window of the frame minus the window of
+   a fresh ngmix_scene_render of all objects but owner[i].  Pixels outside the
+   frame are 0.0 (out, `total` doubles, is zeroed first).  No atomics: two runs
+   give the same bits.  win_host, owner_host: NULL, or the caller's host copies,
+   checked before the launch (a non-positive window shape and an owner outside
+   [-1, nobj) are refused). */
+int ngmix_scene_cut_minus(const double *frame, int nrow, int ncol, const void *gev, int ngauss,
+                          const ngmix_jacobian *jac, int64_t nobj, const int64_t *pair_obj,
+                          int64_t npairs, const int64_t *tile_start, const int32_t *win,
+                          const int32_t *win_host, const int32_t *owner,
+                          const int32_t *owner_host, const int64_t *pix_off, int64_t nwin,
+                          const int32_t *items, int64_t nitems, double *out, int64_t total,
+                          void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

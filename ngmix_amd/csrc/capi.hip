@@ -622,6 +622,19 @@ int ngmix_frame_gather(const double *frame, int nrow, int ncol, const int32_t *w
                                (hipStream_t)stream);
 }
 
+int ngmix_scene_cut_minus(const double *frame, int nrow, int ncol, const void *gev, int ngauss,
+                          const ngmix_jacobian *jac, int64_t nobj, const int64_t *pair_obj,
+                          int64_t npairs, const int64_t *tile_start, const int32_t *win,
+                          const int32_t *win_host, const int32_t *owner,
+                          const int32_t *owner_host, const int64_t *pix_off, int64_t nwin,
+                          const int32_t *items, int64_t nitems, double *out, int64_t total,
+                          void *stream)
+{
+    return launch_scene_cut_minus(frame, nrow, ncol, gev, ngauss, jac, nobj, pair_obj, npairs,
+                                  tile_start, win, win_host, owner, owner_host, pix_off, nwin,
+                                  items, nitems, out, total, (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)

@@ -56,6 +56,13 @@ int launch_scene_render(const void *gev, int ngauss, const ngmix_jacobian *jac,
 int launch_frame_gather(const double *frame, int nrow, int ncol, const int32_t *win,
                         const int32_t *win_host, const int64_t *pix_off, int64_t n, int mode,
                         double *out, hipStream_t s);
+int launch_scene_cut_minus(const double *frame, int nrow, int ncol, const void *gev, int ngauss,
+                           const ngmix_jacobian *jac, int64_t nobj, const int64_t *pair_obj,
+                           int64_t npairs, const int64_t *tile_start, const int32_t *win,
+                           const int32_t *win_host, const int32_t *owner,
+                           const int32_t *owner_host, const int64_t *pix_off, int64_t nwin,
+                           const int32_t *items, int64_t nitems, double *out, int64_t total,
+                           hipStream_t s);
 // noisecov.hip
 int launch_noise_cov_blocks(const double *dimg, const int64_t *stamp_idx, int64_t m,
                             const int64_t *pix_off, const double *ierr, const double *noise,

@@ -12,7 +12,11 @@
 //                        sorted by ascending object, built on the device by
 //                        ngmix_amd/scene.py (_tile_pairs);
 //   frame_gather_kernel  N ragged windows of a frame into the packed stamp
-//                        layout (values, or ierr = sqrt(max(w, 0))).
+//                        layout (values, or ierr = sqrt(max(w, 0)));
+//   scene_cut_minus_kernel  the same windows with the models of every object
+//                        but the window's owner subtracted: one wave per
+//                        (window, frame tile it overlaps), over the renderer's
+//                        tile lists.
 //
 // The order of summation is part of the interface.  Per object
 // m = sum_g value_g in gaussian order starting from 0.0, then pixel = pixel + m,
@@ -24,6 +28,16 @@
 // gaussian's box evaluates to exactly 0.0, so binning by boxes changes no bit
 // (only the sign of a zero).  One wave owns a tile: no atomics, two runs give
 // the same bits.  Built with -ffp-contract=off; no fma is written here.
+//
+// scene_cut_minus_kernel keeps that contract.  For window s with owner o, a
+// pixel p of the window inside the frame gets frame[p] - nbr, where nbr = 0.0,
+// then nbr = nbr + m_j(p) over the objects j != o of p's frame tile in
+// ascending index, m_j the renderer's per-object sum (scene_tile_walk is the
+// one entry walk of both kernels).  So the values of window s are bit for bit
+// cut(frame) - cut(the scene of all objects but o, rendered fresh); owner -1
+// skips nothing (a residual stamp).  Window pixels outside the frame are 0.0.
+// One wave owns a (window, tile) item and every pixel of a window belongs to
+// one item: no atomics, two runs give the same bits.
 #include <string>
 
 #include "device_utils.hpp"
@@ -106,10 +120,40 @@ __global__ __launch_bounds__(BLOCK) void scene_boxes_kernel(
     status[i] = code;
 }
 
-// FRESH: the frame starts from 0.0 and every pixel is written, unread;
-// otherwise a tile without objects is neither read nor written.
+// The entry walk of a tile, for the lane's pixel (row, col) of the tile at
+// (r0, c0): acc = acc + m over the objects pair_obj[first .. last) in order,
+// m = sum_g value_g in gaussian order from 0.0.  SKIP: the object `skip` is
+// passed over (a wave-uniform branch).
 // Everything an entry needs (object index, jacobian, gaussian records) sits at
 // an address that is uniform over the wave: scalar loads, as fisher.hip's A.
+template <bool SKIP>
+__device__ __forceinline__ double scene_tile_walk(
+    const SceneGauss *__restrict__ gev, int G, const ngmix_jacobian *__restrict__ jacs,
+    const int64_t *__restrict__ pair_obj, int64_t first, int64_t last, int r0, int c0, int row,
+    int col, double acc, int64_t skip, const double *tab)
+{
+    for (int64_t k = first; k < last; k++) {
+        const int64_t obj = pair_obj[k];
+        if (SKIP && obj == skip) continue;
+        const ngmix_jacobian jac = jacs[obj];
+        const double area = jac.scale * jac.scale;  // jacobian_nb.py:33-40
+        double v, u;
+        jacobian_vu(jac, (double)row, (double)col, v, u);
+        const SceneGauss *og = gev + obj * G;
+        double m = 0.0;
+        for (int g = 0; g < G; g++) {
+            const PixBox b = og[g].box;
+            if (r0 <= b.rmax && r0 + SCENE_TH - 1 >= b.rmin && c0 <= b.cmax &&
+                c0 + SCENE_TW - 1 >= b.cmin)
+                m += gauss_eval_fast(og[g].e, v, u, area, tab);
+        }
+        acc = acc + m;
+    }
+    return acc;
+}
+
+// FRESH: the frame starts from 0.0 and every pixel is written, unread;
+// otherwise a tile without objects is neither read nor written.
 template <bool FRESH>
 __global__ __launch_bounds__(BLOCK) void scene_render_kernel(
     const SceneGauss *__restrict__ gev, int G, const ngmix_jacobian *__restrict__ jacs,
@@ -136,24 +180,48 @@ __global__ __launch_bounds__(BLOCK) void scene_render_kernel(
     }
     double pix = 0.0;
     if (!FRESH && inb) pix = frame[idx];
-
-    for (int64_t k = first; k < last; k++) {
-        const int64_t obj = pair_obj[k];
-        const ngmix_jacobian jac = jacs[obj];
-        const double area = jac.scale * jac.scale;  // jacobian_nb.py:33-40
-        double v, u;
-        jacobian_vu(jac, (double)row, (double)col, v, u);
-        const SceneGauss *og = gev + obj * G;
-        double m = 0.0;
-        for (int g = 0; g < G; g++) {
-            const PixBox b = og[g].box;
-            if (r0 <= b.rmax && r0 + SCENE_TH - 1 >= b.rmin && c0 <= b.cmax &&
-                c0 + SCENE_TW - 1 >= b.cmin)
-                m += gauss_eval_fast(og[g].e, v, u, area, tab);
-        }
-        pix = pix + m;
-    }
+    pix = scene_tile_walk<false>(gev, G, jacs, pair_obj, first, last, r0, c0, row, col, pix, -1,
+                                 tab);
     if (inb) frame[idx] = pix;
+}
+
+// One wave per work item: items[2 * W ..] = window s, frame tile T (a tile the
+// window overlaps inside the frame).  Lane <-> pixel of the tile, as the
+// renderer; lanes outside the window or the frame are masked.  The frame is
+// read as the tile's whole lines; the result goes to the packed stamp at
+// pix_off[s] + (row - r_lo) * wc + (col - c_lo).  Pixels of a window outside
+// the frame belong to no item: the launcher zeroes out first.
+__global__ __launch_bounds__(BLOCK) void scene_cut_minus_kernel(
+    const double *__restrict__ frame, int nrow, int ncol, int ntx,
+    const SceneGauss *__restrict__ gev, int G, const ngmix_jacobian *__restrict__ jacs,
+    const int64_t *__restrict__ pair_obj, const int64_t *__restrict__ tile_start,
+    const int32_t *__restrict__ win, const int32_t *__restrict__ owner,
+    const int64_t *__restrict__ pix_off, const int32_t *__restrict__ items, int nitems,
+    double *__restrict__ out)
+{
+    __shared__ double tab[16];
+    if (threadIdx.x < 16) tab[threadIdx.x] = c_exp_table_scene[threadIdx.x];
+    __syncthreads();
+
+    const int W = (int)blockIdx.x * NWAVES + wave_id();
+    if (W >= nitems) return;
+    const int64_t s = items[2 * (int64_t)W];
+    const int T = items[2 * (int64_t)W + 1];
+    const int64_t r_lo = win[4 * s], c_lo = win[4 * s + 1];
+    const int wr = win[4 * s + 2], wc = win[4 * s + 3];
+    const int lane = lane_id();
+    const int ty = T / ntx, tx = T - ty * ntx;
+    const int r0 = ty * SCENE_TH, c0 = tx * SCENE_TW;
+    const int row = r0 + lane / SCENE_TW, col = c0 + lane % SCENE_TW;
+    const bool inb = row < nrow && col < ncol;
+    const int64_t wrow = row - r_lo, wcol = col - c_lo;
+    const bool inw = inb && wrow >= 0 && wrow < wr && wcol >= 0 && wcol < wc;
+    double f = 0.0;
+    if (inb) f = frame[(int64_t)row * ncol + col];
+    const double nbr = scene_tile_walk<true>(gev, G, jacs, pair_obj, tile_start[T],
+                                             tile_start[T + 1], r0, c0, row, col, 0.0, owner[s],
+                                             tab);
+    if (inw) out[pix_off[s] + wrow * wc + wcol] = f - nbr;
 }
 
 // win[4 * s ..]: r_lo, c_lo, nrow, ncol of window s (frame pixel indices; any
@@ -290,6 +358,72 @@ int launch_frame_gather(const double *frame, int nrow, int ncol, const int32_t *
     }
     return launch(kernel(frame_gather_kernel, "frame_gather_kernel"), dim3((unsigned)n),
                   dim3(BLOCK), 0, NO_OPTIN, s, frame, nrow, ncol, win, pix_off, mode, out);
+}
+
+// win_host, owner_host: the caller's host copies of win and owner, or null;
+// when given, a window whose shape is not positive and an owner outside
+// [-1, nobj) are refused here.  total: the doubles of out (the packed stamps),
+// zeroed before the kernel: window pixels outside the frame belong to no item.
+int launch_scene_cut_minus(const double *frame, int nrow, int ncol, const void *gev, int ngauss,
+                           const ngmix_jacobian *jac, int64_t nobj, const int64_t *pair_obj,
+                           int64_t npairs, const int64_t *tile_start, const int32_t *win,
+                           const int32_t *win_host, const int32_t *owner,
+                           const int32_t *owner_host, const int64_t *pix_off, int64_t nwin,
+                           const int32_t *items, int64_t nitems, double *out, int64_t total,
+                           hipStream_t s)
+{
+    if (nobj < 0 || npairs < 0 || nwin < 0 || nitems < 0 || total < 0) {
+        set_last_error_msg("scene_cut_minus: nobj, npairs, nwin, nitems and total must not be "
+                           "negative");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (ngauss < 1) {
+        set_last_error_msg("scene_cut_minus: at least one gaussian per object (ngauss >= 1)");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (!scene_frame_ok("scene_cut_minus", nrow, ncol)) return NGMIX_ERR_BAD_ARG;
+    if (nwin == 0) return NGMIX_OK;
+    if (nwin > 0x7fffffffll || nobj > 0x7fffffffll) {
+        set_last_error_msg("scene_cut_minus: window and object indices must fit 32 bits");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (!frame || !tile_start || !win || !owner || !pix_off || (total > 0 && !out) ||
+        (nitems > 0 && !items) || (npairs > 0 && (!gev || !jac || !pair_obj))) {
+        set_last_error_msg("scene_cut_minus: frame, gev, jac, pair_obj, tile_start, win, owner, "
+                           "pix_off, items and out are required");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    for (int64_t i = 0; win_host && i < nwin; i++) {
+        if (win_host[4 * i + 2] <= 0 || win_host[4 * i + 3] <= 0) {
+            set_last_error_msg(("scene_cut_minus: window " + std::to_string(i) +
+                                " has a non-positive shape").c_str());
+            return NGMIX_ERR_BAD_ARG;
+        }
+    }
+    for (int64_t i = 0; owner_host && i < nwin; i++) {
+        if (owner_host[i] < -1 || owner_host[i] >= nobj) {
+            set_last_error_msg(("scene_cut_minus: owner " + std::to_string(owner_host[i]) +
+                                " of window " + std::to_string(i) + " is outside [-1, " +
+                                std::to_string(nobj) + ")").c_str());
+            return NGMIX_ERR_BAD_ARG;
+        }
+    }
+    const int ntx = (ncol + SCENE_TW - 1) / SCENE_TW;
+    const int nty = (nrow + SCENE_TH - 1) / SCENE_TH;
+    if ((int64_t)ntx * nty > 0x7fffffffll) {
+        set_last_error_msg("scene_cut_minus: the frame has more than 2^31 - 1 tiles");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (nitems > 0x7fffffffll) {
+        set_last_error_msg("scene_cut_minus: more than 2^31 - 1 (window, tile) items");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (total > 0) NGMIX_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)total * sizeof(double), s));
+    if (nitems == 0) return NGMIX_OK;
+    return launch(kernel(scene_cut_minus_kernel, "scene_cut_minus_kernel"),
+                  dim3((unsigned)((nitems + NWAVES - 1) / NWAVES)), dim3(BLOCK), 0, NO_OPTIN, s,
+                  frame, nrow, ncol, ntx, (const SceneGauss *)gev, ngauss, jac, pair_obj,
+                  tile_start, win, owner, pix_off, items, (int)nitems, out);
 }
 
 }  // namespace ngmix

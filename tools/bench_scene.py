@@ -8,7 +8,16 @@ index_put_(accumulate=True) into the frame), alternating, median of 5, the
 largest difference of the two frames, and one forward + backward of
 autodiff.scene_render under a squared-residual loss.
 
+The deblend leg (scene.cut_deblended_stamps, scene_cut_minus_kernel): one
+32 x 32 window per object on the same scene; the call end to end and its kernel
+by events, against the long way built from render_scene, a ragged
+StampBatch.render of every object's own model and cut_stamps (cut(frame) -
+cut(scene) + own), alternating, median of 5, and the largest difference of the
+two results relative to the frame's peak.  --deblend-only runs that leg alone
+and appends its lines to the file.
+
     python tools/bench_scene.py [--n 30000] [--size 4096] [--out profiles/scene_bench.txt]
+                                [--deblend-only]
 """
 import argparse
 import os
@@ -51,6 +60,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.txt"))
     ap.add_argument("--no-backward", action="store_true")
+    ap.add_argument("--deblend-only", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -76,6 +86,106 @@ def main():
     def say(text):
         print(text, flush=True)
         lines.append(text)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, (time.perf_counter() - t0) * 1e3
+
+    def write(mode):
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, mode) as f:
+            f.write("\n".join(lines) + "\n")
+
+    def deblend_leg():
+        win = 32
+        say("deblend: %d x %d frame, %d objects, G = %d, one %d x %d window per object"
+            % (size, size, n, G, win, win))
+        frame, _ = scene.render_scene(shape, gm, d_jac)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(99)
+        frame = frame + 0.01 * torch.randn(shape, generator=gen, dtype=torch.float64,
+                                           device="cuda")
+        r_lo = np.round(jac[:, 0]).astype(np.int64) - win // 2
+        c_lo = np.round(jac[:, 1]).astype(np.int64) - win // 2
+        wr = np.full(n, win, dtype=np.int64)
+        off = np.arange(n, dtype=np.int64) * win * win
+        total = n * win * win
+        winarr = np.stack([r_lo, c_lo, wr, wr], axis=1)
+
+        # the kernel alone, by events, on the lists the call would build
+        gev, _, _, pair_obj, tile_start = scene._scene_lists(size, size, gm.data, G, n, d_jac,
+                                                             None)
+        items = scene._window_items(r_lo, c_lo, wr, wr, size, size, torch.device("cuda"))
+        h_win = np.ascontiguousarray(winarr, dtype=np.int32)
+        h_own = np.arange(n, dtype=np.int32)
+        d_win, d_own = torch.from_numpy(h_win).cuda(), torch.from_numpy(h_own).cuda()
+        d_off = torch.from_numpy(off).cuda()
+        out = torch.empty(total, dtype=torch.float64, device="cuda")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t_kern = []
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(L.ngmix_scene_cut_minus(
+                _dptr(frame), size, size, _dptr(gev), G, _dptr(d_jac), n, _dptr(pair_obj),
+                int(pair_obj.shape[0]), _dptr(tile_start), _dptr(d_win), _lib.ptr(h_win),
+                _dptr(d_own), _lib.ptr(h_own), _dptr(d_off), n, _dptr(items),
+                int(items.shape[0]), _dptr(out), total, _stream()), "scene_cut_minus")
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                t_kern.append(e0.elapsed_time(e1))
+        say("deblend: %d (window, tile) items, %.1f per window; scene_cut_minus (zeroing + kernel,"
+            " ms, by events): median %.3f, min %.3f, max %.3f"
+            % (int(items.shape[0]), items.shape[0] / float(n), np.median(t_kern), min(t_kern),
+               max(t_kern)))
+        del out
+
+        # the long way: the scene of all objects, every object's own model on
+        # its window, then cut(frame) - cut(scene) + own
+        wjac = jac.copy()
+        wjac[:, 0] -= r_lo
+        wjac[:, 1] -= c_lo
+        geom = StampBatch(None, None, torch.from_numpy(wjac).cuda(), wr, wr, off, False)
+        # (1.0 inside the frame, 0.0 outside: the own model of a window that
+        # crosses the frame's edge is masked as the cuts are; made once, the
+        # windows do not change)
+        inside = scene._gather(torch.ones(shape, dtype=torch.float64, device="cuda"), winarr, off,
+                               total, 0)
+
+        def long_way():
+            model, _ = scene.render_scene(shape, gm, d_jac)
+            own, _ = geom.render(gm, fast_exp=True)
+            sb = scene.cut_stamps(frame, 1.0, r_lo, c_lo, win, win, d_jac)
+            sb.val = sb.val - scene._gather(model, winarr, off, total, 0) + own * inside
+            return sb
+
+        def new_way():
+            return scene.cut_deblended_stamps(frame, 1.0, r_lo, c_lo, win, win, d_jac, gm)[0]
+
+        timed(new_way)
+        timed(long_way)
+        t_new, t_long = [], []
+        for rep in range(args.reps):
+            sb_new, t = timed(new_way)
+            t_new.append(t)
+            sb_long, t = timed(long_way)
+            t_long.append(t)
+        say("cut_deblended_stamps end to end (ms): median %.3f, min %.3f, max %.3f"
+            % (np.median(t_new), min(t_new), max(t_new)))
+        say("long way (scene + own + cuts) (ms):   median %.3f, min %.3f, max %.3f"
+            % (np.median(t_long), min(t_long), max(t_long)))
+        peak = float(frame.abs().max())
+        say("largest |deblended - long way| / peak: %.3g (peak %.6g)"
+            % (float((sb_new.val - sb_long.val).abs().max()) / peak, peak))
+
+    if args.deblend_only:
+        deblend_leg()
+        write("a")
+        return
 
     say("scene bench: %d x %d frame, %d objects, G = %d" % (size, size, n, G))
 
@@ -145,13 +255,6 @@ def main():
         out.index_put_((flat,), img, accumulate=True)
         return out.reshape(shape)
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return out, (time.perf_counter() - t0) * 1e3
-
     timed(lambda: scene.render_scene(shape, gm, d_jac))
     timed(long_way)
     t_scene, t_long = [], []
@@ -184,9 +287,8 @@ def main():
             % (t, float(p.grad.abs().max()), bool(torch.isfinite(p.grad).all())))
         assert bool((frame == f_scene).all())
 
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    deblend_leg()
+    write("w")
 
 
 if __name__ == "__main__":

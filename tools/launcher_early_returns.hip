@@ -129,6 +129,19 @@ int main()
     expect("frame_gather empty", launch_frame_gather(x, 8, 8, nullptr, nullptr, nullptr, 0, 0, nullptr, s), NGMIX_OK);
     expect("frame_gather null", launch_frame_gather(nullptr, 8, 8, win, nullptr, off, 2, 0, x, s), BAD, "are required");
     expect("frame_gather window shape", launch_frame_gather(x, 8, 8, win, win, off, 2, 0, x, s), BAD, "window 1 has a non-positive shape");
+    int32_t win2[8] = {0, 0, 9, 9, 3, 3, 4, 5};
+    int32_t own[2] = {0, 2}, own_low[2] = {-2, 0}, own_ok[2] = {-1, 1};
+    expect("scene_cut_minus n < 0", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 1, off, win2, win2, own_ok, own_ok, off, -1, st, 1, x, 64, s), BAD, "must not be negative");
+    expect("scene_cut_minus nobj < 0", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, -2, off, 1, off, win2, win2, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "must not be negative");
+    expect("scene_cut_minus G", launch_scene_cut_minus(x, 8, 8, x, 0, nullptr, 2, off, 1, off, win2, win2, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "ngauss >= 1");
+    expect("scene_cut_minus frame", launch_scene_cut_minus(x, 8, 0, x, 1, nullptr, 2, off, 1, off, win2, win2, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "nrow * ncol > 0");
+    expect("scene_cut_minus empty", launch_scene_cut_minus(nullptr, 8, 8, nullptr, 1, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, s), NGMIX_OK);
+    expect("scene_cut_minus null frame", launch_scene_cut_minus(nullptr, 8, 8, x, 1, nullptr, 2, off, 0, off, win2, win2, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "are required");
+    expect("scene_cut_minus null jac", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 1, off, win2, win2, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "are required");
+    expect("scene_cut_minus null owner", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win2, win2, nullptr, nullptr, off, 2, st, 1, x, 64, s), BAD, "are required");
+    expect("scene_cut_minus window shape", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win, win, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "window 1 has a non-positive shape");
+    expect("scene_cut_minus owner high", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win2, win2, own, own, off, 2, st, 1, x, 64, s), BAD, "owner 2 of window 1 is outside [-1, 2)");
+    expect("scene_cut_minus owner low", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win2, win2, own_low, own_low, off, 2, st, 1, x, 64, s), BAD, "owner -2 of window 0 is outside [-1, 2)");
 
     // keys outside a dispatch table: no kernel, and launch() refuses
     struct Row {
