@@ -25,6 +25,17 @@
 // accepted step the state asks (phase JAC) for the forward-difference jacobian
 // at the new point and charges its n evaluations to nfev as fdjac2 does.
 //
+// ONE text of the step, two instantiations.  Every function of the step takes
+// a dimension policy: runtime_dim<NP> (below: the parameter count at run time,
+// NP-strided arrays in memory, a run-time index is an index) or fixed_dim<N>
+// (lm_core_reg.hpp: N at compile time, every loop unrolls, run-time indices are
+// select chains, all arrays in registers -- what the device runs for 6-10
+// parameters).  The text is in the shape the second needs -- constant-stride
+// indexing, full-length loops with the rank tested inside, one call site for
+// the factorisation and one for the proposal -- and only factor_normal's
+// pivot exchange has a body per policy.  (The team form, lm_core_team.hpp, is a
+// different, parallel algorithm and is written separately.)
+//
 // Everything is host+device so the same code is tested on the CPU against
 // scipy.optimize.leastsq (tests/test_lm_core.py).
 #pragma once
@@ -51,22 +62,53 @@ namespace lmcore {
 constexpr double EPSMCH = 2.220446049250313e-16;
 constexpr double DWARF = 2.2250738585072014e-308;
 
-NGMIX_HD double enorm(int n, const double *x)
-{
-    // MINPACK's enorm guards against over/underflow with three accumulators;
-    // the quantities here (parameter steps, scaled gradients) are far from
-    // either limit, where it reduces to this
-    double s = 0.0;
-    for (int i = 0; i < n; i++) s += x[i] * x[i];
-    return sqrt(s);
-}
+// Before every loop of the step: under a compile-time count the loop unrolls in
+// full, which is what lets the arrays live in registers; under a run-time count
+// it is a request the compiler meets where it can (an innermost loop) and
+// reports as not met elsewhere
+#define LM_UNROLL _Pragma("unroll")
 
-// The work arrays and the factor R are NP-strided, NP a template parameter:
+// The dimension policy of a run-time parameter count n <= NP: the work arrays
+// and the factor R are NP-strided, a run-time index is an index.
 // NP = LM_NPMAX on the ngmix_lm_state record itself (host entry points, tests),
 // a smaller NP on a compact copy of the live part of the record (lm_state_n
 // below) in the device kernel -- one thread per fit keeps everything in private
 // memory, and a six-parameter fit in LM_NPMAX = 14 arrays moves five times the
 // bytes it needs.
+template <int NP>
+struct runtime_dim {
+    static constexpr int stride = NP;
+    int count;
+    NGMIX_HD int n() const { return count; }
+    template <class T>
+    static NGMIX_HD T get(const T *a, int idx) { return a[idx]; }
+    template <class T>
+    static NGMIX_HD void set(T *a, int idx, T v) { a[idx] = v; }
+    // factor_normal's pivot exchange k <-> kmax: a swap in memory
+    NGMIX_HD void exchange(double *S, double *R, int32_t *ipvt, int k, int kmax) const
+    {
+        if (kmax == k) return;
+        for (int i = 0; i < count; i++) {
+            const double t = S[i * NP + k];
+            S[i * NP + k] = S[i * NP + kmax];
+            S[i * NP + kmax] = t;
+        }
+        for (int j = 0; j < count; j++) {
+            const double t = S[k * NP + j];
+            S[k * NP + j] = S[kmax * NP + j];
+            S[kmax * NP + j] = t;
+        }
+        for (int i = 0; i < k; i++) {
+            const double t = R[i * NP + k];
+            R[i * NP + k] = R[i * NP + kmax];
+            R[i * NP + kmax] = t;
+        }
+        const int32_t ti = ipvt[k];
+        ipvt[k] = ipvt[kmax];
+        ipvt[kmax] = ti;
+    }
+};
+
 template <int NP>
 struct lm_state_n {
     double x[NP], xt[NP], diag[NP], R[NP * NP], qtf[NP], step[NP];
@@ -77,66 +119,74 @@ struct lm_state_n {
     int32_t n, iter, nfev, njev, info, phase, maxfev, mode, bounded, fonly;
 };
 
+template <class Dim>
+NGMIX_HD double enorm(const Dim d, const double *x)
+{
+    // MINPACK's enorm guards against over/underflow with three accumulators;
+    // the quantities here (parameter steps, scaled gradients) are far from
+    // either limit, where it reduces to this
+    double s = 0.0;
+    LM_UNROLL
+    for (int i = 0; i < d.n(); i++) s += x[i] * x[i];
+    return sqrt(s);
+}
+
 // Pivoted Cholesky of A = J^T J with qrfac's pivot rule (largest remaining
 // column norm first): A P = (QR)^T (QR) P  ->  R^T R = P^T A P.
-// Returns R (upper, n x n in an NP-strided array), ipvt, and
-// acnorm[j] = |J[:, j]|.
-template <int NP = LM_NPMAX>
-NGMIX_HD void factor_normal(int n, const double *A, double *R, int32_t *ipvt,
+// Returns R (upper, n x n in a strided array), ipvt, and acnorm[j] = |J[:, j]|.
+template <class Dim>
+NGMIX_HD void factor_normal(const Dim d, const double *A, double *R, int32_t *ipvt,
                             double *acnorm)
 {
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
+    // (only the leading n x n block of the strided arrays is ever read)
     double S[NP * NP];
+    LM_UNROLL
     for (int i = 0; i < n; i++)
+        LM_UNROLL
         for (int j = 0; j < n; j++) S[i * NP + j] = A[i * NP + j];
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
         ipvt[j] = j;
-        const double d = A[j * NP + j];
-        acnorm[j] = d > 0.0 ? sqrt(d) : 0.0;
+        const double dj = A[j * NP + j];
+        acnorm[j] = dj > 0.0 ? sqrt(dj) : 0.0;
     }
-    // (only the leading n x n block of the NP-strided arrays is ever read)
+    LM_UNROLL
     for (int i = 0; i < n; i++)
+        LM_UNROLL
         for (int j = 0; j < n; j++) R[i * NP + j] = 0.0;
     // S is kept in the permuted order: row/col k of S <-> parameter ipvt[k]
+    LM_UNROLL
     for (int k = 0; k < n; k++) {
+        // the largest remaining diagonal, first one on ties
         int kmax = k;
+        double dmax = S[k * NP + k];
+        LM_UNROLL
         for (int j = k + 1; j < n; j++)
-            if (S[j * NP + j] > S[kmax * NP + kmax]) kmax = j;
-        if (kmax != k) {
-            for (int i = 0; i < n; i++) {
-                const double t = S[i * NP + k];
-                S[i * NP + k] = S[i * NP + kmax];
-                S[i * NP + kmax] = t;
+            if (S[j * NP + j] > dmax) {
+                dmax = S[j * NP + j];
+                kmax = j;
             }
-            for (int j = 0; j < n; j++) {
-                const double t = S[k * NP + j];
-                S[k * NP + j] = S[kmax * NP + j];
-                S[kmax * NP + j] = t;
-            }
-            for (int i = 0; i < k; i++) {
-                const double t = R[i * NP + k];
-                R[i * NP + k] = R[i * NP + kmax];
-                R[i * NP + kmax] = t;
-            }
-            const int32_t ti = ipvt[k];
-            ipvt[k] = ipvt[kmax];
-            ipvt[kmax] = ti;
-        }
-        const double d = S[k * NP + k];
-        if (!(d > 0.0)) {
+        d.exchange(S, R, ipvt, k, kmax);
+        const double dk = S[k * NP + k];
+        if (!(dk > 0.0)) {
             // rank deficient: the remaining columns are (numerically) in the
-            // span of the first k; qrfac leaves rdiag = 0 there
+            // span of the first k; qrfac leaves rdiag = 0 there (R beyond row
+            // k is still zero)
+            LM_UNROLL
             for (int j = k; j < n; j++) R[k * NP + j] = 0.0;
-            for (int kk = k + 1; kk < n; kk++)
-                for (int j = kk; j < n; j++) R[kk * NP + j] = 0.0;
             return;
         }
-        const double rkk = sqrt(d);
+        const double rkk = sqrt(dk);
         R[k * NP + k] = rkk;
+        LM_UNROLL
         for (int j = k + 1; j < n; j++) R[k * NP + j] = S[k * NP + j] / rkk;
+        LM_UNROLL
         for (int i = k + 1; i < n; i++)
+            LM_UNROLL
             for (int j = i; j < n; j++) {
-                const double v = S[i * NP + j] -
-                                 R[k * NP + i] * R[k * NP + j];
+                const double v = S[i * NP + j] - R[k * NP + i] * R[k * NP + j];
                 S[i * NP + j] = v;
                 S[j * NP + i] = v;
             }
@@ -144,12 +194,16 @@ NGMIX_HD void factor_normal(int n, const double *A, double *R, int32_t *ipvt,
 }
 
 // first n components of Q^T f:  R^T qtf = P^T g
-template <int NP = LM_NPMAX>
-NGMIX_HD void qtf_from_gradient(int n, const double *R, const int32_t *ipvt,
+template <class Dim>
+NGMIX_HD void qtf_from_gradient(const Dim d, const double *R, const int32_t *ipvt,
                                 const double *g, double *qtf)
 {
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
-        double s = g[ipvt[j]];
+        double s = d.get(g, ipvt[j]);
+        LM_UNROLL
         for (int i = 0; i < j; i++) s -= R[i * NP + j] * qtf[i];
         const double rjj = R[j * NP + j];
         qtf[j] = rjj != 0.0 ? s / rjj : 0.0;
@@ -159,21 +213,28 @@ NGMIX_HD void qtf_from_gradient(int n, const double *R, const int32_t *ipvt,
 // MINPACK qrsolv.  r: n x n with the upper triangle holding R; on output the
 // strict lower triangle holds the strict upper triangle of S transposed and
 // sdiag the diagonal of S.
-template <int NP = LM_NPMAX>
-NGMIX_HD void qrsolv(int n, double *r, const int32_t *ipvt, const double *diag,
+template <class Dim>
+NGMIX_HD void qrsolv(const Dim d, double *r, const int32_t *ipvt, const double *diag,
                      const double *qtb, double *x, double *sdiag, double *wa)
 {
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
+        LM_UNROLL
         for (int i = j; i < n; i++) r[i * NP + j] = r[j * NP + i];
         x[j] = r[j * NP + j];
         wa[j] = qtb[j];
     }
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
-        const int l = ipvt[j];
-        if (diag[l] != 0.0) {
+        const double dl = d.get(diag, ipvt[j]);
+        if (dl != 0.0) {
+            LM_UNROLL
             for (int k = j; k < n; k++) sdiag[k] = 0.0;
-            sdiag[j] = diag[l];
+            sdiag[j] = dl;
             double qtbpj = 0.0;
+            LM_UNROLL
             for (int k = j; k < n; k++) {
                 if (sdiag[k] == 0.0) continue;
                 double cs, sn;
@@ -191,6 +252,7 @@ NGMIX_HD void qrsolv(int n, double *r, const int32_t *ipvt, const double *diag,
                 double temp = cs * wa[k] + sn * qtbpj;
                 qtbpj = -sn * wa[k] + cs * qtbpj;
                 wa[k] = temp;
+                LM_UNROLL
                 for (int i = k + 1; i < n; i++) {
                     temp = cs * r[i * NP + k] + sn * sdiag[i];
                     sdiag[i] = -sn * r[i * NP + k] + cs * sdiag[i];
@@ -202,44 +264,59 @@ NGMIX_HD void qrsolv(int n, double *r, const int32_t *ipvt, const double *diag,
         r[j * NP + j] = x[j];
     }
     int nsing = n;
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
         if (sdiag[j] == 0.0 && nsing == n) nsing = j;
         if (nsing < n) wa[j] = 0.0;
     }
-    for (int k = 0; k < nsing; k++) {
-        const int j = nsing - 1 - k;
-        double sum = 0.0;
-        for (int i = j + 1; i < nsing; i++) sum += r[i * NP + j] * wa[i];
-        wa[j] = (wa[j] - sum) / sdiag[j];
+    // MINPACK's k = 0 .. nsing-1, j = nsing-1-k: j descending from nsing-1
+    LM_UNROLL
+    for (int j = n - 1; j >= 0; j--) {
+        if (j < nsing) {
+            double sum = 0.0;
+            LM_UNROLL
+            for (int i = j + 1; i < n; i++)
+                if (i < nsing) sum += r[i * NP + j] * wa[i];
+            wa[j] = (wa[j] - sum) / sdiag[j];
+        }
     }
-    for (int j = 0; j < n; j++) x[ipvt[j]] = wa[j];
+    LM_UNROLL
+    for (int j = 0; j < n; j++) d.set(x, ipvt[j], wa[j]);
 }
 
 // MINPACK lmpar.  r is modified as qrsolv leaves it (upper triangle intact).
-template <int NP = LM_NPMAX>
-NGMIX_HD void lmpar(int n, double *r, const int32_t *ipvt, const double *diag,
+template <class Dim>
+NGMIX_HD void lmpar(const Dim d, double *r, const int32_t *ipvt, const double *diag,
                     const double *qtb, double delta, double &par, double *x,
                     double *sdiag)
 {
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
     double wa1[NP], wa2[NP];
     // gauss-newton direction
     int nsing = n;
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
         wa1[j] = qtb[j];
         if (r[j * NP + j] == 0.0 && nsing == n) nsing = j;
         if (nsing < n) wa1[j] = 0.0;
     }
-    for (int k = 0; k < nsing; k++) {
-        const int j = nsing - 1 - k;
-        wa1[j] /= r[j * NP + j];
-        const double temp = wa1[j];
-        for (int i = 0; i < j; i++) wa1[i] -= r[i * NP + j] * temp;
+    LM_UNROLL
+    for (int j = n - 1; j >= 0; j--) {
+        if (j < nsing) {
+            wa1[j] /= r[j * NP + j];
+            const double temp = wa1[j];
+            LM_UNROLL
+            for (int i = 0; i < j; i++) wa1[i] -= r[i * NP + j] * temp;
+        }
     }
-    for (int j = 0; j < n; j++) x[ipvt[j]] = wa1[j];
+    LM_UNROLL
+    for (int j = 0; j < n; j++) d.set(x, ipvt[j], wa1[j]);
 
     int iter = 0;
+    LM_UNROLL
     for (int j = 0; j < n; j++) wa2[j] = diag[j] * x[j];
-    double dxnorm = enorm(n, wa2);
+    double dxnorm = enorm(d, wa2);
     double fp = dxnorm - delta;
     if (fp <= 0.1 * delta) {
         par = 0.0;
@@ -248,25 +325,30 @@ NGMIX_HD void lmpar(int n, double *r, const int32_t *ipvt, const double *diag,
     // lower bound
     double parl = 0.0;
     if (nsing >= n) {
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
             const int l = ipvt[j];
-            wa1[j] = diag[l] * (wa2[l] / dxnorm);
+            wa1[j] = d.get(diag, l) * (d.get(wa2, l) / dxnorm);
         }
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
             double sum = 0.0;
+            LM_UNROLL
             for (int i = 0; i < j; i++) sum += r[i * NP + j] * wa1[i];
             wa1[j] = (wa1[j] - sum) / r[j * NP + j];
         }
-        const double temp = enorm(n, wa1);
+        const double temp = enorm(d, wa1);
         parl = ((fp / delta) / temp) / temp;
     }
     // upper bound
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
         double sum = 0.0;
+        LM_UNROLL
         for (int i = 0; i <= j; i++) sum += r[i * NP + j] * qtb[i];
-        wa1[j] = sum / diag[ipvt[j]];
+        wa1[j] = sum / d.get(diag, ipvt[j]);
     }
-    const double gnorm = enorm(n, wa1);
+    const double gnorm = enorm(d, wa1);
     double paru = gnorm / delta;
     if (paru == 0.0) paru = DWARF / fmin(delta, 0.1);
     par = fmax(par, parl);
@@ -277,26 +359,31 @@ NGMIX_HD void lmpar(int n, double *r, const int32_t *ipvt, const double *diag,
         iter++;
         if (par == 0.0) par = fmax(DWARF, 0.001 * paru);
         double temp = sqrt(par);
+        LM_UNROLL
         for (int j = 0; j < n; j++) wa1[j] = temp * diag[j];
-        qrsolv<NP>(n, r, ipvt, wa1, qtb, x, sdiag, wa2);
+        qrsolv(d, r, ipvt, wa1, qtb, x, sdiag, wa2);
+        LM_UNROLL
         for (int j = 0; j < n; j++) wa2[j] = diag[j] * x[j];
-        dxnorm = enorm(n, wa2);
+        dxnorm = enorm(d, wa2);
         temp = fp;
         fp = dxnorm - delta;
         if (fabs(fp) <= 0.1 * delta || (parl == 0.0 && fp <= temp && temp < 0.0) ||
             iter == 10)
             break;
         // newton correction
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
             const int l = ipvt[j];
-            wa1[j] = diag[l] * (wa2[l] / dxnorm);
+            wa1[j] = d.get(diag, l) * (d.get(wa2, l) / dxnorm);
         }
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
             wa1[j] /= sdiag[j];
             temp = wa1[j];
+            LM_UNROLL
             for (int i = j + 1; i < n; i++) wa1[i] -= r[i * NP + j] * temp;
         }
-        temp = enorm(n, wa1);
+        temp = enorm(d, wa1);
         const double parc = ((fp / delta) / temp) / temp;
         if (fp > 0.0) parl = fmax(parl, par);
         if (fp < 0.0) paru = fmin(paru, par);
@@ -334,11 +421,12 @@ NGMIX_HD double i2e_grad(double v, double lo, double hi)
 
 // the external trial point from the internal one, and fdjac2's points
 // (h = sqrt(eps) |x_j|, sqrt(eps) at 0, in the internal parameters)
-template <class State>
-NGMIX_HD void set_trial(State &s)
+template <class Dim, class State>
+NGMIX_HD void set_trial(const Dim d, State &s)
 {
     constexpr double EPS = 1.4901161193847656e-08;  // sqrt(machine epsilon)
-    for (int j = 0; j < s.n; j++) {
+    LM_UNROLL
+    for (int j = 0; j < d.n(); j++) {
         s.xt[j] = s.bounded ? i2e(s.xti[j], s.lo[j], s.hi[j]) : s.xti[j];
         if (s.mode == NGMIX_LM_MODE_FD) {
             double h = EPS * fabs(s.xti[j]);
@@ -351,21 +439,31 @@ NGMIX_HD void set_trial(State &s)
 
 // lmpar on the stored factor, trial point, and the quantities the ratio test
 // needs afterwards (lmder: the body of the inner loop up to the evaluation)
-template <int NP = LM_NPMAX, class State = lm_state>
-NGMIX_HD void propose(State &s)
+template <class Dim, class State>
+NGMIX_HD void propose(const Dim d, State &s)
 {
-    const int n = s.n;
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
     double r[NP * NP], sdiag[NP], p[NP], wa3[NP];
+    LM_UNROLL
     for (int i = 0; i < n; i++)
+        LM_UNROLL
         for (int j = 0; j < n; j++) r[i * NP + j] = s.R[i * NP + j];
-    lmpar<NP>(n, r, s.ipvt, s.diag, s.qtf, s.delta, s.par, p, sdiag);
+    // (lmpar reads p only after writing all of it through ipvt, a permutation)
+    LM_UNROLL
+    for (int j = 0; j < n; j++) {
+        p[j] = 0.0;
+        sdiag[j] = 0.0;
+    }
+    lmpar(d, r, s.ipvt, s.diag, s.qtf, s.delta, s.par, p, sdiag);
+    LM_UNROLL
     for (int j = 0; j < n; j++) {
         s.step[j] = -p[j];
         s.xti[j] = s.xi[j] + s.step[j];
         wa3[j] = s.diag[j] * s.step[j];
     }
-    set_trial(s);
-    s.pnorm = enorm(n, wa3);
+    set_trial(d, s);
+    s.pnorm = enorm(d, wa3);
     if (s.iter == 1) s.delta = fmin(s.delta, s.pnorm);
     s.fonly = 0;
     if (s.mode == NGMIX_LM_MODE_ANALYTIC_LAZY) {
@@ -378,12 +476,15 @@ NGMIX_HD void propose(State &s)
         // jacobian at its last point; a miss costs this fit one more round
         // (phase JAC), never a different iterate.
         double w3[NP];
+        LM_UNROLL
         for (int j = 0; j < n; j++) w3[j] = 0.0;
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
-            const double temp = s.step[s.ipvt[j]];
+            const double temp = d.get(s.step, s.ipvt[j]);
+            LM_UNROLL
             for (int i = 0; i <= j; i++) w3[i] += s.R[i * NP + j] * temp;
         }
-        const double temp1 = enorm(n, w3) / s.fnorm;
+        const double temp1 = enorm(d, w3) / s.fnorm;
         const double temp2 = (sqrt(s.par) * s.pnorm) / s.fnorm;
         const double prered = temp1 * temp1 + temp2 * temp2 / 0.5;
         if (prered <= s.ftol || s.pnorm / 0.5 <= s.xtol * s.xnorm) s.fonly = 1;
@@ -391,36 +492,40 @@ NGMIX_HD void propose(State &s)
 }
 
 // the outer-loop head of lmder at the point whose normal equations are
-// (A, g): factor, scale, gradient test, then the first proposal.
-// Returns true when the fit has terminated (info set).
-template <int NP = LM_NPMAX, class State = lm_state>
-NGMIX_HD bool new_jacobian(State &s, const double *A, const double *g)
+// (A, g): factor, scale, gradient test.  Returns true when the fit has
+// terminated (info set); otherwise the caller proposes the first step.
+template <class Dim, class State>
+NGMIX_HD bool new_jacobian(const Dim d, State &s, const double *A, const double *g)
 {
-    const int n = s.n;
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
     double acnorm[NP];
     s.njev++;
-    factor_normal<NP>(n, A, s.R, s.ipvt, acnorm);
+    factor_normal(d, A, s.R, s.ipvt, acnorm);
     if (s.iter == 1) {
         double wa3[NP];
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
             s.diag[j] = acnorm[j];
             if (acnorm[j] == 0.0) s.diag[j] = 1.0;
             wa3[j] = s.diag[j] * s.xi[j];
         }
-        s.xnorm = enorm(n, wa3);
+        s.xnorm = enorm(d, wa3);
         s.delta = s.factor * s.xnorm;
         if (s.delta == 0.0) s.delta = s.factor;
     }
-    qtf_from_gradient<NP>(n, s.R, s.ipvt, g, s.qtf);
+    qtf_from_gradient(d, s.R, s.ipvt, g, s.qtf);
     // norm of the scaled gradient
     s.gnorm = 0.0;
     if (s.fnorm != 0.0) {
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
-            const int l = s.ipvt[j];
-            if (acnorm[l] == 0.0) continue;
+            const double acl = d.get(acnorm, s.ipvt[j]);
+            if (acl == 0.0) continue;
             double sum = 0.0;
+            LM_UNROLL
             for (int i = 0; i <= j; i++) sum += s.R[i * NP + j] * (s.qtf[i] / s.fnorm);
-            s.gnorm = fmax(s.gnorm, fabs(sum / acnorm[l]));
+            s.gnorm = fmax(s.gnorm, fabs(sum / acl));
         }
     }
     if (s.gnorm <= s.gtol) {
@@ -428,9 +533,9 @@ NGMIX_HD bool new_jacobian(State &s, const double *A, const double *g)
         s.phase = LM_PHASE_DONE;
         return true;
     }
+    LM_UNROLL
     for (int j = 0; j < n; j++) s.diag[j] = fmax(s.diag[j], acnorm[j]);
-    propose<NP>(s);
-    return false;
+    return false;   // the caller proposes (ONE copy of lmpar / qrsolv in the code)
 }
 
 NGMIX_HD void lm_init(lm_state &s, int n, const double *x0, double ftol, double xtol,
@@ -457,7 +562,7 @@ NGMIX_HD void lm_init(lm_state &s, int n, const double *x0, double ftol, double 
         s.step[j] = 0.0;
         s.ipvt[j] = j;
     }
-    set_trial(s);
+    set_trial(runtime_dim<LM_NPMAX>{n}, s);
     for (int j = 0; j < LM_NPMAX; j++) s.x[j] = s.xt[j];
     for (int i = 0; i < LM_NPMAX * LM_NPMAX; i++) s.R[i] = 0.0;
     s.fnorm = s.xnorm = s.delta = s.par = s.gnorm = s.pnorm = 0.0;
@@ -473,30 +578,43 @@ NGMIX_HD void lm_init(lm_state &s, int n, const double *x0, double ftol, double 
 }
 
 // Consume the evaluation at s.xt:  ff = |f|^2, g = J^T f, A = J^T J
-// (A, g in NP-strided / NP-long arrays).  ff may be +inf (the
+// (A, g in strided / stride-long arrays).  ff may be +inf (the
 // model was out of range at xt: the reference's calc_fdiff returns -inf
 // residuals there); A and g are then ignored.
-template <int NP = LM_NPMAX, class State = lm_state>
-NGMIX_HD void lm_advance(State &s, double ff, const double *g_in, const double *A_in)
+template <class Dim, class State>
+NGMIX_HD void lm_advance(const Dim d, State &s, double ff, const double *g_in,
+                         const double *A_in)
 {
-    const int n = s.n;
+    constexpr int NP = Dim::stride;
+    const int n = d.n();
     if (s.phase == LM_PHASE_DONE) return;
     // analytic jacobians are with respect to the external parameters: the
     // wrapped Dfun of leastsqbound.py:485-489 scales column j by d xt_j / d xti_j
     // (forward differences are taken in the internal parameters already)
-    double gs[NP], As[NP * NP];
-    const double *g = g_in, *A = A_in;
+    double g[NP], A[NP * NP];
     if (s.bounded && s.mode != NGMIX_LM_MODE_FD) {
         double sc[NP];
+        LM_UNROLL
         for (int j = 0; j < n; j++) sc[j] = i2e_grad(s.xti[j], s.lo[j], s.hi[j]);
+        LM_UNROLL
         for (int j = 0; j < n; j++) {
-            gs[j] = g_in[j] * sc[j];
-            for (int k = 0; k < n; k++)
-                As[j * NP + k] = A_in[j * NP + k] * sc[j] * sc[k];
+            g[j] = g_in[j] * sc[j];
+            LM_UNROLL
+            for (int k = 0; k < n; k++) A[j * NP + k] = A_in[j * NP + k] * sc[j] * sc[k];
         }
-        g = gs;
-        A = As;
+    } else {
+        LM_UNROLL
+        for (int j = 0; j < n; j++) g[j] = g_in[j];
+        LM_UNROLL
+        for (int i = 0; i < n; i++)
+            LM_UNROLL
+            for (int j = 0; j < n; j++) A[i * NP + j] = A_in[i * NP + j];
     }
+    // The three places lmder factors a new jacobian (and the two where it
+    // proposes a step) set a flag and meet at ONE call site each at the end:
+    // inlined at every site the step was 45,000 instructions for six parameters,
+    // four copies of lmpar / qrsolv that no instruction cache holds.
+    bool want_jacobian = false, want_proposal = false;
     if (s.phase == LM_PHASE_JAC) {
         // lmdif: the forward-difference jacobian at the accepted point cost
         // n evaluations (fdjac2); then the outer-loop head.  (Mode
@@ -504,10 +622,8 @@ NGMIX_HD void lm_advance(State &s, double ff, const double *g_in, const double *
         // trial -- lmder's own call with iflag = 2, counted by njev alone.)
         if (s.mode == NGMIX_LM_MODE_FD) s.nfev += n;
         s.phase = LM_PHASE_TRIAL;
-        new_jacobian<NP>(s, A, g);
-        return;
-    }
-    if (s.phase == LM_PHASE_INIT) {
+        want_jacobian = true;
+    } else if (s.phase == LM_PHASE_INIT) {
         // lmder / lmdif: fvec at the starting point, then the outer loop
         s.nfev = s.mode == NGMIX_LM_MODE_FD ? 1 + n : 1;
         s.fnorm = sqrt(ff);
@@ -524,86 +640,99 @@ NGMIX_HD void lm_advance(State &s, double ff, const double *g_in, const double *
             return;
         }
         s.phase = LM_PHASE_TRIAL;
-        new_jacobian<NP>(s, A, g);
-        return;
-    }
-
-    // ---- LM_PHASE_TRIAL: the rest of lmder's inner loop
-    s.nfev++;
-    // an out-of-range trial is a residual vector of -inf in the reference;
-    // MINPACK's enorm of that is NaN (inf/inf in its scaled sums), and the
-    // comparisons below then go the way they go for a NaN
-    const double fnorm1 = ff < INFINITY ? sqrt(ff) : NAN;
-    double actred = -1.0;
-    if (0.1 * fnorm1 < s.fnorm) {
-        const double t = fnorm1 / s.fnorm;
-        actred = 1.0 - t * t;
-    }
-    // predicted reduction and directional derivative
-    double wa3[NP];
-    for (int j = 0; j < n; j++) wa3[j] = 0.0;
-    for (int j = 0; j < n; j++) {
-        const double temp = s.step[s.ipvt[j]];
-        for (int i = 0; i <= j; i++) wa3[i] += s.R[i * NP + j] * temp;
-    }
-    const double temp1 = enorm(n, wa3) / s.fnorm;
-    const double temp2 = (sqrt(s.par) * s.pnorm) / s.fnorm;
-    const double prered = temp1 * temp1 + temp2 * temp2 / 0.5;
-    const double dirder = -(temp1 * temp1 + temp2 * temp2);
-    double ratio = 0.0;
-    if (prered != 0.0) ratio = actred / prered;
-    // update the step bound
-    if (ratio <= 0.25) {
-        double temp = 0.5;
-        if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-        if (0.1 * fnorm1 >= s.fnorm || temp < 0.1) temp = 0.1;
-        s.delta = temp * fmin(s.delta, s.pnorm / 0.1);
-        s.par = s.par / temp;
-    } else if (s.par == 0.0 || ratio >= 0.75) {
-        s.delta = s.pnorm / 0.5;
-        s.par = 0.5 * s.par;
-    }
-    const bool accepted = ratio >= 1.0e-4;
-    if (accepted) {
-        double w[NP];
-        for (int j = 0; j < n; j++) {
-            s.x[j] = s.xt[j];
-            s.xi[j] = s.xti[j];
-            w[j] = s.diag[j] * s.xi[j];
-        }
-        s.xnorm = enorm(n, w);
-        s.fnorm = fnorm1;
-        s.iter++;
-    }
-    // convergence tests
-    int info = 0;
-    if (fabs(actred) <= s.ftol && prered <= s.ftol && 0.5 * ratio <= 1.0) info = 1;
-    if (s.delta <= s.xtol * s.xnorm) info = 2;
-    if (fabs(actred) <= s.ftol && prered <= s.ftol && 0.5 * ratio <= 1.0 && info == 2)
-        info = 3;
-    if (info == 0) {
-        // termination and stringent tolerances
-        if (s.nfev >= s.maxfev) info = 5;
-        if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
-        if (s.delta <= EPSMCH * s.xnorm) info = 7;
-        if (s.gnorm <= EPSMCH) info = 8;
-    }
-    if (info != 0) {
-        s.info = info;
-        s.phase = LM_PHASE_DONE;
-        return;
-    }
-    if (!accepted) {
-        propose<NP>(s);  // same factor, smaller region
-    } else if (s.mode == NGMIX_LM_MODE_FD || s.fonly) {
-        // ask for the jacobian at the new point
-        for (int j = 0; j < n; j++) s.xti[j] = s.xi[j];
-        set_trial(s);
-        s.phase = LM_PHASE_JAC;
-        s.fonly = 0;
+        want_jacobian = true;
     } else {
-        new_jacobian<NP>(s, A, g);  // the trial point's jacobian is the new one
+        // ---- LM_PHASE_TRIAL: the rest of lmder's inner loop
+        s.nfev++;
+        // an out-of-range trial is a residual vector of -inf in the reference;
+        // MINPACK's enorm of that is NaN (inf/inf in its scaled sums), and the
+        // comparisons below then go the way they go for a NaN
+        const double fnorm1 = ff < INFINITY ? sqrt(ff) : NAN;
+        double actred = -1.0;
+        if (0.1 * fnorm1 < s.fnorm) {
+            const double t = fnorm1 / s.fnorm;
+            actred = 1.0 - t * t;
+        }
+        // predicted reduction and directional derivative
+        double wa3[NP];
+        LM_UNROLL
+        for (int j = 0; j < n; j++) wa3[j] = 0.0;
+        LM_UNROLL
+        for (int j = 0; j < n; j++) {
+            const double temp = d.get(s.step, s.ipvt[j]);
+            LM_UNROLL
+            for (int i = 0; i <= j; i++) wa3[i] += s.R[i * NP + j] * temp;
+        }
+        const double temp1 = enorm(d, wa3) / s.fnorm;
+        const double temp2 = (sqrt(s.par) * s.pnorm) / s.fnorm;
+        const double prered = temp1 * temp1 + temp2 * temp2 / 0.5;
+        const double dirder = -(temp1 * temp1 + temp2 * temp2);
+        double ratio = 0.0;
+        if (prered != 0.0) ratio = actred / prered;
+        // update the step bound
+        if (ratio <= 0.25) {
+            double temp = 0.5;
+            if (actred < 0.0) temp = 0.5 * dirder / (dirder + 0.5 * actred);
+            if (0.1 * fnorm1 >= s.fnorm || temp < 0.1) temp = 0.1;
+            s.delta = temp * fmin(s.delta, s.pnorm / 0.1);
+            s.par = s.par / temp;
+        } else if (s.par == 0.0 || ratio >= 0.75) {
+            s.delta = s.pnorm / 0.5;
+            s.par = 0.5 * s.par;
+        }
+        const bool accepted = ratio >= 1.0e-4;
+        if (accepted) {
+            double w[NP];
+            LM_UNROLL
+            for (int j = 0; j < n; j++) {
+                s.x[j] = s.xt[j];
+                s.xi[j] = s.xti[j];
+                w[j] = s.diag[j] * s.xi[j];
+            }
+            s.xnorm = enorm(d, w);
+            s.fnorm = fnorm1;
+            s.iter++;
+        }
+        // convergence tests
+        int info = 0;
+        if (fabs(actred) <= s.ftol && prered <= s.ftol && 0.5 * ratio <= 1.0) info = 1;
+        if (s.delta <= s.xtol * s.xnorm) info = 2;
+        if (fabs(actred) <= s.ftol && prered <= s.ftol && 0.5 * ratio <= 1.0 && info == 2)
+            info = 3;
+        if (info == 0) {
+            // termination and stringent tolerances
+            if (s.nfev >= s.maxfev) info = 5;
+            if (fabs(actred) <= EPSMCH && prered <= EPSMCH && 0.5 * ratio <= 1.0) info = 6;
+            if (s.delta <= EPSMCH * s.xnorm) info = 7;
+            if (s.gnorm <= EPSMCH) info = 8;
+        }
+        if (info != 0) {
+            s.info = info;
+            s.phase = LM_PHASE_DONE;
+            return;
+        }
+        if (!accepted) {
+            want_proposal = true;   // same factor, smaller region
+        } else if (s.mode == NGMIX_LM_MODE_FD || s.fonly) {
+            // ask for the jacobian at the new point
+            LM_UNROLL
+            for (int j = 0; j < n; j++) s.xti[j] = s.xi[j];
+            set_trial(d, s);
+            s.phase = LM_PHASE_JAC;
+            s.fonly = 0;
+        } else {
+            want_jacobian = true;   // the trial point's jacobian is the new one
+        }
     }
+    if (want_jacobian) want_proposal = !new_jacobian(d, s, A, g);
+    if (want_proposal) propose(d, s);
+}
+
+// a fit of s.n <= NP parameters in NP-strided arrays
+template <int NP = LM_NPMAX, class State = lm_state>
+NGMIX_HD void lm_advance(State &s, double ff, const double *g, const double *A)
+{
+    lm_advance(runtime_dim<NP>{s.n}, s, ff, g, A);
 }
 
 // ---- the separable joint prior (ngmix_simple_sep_prior) --------------------

@@ -661,7 +661,7 @@ struct Step {
         }
     }
 
-    // lmcore::new_jacobian with A = f.M, g = f.g, up to its call of propose:
+    // lmcore::new_jacobian with A = f.M, g = f.g (the caller proposes):
     // returns true when the fit has terminated
     static __device__ __forceinline__ bool new_jacobian(Fit &f)
     {

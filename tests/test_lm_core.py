@@ -407,10 +407,12 @@ def test_batch_prior_equals_the_reference_prior(golden, tag):
 @pytest.mark.parametrize("mode", [0, 1, 2])
 @pytest.mark.parametrize("bounded", [False, True])
 def test_register_form_equals_generic_form_bit_for_bit(n, mode, bounded, monkeypatch):
-    """lm_core_reg.hpp (compile-time parameter count, arrays in registers: what
-    the device runs for 6-10 parameters) against lm_core.hpp: the same state
-    record, byte for byte, after every step of every fit -- including a
-    rank-deficient jacobian and rejected steps"""
+    """The two instantiations of lm_core.hpp's one text of the step: under
+    lm_core_reg.hpp's fixed_dim<N> (compile-time parameter count, run-time
+    indices as select chains, arrays in registers: what the device runs for
+    6-10 parameters) against runtime_dim<LM_NPMAX> (what the MINPACK tests
+    above run): the same state record, byte for byte, after every step of
+    every fit -- including a rank-deficient jacobian and rejected steps"""
     L = _lib.lib()
     rng = np.random.RandomState(100 * n + 10 * mode + int(bounded))
     nfit, m = 12, 40
@@ -486,6 +488,71 @@ def test_register_form_equals_generic_form_bit_for_bit(n, mode, bounded, monkeyp
         assert a == b, "state records differ after step %d" % r
     # the fits did something: several steps, several outcomes
     assert len(states["generic"]) > 4
+
+
+@pytest.mark.parametrize("n", [6, 10])
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("case", ["zero_A", "increasing_diag"])
+def test_register_form_equals_generic_form_at_the_pivot_edges(n, mode, case, monkeypatch):
+    """the two instantiations again, byte for byte after every step, where the
+    pivoting is at its extremes.  zero_A: normal equations that are all zeros
+    (rank deficient at k = 0), from the first evaluation on and from a later
+    accepted step on.  increasing_diag: diag(A) strictly increasing, so the
+    pivot order is the full reversal -- every position of the get / set select
+    chains and every pivot exchange is taken"""
+    L = _lib.lib()
+    rng = np.random.RandomState(7000 + 100 * n + 10 * mode + len(case))
+    nfit, m = 3, n + 4
+    # residuals J0 x - y + 0.05 sin(J0 x): J0's columns are orthogonal with
+    # norms 1.5^j, the jacobian scales its rows by 1 +- 0.05
+    Q, _ = np.linalg.qr(rng.normal(size=(m, n)))
+    J0 = Q * 1.5 ** np.arange(n)
+    truth = rng.uniform(0.5, 1.5, size=(nfit, n))
+    data = truth @ J0.T + 0.01 * rng.normal(size=(nfit, m))
+    x0 = truth * rng.uniform(0.7, 1.3, size=truth.shape)
+    x0[1] *= 5.0                                   # a poor guess
+    states = {}
+    for form in ("generic", "register"):
+        if form == "generic":
+            monkeypatch.setenv("NGMIX_LM_GENERIC", "1")
+        else:
+            monkeypatch.delenv("NGMIX_LM_GENERIC", raising=False)
+        st = np.zeros(nfit, dtype=_lib.LM_STATE_DTYPE)
+        assert L.ngmix_lm_init(_lib.ptr(st), nfit, n, _lib.ptr(x0), 1e-8, 1e-8, 0.0,
+                               60, 100.0, mode, None, None) == 0
+        history = []
+        for rounds in range(200):
+            if np.all(st["phase"] == _lib.LM_PHASE_DONE):
+                break
+            ff = np.zeros(nfit)
+            g = np.zeros((nfit, NP))
+            A = np.zeros((nfit, NP, NP))
+            for i in range(nfit):
+                u = J0 @ st["xt"][i, :n]
+                f = u - data[i] + 0.05 * np.sin(u)
+                J = (1.0 + 0.05 * np.cos(u))[:, None] * J0
+                ff[i] = f @ f
+                g[i, :n] = J.T @ f
+                A[i, :n, :n] = J.T @ J
+                if case == "increasing_diag":
+                    assert np.all(np.diff(np.diag(A[i, :n, :n])) > 0.0)
+                elif i == 0 or (i == 1 and rounds >= 2):
+                    A[i] = 0.0
+            L.ngmix_lm_advance_host(_lib.ptr(st), nfit, _lib.ptr(ff), _lib.ptr(g),
+                                    _lib.ptr(A))
+            if rounds == 0 and case == "increasing_diag":
+                assert np.all(st["ipvt"][:, :n] == np.arange(n)[::-1])
+            history.append(st.copy().tobytes())
+        assert np.all(st["phase"] == _lib.LM_PHASE_DONE)
+        if case == "zero_A":
+            # all-zero normal equations end a fit by the gradient test
+            assert st["info"][0] == 4 and st["nfev"][0] == (1 + n if mode == 1 else 1)
+            assert st["info"][1] == 4 and st["iter"][1] > 1
+        states[form] = history
+    assert len(states["generic"]) == len(states["register"])
+    for r, (a, b) in enumerate(zip(states["generic"], states["register"])):
+        assert a == b, "state records differ after step %d" % r
+    assert len(states["generic"]) > 3
 
 
 def run_lm_lazy(func, jac, x0, mode, **kw):

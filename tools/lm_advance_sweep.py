@@ -1,5 +1,6 @@
 """lm_advance per launch for n = 6..14 parameters (an "exp" fit over 1..9
-bands), each form of the step A/B'd in one process: the register form (6..10),
+bands), each form of the step A/B'd in one process: the register form (6..10;
+"default" picks it below 9, "register" = NGMIX_LM_TEAM_MIN=11 at 9 and 10 too),
 the team form with 4 / 2 / 1 fits per wave (NGMIX_LM_TEAM_MIN / NGMIX_LM_TEAMS
 are read at every launch), the generic one-thread form.  HIP-event time of
 the advance launches and of the whole fit.
@@ -17,7 +18,8 @@ from ngmix_amd.lm_batch import LMBatchFitter  # noqa: E402
 
 nobj = int(sys.argv[1]) if len(sys.argv) > 1 else 50000
 bands = [int(a) for a in sys.argv[2:]] or [1, 2, 3, 4, 5, 6, 8, 9]
-FORMS = [("default", {}, True), ("team x4", {"NGMIX_LM_TEAM_MIN": "6", "NGMIX_LM_TEAMS": "4"}, True),
+FORMS = [("default", {}, True), ("register", {"NGMIX_LM_TEAM_MIN": "11"}, True),
+         ("team x4", {"NGMIX_LM_TEAM_MIN": "6", "NGMIX_LM_TEAMS": "4"}, True),
          ("team x2", {"NGMIX_LM_TEAM_MIN": "6", "NGMIX_LM_TEAMS": "2"}, True),
          ("team x1", {"NGMIX_LM_TEAM_MIN": "6", "NGMIX_LM_TEAMS": "1"}, True),
          ("generic", {}, False)]
