@@ -342,6 +342,8 @@ struct TileEnt {
 };
 static_assert(sizeof(TileEnt) == 32, "TileEnt");
 
+typedef __attribute__((address_space(3))) int LdsInt;   // an int in LDS, by its 32-bit address
+
 // Untracked loads for the look-ahead of the FULL tile loop.  hipcc counts its
 // own memory operations but is conservative across loop back-edges and
 // branches (it drains to vmcnt(0) once per trip); these loads are invisible to
@@ -474,7 +476,11 @@ __device__ __forceinline__ void wait_vm_all(double &a, double &b, double &c, dou
 // An overwriting render is instantiated without it and runs the plain loop.
 // UE: the kernel honours NGMIX_STAMP_UNIFORM_IERR (ie_on below); the kernels
 // launched for batches without such a stamp are instantiated without it.
-template <int OP, bool MASKED, bool FAST, bool FULL, int TW, bool SKIP, bool UE>
+// NG8: the kernel serves batches of mixtures of at most 8 gaussians (the
+// launcher picks it by max_ngauss): the pair loop is unrolled over the gaussian
+// index, bit g of the tile's mask is tested on the scalar unit and record g is
+// read at a compile-time LDS address.
+template <int OP, bool MASKED, bool FAST, bool FULL, int TW, bool SKIP, bool UE, bool NG8>
 __device__ __forceinline__ void wave_tiles(
     const LdsLayout &L, const GaussFused *gf, const TileBox *gbox, const TileEnt *te,
     int ng,
@@ -544,7 +550,7 @@ __device__ __forceinline__ void wave_tiles(
 
     // (tile, gaussian) box tests, CH tiles per ballot: lane = k*ng + g holds
     // gaussian g's box and tests it against tile T + k
-    const bool chunked = ng <= 32;
+    const bool chunked = NG8 || ng <= 32;
     const int CH = chunked ? WAVE / ng : 0;
     const unsigned ngmask = chunked ? (unsigned)((1ull << ng) - 1ull) : 0u;
     int k_l = 0;
@@ -555,6 +561,14 @@ __device__ __forceinline__ void wave_tiles(
         lane_valid = k_l < CH;
         mybox_p = &gbox[lane - k_l * ng];
     }
+    // NG8: k_l (< 64) and the LDS address of the lane's box (< 2^18) share one
+    // register, taken apart at each ballot -- the register pays for the one that
+    // holds the base of the gaussian records at immediate offsets
+    // (the loop of stamps without a shared centre holds two more coordinates per
+    // pair and has no register to spare for that base: it keeps the generic loop)
+    constexpr bool kUnroll = NG8 && FAST;
+    unsigned kbox = 0;
+    if (kUnroll) kbox = ((unsigned)k_l << 18) | (unsigned)(size_t)(const LdsInt *)(const int *)mybox_p;
     const unsigned long long valid_mask = __builtin_amdgcn_ballot_w64(lane_valid);
     unsigned long long allmask = 0ull;
     int kc = 0;
@@ -626,16 +640,65 @@ __device__ __forceinline__ void wave_tiles(
         double v2 = dv * dv, u2 = du * du, vu = dv * du;
         double model = 0.0;
 
-        for (int g0 = 0; g0 < ng; g0 += 32) {
+        // one (tile, gaussian) pair that passed the box test
+        auto pair = [&](const GaussFused &G) {
+            const double ga = G.a, gb = G.b, gc = G.c, gpa = G.pa;
+            if (!FAST) {
+                dv = v - G.row;
+                du = u - G.col;
+                v2 = dv * dv;
+                u2 = du * du;
+                vu = dv * du;
+            }
+            const double y = fma(ga, v2, fma(gb, u2, gc * vu));  // chi2/2
+            // 0 <= chi2 < 25  <=>  y in [+0, 12.5)
+            const bool pass = FAST ? ((unsigned)__double2hiint(y) < 0x40290000u)
+                                   : (y < 12.5 && y >= 0.0);
+            if (pass) {
+                double e = fexp_neg_fused(y, L.tab, K);
+                const bool band = FAST ? ((unsigned)__double2hiint(y) >= 0x40240000u)
+                                       : (y > 10.0);
+                if (band) {
+                    // apod_window (fastexp_nb.py:97-117): W = u^3 (10 - 15 u
+                    // + 6 u^2), u = (12.5 - y) * 0.4, written in b = 0.8 u:
+                    //   W = kappa b^3 ((b - 1)^2 + 1/15), kappa = 9.375 / 0.512
+                    // -- b is ONE fma (4.0 and 1.0 are inline constants), and no
+                    // step reads two SGPR constants, so none has to be moved to
+                    // a VGPR first: 8 instructions against 10 for the textbook
+                    // form.  W(chi2 == 20) = 1 to 1 ulp.
+                    const double bb = fma(y, K.wb, 4.0);
+                    const double bm = bb - 1.0;
+                    const double bq = fma(bm, bm, K.wq);
+                    e *= (bb * bb) * (bb * bq);
+                    e *= K.wk;
+                }
+                model = fma(gpa, e, model);
+            }
+        };
+
+        for (int g0 = 0; g0 < (NG8 ? 1 : ng); g0 += 32) {
             unsigned gmask;
             if (chunked) {
                 if (kc == 0) {
                     int Tk;  // = Tc + k_l; asm so that it is not hoisted out
-                    asm volatile("v_add_u32 %0, %1, %2" : "=v"(Tk) : "s"(Tc), "v"(k_l));
+                    if (kUnroll)
+                        asm volatile("v_lshrrev_b32 %0, 18, %2\n\tv_add_u32 %0, %1, %0"
+                                     : "=&v"(Tk) : "s"(Tc), "v"(kbox));
+                    else
+                        asm volatile("v_add_u32 %0, %1, %2" : "=v"(Tk) : "s"(Tc), "v"(k_l));
                     if (Tk > ntiles) Tk = ntiles;  // a sentinel (SKIP: or a tile past the last
                                                    // walked band; its slots are never consumed)
                     const int r0k = te[Tk].r0, c0k = te[Tk].c0;
-                    const TileBox mybox = *mybox_p;
+                    TileBox mybox;
+                    if (kUnroll) {
+                        const LdsInt *q = (const LdsInt *)(size_t)(kbox & 0x3ffffu);
+                        mybox.r_lo = q[0];
+                        mybox.r_span = (unsigned)q[1];
+                        mybox.c_lo = q[2];
+                        mybox.c_span = (unsigned)q[3];
+                    } else {
+                        mybox = *mybox_p;
+                    }
                     allmask = tile_hits(mybox, r0k, c0k) & valid_mask;
                 }
                 gmask = (unsigned)allmask & ngmask;
@@ -649,41 +712,17 @@ __device__ __forceinline__ void wave_tiles(
                 gmask = (unsigned)(tile_hits(box, r0, c0) &
                                    __builtin_amdgcn_ballot_w64((lane < 32) & (g0 + lane < ng)));
             }
-            while (gmask) {
-                const int g = g0 + __builtin_ctz(gmask);
-                gmask &= gmask - 1u;
-                const GaussFused &G = gf[g];
-                const double ga = G.a, gb = G.b, gc = G.c, gpa = G.pa;
-                if (!FAST) {
-                    dv = v - G.row;
-                    du = u - G.col;
-                    v2 = dv * dv;
-                    u2 = du * du;
-                    vu = dv * du;
-                }
-                const double y = fma(ga, v2, fma(gb, u2, gc * vu));  // chi2/2
-                // 0 <= chi2 < 25  <=>  y in [+0, 12.5)
-                const bool pass = FAST ? ((unsigned)__double2hiint(y) < 0x40290000u)
-                                       : (y < 12.5 && y >= 0.0);
-                if (pass) {
-                    double e = fexp_neg_fused(y, L.tab, K);
-                    const bool band = FAST ? ((unsigned)__double2hiint(y) >= 0x40240000u)
-                                           : (y > 10.0);
-                    if (band) {
-                        // apod_window (fastexp_nb.py:97-117): W = u^3 (10 - 15 u
-                        // + 6 u^2), u = (12.5 - y) * 0.4, written in b = 0.8 u:
-                        //   W = kappa b^3 ((b - 1)^2 + 1/15), kappa = 9.375 / 0.512
-                        // -- b is ONE fma (4.0 and 1.0 are inline constants), and no
-                        // step reads two SGPR constants, so none has to be moved to
-                        // a VGPR first: 8 instructions against 10 for the textbook
-                        // form.  W(chi2 == 20) = 1 to 1 ulp.
-                        const double bb = fma(y, K.wb, 4.0);
-                        const double bm = bb - 1.0;
-                        const double bq = fma(bm, bm, K.wq);
-                        e *= (bb * bb) * (bb * bq);
-                        e *= K.wk;
-                    }
-                    model = fma(gpa, e, model);
+            if constexpr (kUnroll) {
+                // index order, like the loop below: bit g on the scalar unit, record g
+                // at an immediate offset
+#pragma unroll
+                for (int g = 0; g < 8; g++)
+                    if (gmask & (1u << g)) pair(gf[g]);
+            } else {
+                while (gmask) {
+                    const int g = g0 + __builtin_ctz(gmask);
+                    gmask &= gmask - 1u;
+                    pair(gf[g]);
                 }
             }
         }
@@ -784,7 +823,7 @@ __device__ __forceinline__ void wave_tiles(
 // every pixel and is launched as the LS = false kernel: the plain loop, the
 // early request, no union of the boxes -- the launcher picks by that flag, and
 // the LS kernel does not look at it.
-template <int OP, bool MASKED, int TW, bool LS = (OP == OP_RENDER_FAST), bool UE = true>
+template <int OP, bool MASKED, int TW, bool NG8, bool LS = (OP == OP_RENDER_FAST), bool UE = true>
 __device__ __forceinline__ void pixpass_wave_body(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
@@ -967,16 +1006,16 @@ __device__ __forceinline__ void pixpass_wave_body(
         // (render: the line skip when the image is accumulated into; an
         // overwriting render writes every pixel and runs the plain loop)
         if (fast && full)
-            wave_tiles<OP, MASKED, true, true, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+            wave_tiles<OP, MASKED, true, true, TW, LS, ue, NG8>(L, gf, gbox, te, ng, st, sval, sierr, masked,
                 out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
         else if (fast)
-            wave_tiles<OP, MASKED, true, false, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+            wave_tiles<OP, MASKED, true, false, TW, LS, ue, NG8>(L, gf, gbox, te, ng, st, sval, sierr, masked,
                 out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
         else if (full)
-            wave_tiles<OP, MASKED, false, true, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+            wave_tiles<OP, MASKED, false, true, TW, LS, ue, NG8>(L, gf, gbox, te, ng, st, sval, sierr, masked,
                 out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
         else
-            wave_tiles<OP, MASKED, false, false, TW, LS, ue>(L, gf, gbox, te, ng, st, sval, sierr, masked,
+            wave_tiles<OP, MASKED, false, false, TW, LS, ue, NG8>(L, gf, gbox, te, ng, st, sval, sierr, masked,
                 out, out_base, jac, pv, pe, acc_ll, acc_sn, acc_sd, keep, ub, ie_on);
     } else if (OP != OP_RENDER_FAST) {
         // an empty mixture: model == 0 everywhere
@@ -1024,26 +1063,26 @@ __device__ __forceinline__ void pixpass_wave_body(
     }
 }
 
-template <int OP, bool MASKED, int TW>
+template <int OP, bool MASKED, int TW, bool NG8>
 __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
     int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
 {
-    pixpass_wave_body<OP, MASKED, TW>(stamps, val, ierr, jacs, gmix, out, out_start, status,
+    pixpass_wave_body<OP, MASKED, TW, NG8>(stamps, val, ierr, jacs, gmix, out, out_start, status,
                                       max_ngauss, nchunks_cap, no_skip, tile_cap);
 }
 
 // the render that overwrites (writes every pixel, reads none): no line skip
-template <int OP, bool MASKED, int TW>
+template <int OP, bool MASKED, int TW, bool NG8>
 __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_plain(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
     int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
 {
-    pixpass_wave_body<OP, MASKED, TW, false>(stamps, val, ierr, jacs, gmix, out, out_start,
+    pixpass_wave_body<OP, MASKED, TW, NG8, false>(stamps, val, ierr, jacs, gmix, out, out_start,
                                              status, max_ngauss, nchunks_cap, no_skip, tile_cap);
 }
 
@@ -1051,7 +1090,7 @@ __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_plain(
 // (the boxes re-read at each ballot, the window in the form that needs no VGPR constant), and
 // with instruction issue and memory both ~80 % busy one more resident wave per
 // SIMD is what overlaps them better
-template <int OP, bool MASKED, int TW>
+template <int OP, bool MASKED, int TW, bool NG8>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7)))
 void pixpass_wave_kernel7(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
@@ -1059,26 +1098,26 @@ void pixpass_wave_kernel7(
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
     int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
 {
-    pixpass_wave_body<OP, MASKED, TW>(stamps, val, ierr, jacs, gmix, out, out_start, status,
+    pixpass_wave_body<OP, MASKED, TW, NG8>(stamps, val, ierr, jacs, gmix, out, out_start, status,
                                       max_ngauss, nchunks_cap, no_skip, tile_cap);
 }
 
 // loglike / fdiff / s2n of a batch in which no stamp is flagged
 // NGMIX_STAMP_UNIFORM_IERR (or with NGMIX_BATCH_STREAM_IERR): every weight map
 // is streamed, and the kernel carries nothing of the other path
-template <int OP, bool MASKED, int TW>
+template <int OP, bool MASKED, int TW, bool NG8>
 __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_stream(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
     int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
 {
-    pixpass_wave_body<OP, MASKED, TW, false, false>(stamps, val, ierr, jacs, gmix, out,
+    pixpass_wave_body<OP, MASKED, TW, NG8, false, false>(stamps, val, ierr, jacs, gmix, out,
                                                     out_start, status, max_ngauss,
                                                     nchunks_cap, no_skip, tile_cap);
 }
 
-template <int OP, bool MASKED, int TW>
+template <int OP, bool MASKED, int TW, bool NG8>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7)))
 void pixpass_wave_kernel7_stream(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
@@ -1086,7 +1125,7 @@ void pixpass_wave_kernel7_stream(
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
     int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
 {
-    pixpass_wave_body<OP, MASKED, TW, false, false>(stamps, val, ierr, jacs, gmix, out,
+    pixpass_wave_body<OP, MASKED, TW, NG8, false, false>(stamps, val, ierr, jacs, gmix, out,
                                                     out_start, status, max_ngauss,
                                                     nchunks_cap, no_skip, tile_cap);
 }
@@ -1122,33 +1161,43 @@ static auto pick_grid_kernel(bool k4)
 // (The census counts the streaming kernels under the names of the kernels they
 // stand in for: the form of the loop is the same, and what a census asserts is
 // that no generic kernel served the workload.)
-using WaveKernel = decltype(kernel(pixpass_wave_kernel<OP_LOGLIKE, false, 8>, ""));
+using WaveKernel = decltype(kernel(pixpass_wave_kernel<OP_LOGLIKE, false, 8, false>, ""));
 
-template <int FOP, int TW>
-static WaveKernel pick_wave_kernel(bool masked, bool seven, bool stream, bool overwrite)
+template <int FOP, int TW, bool NG8>
+static WaveKernel pick_wave_kernel_ng(bool masked, bool seven, bool stream, bool overwrite)
 {
     if constexpr (FOP == OP_LOGLIKE) {
         constexpr const char *n7 = "pixpass_wave_kernel7<loglike>";
         if (seven && stream)
-            return masked ? kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, true, 8>, n7)
-                          : kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8>, n7);
+            return masked ? kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, true, 8, NG8>, n7)
+                          : kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8, NG8>, n7);
         if (seven)
-            return masked ? kernel(pixpass_wave_kernel7<OP_LOGLIKE, true, 8>, n7)
-                          : kernel(pixpass_wave_kernel7<OP_LOGLIKE, false, 8>, n7);
+            return masked ? kernel(pixpass_wave_kernel7<OP_LOGLIKE, true, 8, NG8>, n7)
+                          : kernel(pixpass_wave_kernel7<OP_LOGLIKE, false, 8, NG8>, n7);
     }
     constexpr const char *n = FOP == OP_LOGLIKE ? "pixpass_wave_kernel<loglike>"
                               : FOP == OP_FDIFF ? "pixpass_wave_kernel<fdiff>"
                               : FOP == OP_S2N   ? "pixpass_wave_kernel<s2n>"
                                                 : "pixpass_wave_kernel<render>";
     if constexpr (FOP == OP_RENDER_FAST) {
-        if (overwrite) return kernel(pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16>, n);
+        if (overwrite) return kernel(pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16, NG8>, n);
     } else {
         if (stream)
-            return masked ? kernel(pixpass_wave_kernel_stream<FOP, true, TW>, n)
-                          : kernel(pixpass_wave_kernel_stream<FOP, false, TW>, n);
+            return masked ? kernel(pixpass_wave_kernel_stream<FOP, true, TW, NG8>, n)
+                          : kernel(pixpass_wave_kernel_stream<FOP, false, TW, NG8>, n);
     }
-    return masked ? kernel(pixpass_wave_kernel<FOP, true, TW>, n)
-                  : kernel(pixpass_wave_kernel<FOP, false, TW>, n);
+    return masked ? kernel(pixpass_wave_kernel<FOP, true, TW, NG8>, n)
+                  : kernel(pixpass_wave_kernel<FOP, false, TW, NG8>, n);
+}
+
+// ng8: no stamp of the batch has more than 8 gaussians -- the kernels whose pair
+// loop is unrolled over the gaussian index (wave_tiles, NG8)
+template <int FOP, int TW>
+static WaveKernel pick_wave_kernel(bool masked, bool seven, bool stream, bool overwrite,
+                                   bool ng8)
+{
+    return ng8 ? pick_wave_kernel_ng<FOP, TW, true>(masked, seven, stream, overwrite)
+               : pick_wave_kernel_ng<FOP, TW, false>(masked, seven, stream, overwrite);
 }
 
 template <int OP>
@@ -1192,7 +1241,7 @@ static int launch_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
     // says so with NGMIX_BATCH_STREAM_IERR, which is also the diagnostic)
     const WaveKernel k = pick_wave_kernel<FOP, TW>(
         b->any_masked && FOP != OP_RENDER_FAST, !six_waves,
-        (b->flags & NGMIX_BATCH_STREAM_IERR) != 0, (no_skip & 4) != 0);
+        (b->flags & NGMIX_BATCH_STREAM_IERR) != 0, (no_skip & 4) != 0, max_ng <= 8);
     const size_t flds = lds_bytes(max_ng, nchunks_cap, a_tc);
     if (flds > 160 * 1024) {
         set_last_error_msg("stamp needs more than 160 KiB of LDS");

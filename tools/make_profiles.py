@@ -4,6 +4,7 @@ profiles/pmc_traffic.json (HBM bytes per launch, read by bench.py).
 
 python tools/make_profiles.py gpurun_out/<dir> <tag> <nstamps>"""
 import csv
+import re
 import glob
 import json
 import os
@@ -34,6 +35,10 @@ for d in sorted(glob.glob(os.path.join(src, "pmc_*"))):
     team_dir = os.path.basename(d).startswith("pmc_team")
     for row in csv.DictReader(open(f)):
         k = row["Kernel_Name"].split("(")[0].replace("void ngmix::", "")
+        # (the fused pixel kernels' fourth parameter -- mixtures of at most 8
+        # gaussians -- does not name another kernel of the tables below)
+        if k.startswith("pixpass_wave_kernel"):
+            k = re.sub(r"^(pixpass_wave_kernel\w*<\d+, \w+, \d+), \w+>$", r"\1>", k)
         # (the team passes run another workload -- tools/team_probe.py, 20,000
         # objects x 9 bands: only the team kernel is taken from them)
         if team_dir != k.startswith("lm_advance_team"):
