@@ -538,6 +538,28 @@ int ngmix_scene_cut_minus(const double *frame, int nrow, int ncol, const void *g
                           const int32_t *owner_host, const int64_t *pix_off, int64_t nwin,
                           const int32_t *items, int64_t nitems, double *out, int64_t total,
                           void *stream);
+/* the normal equations of a frame (csrc/scene_normal.hip): the Gauss-Newton
+   blocks between the n objects of ngmix_scene_boxes (gmix with its norms as
+   that call leaves them, jac, boxes), each with K parameters (1 <= K <= 8).
+   tangents: d theta / d q per gaussian, (n * ngauss, 6, K), theta = (p, row,
+   col, irr, irc, icc).  items[2 * i ..] = a, b; one wave each, in any order:
+     b >= 0 (a < b): out_mat[i] (K x K, row-major) = sum w J_a,k J_b,l over the
+                     pixels of box_a n box_b (clipped union boxes); out_vec[i] = 0;
+     b == -1:        out_mat[i] = sum w J_a,k J_a,l over box_a, symmetric to the
+                     bit; out_vec[i] (K) = sum w r J_a,k;
+     J_o,k[pix] = sum_g sum_alpha d model_o[pix] / d theta_alpha(g)
+                                 * tangents[((o * ngauss + g) * 6 + alpha) * K + k]
+   in deriv_images' convention (fast exp, as ngmix_fisher_batch with fast_exp
+   != 0), w = max(weight[pix], 0) or 1 (weight == NULL), r = resid[pix]; weight
+   and resid are nrow x ncol frames.  An empty rectangle gives zeros.  No
+   atomics; the bits of an item depend on that item alone.  items_host: NULL,
+   or the caller's host copy of items, checked before the launch (a outside
+   [0, n), b outside [-1, n), or b <= a with b != -1 are refused). */
+int ngmix_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac,
+                       int64_t n, const double *tangents, int K, const double *weight,
+                       const double *resid, int nrow, int ncol, const int32_t *boxes,
+                       const int32_t *items, const int32_t *items_host, int64_t nitems,
+                       double *out_mat, double *out_vec, void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

@@ -635,6 +635,17 @@ int ngmix_scene_cut_minus(const double *frame, int nrow, int ncol, const void *g
                                   items, nitems, out, total, (hipStream_t)stream);
 }
 
+int ngmix_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac,
+                       int64_t n, const double *tangents, int K, const double *weight,
+                       const double *resid, int nrow, int ncol, const int32_t *boxes,
+                       const int32_t *items, const int32_t *items_host, int64_t nitems,
+                       double *out_mat, double *out_vec, void *stream)
+{
+    return launch_scene_normal(gmix, ngauss, jac, n, tangents, K, weight, resid, nrow, ncol,
+                               boxes, items, items_host, nitems, out_mat, out_vec,
+                               (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)

@@ -63,6 +63,12 @@ int launch_scene_cut_minus(const double *frame, int nrow, int ncol, const void *
                            const int32_t *owner_host, const int64_t *pix_off, int64_t nwin,
                            const int32_t *items, int64_t nitems, double *out, int64_t total,
                            hipStream_t s);
+// scene_normal.hip
+int launch_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac,
+                        int64_t n, const double *tangents, int K, const double *weight,
+                        const double *resid, int nrow, int ncol, const int32_t *boxes,
+                        const int32_t *items, const int32_t *items_host, int64_t nitems,
+                        double *out_mat, double *out_vec, hipStream_t s);
 // noisecov.hip
 int launch_noise_cov_blocks(const double *dimg, const int64_t *stamp_idx, int64_t m,
                             const int64_t *pix_off, const double *ierr, const double *noise,

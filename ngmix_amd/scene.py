@@ -27,15 +27,28 @@ owner)).  fit_deblended alternates it with the lock-step LM fitter: every object
 is fitted alone on a stamp from which its neighbours' models of the previous
 pass are gone.
 
-torch does the plumbing (the binning of _tile_pairs); the pixel work is HIP
-(csrc/scene.hip).
+    ne = scene.normal_equations(frame, weight, jacobians, pars, "exp", psf=psf)
+    cov = scene.joint_covariance(frame, weight, jacobians, pars, "exp", psf=psf)
+    res = scene.fit_joint(frame, weight, jacobians, guess, "exp", psf=psf)
+
+normal_equations gives the Gauss-Newton blocks of the whole frame at once
+(csrc/scene_normal.hip): every object's own block and
+gradient, and the cross block of every pair of objects that share a tile and
+whose boxes meet, each object with a jacobian of its own.  joint_covariance
+inverts them per group of connected objects (the covariance of an object
+marginalised over its neighbours), and fit_joint is a Levenberg-Marquardt fit of
+all the objects of a frame together over them.
+
+torch does the plumbing (the binning of _tile_pairs, the dense solves of the
+groups); the pixel work is HIP (csrc/scene.hip, csrc/scene_normal.hip).
 """
 import numpy as np
 
 from . import _lib
 from .batch import GMixBatch, StampBatch, _dptr, _on_device, _require_cuda, _stream, _torch
 
-__all__ = ["render_scene", "cut_stamps", "cut_deblended_stamps", "fit_deblended"]
+__all__ = ["render_scene", "cut_stamps", "cut_deblended_stamps", "fit_deblended",
+           "normal_equations", "joint_covariance", "fit_joint"]
 
 TILE_H = 4      # csrc/scene.hip: SCENE_TH, SCENE_TW
 TILE_W = 16
@@ -542,3 +555,674 @@ def fit_deblended(frame, weight, r_lo, c_lo, nrow, ncol, jacobians, guess, model
     res["deblend_dpars"] = dpars
     res["deblend_status"] = status.cpu().numpy().astype(np.int32)
     return res
+
+
+# ------------------------------------------------ normal equations of a frame
+
+NORMAL_KMAX = 8          # csrc/scene_normal.hip: SN_KT
+LAMBDA_FLOOR = 1.0e-9    # fit_joint: no damping factor goes below this
+
+
+def _scene_pairs(pair_obj, tile_start, boxes, n, max_pairs=None):
+    """
+    The pairs (a, b), a < b, of objects that share a frame tile AND whose
+    clipped boxes intersect, from the (tile -> object) lists of _tile_pairs
+    (any device): every tile with n_t objects gives n_t (n_t - 1) / 2
+    candidates (never an N x N array), which are made unique and then tested
+    against boxes (n, >= 4) [rmin, rmax, cmin, cmax, ...].  The candidate count
+    is checked against max_pairs (default 2^31 - 1) before anything of that
+    size is allocated.  Returns (P, 2) int64, sorted by (a, b).
+    """
+    torch = _torch()
+    dev = pair_obj.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    E = int(pair_obj.shape[0])
+    limit = MAX_PAIRS if max_pairs is None else int(max_pairs)
+    if E == 0:
+        return torch.zeros((0, 2), **i64)
+    cnt = tile_start[1:] - tile_start[:-1]
+    total = int((cnt * (cnt - 1)).sum()) // 2
+    if total > limit:
+        raise ValueError("scene: %d candidate object pairs exceed max_pairs = %d"
+                         % (total, limit))
+    if total == 0:
+        return torch.zeros((0, 2), **i64)
+    tile = torch.repeat_interleave(torch.arange(cnt.shape[0], **i64), cnt, output_size=E)
+    later = cnt[tile] - 1 - (torch.arange(E, **i64) - tile_start[tile])
+    first = torch.repeat_interleave(torch.arange(E, **i64), later, output_size=total)
+    second = first + 1 + torch.arange(total, **i64) - (torch.cumsum(later, 0) - later)[first]
+    key = torch.unique(pair_obj[first] * int(n) + pair_obj[second])
+    a = torch.div(key, int(n), rounding_mode="floor")
+    b = key - a * int(n)
+    bx = boxes.to(device=dev, dtype=torch.int64)
+    meet = (torch.maximum(bx[a, 0], bx[b, 0]) <= torch.minimum(bx[a, 1], bx[b, 1])) & \
+        (torch.maximum(bx[a, 2], bx[b, 2]) <= torch.minimum(bx[a, 3], bx[b, 3]))
+    return torch.stack([a[meet], b[meet]], dim=1)
+
+
+def _components(n, a, b):
+    """labels (n,) int64 of the connected components of the graph with edges
+    (a[i], b[i]) on n nodes: every node gets the smallest index of its component
+    (host arrays; hooking to the smaller root, then pointer jumping)"""
+    label = np.arange(n, dtype=np.int64)
+    a = np.asarray(a, dtype=np.int64)
+    b = np.asarray(b, dtype=np.int64)
+    for _ in range(n + 1):
+        la, lb = label[a], label[b]
+        m = np.minimum(la, lb)
+        new = label.copy()
+        np.minimum.at(new, la, m)
+        np.minimum.at(new, lb, m)
+        for _ in range(64):
+            nxt = new[new]
+            if np.array_equal(nxt, new):
+                break
+            new = nxt
+        if np.array_equal(new, label):
+            break
+        label = new
+    return label
+
+
+def _scene_groups(pair_obj, tile_start, n):
+    """
+    The connected components of the tile-sharing graph, on the host: objects in
+    one tile's list are connected.  pair_obj, tile_start: host int64 arrays.
+    Returns (group (n,) int64, tile_group (ntiles,) int64): groups numbered
+    0, 1, ... by their smallest member (an object in no tile is a group of its
+    own), and the group of every tile (-1: a tile without objects).
+    """
+    pair_obj = np.asarray(pair_obj, dtype=np.int64)
+    tile_start = np.asarray(tile_start, dtype=np.int64)
+    E = pair_obj.shape[0]
+    cnt = np.diff(tile_start)
+    # a chain through each tile's list connects what the n_t^2 pairs connect
+    same = np.ones(max(E - 1, 0), dtype=bool)
+    ends = tile_start[1:-1]
+    ends = ends[(ends > 0) & (ends < E)]
+    same[ends - 1] = False
+    idx = np.nonzero(same)[0]
+    label = _components(n, pair_obj[idx], pair_obj[idx + 1])
+    _, group = np.unique(label, return_inverse=True)
+    group = group.astype(np.int64).reshape(-1)
+    tile_group = np.full(cnt.shape[0], -1, dtype=np.int64)
+    has = cnt > 0
+    tile_group[has] = group[pair_obj[tile_start[:-1][has]]]
+    return group, tile_group
+
+
+def _segment_sums(values, seg, nseg):
+    """sums of values (host float64) per segment id seg (>= 0; < 0: left out),
+    added in a fixed order: a stable sort by segment, then np.add.reduceat"""
+    values = np.asarray(values, dtype=np.float64).reshape(-1)
+    seg = np.asarray(seg, dtype=np.int64).reshape(-1)
+    out = np.zeros(nseg, dtype=np.float64)
+    keep = seg >= 0
+    values, seg = values[keep], seg[keep]
+    if values.shape[0] == 0:
+        return out
+    order = np.argsort(seg, kind="stable")
+    seg, values = seg[order], values[order]
+    starts = np.concatenate([[0], np.nonzero(np.diff(seg))[0] + 1])
+    out[seg[starts]] = np.add.reduceat(values, starts)
+    return out
+
+
+def _tile_sums(x):
+    """the sum of the (nrow, ncol) tensor x over every 4 x 16 frame tile,
+    (nty * ntx,) in tile order"""
+    nrow, ncol = int(x.shape[0]), int(x.shape[1])
+    ntx = (ncol + TILE_W - 1) // TILE_W
+    nty = (nrow + TILE_H - 1) // TILE_H
+    pad = x.new_zeros((nty * TILE_H, ntx * TILE_W))
+    pad[:nrow, :ncol] = x
+    return pad.reshape(nty, TILE_H, ntx, TILE_W).sum(dim=(1, 3)).reshape(-1)
+
+
+class _GroupLayout(object):
+    """
+    How the objects of a frame fall into dense per-group systems.  group: (N,)
+    host labels 0 .. ngroups - 1.  A group of up to max_group objects is one
+    system of (size K) unknowns, its members in ascending index; the systems
+    are bucketed by size (1, 2, 4, ... up to max_group), a bucket's smaller
+    groups padded with identity blocks.  The members of a larger group are
+    systems of one object each (their own blocks only): oversized.
+    """
+
+    def __init__(self, group, max_group):
+        group = np.asarray(group, dtype=np.int64).reshape(-1)
+        n = group.shape[0]
+        max_group = int(max_group)
+        if max_group < 1:
+            raise ValueError("scene: max_group must be at least 1, got %d" % max_group)
+        size = np.bincount(group, minlength=(int(group.max()) + 1 if n else 0))
+        order = np.argsort(group, kind="stable")
+        start = np.concatenate([[0], np.cumsum(size)[:-1]]) if size.shape[0] else size
+        slot = np.empty(n, dtype=np.int64)
+        slot[order] = np.arange(n) - start[group[order]]
+        self.n = n
+        self.oversized = size[group] > max_group if n else np.zeros(0, dtype=bool)
+        # the system of every object: a group, or (oversized) the object itself
+        sys_of = np.where(self.oversized, size.shape[0] + np.arange(n), group)
+        self.slot = np.where(self.oversized, 0, slot)
+        sys_size = np.where(self.oversized, 1, size[group] if n else 0)
+        widths = []
+        w = 1
+        while w < max_group:
+            widths.append(w)
+            w *= 2
+        widths.append(max_group)
+        self.buckets = []     # (width m, objects (host), row of each in the bucket, nrows)
+        self.bucket_of = np.full(n, -1, dtype=np.int64)
+        self.row = np.zeros(n, dtype=np.int64)
+        lo = 0
+        for m in widths:
+            objs = np.nonzero((sys_size > lo) & (sys_size <= m))[0]
+            lo = m
+            if objs.shape[0] == 0:
+                continue
+            ids, row = np.unique(sys_of[objs], return_inverse=True)
+            self.bucket_of[objs] = len(self.buckets)
+            self.row[objs] = row.reshape(-1)
+            self.buckets.append((m, objs, row.reshape(-1), ids.shape[0]))
+
+    def dense(self, F_self, pairs, F_cross):
+        """the buckets' matrices [(nrows, m K, m K) tensor, ...] from the blocks:
+        F_self (N, K, K), pairs (P, 2), F_cross (P, K, K) tensors on one device;
+        a pair across two systems (an oversized group's) is left out"""
+        torch = _torch()
+        dev = F_self.device
+        K = int(F_self.shape[1])
+        pa = pairs[:, 0].cpu().numpy() if pairs.shape[0] else np.zeros(0, dtype=np.int64)
+        pb = pairs[:, 1].cpu().numpy() if pairs.shape[0] else np.zeros(0, dtype=np.int64)
+        inside = ~self.oversized[pa] & ~self.oversized[pb] if pa.shape[0] else \
+            np.zeros(0, dtype=bool)
+        out = []
+        for k, (m, objs, row, nrows) in enumerate(self.buckets):
+            M = torch.zeros((nrows, m, K, m, K), dtype=F_self.dtype, device=dev)
+            used = torch.zeros((nrows, m), dtype=torch.bool, device=dev)
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            r, sl, o = t(row), t(self.slot[objs]), t(objs)
+            M[r, sl, :, sl, :] = F_self[o]
+            used[r, sl] = True
+            sel = np.nonzero(inside & (self.bucket_of[pa] == k))[0] if pa.shape[0] else pa
+            if sel.shape[0]:
+                ra, sa, sb = t(self.row[pa[sel]]), t(self.slot[pa[sel]]), t(self.slot[pb[sel]])
+                C = F_cross[t(sel)]
+                M[ra, sa, :, sb, :] = C
+                M[ra, sb, :, sa, :] = C.transpose(1, 2)
+            M = M.reshape(nrows, m * K, m * K)
+            # identity in the slots that no object fills
+            pad = (~used).to(F_self.dtype)[:, :, None].expand(nrows, m, K)
+            out.append(M + torch.diag_embed(pad.reshape(nrows, m * K)))
+        return out
+
+    def blocks(self, mats, K):
+        """every object's K x K diagonal block of its system's matrix: (N, K, K)"""
+        torch = _torch()
+        dev = mats[0].device if mats else None
+        res = None
+        for (m, objs, row, nrows), M in zip(self.buckets, mats):
+            if res is None:
+                res = torch.zeros((self.n, K, K), dtype=M.dtype, device=dev)
+            M5 = M.reshape(nrows, m, K, m, K)
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            r, sl = t(row), t(self.slot[objs])
+            res[t(objs)] = M5[r, sl, :, sl, :]
+        return res
+
+    def gather(self, vec, k):
+        """bucket k's right-hand sides (nrows, m K) from per-object rows (N, K)"""
+        torch = _torch()
+        m, objs, row, nrows = self.buckets[k]
+        K = int(vec.shape[1])
+        dev = vec.device
+        out = torch.zeros((nrows, m, K), dtype=vec.dtype, device=dev)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        out[t(row), t(self.slot[objs])] = vec[t(objs)]
+        return out.reshape(nrows, m * K)
+
+    def scatter(self, sols, K, like):
+        """per-object rows (N, K) from the buckets' solutions [(nrows, m K), ...]"""
+        torch = _torch()
+        res = torch.zeros((self.n, K), dtype=like.dtype, device=like.device)
+        for (m, objs, row, nrows), x in zip(self.buckets, sols):
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(like.device)  # noqa: E731
+            res[t(objs)] = x.reshape(nrows, m, K)[t(row), t(self.slot[objs])]
+        return res
+
+    def per_object(self, values, k):
+        """bucket k's per-system values (nrows, ...) at its objects"""
+        m, objs, row, nrows = self.buckets[k]
+        return objs, values[_torch().from_numpy(np.ascontiguousarray(row)).to(values.device)]
+
+
+def _joint_arguments(frame, weight, jacobians, pars, model, psf, who):
+    """the arguments every joint call shares, checked on the host before a
+    device is asked for.  Returns (pars tensor (N, K) float64 on the frame's
+    device, model name)"""
+    from . import autodiff
+    torch = _torch()
+    if not isinstance(frame, torch.Tensor) or frame.ndim != 2:
+        raise ValueError("%s: frame must be a 2-d device tensor" % who)
+    if frame.shape[0] < 1 or frame.shape[1] < 1:
+        raise ValueError("%s: the frame needs nrow * ncol > 0" % who)
+    if frame.dtype != torch.float64:
+        raise ValueError("%s: frame must be float64" % who)
+    if isinstance(weight, torch.Tensor) and weight.ndim != 0:
+        if tuple(weight.shape) != tuple(frame.shape):
+            raise ValueError("%s: weight must be None, a scalar or have the frame's shape" % who)
+        if weight.device != frame.device:
+            raise ValueError("%s: weight must be on the frame's device (%s)"
+                             % (who, frame.device))
+    if isinstance(pars, torch.Tensor):
+        if pars.device != frame.device:
+            raise ValueError("%s: pars must be on the frame's device (%s)" % (who, frame.device))
+        p = pars.detach().to(torch.float64)
+    else:
+        p = torch.from_numpy(np.array(pars, dtype=np.float64))
+    if p.ndim != 2:
+        raise ValueError("%s: pars must be (nobj, npars)" % who)
+    n, K = int(p.shape[0]), int(p.shape[1])
+    name = autodiff._model_name(model)
+    if K > NORMAL_KMAX:
+        raise ValueError("%s: at most %d parameters per object (one band), got K = %d"
+                         % (who, NORMAL_KMAX, K))
+    if name == "coellip" or K != autodiff._NLOC[name]:
+        raise ValueError("%s: model '%s' with one flux needs %s parameters, got %d"
+                         % (who, name, autodiff._NLOC.get(name, "at most 8"), K))
+    _check_jacobians(jacobians, n, who)
+    if psf is not None:
+        if isinstance(psf, GMixBatch):
+            if psf.n != n:
+                raise ValueError("%s: psf must hold one mixture per object" % who)
+            if psf.device != frame.device:
+                raise ValueError("%s: psf must be on the frame's device (%s)"
+                                 % (who, frame.device))
+        elif isinstance(psf, torch.Tensor):
+            if psf.ndim != 3 or psf.shape[0] != n or psf.shape[2] != 6:
+                raise ValueError("%s: psf: (nobj, ngauss_psf, 6) tensor or a GMixBatch" % who)
+            if psf.device != frame.device:
+                raise ValueError("%s: psf must be on the frame's device (%s)"
+                                 % (who, frame.device))
+        else:
+            raise ValueError("%s: psf: (nobj, ngauss_psf, 6) tensor or a GMixBatch" % who)
+    return p, name
+
+
+def _weight_frame(frame, weight):
+    """(the weight frame for the kernel, or None for w = 1; max(w, 0) as a
+    tensor or the float 1.0)"""
+    torch = _torch()
+    if weight is None:
+        return None, 1.0
+    if isinstance(weight, torch.Tensor) and weight.ndim == 2:
+        w = weight.detach().to(torch.float64).contiguous()
+    else:
+        if float(weight) == 1.0:
+            return None, 1.0
+        w = torch.full(tuple(frame.shape), float(weight), dtype=torch.float64,
+                       device=frame.device)
+    return w, torch.clamp(w, min=0.0)
+
+
+def _joint_model(shape, jac, pars, name, psf, ngauss, max_pairs, tangents):
+    """the objects at pars: mixtures (with tangents: and d mixture / d pars),
+    the scene lists and the model frame (render_scene's bits; a refused object
+    is left out)"""
+    from . import autodiff
+    torch = _torch()
+    nrow, ncol = shape
+    dev = pars.device
+    n = int(pars.shape[0])
+    geom = autodiff._SceneGeometry(n, dev)
+    if tangents:
+        (_, _, mix, code, _), dmix = autodiff._mixture_tangents(geom, pars, name, psf, None, None,
+                                                                ngauss)
+    else:
+        _, _, mix, code, _ = autodiff._stamp_mixtures(geom, pars, name, psf, None, None, ngauss)
+        dmix = None
+    G = int(mix.shape[1])
+    rec = autodiff._gauss_records(mix, True)
+    # an object refused before the kernels is left out: all-zero records, which
+    # the norms refuse (as autodiff.scene_render)
+    rec = torch.where((code != 0).repeat_interleave(G)[:, None], torch.zeros_like(rec), rec)
+    gev, status, hb, pair_obj, tile_start = _scene_lists(nrow, ncol, rec, G, n, jac, max_pairs,
+                                                         boxes_to_host=True)
+    model = torch.empty((nrow, ncol), dtype=torch.float64, device=dev)
+    with _on_device(dev):
+        st = _lib.lib().ngmix_scene_render(_dptr(gev), G, _dptr(jac), _dptr(pair_obj),
+                                           int(pair_obj.shape[0]), _dptr(tile_start), nrow, ncol,
+                                           _dptr(model), 1, _stream())
+    _lib.check(st, "ngmix_scene_render")
+    flag = torch.where(code == 0, status, code)
+    return dict(G=G, rec=rec, dmix=dmix, flag=flag, boxes=hb, pair_obj=pair_obj,
+                tile_start=tile_start, model=model)
+
+
+def _scene_normal(rec, G, jac, dmix, wframe, resid, boxes_host, items_host):
+    """ngmix_scene_normal over the (nitems, 2) int32 host table: (blocks
+    (nitems, K, K), vectors (nitems, K))"""
+    torch = _torch()
+    dev = rec.device
+    n, K = int(dmix.shape[0]), int(dmix.shape[3])
+    nitems = int(items_host.shape[0])
+    nrow, ncol = int(resid.shape[0]), int(resid.shape[1])
+    mat = torch.empty((nitems, K, K), dtype=torch.float64, device=dev)
+    vec = torch.empty((nitems, K), dtype=torch.float64, device=dev)
+    items_host = np.ascontiguousarray(items_host, dtype=np.int32)
+    items = torch.from_numpy(items_host).to(dev)
+    boxes = torch.from_numpy(np.ascontiguousarray(boxes_host, dtype=np.int32)).to(dev)
+    A = dmix.detach().to(torch.float64).contiguous()
+    with _on_device(dev):
+        st = _lib.lib().ngmix_scene_normal(
+            _dptr(rec), G, _dptr(jac), n, _dptr(A), K,
+            _dptr(wframe) if wframe is not None else None, _dptr(resid), nrow, ncol,
+            _dptr(boxes), _dptr(items), _lib.ptr(items_host), nitems, _dptr(mat), _dptr(vec),
+            _stream())
+    _lib.check(st, "ngmix_scene_normal")
+    return mat, vec
+
+
+def _normal(frame, wframe, wpos, jac, pars, name, psf, ngauss, max_pairs):
+    """normal_equations on checked arguments; its dict plus what fit_joint
+    reads: tile_chi2 (host), tile_group (host), model"""
+    torch = _torch()
+    dev = pars.device
+    n, K = int(pars.shape[0]), int(pars.shape[1])
+    nrow, ncol = int(frame.shape[0]), int(frame.shape[1])
+    if n == 0:
+        f64 = dict(dtype=torch.float64, device=dev)
+        ntiles = ((nrow + TILE_H - 1) // TILE_H) * ((ncol + TILE_W - 1) // TILE_W)
+        return dict(F_self=torch.zeros((0, K, K), **f64), grad=torch.zeros((0, K), **f64),
+                    pairs=torch.zeros((0, 2), dtype=torch.int64, device=dev),
+                    F_cross=torch.zeros((0, K, K), **f64),
+                    group=torch.zeros(0, dtype=torch.int64, device=dev),
+                    chi2_group=torch.zeros(0, **f64),
+                    status=torch.zeros(0, dtype=torch.int32, device=dev),
+                    _tile_chi2=_tile_sums(frame * frame * wpos).cpu().numpy(),
+                    _tile_group=np.full(ntiles, -1, dtype=np.int64),
+                    _group=np.zeros(0, dtype=np.int64), _model=torch.zeros_like(frame))
+    jm = _joint_model((nrow, ncol), jac, pars, name, psf, ngauss, max_pairs, True)
+    resid = (frame - jm["model"]).contiguous()
+    pairs = _scene_pairs(jm["pair_obj"], jm["tile_start"],
+                         torch.from_numpy(jm["boxes"].astype(np.int64)), n, max_pairs)
+    P = int(pairs.shape[0])
+    group, tile_group = _scene_groups(jm["pair_obj"].cpu().numpy(),
+                                      jm["tile_start"].cpu().numpy(), n)
+    ngroups = int(group.max()) + 1 if n else 0
+    tile_chi2 = _tile_sums(resid * resid * wpos).cpu().numpy()
+    chi2_group = _segment_sums(tile_chi2, tile_group, ngroups)
+    items = np.empty((n + P, 2), dtype=np.int32)
+    items[:n, 0] = np.arange(n)
+    items[:n, 1] = -1
+    items[n:] = pairs.cpu().numpy()
+    if n + P:
+        mat, vec = _scene_normal(jm["rec"], jm["G"], jac, jm["dmix"], wframe, resid, jm["boxes"],
+                                 items)
+    else:
+        mat = torch.zeros((0, K, K), dtype=torch.float64, device=dev)
+        vec = torch.zeros((0, K), dtype=torch.float64, device=dev)
+    bad = jm["flag"] != 0
+    nan = float("nan")
+    F_self = torch.where(bad[:, None, None], torch.full_like(mat[:n], nan), mat[:n])
+    grad = torch.where(bad[:, None], torch.full_like(vec[:n], nan), vec[:n])
+    return dict(F_self=F_self, grad=grad, pairs=pairs, F_cross=mat[n:],
+                group=torch.from_numpy(group).to(dev),
+                chi2_group=torch.from_numpy(chi2_group).to(dev), status=jm["flag"],
+                _tile_chi2=tile_chi2, _tile_group=tile_group, _group=group, _model=jm["model"])
+
+
+def _public(res):
+    return {k: v for k, v in res.items() if not k.startswith("_")}
+
+
+def _joint_setup(frame, weight, jacobians, pars, model, psf, who):
+    pars, name = _joint_arguments(frame, weight, jacobians, pars, model, psf, who)
+    dev = _require_cuda(frame.device)
+    pars = pars.to(dev)
+    frame = frame.detach().contiguous()
+    wframe, wpos = _weight_frame(frame, weight)
+    jac = _jacobian_tensor(jacobians, int(pars.shape[0]), dev)
+    return frame, wframe, wpos, jac, pars, name
+
+
+def normal_equations(frame, weight, jacobians, pars, model, psf=None, ngauss=None,
+                     max_pairs=None):
+    """
+    The Gauss-Newton normal equations of a frame at pars, one band, no prior:
+    with r = frame - render_scene(objects at pars) (computed here), w =
+    max(weight, 0) and J_a = d model_a / d pars_a (deriv_images' convention, as
+    autodiff.fisher(fast_exp=True)),
+        F_self[a] = sum w J_a J_a^T   over a's clipped box, symmetric to the bit
+        grad[a]   = sum w r J_a       (minus half the gradient of chi2)
+        F_cross[p] = sum w J_a J_b^T  over box_a n box_b, (a, b) = pairs[p].
+
+    frame: (nrow, ncol) float64 device tensor; weight: None (1), a scalar, or a
+        tensor of the frame's shape (negative and zero weights drop out)
+    jacobians: as render_scene's, one per object, in FRAME coordinates
+    pars: (N, K) array or tensor, the model's parameters with one flux, K <= 8
+    psf: GMixBatch or (N, P, 6) tensor with one mixture per object, or None
+    max_pairs: refuse (ValueError naming the count) more (tile, object) pairs,
+        or more candidate object pairs, than this; default 2^31 - 1
+
+    Returns a dict of device tensors: F_self (N, K, K), grad (N, K), pairs
+    (P, 2) int64 with a < b sorted by (a, b): the objects that share a frame
+    tile and whose boxes intersect, F_cross (P, K, K), group (N,) int64: the
+    connected components of the tile-sharing graph, numbered by their smallest
+    member, chi2_group (ngroups,): sum w r^2 over the tiles of each group (every
+    tile with objects belongs to exactly one group; summed in a fixed order),
+    status (N,) int32: 0 or the code (_lib.ERR_*) with which the object was
+    refused.  A refused object is left out of the model; its F_self and grad
+    are NaN, it is in no pair, and every other object's numbers are bit for bit
+    those of the catalogue without it.  No atomics: two calls give the same
+    bits (csrc/scene_normal.hip).
+    """
+    frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, pars, model,
+                                                        psf, "normal_equations")
+    return _public(_normal(frame, wframe, wpos, jac, pars, name, psf, ngauss, max_pairs))
+
+
+def _own_inverse(F, bad):
+    """(the inverse of every K x K block by Cholesky, not positive definite)"""
+    torch = _torch()
+    eye = torch.eye(F.shape[1], dtype=F.dtype, device=F.device).expand_as(F)
+    L, info = torch.linalg.cholesky_ex(torch.where(bad[:, None, None], eye, F))
+    return torch.cholesky_inverse(L), (info != 0) & ~bad
+
+
+def _covariance(ne, max_group):
+    """joint_covariance from a _normal result"""
+    from .flags import LM_SINGULAR_MATRIX
+    torch = _torch()
+    F = ne["F_self"]
+    n, K = int(F.shape[0]), int(F.shape[1])
+    dev = F.device
+    layout = _GroupLayout(ne["_group"], max_group)
+    flag = ne["status"].clone()
+    bad = flag != 0
+    eye = torch.eye(K, dtype=F.dtype, device=dev).expand_as(F)
+    mats = layout.dense(torch.where(bad[:, None, None], eye, F), ne["pairs"], ne["F_cross"])
+    inv, sing = [], torch.zeros(n, dtype=torch.bool, device=dev)
+    for k, M in enumerate(mats):
+        L, info = torch.linalg.cholesky_ex(M)
+        inv.append(torch.cholesky_inverse(L))
+        objs, failed = layout.per_object(info != 0, k)
+        sing[torch.from_numpy(objs).to(dev)] = failed
+    cov = layout.blocks(inv, K) if n else F.clone()
+    sing = sing & ~bad
+    cov = torch.where((bad | sing)[:, None, None], torch.full_like(cov, float("nan")), cov)
+    flag = torch.where(sing, torch.full_like(flag, LM_SINGULAR_MATRIX), flag)
+    joint_status = torch.from_numpy(layout.oversized.astype(np.int32)).to(dev)
+    return dict(pars_cov=cov, flags=flag, group=ne["group"], joint_status=joint_status)
+
+
+def joint_covariance(frame, weight, jacobians, pars, model, psf=None, ngauss=None,
+                     max_pairs=None, max_group=16):
+    """
+    The covariance of every object of a frame marginalised over its neighbours:
+    per group of connected objects (normal_equations' group) the dense
+    (n_g K) x (n_g K) matrix of the group's F_self and F_cross blocks is
+    inverted by Cholesky (groups bucketed by size, padded with identity) and
+    each object gets its own K x K diagonal block of the inverse.
+    LMBatchFitter's pars_cov0 convention: not rescaled by chi2 / dof.  For an
+    isolated object this is autodiff.covariance of its pixels.
+
+    Arguments as normal_equations; max_group: the objects of a larger group get
+    the inverse of their own block alone, and joint_status 1.
+
+    Returns a dict of device tensors: pars_cov (N, K, K), flags (N,) int32 as
+    autodiff.covariance's (the refusal's code; a matrix that is not positive
+    definite: NaN for every object of that group and flags.LM_SINGULAR_MATRIX),
+    group (N,) int64, joint_status (N,) int32 (1: own block only).
+    """
+    _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
+    frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, pars, model,
+                                                        psf, "joint_covariance")
+    ne = _normal(frame, wframe, wpos, jac, pars, name, psf, ngauss, max_pairs)
+    return _covariance(ne, max_group)
+
+
+def _joint_step(ne, layout, lam):
+    """(delta (N, K), predicted decrease delta^T g per object's system (N,),
+    solved (N,) bool) of (F + lam diag F) delta = g per system; lam: (N,) host,
+    equal over a system's objects"""
+    torch = _torch()
+    F, g = ne["F_self"], ne["grad"]
+    n, K = int(F.shape[0]), int(F.shape[1])
+    dev = F.device
+    bad = ne["status"] != 0
+    eye = torch.eye(K, dtype=F.dtype, device=dev).expand_as(F)
+    mats = layout.dense(torch.where(bad[:, None, None], eye, F), ne["pairs"], ne["F_cross"])
+    g0 = torch.where(bad[:, None], torch.zeros_like(g), g)
+    d_lam = torch.from_numpy(lam).to(dev)
+    sols = []
+    pred = torch.zeros(n, dtype=F.dtype, device=dev)
+    solved = torch.zeros(n, dtype=torch.bool, device=dev)
+    for k, M in enumerate(mats):
+        rhs = layout.gather(g0, k)
+        lam_k = layout.gather(d_lam[:, None].expand(n, K).contiguous(), k)
+        D = torch.diagonal(M, dim1=1, dim2=2)
+        L, info = torch.linalg.cholesky_ex(M + torch.diag_embed(lam_k * D))
+        x = torch.cholesky_solve(rhs[:, :, None], L)[:, :, 0]
+        ok = info == 0
+        x = torch.where(ok[:, None], x, torch.zeros_like(x))
+        sols.append(x)
+        objs, p = layout.per_object((x * rhs).sum(dim=1), k)
+        o = torch.from_numpy(objs).to(dev)
+        pred[o] = p
+        solved[o] = layout.per_object(ok, k)[1]
+    delta = layout.scatter(sols, K, g) if n else g.clone()
+    return delta, pred, solved & ~bad
+
+
+def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=1e-6,
+              lambda0=1e-3, max_group=16):
+    """
+    Fit all the objects of a frame together (a joint, MOF-style fit), ONE band
+    and NO prior: Levenberg-Marquardt over normal_equations, with one damping
+    factor lambda per group of connected objects.
+
+    frame, weight, jacobians, psf: normal_equations' arguments
+    guess: (N, K) starting parameters, the model's with one flux, K <= 8
+    maxiter: iterations; each makes one normal_equations call and one trial
+        render_scene (every loop here is bounded by it)
+    tol: a group has converged when an accepted step's predicted decrease
+        delta^T g is at most tol.  The unit is chi2, so the default 1e-6 is far
+        below any statistical meaning
+    lambda0: the starting lambda; it never goes below scene.LAMBDA_FLOOR
+    max_group: the objects of a larger group step with their own blocks only
+        (block-Jacobi) and carry joint_status 1
+
+    Per iteration the groups are those of the current parameters.  Every group
+    that has not converged solves (F + lambda diag F) delta = g over its dense
+    system; the trial parameters of all groups are rendered into one frame, and
+    a group accepts its step when chi2 = sum w r^2 over ITS CURRENT TILES
+    decreases: lambda <- lambda / 10; otherwise, or when a trial object is
+    refused or the system cannot be solved, lambda <- 10 lambda and the group
+    keeps its parameters.  The decision ignores what the trial's grown boxes add
+    outside those tiles (inside another group's tiles or in empty ones); the
+    next iteration's groups see it.  When groups merge, the merged group takes
+    its members' largest lambda and converges anew.
+
+    Returns a dict of host arrays: pars (N, K), pars_cov (N, K, K):
+    joint_covariance at pars, bit for bit, pars_err (N, K), flags (N,) int32
+    (joint_covariance's; flags.MAXITER for an object of a group that did not
+    converge), group (N,), niter (N,): the iterations the object's group took
+    part in, converged (N,) bool, joint_status (N,), chi2: sum w r^2 of the
+    whole frame at pars, recomputed, and lambda (N,).
+    """
+    from .flags import MAXITER
+    torch = _torch()
+    maxiter = int(maxiter)
+    if maxiter < 1:
+        raise ValueError("fit_joint: maxiter must be at least 1, got %d" % maxiter)
+    if not (float(tol) >= 0.0) or not (float(lambda0) > 0.0):
+        raise ValueError("fit_joint: tol must be >= 0 and lambda0 > 0")
+    _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
+    frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, guess, model,
+                                                        psf, "fit_joint")
+    dev = pars.device
+    n, K = int(pars.shape[0]), int(pars.shape[1])
+    shape = (int(frame.shape[0]), int(frame.shape[1]))
+    lam = np.full(n, float(lambda0))
+    conv = np.zeros(n, dtype=bool)
+    niter = np.zeros(n, dtype=np.int64)
+    for _ in range(maxiter):
+        ne = _normal(frame, wframe, wpos, jac, pars, name, psf, None, None)
+        group = ne["_group"]
+        ngroups = int(group.max()) + 1 if n else 0
+        ok_obj = ne["status"].cpu().numpy() == 0
+        # a group is at rest when all of its (fittable) members have converged
+        g_lam = np.zeros(ngroups)
+        np.maximum.at(g_lam, group, lam)
+        g_rest = np.ones(ngroups, dtype=bool)
+        np.logical_and.at(g_rest, group, conv | ~ok_obj)
+        lam = g_lam[group]
+        conv = np.where(ok_obj, g_rest[group], False)
+        active = ~g_rest[group] & ok_obj
+        if not active.any():
+            break
+        niter[active] += 1
+        layout = _GroupLayout(group, max_group)
+        delta, pred, solved = _joint_step(ne, layout, lam)
+        d_active = torch.from_numpy(active).to(dev)
+        trial = torch.where(d_active[:, None], pars + delta, pars)
+        jm = _joint_model(shape, jac, trial, name, psf, None, None, False)
+        r = frame - jm["model"]
+        new = _segment_sums(_tile_sums(r * r * wpos).cpu().numpy(), ne["_tile_group"], ngroups)
+        old = ne["chi2_group"].cpu().numpy()
+        refused = np.zeros(ngroups, dtype=bool)
+        np.logical_or.at(refused, group, (jm["flag"].cpu().numpy() != 0) & ok_obj)
+        unsolved = np.zeros(ngroups, dtype=bool)
+        np.logical_or.at(unsolved, group, ~solved.cpu().numpy() & ok_obj)
+        accept_g = (new < old) & ~refused & ~unsolved
+        if layout.oversized.any():
+            # block-Jacobi members step one by one but are judged with their group
+            pred_g = np.zeros(ngroups)
+            np.add.at(pred_g, group, np.where(active, pred.cpu().numpy(), 0.0))
+            pred_o = pred_g[group]
+        else:
+            pred_o = pred.cpu().numpy()
+        accept = accept_g[group] & active
+        pars = torch.where(torch.from_numpy(accept).to(dev)[:, None], trial, pars)
+        lam = np.where(accept, np.maximum(lam / 10.0, LAMBDA_FLOOR),
+                       np.where(active, lam * 10.0, lam))
+        conv = conv | (accept & (pred_o <= float(tol)))
+    ne = _normal(frame, wframe, wpos, jac, pars, name, psf, None, None)
+    cov = _covariance(ne, max_group)
+    group = ne["_group"]
+    ngroups = int(group.max()) + 1 if n else 0
+    g_conv = np.ones(ngroups, dtype=bool)
+    np.logical_and.at(g_conv, group, conv)
+    conv = g_conv[group] if n else conv
+    flags = cov["flags"].cpu().numpy().astype(np.int32)
+    flags = np.where((flags == 0) & ~conv, MAXITER, flags).astype(np.int32)
+    pars_cov = cov["pars_cov"].cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        pars_err = np.sqrt(np.einsum("nii->ni", pars_cov))
+    r = frame - ne["_model"]
+    return {"pars": pars.cpu().numpy(), "pars_cov": pars_cov, "pars_err": pars_err,
+            "flags": flags, "group": group.copy(), "niter": niter, "converged": conv,
+            "joint_status": cov["joint_status"].cpu().numpy(),
+            "chi2": float((r * r * wpos).sum()), "lambda": lam}

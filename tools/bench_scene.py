@@ -16,8 +16,15 @@ cut(scene) + own), alternating, median of 5, and the largest difference of the
 two results relative to the frame's peak.  --deblend-only runs that leg alone
 and appends its lines to the file.
 
+The joint leg (--joint-only; scene.normal_equations, scene_normal_kernel; DESIGN.md
+section 3.16) on the same scene, written to profiles/scene_joint_bench.txt: the
+pairs, the items and the histogram of group sizes, ngmix_scene_normal by
+events, normal_equations end to end, and for the self blocks the long way
+(cut_stamps of every object's union box + autodiff.stamp_fisher), with the
+largest difference of the two.
+
     python tools/bench_scene.py [--n 30000] [--size 4096] [--out profiles/scene_bench.txt]
-                                [--deblend-only]
+                                [--deblend-only] [--joint-only]
 """
 import argparse
 import os
@@ -61,6 +68,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.txt"))
     ap.add_argument("--no-backward", action="store_true")
     ap.add_argument("--deblend-only", action="store_true")
+    ap.add_argument("--joint-only", action="store_true")
+    ap.add_argument("--joint-out",
+                    default=os.path.join(ROOT, "profiles", "scene_joint_bench.txt"))
     args = ap.parse_args()
 
     import torch
@@ -94,9 +104,10 @@ def main():
         torch.cuda.synchronize()
         return out, (time.perf_counter() - t0) * 1e3
 
-    def write(mode):
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, mode) as f:
+    def write(mode, path=None):
+        path = args.out if path is None else path
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, mode) as f:
             f.write("\n".join(lines) + "\n")
 
     def deblend_leg():
@@ -182,6 +193,100 @@ def main():
         say("largest |deblended - long way| / peak: %.3g (peak %.6g)"
             % (float((sb_new.val - sb_long.val).abs().max()) / peak, peak))
 
+    def joint_leg():
+        say("joint: %d x %d frame, %d objects, G = %d, K = 6" % (size, size, n, G))
+        frame, _ = scene.render_scene(shape, gm, d_jac)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(99)
+        frame = frame + 0.01 * torch.randn(shape, generator=gen, dtype=torch.float64,
+                                           device="cuda")
+        # the lists and the item table the call would build
+        jm = scene._joint_model(shape, d_jac, d_pars, "exp", d_psf, None, None, True)
+        hb = jm["boxes"].astype(np.int64)
+        pairs = scene._scene_pairs(jm["pair_obj"], jm["tile_start"], torch.from_numpy(hb), n)
+        group, _ = scene._scene_groups(jm["pair_obj"].cpu().numpy(),
+                                       jm["tile_start"].cpu().numpy(), n)
+        P = int(pairs.shape[0])
+        gsize = np.bincount(group)
+        edges = [1, 2, 3, 5, 9, 17, 65, 257, 1025, 1 << 30]
+        hist = ["%s: %d" % ("%d" % lo if hi == lo + 1 else
+                            ("%d+" % lo if hi == 1 << 30 else "%d-%d" % (lo, hi - 1)),
+                            int(((gsize >= lo) & (gsize < hi)).sum()))
+                for lo, hi in zip(edges[:-1], edges[1:])]
+        say("joint: %d pairs (%.1f per object), %d items; %d groups, largest %d objects, "
+            "%.1f%% of the objects in groups above 16"
+            % (P, P / float(n), n + P, gsize.shape[0], gsize.max(),
+               100.0 * (gsize[group] > 16).mean()))
+        say("joint: groups by size: " + ", ".join(hist))
+        items = np.empty((n + P, 2), dtype=np.int32)
+        items[:n, 0] = np.arange(n)
+        items[:n, 1] = -1
+        items[n:] = pairs.cpu().numpy()
+        resid = (frame - jm["model"]).contiguous()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        d_items = torch.from_numpy(items).cuda()
+        d_boxes = torch.from_numpy(jm["boxes"]).cuda()
+        K = 6
+        mat = torch.empty((n + P, K, K), dtype=torch.float64, device="cuda")
+        vec = torch.empty((n + P, K), dtype=torch.float64, device="cuda")
+        A = jm["dmix"].contiguous()
+        t_kern = []
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(L.ngmix_scene_normal(
+                _dptr(jm["rec"]), G, _dptr(d_jac), n, _dptr(A), K, None, _dptr(resid), size, size,
+                _dptr(d_boxes), _dptr(d_items), None, n + P, _dptr(mat), _dptr(vec), _stream()),
+                "scene_normal")
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                t_kern.append(e0.elapsed_time(e1))
+        say("joint: ngmix_scene_normal (ms, by events): median %.3f, min %.3f, max %.3f; "
+            "which bound: not established (no counter run was made)"
+            % (np.median(t_kern), min(t_kern), max(t_kern)))
+        F_kernel = mat[:n].clone()
+        del mat, vec
+
+        # the self blocks the long way: every union box cut out, then the
+        # one-stamp Fisher kernel
+        hit = hb[:, 1] >= hb[:, 0]
+        idx = np.nonzero(hit)[0]
+        r_lo, c_lo = hb[idx, 0], hb[idx, 2]
+        wr, wc = hb[idx, 1] - hb[idx, 0] + 1, hb[idx, 3] - hb[idx, 2] + 1
+        d_idx = torch.from_numpy(idx).cuda()
+        mix_hit, dmix_hit = mix[d_idx].contiguous(), jm["dmix"][d_idx].contiguous()
+
+        def long_way():
+            sb = scene.cut_stamps(frame, 1.0, r_lo, c_lo, wr, wc, jac[idx])
+            return autodiff.stamp_fisher(sb, mix_hit, dmix_hit)[0]
+
+        def new_way():
+            return scene.normal_equations(frame, None, d_jac, d_pars, "exp", psf=d_psf)
+
+        timed(new_way)
+        timed(long_way)
+        t_new, t_long = [], []
+        for rep in range(args.reps):
+            ne, t = timed(new_way)
+            t_new.append(t)
+            F_long, t = timed(long_way)
+            t_long.append(t)
+        say("joint: normal_equations end to end (ms): median %.3f, min %.3f, max %.3f"
+            % (np.median(t_new), min(t_new), max(t_new)))
+        say("joint: self blocks the long way (cut_stamps + stamp_fisher, %d windows) (ms): "
+            "median %.3f, min %.3f, max %.3f" % (len(idx), np.median(t_long), min(t_long),
+                                                 max(t_long)))
+        scale = F_long.abs().flatten(1).max(dim=1).values[:, None, None]
+        say("joint: largest |F_self - long way| / max of the block: %.3g; kernel call and "
+            "normal_equations agree bit for bit: %s"
+            % (float(((ne["F_self"][d_idx] - F_long).abs() / scale).max()),
+               bool((ne["F_self"] == F_kernel).all())))
+
+    if args.joint_only:
+        joint_leg()
+        write("w", args.joint_out)
+        return
     if args.deblend_only:
         deblend_leg()
         write("a")

@@ -142,6 +142,28 @@ int main()
     expect("scene_cut_minus window shape", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win, win, own_ok, own_ok, off, 2, st, 1, x, 64, s), BAD, "window 1 has a non-positive shape");
     expect("scene_cut_minus owner high", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win2, win2, own, own, off, 2, st, 1, x, 64, s), BAD, "owner 2 of window 1 is outside [-1, 2)");
     expect("scene_cut_minus owner low", launch_scene_cut_minus(x, 8, 8, x, 1, nullptr, 2, off, 0, off, win2, win2, own_low, own_low, off, 2, st, 1, x, 64, s), BAD, "owner -2 of window 0 is outside [-1, 2)");
+    // the frame's normal equations (gmix / jac null where the check under test comes first)
+    const ngmix_gauss2d *gm1 = (const ngmix_gauss2d *)x;
+    const ngmix_jacobian *jc1 = (const ngmix_jacobian *)x;
+    int32_t it_ok[4] = {0, -1, 0, 1}, it_hi[4] = {0, -1, 1, 2}, it_neg[2] = {-1, 1};
+    int32_t it_same[2] = {1, 1}, it_back[2] = {1, 0}, it_low[2] = {0, -2};
+    expect("scene_normal n < 0", launch_scene_normal(gm1, 1, jc1, -1, x, 6, x, x, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "must not be negative");
+    expect("scene_normal nitems < 0", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_ok, it_ok, -2, x, x, s), BAD, "must not be negative");
+    expect("scene_normal K 0", launch_scene_normal(gm1, 1, jc1, 2, x, 0, x, x, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "K must be 1..8");
+    expect("scene_normal K 9", launch_scene_normal(gm1, 1, jc1, 2, x, 9, x, x, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "K must be 1..8");
+    expect("scene_normal G", launch_scene_normal(gm1, 0, jc1, 2, x, 6, x, x, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "ngauss >= 1");
+    expect("scene_normal frame", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 0, st, it_ok, it_ok, 2, x, x, s), BAD, "nrow * ncol > 0");
+    expect("scene_normal lds", launch_scene_normal(gm1, 355, jc1, 2, x, 6, x, x, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "LDS budget");
+    expect("scene_normal lds huge", launch_scene_normal(gm1, 0x7fffffff, jc1, 2, x, 6, x, x, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "LDS budget");
+    expect("scene_normal empty", launch_scene_normal(nullptr, 1, nullptr, 0, nullptr, 6, nullptr, nullptr, 8, 8, nullptr, nullptr, nullptr, 0, nullptr, nullptr, s), NGMIX_OK);
+    expect("scene_normal null items", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, nullptr, nullptr, 2, x, x, s), BAD, "are required");
+    expect("scene_normal null resid", launch_scene_normal(gm1, 1, jc1, 2, x, 6, nullptr, nullptr, 8, 8, st, it_ok, it_ok, 2, x, x, s), BAD, "are required");
+    expect("scene_normal null out", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_ok, it_ok, 2, nullptr, x, s), BAD, "are required");
+    expect("scene_normal b high", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_hi, it_hi, 2, x, x, s), BAD, "item 1 (1, 2)");
+    expect("scene_normal a < 0", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_neg, it_neg, 1, x, x, s), BAD, "item 0 (-1, 1)");
+    expect("scene_normal b == a", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_same, it_same, 1, x, x, s), BAD, "item 0 (1, 1)");
+    expect("scene_normal b < a", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_back, it_back, 1, x, x, s), BAD, "item 0 (1, 0)");
+    expect("scene_normal b < -1", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_low, it_low, 1, x, x, s), BAD, "item 0 (0, -2)");
 
     // keys outside a dispatch table: no kernel, and launch() refuses
     struct Row {
