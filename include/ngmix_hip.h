@@ -560,6 +560,44 @@ int ngmix_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobi
                        const double *resid, int nrow, int ncol, const int32_t *boxes,
                        const int32_t *items, const int32_t *items_host, int64_t nitems,
                        double *out_mat, double *out_vec, void *stream);
+/* the block-sparse operator of those blocks (csrc/scene_solve.hip): F_self
+   (n, K, K) and F_cross (npairs, K, K) as ngmix_scene_normal wrote them,
+   1 <= K <= 8.  Object a's row list is row_ent[2 * e ..] = neighbour, code for e
+   in [row_start[a], row_start[a + 1]) (row_start has n + 1 entries, the last
+   nent), in ascending neighbour index: code = p >= 0 uses F_cross[p] as stored
+   (a is the pair's first member), code = -1 - p its transpose.
+     y_a = (F_aa + lam_a diag F_aa) x_a + sum over the row list of C x_nbr
+   (lam: n doubles or NULL for 0).  Order of summation: every block row is a dot
+   product in ascending column from 0.0, the own block first, then the row
+   list's in list order; no fma.  xy: NULL, or n doubles: xy[a] = x_a . y_a
+   summed in ascending k from 0.0.  x and y (n, K) must not alias.  No atomics:
+   the bits of row a depend on row a's blocks and the x it reads alone. */
+int ngmix_scene_block_matvec(const double *F_self, const double *F_cross, int64_t n,
+                             int64_t npairs, int K, const int64_t *row_start,
+                             const int32_t *row_ent, int64_t nent, const double *lam,
+                             const double *x, double *y, double *xy, void *stream);
+/* preconditioned conjugate gradients on (F + lam diag F) delta = g for every
+   group at once: the operator of ngmix_scene_block_matvec, the block-Jacobi
+   preconditioner Minv (n, K, K) = (F_aa + lam_a diag F_aa)^-1, lam equal over a
+   group.  obj_group[a]: the group of object a in [0, ngroups), or -1: the
+   object takes no part (its x is not written).  Group G's members are
+   seg_order[seg_start[G] .. seg_start[G + 1]) (nseg entries in all, <= n).
+   State in the caller's buffers: x, r, p, z, q (n, K), part (n), gscal
+   (ngroups, 4) doubles: rz = r^T Minv r, rz0, alpha, beta; grec (ngroups, 4)
+   int32: done, iterations, failed, 0.  init != 0 first sets x = 0, r = g, z =
+   Minv r, p = z, rz0 (a group with rz0 == 0 is done with 0 iterations); then
+   niter iterations are enqueued with no host synchronisation.  A group is done
+   when rz <= tol^2 rz0, done and failed when p.q <= 0 or a scalar is not
+   finite; a done group is frozen: its x, r, p are not written again, so its bits
+   do not depend on how long other groups run or on how the iterations are cut
+   into calls.  A group's sums walk its segment in a fixed stride and tree. */
+int ngmix_scene_pcg(const double *F_self, const double *F_cross, int64_t n, int64_t npairs, int K,
+                    const int64_t *row_start, const int32_t *row_ent, int64_t nent,
+                    const double *lam, const double *Minv, const double *g,
+                    const int32_t *obj_group, const int64_t *seg_order, int64_t nseg,
+                    const int64_t *seg_start, int64_t ngroups, double *x, double *r, double *p,
+                    double *z, double *q, double *part, double *gscal, int32_t *grec, double tol,
+                    int init, int niter, void *stream);
 /* fill_fdiff per stamp: the k-th kept pixel writes fdiff[fdiff_start[i]+k] */
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,

@@ -247,6 +247,11 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ngmix_scene_normal": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp,
                                   _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ngmix_scene_block_matvec": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "ngmix_scene_pcg": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                               _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _f64, _i32, _i32, _vp]),
     "ngmix_fill_fdiff_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
     "ngmix_render_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _vp]),
     "ngmix_model_s2n_sum_batch": (_i32, [_pb, _vp, _vp, _vp, _vp]),

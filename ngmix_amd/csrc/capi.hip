@@ -646,6 +646,28 @@ int ngmix_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobi
                                (hipStream_t)stream);
 }
 
+int ngmix_scene_block_matvec(const double *F_self, const double *F_cross, int64_t n,
+                             int64_t npairs, int K, const int64_t *row_start,
+                             const int32_t *row_ent, int64_t nent, const double *lam,
+                             const double *x, double *y, double *xy, void *stream)
+{
+    return launch_scene_block_matvec(F_self, F_cross, n, npairs, K, row_start, row_ent, nent, lam,
+                                     x, y, xy, (hipStream_t)stream);
+}
+
+int ngmix_scene_pcg(const double *F_self, const double *F_cross, int64_t n, int64_t npairs, int K,
+                    const int64_t *row_start, const int32_t *row_ent, int64_t nent,
+                    const double *lam, const double *Minv, const double *g,
+                    const int32_t *obj_group, const int64_t *seg_order, int64_t nseg,
+                    const int64_t *seg_start, int64_t ngroups, double *x, double *r, double *p,
+                    double *z, double *q, double *part, double *gscal, int32_t *grec, double tol,
+                    int init, int niter, void *stream)
+{
+    return launch_scene_pcg(F_self, F_cross, n, npairs, K, row_start, row_ent, nent, lam, Minv, g,
+                            obj_group, seg_order, nseg, seg_start, ngroups, x, r, p, z, q, part,
+                            gscal, grec, tol, init, niter, (hipStream_t)stream);
+}
+
 int ngmix_fill_fdiff_batch(const ngmix_batch *batch, ngmix_gauss2d *gmix,
                            double *fdiff, const int64_t *fdiff_start,
                            int32_t *status, void *stream)

@@ -69,6 +69,18 @@ int launch_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacob
                         const double *resid, int nrow, int ncol, const int32_t *boxes,
                         const int32_t *items, const int32_t *items_host, int64_t nitems,
                         double *out_mat, double *out_vec, hipStream_t s);
+// scene_solve.hip
+int launch_scene_block_matvec(const double *F_self, const double *F_cross, int64_t n,
+                              int64_t npairs, int K, const int64_t *row_start,
+                              const int32_t *row_ent, int64_t nent, const double *lam,
+                              const double *x, double *y, double *xy, hipStream_t s);
+int launch_scene_pcg(const double *F_self, const double *F_cross, int64_t n, int64_t npairs,
+                     int K, const int64_t *row_start, const int32_t *row_ent, int64_t nent,
+                     const double *lam, const double *Minv, const double *g,
+                     const int32_t *obj_group, const int64_t *seg_order, int64_t nseg,
+                     const int64_t *seg_start, int64_t ngroups, double *x, double *r, double *p,
+                     double *z, double *q, double *part, double *gscal, int32_t *grec,
+                     double tol, int init, int niter, hipStream_t s);
 // noisecov.hip
 int launch_noise_cov_blocks(const double *dimg, const int64_t *stamp_idx, int64_t m,
                             const int64_t *pix_off, const double *ierr, const double *noise,

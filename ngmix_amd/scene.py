@@ -39,8 +39,19 @@ inverts them per group of connected objects (the covariance of an object
 marginalised over its neighbours), and fit_joint is a Levenberg-Marquardt fit of
 all the objects of a frame together over them.
 
-torch does the plumbing (the binning of _tile_pairs, the dense solves of the
-groups); the pixel work is HIP (csrc/scene.hip, csrc/scene_normal.hip).
+    sol = scene.solve_normal(ne, lam=1e-3)
+    res = scene.fit_joint(frame, weight, jacobians, guess, "exp", psf=psf, large_groups="cg")
+
+solve_normal solves (F + lam diag F) delta = grad over those blocks, every
+group as one system, by preconditioned conjugate gradients on the device
+(csrc/scene_solve.hip): the operator over the block rows
+and the CG updates are HIP, no atomics, and a group's bits depend on that group
+alone.  fit_joint(large_groups="cg") steps the groups that are too large for a
+dense solve with it, instead of with their own blocks only.
+
+torch does the plumbing (the binning of _tile_pairs, the row lists of
+_block_rows, the dense solves of the groups); the pixel work and the sparse
+solve are HIP (csrc/scene.hip, csrc/scene_normal.hip, csrc/scene_solve.hip).
 """
 import numpy as np
 
@@ -48,7 +59,7 @@ from . import _lib
 from .batch import GMixBatch, StampBatch, _dptr, _on_device, _require_cuda, _stream, _torch
 
 __all__ = ["render_scene", "cut_stamps", "cut_deblended_stamps", "fit_deblended",
-           "normal_equations", "joint_covariance", "fit_joint"]
+           "normal_equations", "joint_covariance", "fit_joint", "solve_normal"]
 
 TILE_H = 4      # csrc/scene.hip: SCENE_TH, SCENE_TW
 TILE_W = 16
@@ -1116,8 +1127,253 @@ def _joint_step(ne, layout, lam):
     return delta, pred, solved & ~bad
 
 
+# ------------------------------------------- conjugate gradients over the blocks
+
+def _block_rows(pairs, n):
+    """
+    The row lists of the block-sparse matrix of n objects whose off-diagonal
+    blocks are `pairs` (P, 2) (an integer tensor, on any device; a < b in every
+    pair): object a gets one entry per pair that contains it, in ascending
+    neighbour index.  Returns (row_start (n + 1,) int64, row_ent (2 P, 2)
+    int32): the entries of object a are row_ent[row_start[a]:row_start[a + 1]],
+    each (neighbour, code) with code = p when a is the first member of pair p
+    (the block as stored) and -1 - p when it is the second (the block
+    transposed).  One stable sort of 2 P keys; never an N x N array.
+    """
+    torch = _torch()
+    dev = pairs.device
+    n, P = int(n), int(pairs.shape[0])
+    i64 = dict(dtype=torch.int64, device=dev)
+    if P == 0:
+        return torch.zeros(n + 1, **i64), torch.zeros((0, 2), dtype=torch.int32, device=dev)
+    a, b = pairs[:, 0].to(torch.int64), pairs[:, 1].to(torch.int64)
+    p = torch.arange(P, **i64)
+    owner, nbr, code = torch.cat([a, b]), torch.cat([b, a]), torch.cat([p, -1 - p])
+    _, order = torch.sort(owner * n + nbr, stable=True)
+    row_ent = torch.stack([nbr[order], code[order]], dim=1).to(torch.int32).contiguous()
+    counts = torch.bincount(owner, minlength=n)
+    return torch.cat([torch.zeros(1, **i64), torch.cumsum(counts, 0)]), row_ent
+
+
+def _group_segments(group, keep=None):
+    """
+    The objects sorted by group: group (n,) integer labels (a tensor, on any
+    device), keep: None or an (n,) bool tensor, the objects that take part.
+    Returns (seg_order (m,) int64, seg_start (ngroups + 1,) int64, index (n,)
+    int64): the labels in ascending order are groups 0 .. ngroups - 1, index is
+    every object's group, and group G's members that take part are
+    seg_order[seg_start[G]:seg_start[G + 1]] in ascending index (a group of
+    which no member takes part is an empty segment).
+    """
+    torch = _torch()
+    dev = group.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    if int(group.shape[0]) == 0:
+        return torch.zeros(0, **i64), torch.zeros(1, **i64), torch.zeros(0, **i64)
+    uniq, index = torch.unique(group.to(torch.int64), return_inverse=True)
+    ngroups = int(uniq.shape[0])
+    order = torch.argsort(index, stable=True)
+    if keep is not None:
+        order = order[keep[order]]
+        counts = torch.bincount(index[keep], minlength=ngroups)
+    else:
+        counts = torch.bincount(index, minlength=ngroups)
+    return order, torch.cat([torch.zeros(1, **i64), torch.cumsum(counts, 0)]), index
+
+
+def _block_matvec(F_self, F_cross, row_start, row_ent, lam, x, want_xy=False):
+    """ngmix_scene_block_matvec on contiguous float64 device tensors: y (n, K),
+    and (want_xy) the per-object x . y (n,)"""
+    torch = _torch()
+    dev = F_self.device
+    n, K = int(F_self.shape[0]), int(F_self.shape[1])
+    y = torch.empty((n, K), dtype=torch.float64, device=dev)
+    xy = torch.empty(n, dtype=torch.float64, device=dev) if want_xy else None
+    with _on_device(dev):
+        st = _lib.lib().ngmix_scene_block_matvec(
+            _dptr(F_self), _dptr(F_cross), n, int(F_cross.shape[0]), K, _dptr(row_start),
+            _dptr(row_ent), int(row_ent.shape[0]), _dptr(lam), _dptr(x), _dptr(y), _dptr(xy),
+            _stream())
+    _lib.check(st, "ngmix_scene_block_matvec")
+    return (y, xy) if want_xy else y
+
+
+_SOLVE_KEYS = ("F_self", "grad", "pairs", "F_cross", "group", "status")
+
+
+def _solve_arguments(ne, lam, tol, maxiter, check_every, who):
+    """solve_normal's arguments, checked on the host before a device is asked
+    for.  Returns lam as an (N,) host array"""
+    torch = _torch()
+    if not hasattr(ne, "keys") or any(k not in ne for k in _SOLVE_KEYS):
+        raise ValueError("%s: ne must be a dict with %s" % (who, ", ".join(_SOLVE_KEYS)))
+    for k in _SOLVE_KEYS:
+        if not isinstance(ne[k], torch.Tensor):
+            raise ValueError("%s: ne['%s'] must be a tensor" % (who, k))
+        if ne[k].device != ne["F_self"].device:
+            raise ValueError("%s: ne['%s'] must be on the device of F_self (%s)"
+                             % (who, k, ne["F_self"].device))
+    F, C, pairs = ne["F_self"], ne["F_cross"], ne["pairs"]
+    if F.ndim != 3 or F.shape[1] != F.shape[2]:
+        raise ValueError("%s: F_self must be (N, K, K)" % who)
+    n, K = int(F.shape[0]), int(F.shape[1])
+    if K < 1 or K > NORMAL_KMAX:
+        raise ValueError("%s: K must be 1..%d parameters per object, got %d"
+                         % (who, NORMAL_KMAX, K))
+    if tuple(ne["grad"].shape) != (n, K):
+        raise ValueError("%s: grad must be (%d, %d)" % (who, n, K))
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int64:
+        raise ValueError("%s: pairs must be (P, 2) int64" % who)
+    if tuple(C.shape) != (int(pairs.shape[0]), K, K):
+        raise ValueError("%s: F_cross must be (%d, %d, %d)" % (who, int(pairs.shape[0]), K, K))
+    for k in ("F_self", "grad", "F_cross"):
+        if ne[k].dtype != torch.float64:
+            raise ValueError("%s: %s must be float64" % (who, k))
+    for k in ("group", "status"):
+        if tuple(ne[k].shape) != (n,) or ne[k].dtype.is_floating_point:
+            raise ValueError("%s: %s must be (%d,) integers" % (who, k, n))
+    if isinstance(lam, torch.Tensor):
+        lam = lam.detach().cpu().numpy()
+    try:
+        lam = np.asarray(lam, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: lam must be a scalar or an (N,) array" % who)
+    if lam.ndim == 0:
+        lam = np.full(n, float(lam))
+    if lam.shape != (n,):
+        raise ValueError("%s: lam must be a scalar or have one entry per object (%d)" % (who, n))
+    if not np.all(np.isfinite(lam)) or np.any(lam < 0.0):
+        raise ValueError("%s: lam must be finite and >= 0" % who)
+    _cg_arguments(tol, maxiter, who, "tol", "maxiter")
+    if int(check_every) < 1:
+        raise ValueError("%s: check_every must be at least 1, got %d" % (who, int(check_every)))
+    return lam
+
+
+def _cg_arguments(tol, maxiter, who, tol_name, maxiter_name):
+    if not (float(tol) >= 0.0) or not np.isfinite(float(tol)):
+        raise ValueError("%s: %s must be finite and >= 0" % (who, tol_name))
+    if int(maxiter) < 1:
+        raise ValueError("%s: %s must be at least 1, got %d" % (who, maxiter_name, int(maxiter)))
+
+
+def _solve(ne, lam, tol, maxiter, check_every, only=None):
+    """solve_normal on checked arguments; lam (N,) host, equal over a group;
+    only: None, or an (N,) host bool array: the objects that take part (whole
+    groups), the others are left out as refused objects are"""
+    torch = _torch()
+    F, g, pairs, C = ne["F_self"], ne["grad"], ne["pairs"], ne["F_cross"]
+    dev = _require_cuda(F.device)
+    n, K = int(F.shape[0]), int(F.shape[1])
+    f64 = dict(dtype=torch.float64, device=dev)
+    if n == 0:
+        return dict(delta=torch.zeros((0, K), **f64),
+                    cg_iter=torch.zeros(0, dtype=torch.int64, device=dev),
+                    cg_converged=torch.zeros(0, dtype=torch.bool, device=dev),
+                    cg_failed=torch.zeros(0, dtype=torch.bool, device=dev),
+                    cg_resid=torch.zeros(0, **f64))
+    take = ne["status"] == 0
+    if only is not None:
+        take = take & torch.from_numpy(np.ascontiguousarray(only, dtype=bool)).to(dev)
+    eye = torch.eye(K, **f64).expand(n, K, K)
+    Fu = torch.where(take[:, None, None], F, eye).contiguous()
+    gu = torch.where(take[:, None], g, torch.zeros_like(g)).contiguous()
+    if int(pairs.shape[0]) and int(take.sum()) < n:
+        inside = take[pairs[:, 0]] & take[pairs[:, 1]]
+        pairs, C = pairs[inside], C[inside]
+    C = C.contiguous()
+    row_start, row_ent = _block_rows(pairs, n)
+    seg_order, seg_start, index = _group_segments(ne["group"], take)
+    ngroups = int(seg_start.shape[0]) - 1
+    obj_group = torch.where(take, index, torch.full_like(index, -1)).to(torch.int32)
+    d_lam = torch.from_numpy(np.ascontiguousarray(lam, dtype=np.float64)).to(dev)
+    own = Fu + d_lam[:, None, None] * torch.diag_embed(torch.diagonal(Fu, dim1=1, dim2=2))
+    Minv, sing = _own_inverse(own, ~take)
+    # an own block that is not positive definite: NaN, so the group's first
+    # r^T Minv r is not finite and the group is failed before it iterates
+    Minv = torch.where(sing[:, None, None], torch.full_like(Minv, float("nan")),
+                       Minv).contiguous()
+    x, r, p, z, q = (torch.zeros((n, K), **f64) for _ in range(5))
+    part = torch.zeros(n, **f64)
+    gscal = torch.zeros((ngroups, 4), **f64)
+    grec = torch.zeros((ngroups, 4), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    spent, init = 0, 1
+    while True:
+        k = min(int(check_every), int(maxiter) - spent)
+        with _on_device(dev):
+            st = L.ngmix_scene_pcg(
+                _dptr(Fu), _dptr(C), n, int(C.shape[0]), K, _dptr(row_start), _dptr(row_ent),
+                int(row_ent.shape[0]), _dptr(d_lam), _dptr(Minv), _dptr(gu), _dptr(obj_group),
+                _dptr(seg_order), int(seg_order.shape[0]), _dptr(seg_start), ngroups, _dptr(x),
+                _dptr(r), _dptr(p), _dptr(z), _dptr(q), _dptr(part), _dptr(gscal), _dptr(grec),
+                float(tol), init, k, _stream())
+        _lib.check(st, "ngmix_scene_pcg")
+        spent, init = spent + k, 0
+        # the one read-back per check_every iterations
+        if bool(grec[:, 0].cpu().numpy().all()) or spent >= int(maxiter):
+            break
+    done, failed = grec[index, 0] != 0, grec[index, 2] != 0
+    rz, rz0 = gscal[index, 0], gscal[index, 1]
+    resid = torch.where(rz0 > 0.0, torch.sqrt(torch.clamp(rz, min=0.0) / rz0),
+                        torch.where(failed, torch.full_like(rz, float("nan")),
+                                    torch.zeros_like(rz)))
+    return dict(delta=torch.where(take[:, None], x, torch.zeros_like(x)),
+                cg_iter=torch.where(take, grec[index, 1].to(torch.int64),
+                                    torch.zeros_like(index)),
+                cg_converged=take & done & ~failed, cg_failed=take & failed,
+                cg_resid=torch.where(take, resid, torch.zeros_like(resid)))
+
+
+def solve_normal(ne, lam=0.0, tol=1e-8, maxiter=200, check_every=8):
+    """
+    Solve (F + lam diag F) delta = grad over the blocks of normal_equations,
+    every group of connected objects as one system, by block-Jacobi
+    preconditioned conjugate gradients on the device (csrc/scene_solve.hip;
+    DESIGN.md section 3.17): what a group too large for a dense solve steps
+    with.  F is the block-sparse symmetric matrix of F_self and F_cross.
+
+    ne: a normal_equations result, or any dict of device tensors with F_self
+        (N, K, K), grad (N, K), pairs (P, 2) int64 (a < b), F_cross (P, K, K),
+        group (N,) and status (N,)
+    lam: the damping factor, a scalar or an (N,) array that is equal over a
+        group (a group takes its members' largest)
+    tol: a group has converged when r^T M^-1 r <= tol^2 times its starting
+        value, r the (recurred) residual and M the preconditioner: the own
+        blocks (F_aa + lam diag F_aa)
+    maxiter: iterations at most (block-Jacobi is a weak preconditioner for a
+        frame that percolates into one group: DESIGN.md section 3.17 measured 701
+        iterations to tol = 1e-8 on 29,970 connected objects)
+    check_every: the host reads the groups' done flags back once per this many
+        iterations (the only synchronisation) and stops when all are done
+
+    Returns a dict of device tensors: delta (N, K), cg_iter (N,) int64: the
+    iterations of the object's group, cg_converged (N,) bool, cg_failed (N,)
+    bool: breakdown, p^T A p <= 0 or a scalar that is not finite (the matrix is
+    not positive definite to rounding; also an own block that Cholesky refuses),
+    cg_resid (N,): sqrt(r^T M^-1 r / its starting value) of the object's group.
+    A group with a zero right-hand side has delta = 0 after 0 iterations.  A
+    group that is done is frozen on the device: its bits depend neither on the
+    other groups nor on check_every.  An object with status != 0 (NaN blocks)
+    gets delta = 0 and converged False, is in no row list and no sum, and leaves
+    every other object's bits those of the catalogue without it.  No atomics:
+    two calls give the same bits.
+    """
+    lam = _solve_arguments(ne, lam, tol, maxiter, check_every, "solve_normal")
+    dev = _require_cuda(ne["F_self"].device)
+    n = int(lam.shape[0])
+    if n:
+        group = np.asarray(ne["_group"]) if "_group" in ne else ne["group"].cpu().numpy()
+        _, index = np.unique(group, return_inverse=True)
+        g_lam = np.zeros(int(index.max()) + 1)
+        np.maximum.at(g_lam, index.reshape(-1), lam)
+        lam = g_lam[index.reshape(-1)]
+    with _on_device(dev):
+        return _solve(ne, lam, float(tol), int(maxiter), int(check_every))
+
+
 def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=1e-6,
-              lambda0=1e-3, max_group=16):
+              lambda0=1e-3, max_group=16, large_groups="jacobi", cg_tol=1e-8, cg_maxiter=200):
     """
     Fit all the objects of a frame together (a joint, MOF-style fit), ONE band
     and NO prior: Levenberg-Marquardt over normal_equations, with one damping
@@ -1132,7 +1388,16 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
         below any statistical meaning
     lambda0: the starting lambda; it never goes below scene.LAMBDA_FLOOR
     max_group: the objects of a larger group step with their own blocks only
-        (block-Jacobi) and carry joint_status 1
+        (block-Jacobi) and carry joint_status 1 -- with large_groups="jacobi"
+    large_groups: "jacobi", or "cg": a group of more than max_group objects
+        steps with solve_normal's delta at the group's lambda (conjugate
+        gradients over all of its blocks, to cg_tol, cg_maxiter iterations at
+        most); its predicted decrease is delta^T g summed in a fixed order, and
+        a solve that failed or did not converge counts as a system that cannot
+        be solved.  Such objects carry joint_status 2.  Groups of up to
+        max_group objects take the dense solve either way, with the same bits.
+        pars_cov of a joint_status 2 object is still the inverse of its own
+        block: its marginal covariance would take K solves per object
 
     Per iteration the groups are those of the current parameters.  Every group
     that has not converged solves (F + lambda diag F) delta = g over its dense
@@ -1150,7 +1415,9 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
     (joint_covariance's; flags.MAXITER for an object of a group that did not
     converge), group (N,), niter (N,): the iterations the object's group took
     part in, converged (N,) bool, joint_status (N,), chi2: sum w r^2 of the
-    whole frame at pars, recomputed, and lambda (N,).
+    whole frame at pars, recomputed, lambda (N,), and cg_iter (N,): the
+    conjugate-gradient iterations spent on the object's groups, all LM
+    iterations together (0 with large_groups="jacobi").
     """
     from .flags import MAXITER
     torch = _torch()
@@ -1159,6 +1426,11 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
         raise ValueError("fit_joint: maxiter must be at least 1, got %d" % maxiter)
     if not (float(tol) >= 0.0) or not (float(lambda0) > 0.0):
         raise ValueError("fit_joint: tol must be >= 0 and lambda0 > 0")
+    if large_groups not in ("jacobi", "cg"):
+        raise ValueError("fit_joint: large_groups must be 'jacobi' or 'cg', got %r"
+                         % (large_groups,))
+    _cg_arguments(cg_tol, cg_maxiter, "fit_joint", "cg_tol", "cg_maxiter")
+    cg = large_groups == "cg"
     _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
     frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, guess, model,
                                                         psf, "fit_joint")
@@ -1168,6 +1440,7 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
     lam = np.full(n, float(lambda0))
     conv = np.zeros(n, dtype=bool)
     niter = np.zeros(n, dtype=np.int64)
+    cg_iter = np.zeros(n, dtype=np.int64)
     for _ in range(maxiter):
         ne = _normal(frame, wframe, wpos, jac, pars, name, psf, None, None)
         group = ne["_group"]
@@ -1186,6 +1459,13 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
         niter[active] += 1
         layout = _GroupLayout(group, max_group)
         delta, pred, solved = _joint_step(ne, layout, lam)
+        big = layout.oversized & active if cg else np.zeros(n, dtype=bool)
+        if big.any():
+            sol = _solve(ne, lam, float(cg_tol), int(cg_maxiter), 8, only=big)
+            d_big = torch.from_numpy(big).to(dev)
+            delta = torch.where(d_big[:, None], sol["delta"], delta)
+            solved = torch.where(d_big, sol["cg_converged"], solved)
+            cg_iter[big] += sol["cg_iter"].cpu().numpy()[big]
         d_active = torch.from_numpy(active).to(dev)
         trial = torch.where(d_active[:, None], pars + delta, pars)
         jm = _joint_model(shape, jac, trial, name, psf, None, None, False)
@@ -1197,7 +1477,17 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
         unsolved = np.zeros(ngroups, dtype=bool)
         np.logical_or.at(unsolved, group, ~solved.cpu().numpy() & ok_obj)
         accept_g = (new < old) & ~refused & ~unsolved
-        if layout.oversized.any():
+        if big.any():
+            # delta^T g of a group: per object in ascending parameter, then the
+            # group's objects in ascending index
+            dg = (delta * ne["grad"]).cpu().numpy()
+            pred_b = np.zeros(n)
+            for k in range(K):
+                pred_b = pred_b + np.where(big, dg[:, k], 0.0)
+            pred_g = np.zeros(ngroups)
+            np.add.at(pred_g, group, pred_b)
+            pred_o = np.where(big, pred_g[group], pred.cpu().numpy())
+        elif layout.oversized.any() and not cg:
             # block-Jacobi members step one by one but are judged with their group
             pred_g = np.zeros(ngroups)
             np.add.at(pred_g, group, np.where(active, pred.cpu().numpy(), 0.0))
@@ -1224,5 +1514,5 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
     r = frame - ne["_model"]
     return {"pars": pars.cpu().numpy(), "pars_cov": pars_cov, "pars_err": pars_err,
             "flags": flags, "group": group.copy(), "niter": niter, "converged": conv,
-            "joint_status": cov["joint_status"].cpu().numpy(),
-            "chi2": float((r * r * wpos).sum()), "lambda": lam}
+            "joint_status": cov["joint_status"].cpu().numpy() * (2 if cg else 1),
+            "chi2": float((r * r * wpos).sum()), "lambda": lam, "cg_iter": cg_iter}

@@ -23,8 +23,15 @@ events, normal_equations end to end, and for the self blocks the long way
 (cut_stamps of every object's union box + autodiff.stamp_fisher), with the
 largest difference of the two.
 
+The conjugate-gradient leg (--joint-cg; scene.solve_normal, csrc/scene_solve.hip;
+DESIGN.md section 3.17) on the same scene, written to
+profiles/scene_joint_cg_bench.txt: the block operator by events, one
+solve_normal at lambda = 1e-3 and tol = 1e-8 end to end with the iterations the
+largest group took, and one fit_joint iteration with large_groups="cg" and with
+"jacobi".
+
     python tools/bench_scene.py [--n 30000] [--size 4096] [--out profiles/scene_bench.txt]
-                                [--deblend-only] [--joint-only]
+                                [--deblend-only] [--joint-only] [--joint-cg]
 """
 import argparse
 import os
@@ -69,6 +76,9 @@ def main():
     ap.add_argument("--no-backward", action="store_true")
     ap.add_argument("--deblend-only", action="store_true")
     ap.add_argument("--joint-only", action="store_true")
+    ap.add_argument("--joint-cg", action="store_true")
+    ap.add_argument("--joint-cg-out",
+                    default=os.path.join(ROOT, "profiles", "scene_joint_cg_bench.txt"))
     ap.add_argument("--joint-out",
                     default=os.path.join(ROOT, "profiles", "scene_joint_bench.txt"))
     args = ap.parse_args()
@@ -283,6 +293,81 @@ def main():
             % (float(((ne["F_self"][d_idx] - F_long).abs() / scale).max()),
                bool((ne["F_self"] == F_kernel).all())))
 
+    def joint_cg_leg():
+        K = 6
+        say("joint cg: %d x %d frame, %d objects, G = %d, K = %d" % (size, size, n, G, K))
+        frame, _ = scene.render_scene(shape, gm, d_jac)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(99)
+        frame = frame + 0.01 * torch.randn(shape, generator=gen, dtype=torch.float64,
+                                           device="cuda")
+        ne = scene.normal_equations(frame, None, d_jac, d_pars, "exp", psf=d_psf)
+        group = ne["group"].cpu().numpy()
+        gsize = np.bincount(group)
+        big = int(np.argmax(gsize))
+        member = int(np.nonzero(group == big)[0][0])
+        P = int(ne["pairs"].shape[0])
+        row_start, row_ent = scene._block_rows(ne["pairs"], n)
+        say("joint cg: %d pairs, %d row entries (%.1f per object, at most %d); %d groups, the "
+            "largest of %d objects" % (P, int(row_ent.shape[0]), row_ent.shape[0] / float(n),
+                                       int((row_start[1:] - row_start[:-1]).max()),
+                                       gsize.shape[0], gsize.max()))
+        F, C = ne["F_self"].contiguous(), ne["F_cross"].contiguous()
+        lam = torch.full((n,), 1e-3, dtype=torch.float64, device="cuda")
+        x = torch.randn((n, K), generator=gen, dtype=torch.float64, device="cuda")
+        y = torch.empty_like(x)
+        xy = torch.empty(n, dtype=torch.float64, device="cuda")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t_kern = []
+        for rep in range(4 * args.reps + 1):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(L.ngmix_scene_block_matvec(
+                _dptr(F), _dptr(C), n, P, K, _dptr(row_start), _dptr(row_ent),
+                int(row_ent.shape[0]), _dptr(lam), _dptr(x), _dptr(y), _dptr(xy), _stream()),
+                "scene_block_matvec")
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                t_kern.append(e0.elapsed_time(e1))
+        nbytes = 8 * (n * K * K + P * K * K * 2 + 3 * n * K) + 8 * int(row_ent.shape[0])
+        say("joint cg: ngmix_scene_block_matvec with x.y (ms, by events): median %.4f, min %.4f, "
+            "max %.4f; %.1f MB of blocks, entries and vectors per call; which bound: not "
+            "established (no counter run was made)"
+            % (np.median(t_kern), min(t_kern), max(t_kern), nbytes / 1e6))
+
+        def solve():
+            return scene.solve_normal(ne, lam=1e-3, tol=1e-8, maxiter=1000)
+
+        timed(solve)
+        t_solve = []
+        for rep in range(args.reps):
+            sol, t = timed(solve)
+            t_solve.append(t)
+        it = sol["cg_iter"].cpu().numpy()
+        say("joint cg: solve_normal(lam=1e-3, tol=1e-8) end to end (ms): median %.3f, min %.3f, "
+            "max %.3f" % (np.median(t_solve), min(t_solve), max(t_solve)))
+        say("joint cg: the largest group took %d iterations (5 launches each), residual "
+            "sqrt(rz / rz0) %.3e; converged %d of %d objects, failed %d; iterations over all "
+            "objects: median %d, max %d"
+            % (it[member], float(sol["cg_resid"][member]), int(sol["cg_converged"].sum()), n,
+               int(sol["cg_failed"].sum()), np.median(it), it.max()))
+        for mode in ("cg", "jacobi"):
+            def one():
+                return scene.fit_joint(frame, None, d_jac, d_pars, "exp", psf=d_psf, maxiter=1,
+                                       large_groups=mode, cg_maxiter=1000)
+            timed(one)
+            res, t = timed(one)
+            say("joint cg: one fit_joint iteration, large_groups=%r (ms, one run after a warm-up): "
+                "%.3f; chi2 %.9g, cg_iter max %d, objects at joint_status 0/1/2: %d/%d/%d"
+                % (mode, t, res["chi2"], int(res["cg_iter"].max()),
+                   int((res["joint_status"] == 0).sum()), int((res["joint_status"] == 1).sum()),
+                   int((res["joint_status"] == 2).sum())))
+
+    if args.joint_cg:
+        joint_cg_leg()
+        write("w", args.joint_cg_out)
+        return
     if args.joint_only:
         joint_leg()
         write("w", args.joint_out)

@@ -165,6 +165,38 @@ int main()
     expect("scene_normal b < a", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_back, it_back, 1, x, x, s), BAD, "item 0 (1, 0)");
     expect("scene_normal b < -1", launch_scene_normal(gm1, 1, jc1, 2, x, 6, x, x, 8, 8, st, it_low, it_low, 1, x, x, s), BAD, "item 0 (0, -2)");
 
+    // the block operator and the conjugate-gradient loop over it
+    int64_t rs[3] = {0, 1, 2};
+    int32_t re[4] = {1, 0, 0, -1};
+    double y[64] = {0};
+    expect("block_matvec K 0", launch_scene_block_matvec(x, x, 2, 1, 0, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "K must be 1..8");
+    expect("block_matvec K 9", launch_scene_block_matvec(x, x, 2, 1, 9, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "K must be 1..8");
+    expect("block_matvec n < 0", launch_scene_block_matvec(x, x, -2, 1, 6, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "must not be negative");
+    expect("block_matvec npairs < 0", launch_scene_block_matvec(x, x, 2, -1, 6, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "must not be negative");
+    expect("block_matvec nent < 0", launch_scene_block_matvec(x, x, 2, 1, 6, rs, re, -2, nullptr, x, y, nullptr, s), BAD, "must not be negative");
+    expect("block_matvec null F_self", launch_scene_block_matvec(nullptr, x, 2, 1, 6, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "are required");
+    expect("block_matvec null row_start", launch_scene_block_matvec(x, x, 2, 1, 6, nullptr, re, 2, nullptr, x, y, nullptr, s), BAD, "are required");
+    expect("block_matvec null F_cross", launch_scene_block_matvec(x, nullptr, 2, 1, 6, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "are required");
+    expect("block_matvec null row_ent", launch_scene_block_matvec(x, x, 2, 1, 6, rs, nullptr, 2, nullptr, x, y, nullptr, s), BAD, "are required");
+    expect("block_matvec entries without pairs", launch_scene_block_matvec(x, nullptr, 2, 0, 6, rs, re, 2, nullptr, x, y, nullptr, s), BAD, "need pairs");
+    expect("block_matvec null x", launch_scene_block_matvec(x, x, 2, 1, 6, rs, re, 2, nullptr, nullptr, y, nullptr, s), BAD, "must not alias");
+    expect("block_matvec x is y", launch_scene_block_matvec(x, x, 2, 1, 6, rs, re, 2, nullptr, y, y, nullptr, s), BAD, "must not alias");
+    expect("block_matvec empty", launch_scene_block_matvec(nullptr, nullptr, 0, 0, 6, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, s), NGMIX_OK);
+    int64_t so[2] = {0, 1}, ss[2] = {0, 2};
+    expect("pcg K 0", launch_scene_pcg(x, x, 2, 1, 0, rs, re, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "K must be 1..8");
+    expect("pcg K 9", launch_scene_pcg(x, x, 2, 1, 9, rs, re, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "K must be 1..8");
+    expect("pcg n < 0", launch_scene_pcg(x, x, -2, 1, 6, rs, re, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "must not be negative");
+    expect("pcg null row_ent", launch_scene_pcg(x, x, 2, 1, 6, rs, nullptr, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "are required");
+    expect("pcg ngroups < 0", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, x, x, st, so, 2, ss, -1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "must not be negative");
+    expect("pcg nseg > n", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, x, x, st, so, 3, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "nseg <= n");
+    expect("pcg niter < 0", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, -1, s), BAD, "niter must not be negative");
+    expect("pcg tol < 0", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, -1.0, 1, 1, s), BAD, "tol must be");
+    expect("pcg null Minv", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, nullptr, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "are required");
+    expect("pcg null segments", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, x, x, st, nullptr, 2, ss, 1, y, y, y, y, y, y, y, st, 1e-8, 1, 1, s), BAD, "are required");
+    expect("pcg null record", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, x, x, st, so, 2, ss, 1, y, y, y, y, y, y, y, nullptr, 1e-8, 1, 1, s), BAD, "are required");
+    expect("pcg no groups", launch_scene_pcg(x, x, 2, 1, 6, rs, re, 2, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1e-8, 1, 1, s), NGMIX_OK);
+    expect("pcg empty", launch_scene_pcg(nullptr, nullptr, 0, 0, 6, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1e-8, 1, 0, s), NGMIX_OK);
+
     // keys outside a dispatch table: no kernel, and launch() refuses
     struct Row {
         int key;
