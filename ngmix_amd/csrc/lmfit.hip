@@ -1165,8 +1165,14 @@ void lm_eval_fd_kernel(
                 rowd = (double)(r0 + lrow) - jac.row0;
                 cold = (double)(c0 + lcol) - jac.col0;
             }
-            const double v = fma(jac.dvdrow, rowd, jac.dvdcol * cold);
-            const double u = fma(jac.dudrow, rowd, jac.dudcol * cold);
+            // two rounded products and a sum, not an fma: the sum commutes, so a
+            // transposed stamp (rows and columns of the image and of the jacobian
+            // swapped) gives every pixel the same bits of (v, u).  The forward
+            // difference divides the rounding of v - cen by h ~ 1e-8 |x|: with an
+            // fma here the sums of a stamp and of its transpose differed by up
+            // to 5e-7 of their largest entry (tests/test_gpu_wcs_symmetry.py)
+            const double v = jac.dvdrow * rowd + jac.dvdcol * cold;
+            const double u = jac.dudrow * rowd + jac.dudcol * cold;
             // dv^2, du^2, dv du about the three centres
             double q0[3] = {0.0, 0.0, 0.0}, q1[3] = {0.0, 0.0, 0.0}, q2[3] = {0.0, 0.0, 0.0};
             if (COCEN) {
