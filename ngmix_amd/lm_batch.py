@@ -30,8 +30,10 @@ object's residual vector and its bounds run leastsqbound's parameter transform
 inside the iteration; prior=None is legal as in the reference (zero prior rows,
 no bounds, results.py:354-357).
 """
+import collections
 import ctypes
 import os
+import time
 
 import numpy as np
 
@@ -138,34 +140,71 @@ class LMBatchResult(dict):
 
 
 class _Job(object):
-    """one batch on its way through LMBatchFitter (device arrays, events)"""
+    """one batch on its way through LMBatchFitter: what the stages of _enqueue_on
+    leave for each other and for _collect (an undeclared field cannot be set)"""
+    __slots__ = (
+        # the call: device, raw stream handle, arguments, host timing
+        "dev", "stream", "streaming", "check_every", "phases", "tmark", "host_enqueue_ms",
+        # the batch and its layout (_stamp_maps, _psf_records)
+        "stamps", "batch", "psf", "npsf", "nobj", "npars", "nband", "ns", "nsum", "sobj",
+        "sband", "obj_start", "trivial_map", "npix_obj", "maxfev", "modnum",
+        # device buffers (_alloc_buffers): views of the arena or separate tensors
+        "arena", "out_shapes", "d_states", "d_sums", "d_status", "d_sstats", "d_ostats",
+        "d_flat", "d_tri", "d_rec",
+        # the one pinned upload and its views (_upload)
+        "h_all", "d_all", "d_guess", "d_npix", "d_sobj", "d_sband", "d_start",
+        # the prior record and the precise-covariance buffers
+        "prior_desc", "d_osums", "d_prior_lnp", "d_jacpt", "d_psums",
+        # the lock-step loop: its form, the library's problem record, what ran
+        "loop_stats", "nsplit", "host_loop", "problem", "chunks", "useful_rounds",
+        "loop_ms_host", "legacy_ev", "ev_init", "ev_post",
+        # the results (_queue_results): device views, pinned downloads, events
+        "d_cov0", "fit_ctx", "h_flat", "h_tri", "h_cov0", "copied", "cov_copied")
+
+    def __init__(self):   # the fields that are read before their stage has run
+        self.problem = self.d_psums = self.d_prior_lnp = self.useful_rounds = None
+        self.ev_post = self.legacy_ev = None
+        self.chunks, self.loop_ms_host = [], 0.0
+
+
+# one call of ngmix_lm_rounds_batch: rounds queued, their counts of running fits (device,
+# pinned host), the per-launch timing events or None, the _HipEvents pair around the call
+_Chunk = collections.namedtuple("_Chunk", "nrounds d_counts h_counts events span")
+
+
+class _Piece(object):
+    """a run of whole objects in the host-driven loop: objects [o_lo, o_hi),
+    stamps [s_lo, s_hi), its ngmix_batch record, side stream, device counter of
+    running fits, the pinned ring it comes back through, reads pending, rounds"""
+    __slots__ = ("o_lo", "o_hi", "s_lo", "s_hi", "batch", "stream", "nact", "live", "active",
+                 "ring", "pend", "launched", "ev_idx")
 
 
 class _HipEvents(object):
-    """n hipEvent_t of the library (ngmix_events_create), destroyed with the
-    object"""
+    """n hipEvent_t of the library (ngmix_events_create), destroyed with it"""
 
     def __init__(self, n):
         self.n = n
         self.handles = (ctypes.c_void_p * n)()
         _lib.check(_lib.lib().ngmix_events_create(n, self.handles), "ngmix_events_create")
 
-    def record(self, i, stream=None):
-        _lib.check(_lib.lib().ngmix_event_record(self.handles[i], stream or _stream()),
-                   "ngmix_event_record")
-
-    def elapsed_ms(self, i, j):
-        ms = ctypes.c_float()
-        _lib.check(_lib.lib().ngmix_event_elapsed_ms(self.handles[i], self.handles[j],
-                                                      ctypes.byref(ms)),
-                   "ngmix_event_elapsed_ms")
-        return float(ms.value)
-
     def __del__(self):
         try:
             _lib.lib().ngmix_events_destroy(self.n, self.handles)
         except Exception:
             pass
+
+
+def _record(events, i, stream):
+    """record event i of an array of hipEvent_t on a stream (None: no timing)"""
+    if events is not None:
+        _lib.check(_lib.lib().ngmix_event_record(events[i], stream), "ngmix_event_record")
+
+
+def _elapsed_ms(a, b, context="ngmix_event_elapsed_ms"):
+    ms = ctypes.c_float()
+    _lib.check(_lib.lib().ngmix_event_elapsed_ms(a, b, ctypes.byref(ms)), context)
+    return float(ms.value)
 
 
 class _EventPool(object):
@@ -222,6 +261,81 @@ def _carve(torch, dev, pieces):
     return buf, views, offs
 
 
+def _stamp_maps(ns, npix_kept, guess, stamp_obj, stamp_band, nloc):
+    """the layout of a batch, checked, in host arrays (numpy alone): ns stamps of
+    npix_kept pixels, guess (nobj, nloc - 1 + nband) or one row, the stamps'
+    object and band indices or None.  Returns guess (2-d float64), sobj, sband
+    (int32), obj_start (nobj + 1 stamp offsets), trivial_map (no map given: stamp
+    i is object i in band 0), npix_obj (pixels per object) and nband."""
+    guess = np.ascontiguousarray(np.atleast_2d(guess), dtype="f8")
+    nobj, npars = guess.shape
+    nshape = nloc - 1
+    nband = npars - nshape
+    if nband < 1 or npars > _lib.LM_NPMAX:
+        raise ValueError("guess must have %d + nband (1..%d) columns"
+                         % (nshape, _lib.LM_NPMAX - nshape))
+    if stamp_obj is None:
+        if ns != nobj:
+            raise ValueError("stamp_obj is needed when objects have several stamps")
+        sobj = np.arange(ns, dtype=np.int32)
+    else:
+        sobj = np.ascontiguousarray(stamp_obj, dtype=np.int32)
+        if sobj.shape != (ns,):
+            raise ValueError("stamp_obj must be (nstamps,) and non-decreasing")
+        if nobj == 1:
+            # (a one-object fit: the per-object interface's batches)
+            if sobj.any():
+                raise ValueError("stamp_obj out of range")
+        else:
+            if np.any(np.diff(sobj) < 0):
+                raise ValueError("stamp_obj must be (nstamps,) and non-decreasing")
+            if sobj.min() < 0 or sobj.max() >= nobj:
+                raise ValueError("stamp_obj out of range")
+    if stamp_band is None:
+        sband = np.zeros(ns, dtype=np.int32)
+    else:
+        sband = np.ascontiguousarray(stamp_band, dtype=np.int32)
+        if sband.shape != (ns,) or sband.min() < 0 or sband.max() >= nband:
+            raise ValueError("stamp_band out of range")
+    trivial_map = stamp_obj is None and stamp_band is None
+    npix_obj = np.asarray(npix_kept).astype(np.int64)
+    if trivial_map:
+        obj_start = np.arange(nobj + 1, dtype=np.int64)
+    else:
+        obj_start = np.array([0, ns], dtype=np.int64) if nobj == 1 else \
+            np.searchsorted(sobj, np.arange(nobj + 1)).astype(np.int64)
+    if ns < nobj or (nobj > 1 and np.any(np.diff(obj_start) == 0)) or ns == 0:
+        raise ValueError("every object needs at least one stamp")
+    if not trivial_map:
+        npix_obj = np.add.reduceat(npix_obj, obj_start[:-1])
+    return guess, sobj, sband, obj_start, trivial_map, npix_obj, nband
+
+
+def _psf_records(psf, ns):
+    """the psf argument of a fit -> (npsf, psf_host): gaussians per stamp, and
+    host gauss2d records (nstamps, npsf) as the array that rides in the upload
+    (Fitter.go's one-object batches); None for a GMixBatch and for no psf"""
+    if psf is None:
+        return 0, None
+    if isinstance(psf, np.ndarray):
+        psf_host = np.ascontiguousarray(psf, dtype=_lib.GAUSS2D_DTYPE).reshape(ns, -1)
+        return psf_host.shape[1], psf_host
+    assert psf.n == ns, "one psf mixture per stamp"
+    return psf.ngauss, None
+
+
+def _state_cols(d_states, name, n):
+    """the first n entries of the per-parameter array `name` of every state
+    record, as a float64 view (nobj, n) of the records on the device"""
+    a = _lib.LM_STATE_DTYPE.fields[name][1] // 8
+    return d_states.view(_torch().float64)[:, a:a + n]
+
+
+def _off(t, nbytes):
+    """the address nbytes into a device tensor (None for None)"""
+    return ctypes.c_void_p(t.data_ptr() + int(nbytes)) if t is not None else None
+
+
 class LMBatchFitter(object):
     """
     fitter = LMBatchFitter(model='exp')
@@ -272,6 +386,8 @@ class LMBatchFitter(object):
         if use_noise_image and model == "coellip":
             raise ValueError("use_noise_image is not available for coellip")
         self.use_noise_image = bool(use_noise_image)
+        self._event_pool = _EventPool()   # the timing events of time_kernels
+        self._side_streams = {}           # (device, which) -> torch stream
 
     def go(self, stamps, guess, psf=None, stamp_obj=None, stamp_band=None,
            check_every=1, noise=None):
@@ -324,6 +440,18 @@ class LMBatchFitter(object):
     # (_collect after the wait) -- a pipeline keeps up as long as enqueue +
     # package stays below the GPU's time per batch
     host_ms = None
+    # switches of the driver (tests, tools/, bench.py): the fit is the same to the bit
+    time_phases = False     # wall clock per phase into phase_ms (True: synced; "nosync")
+    time_kernels = False    # HIP events around every launch: kernel_ms, eval_launches
+    stats_pass = False      # True: statistics by a loglike pass, not by the loop's sums
+    precise_cov = True      # double-double covariance for fd fits of nloc >= 10
+    host_loop = False       # True: the host-driven loop where the blind one would serve
+    lazy_jacobian = True    # lmder without the jacobian in trials predicted to end a fit
+    advance_hint = True     # False: the generic one-thread form of lm_advance
+    keep_job = False        # True: the collected job stays in fitter.last_job
+    round_hook = None       # hook(job, round) after every round of the host-driven loop
+    nsplit = None           # pieces on separate streams (None: NGMIX_LM_NSPLIT, else 1)
+    _rounds_hint = None     # rounds the next fit queues blind (the last fit's + 1)
 
     def go_stream(self, batches, check_every=1):
         """
@@ -354,16 +482,11 @@ class LMBatchFitter(object):
         if prev is not None:
             yield self._apply_noise_cov(prev[0], self._collect(prev[0]), prev[1])
 
-    # ------------------------------------------------------------------
-    # the two halves of a fit: everything the device needs, queued; then the
-    # host's half
-    # ------------------------------------------------------------------
+    # the two halves of a fit: all the device needs, queued; then the host's half
 
     def _mark(self, job, name):
-        # fitter.time_phases = True: wall-clock per phase of this call, each
-        # phase closed by a device synchronisation (a diagnostic: it removes
-        # the overlap between phases); "nosync": host time only
-        import time
+        # time_phases: wall clock per phase of this call, each phase closed by a
+        # device synchronisation (which removes the overlap between phases)
         if job.phases is None:
             return
         if self.time_phases != "nosync":
@@ -375,17 +498,12 @@ class LMBatchFitter(object):
     def _enqueue(self, stamps, guess, psf, stamp_obj, stamp_band, check_every, streaming):
         """set a batch up and queue its whole fit on the current stream; returns
         the job _collect() turns into the result dict"""
-        import time
-        torch = _torch()
-        L = _lib.lib()
-        dev = stamps.device
         job = _Job()
-        job.dev = dev
+        job.dev = stamps.device
         # (the device context and the stream handle are looked up once per fit:
-        # each torch.cuda.device(...) / current_stream() costs ~10 us of host
-        # time, a tenth of a one-object fit when done per launch)
+        # ~10 us each, a tenth of a one-object fit when done per launch)
         t0 = time.perf_counter()
-        with _on_device(dev):
+        with _on_device(job.dev):
             job.stream = _stream()
             self._enqueue_on(job, stamps, guess, psf, stamp_obj, stamp_band,
                              check_every, streaming)
@@ -394,242 +512,193 @@ class LMBatchFitter(object):
 
     def _enqueue_on(self, job, stamps, guess, psf, stamp_obj, stamp_band, check_every,
                     streaming):
-        import time
+        """the stages of a fit's set-up, each leaving its fields on the job,
+        then the lock-step rounds and the results queued behind them"""
         torch = _torch()
-        L = _lib.lib()
-        dev = job.dev
-        job.phases = {} if getattr(self, "time_phases", False) else None
+        job.phases = {} if self.time_phases else None
         job.tmark = time.perf_counter()
         self.phase_ms = job.phases
-        guess = np.ascontiguousarray(np.atleast_2d(guess), dtype="f8")
-        nobj, npars = guess.shape
-        nshape = self.nloc - 1
-        nband = npars - nshape
-        if nband < 1 or npars > _lib.LM_NPMAX:
-            raise ValueError("guess must have %d + nband (1..%d) columns"
-                             % (nshape, _lib.LM_NPMAX - nshape))
-        ns = stamps.n
-        if stamp_obj is None:
-            if ns != nobj:
-                raise ValueError("stamp_obj is needed when objects have several stamps")
-            sobj = np.arange(ns, dtype=np.int32)
-        else:
-            sobj = np.ascontiguousarray(stamp_obj, dtype=np.int32)
-            if sobj.shape != (ns,):
-                raise ValueError("stamp_obj must be (nstamps,) and non-decreasing")
-            if nobj == 1:
-                # (a one-object fit: the per-object interface's batches)
-                if sobj.any():
-                    raise ValueError("stamp_obj out of range")
-            else:
-                if np.any(np.diff(sobj) < 0):
-                    raise ValueError("stamp_obj must be (nstamps,) and non-decreasing")
-                if sobj.min() < 0 or sobj.max() >= nobj:
-                    raise ValueError("stamp_obj out of range")
-        if stamp_band is None:
-            sband = np.zeros(ns, dtype=np.int32)
-        else:
-            sband = np.ascontiguousarray(stamp_band, dtype=np.int32)
-            if sband.shape != (ns,) or sband.min() < 0 or sband.max() >= nband:
-                raise ValueError("stamp_band out of range")
-        trivial_map = stamp_obj is None and stamp_band is None   # stamp i = object i
-        if trivial_map:
-            obj_start = np.arange(nobj + 1, dtype=np.int64)
-        elif nobj == 1:
-            obj_start = np.array([0, ns], dtype=np.int64)
-        else:
-            obj_start = np.searchsorted(sobj, np.arange(nobj + 1)).astype(np.int64)
-        if ns < nobj or (nobj > 1 and np.any(np.diff(obj_start) == 0)) or ns == 0:
-            raise ValueError("every object needs at least one stamp")
-        npsf = 0
-        psf_host = None
-        if psf is not None and isinstance(psf, np.ndarray):
-            # host gauss2d records (nstamps, npsf): uploaded with the batch's
-            # other small arrays (Fitter.go's one-object batches)
-            psf_host = np.ascontiguousarray(psf, dtype=_lib.GAUSS2D_DTYPE).reshape(ns, -1)
-            npsf = psf_host.shape[1]
-        elif psf is not None:
-            assert psf.n == ns, "one psf mixture per stamp"
-            npsf = psf.ngauss
-
-        fp = self.fit_pars
-        lo = hi = None
-        if self.prior is not None and getattr(self.prior, "bounds", None) is not None:
-            lo, hi = bounds_arrays(self.prior.bounds, npars)
+        job.stamps, job.ns = stamps, stamps.n
+        job.streaming, job.check_every = streaming, check_every
+        (guess, job.sobj, job.sband, job.obj_start, job.trivial_map, job.npix_obj,
+         job.nband) = _stamp_maps(stamps.n, stamps.npix_kept, guess, stamp_obj, stamp_band,
+                                  self.nloc)
+        job.nobj, job.npars = guess.shape
+        job.psf = psf
+        job.npsf, psf_host = _psf_records(psf, job.ns)
         # leastsq's convention: maxfev = 0 (or absent) means 100 (n + 1) function
         # calls with an analytic jacobian, 200 (n + 1) in forward-difference mode
-        maxfev = int(fp.get("maxfev", 0)) or (200 if self.fd else 100) * (npars + 1)
-        ev_init = self._timing_events(2)
-        nsplit = self._nsplit_wanted()
-        nsum = self.nloc * (self.nloc + 1) // 2 + self.nloc + 1
+        job.maxfev = int(self.fit_pars.get("maxfev", 0)) or \
+            (200 if self.fd else 100) * (job.npars + 1)
+        job.ev_init = self._timing_events(2)
+        nsplit = int(self.nsplit if self.nsplit is not None
+                     else (os.environ.get("NGMIX_LM_NSPLIT") or 1))   # (an A/B knob)
+        job.nsum = self.nloc * (self.nloc + 1) // 2 + self.nloc + 1
         # the loglike statistics of set_fit_result ride with the analytic
         # kernel's sums (lnprob = -fnorm^2 / 2 has no prior term to add)
-        loop_stats = not self.fd and self.prior is None and \
-            not getattr(self, "stats_pass", False) and \
+        job.loop_stats = not self.fd and self.prior is None and not self.stats_pass and \
             not os.environ.get("NGMIX_LM_JBASIS")
-        # (see SMALL_BATCH: every device buffer of the fit out of one allocation)
-        arena = None
-        if nobj <= SMALL_BATCH and ns <= 16 * SMALL_BATCH and nsplit <= 1 and \
-                not os.environ.get("NGMIX_LM_NO_ARENA"):
-            ntri = npars * (npars + 1) // 2
-            abuf, arena, arena_off = _carve(torch, dev, [
-                ("states", (nobj, _lib.LM_STATE_DTYPE.itemsize), torch.uint8),
-                ("sums", (ns, nsum), torch.float64),
-                ("status", (ns,), torch.int32),
-                ("sstats", (ns, 2), torch.float64),
-                # the three outputs, contiguous: one download
-                ("flat", (nobj * (2 * npars + _lib.LM_NCOLS),), torch.float64),
-                ("tri", (nobj, ntri), torch.float64),
-                ("rec", (nobj, 4 + 2 * npars + 2 * npars * npars), torch.float64)])
-            arena["out"] = abuf[arena_off["flat"][0]:
-                                arena_off["rec"][0] + arena_off["rec"][1]]
-            arena["out_off"] = {k: arena_off[k][0] - arena_off["flat"][0]
-                                for k in ("flat", "tri", "rec")}
-        d_states = arena["states"] if arena is not None else torch.empty(
-            (nobj, _lib.LM_STATE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if trivial_map:
-            npix_obj = stamps.npix_kept.astype(np.int64)
-        elif nobj == 1:
-            npix_obj = np.array([stamps.npix_kept.sum()], dtype=np.int64)
-        else:
-            npix_obj = np.add.reduceat(stamps.npix_kept.astype(np.int64), obj_start[:-1])
-        # ONE upload for the guess, the stamp -> object / band maps, the object
-        # offsets and the pixel counts (a host-to-device copy costs ~30 us
-        # whatever its size; a one-object fit made five): 8-byte aligned pieces
-        # of one buffer, viewed in their own types on the device
-        need_maps = not trivial_map
-        ns_pad = (ns + 1) // 2 * 2
-        pieces = [("guess", guess.view(np.uint8).reshape(-1)),
-                  ("npix", npix_obj.view(np.uint8).reshape(-1))]
-        if arena is not None and loop_stats:
-            pieces.append(("ostats", np.zeros(16 * nobj, dtype=np.uint8)))
-        if psf_host is not None:
-            pieces.append(("psf", psf_host.view(np.uint8).reshape(-1)))
-        if need_maps:
-            pad32 = lambda a: np.concatenate([a, np.zeros(ns_pad - ns, dtype=np.int32)])
-            pieces += [("start", obj_start.view(np.uint8).reshape(-1)),
-                       ("sobj", pad32(sobj).view(np.uint8).reshape(-1)),
-                       ("sband", pad32(sband).view(np.uint8).reshape(-1))]
-        # (through pinned memory, asynchronously: a copy from pageable memory
-        # makes torch synchronise the stream -- the host would wait there for
-        # everything queued before, i.e. for the previous batch of a pipeline,
-        # and the GPU would idle while the rest of this batch is being queued)
-        nbytes = sum(a.size for _, a in pieces)
-        h_all = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        np.concatenate([a for _, a in pieces], out=h_all.numpy())
-        d_all = h_all.to(dev, non_blocking=True)
-        view, at = {}, 0
-        for name, a in pieces:
-            view[name] = d_all[at:at + a.size]
-            at += a.size
-        d_guess = view["guess"].view(torch.float64).reshape(nobj, npars)
-        d_npix = view["npix"].view(torch.int64)
-        if psf_host is not None:
-            psf = GMixBatch(view["psf"].view(torch.float64).reshape(-1, 13), ns, npsf)
-        d_sobj = d_sband = d_start = None
-        if need_maps:
-            d_start = view["start"].view(torch.int64)
-            d_sobj = view["sobj"].view(torch.int32)[:ns]
-            d_sband = view["sband"].view(torch.int32)[:ns]
-        elif nsplit > 1:
-            # stamp i is object i in band 0: the kernels take NULL for the three
-            # maps (as pieces on several streams they need the absolute indices)
-            d_sobj = torch.arange(ns, dtype=torch.int32, device=dev)
-            d_sband = torch.zeros(ns, dtype=torch.int32, device=dev)
-            d_start = torch.arange(nobj + 1, dtype=torch.int64, device=dev)
-        if True:
-            self._record(ev_init, 0, job.stream)
-            _lib.check(L.ngmix_lm_init_batch(
-                _dptr(d_states), nobj, npars, _dptr(d_guess),
-                float(fp.get("ftol", 1.49012e-8)), float(fp.get("xtol", 1.49012e-8)),
-                float(fp.get("gtol", 0.0)), maxfev, float(fp.get("factor", 100.0)),
-                self._lm_mode(),
-                _lib.ptr(lo) if lo is not None else None,
-                _lib.ptr(hi) if hi is not None else None, job.stream),
-                "ngmix_lm_init_batch")
-            self._record(ev_init, 1, job.stream)
-        d_sstats = d_ostats = None
-        if arena is not None:
-            d_sums, d_status = arena["sums"], arena["status"]
-            if loop_stats:
-                d_sstats = arena["sstats"]
-                d_ostats = view["ostats"].view(torch.float64).reshape(nobj, 2)
-        else:
-            # (every row is written by the first round's launch)
-            d_sums = torch.empty((ns, nsum), dtype=torch.float64, device=dev)
-            d_status = torch.empty(ns, dtype=torch.int32, device=dev)
-            if loop_stats:
-                d_sstats = torch.empty((ns, 2), dtype=torch.float64, device=dev)
-                d_ostats = torch.zeros((nobj, 2), dtype=torch.float64, device=dev)
-        modnum = get_model_num(self.model)
-        if self.ngauss is not None:
-            modnum += 256 * self.ngauss   # the count rides with the model id
-            if nband != 1:
-                raise ValueError("coellip fits one band: guess needs %d columns" % self.nloc)
-        d_osums = None
-        prior_desc = None
-        if self.prior is not None and self.device_prior and hasattr(self.prior, "descriptor"):
-            prior_desc = self.prior.descriptor()
-            if prior_desc is not None and nshape != 5 + int(prior_desc["nmid"][0]):
-                raise ValueError("the prior is laid out for %d parameters before the fluxes, "
-                                 "model '%s' has %d" % (5 + int(prior_desc["nmid"][0]),
-                                                        self.model, nshape))
-            if prior_desc is not None and int(prior_desc["nband"][0]) != nband:
-                raise ValueError("the prior has %d flux terms, the guess %d bands"
-                                 % (int(prior_desc["nband"][0]), nband))
-        if prior_desc is not None:
-            d_osums = torch.zeros((nobj, npars * (npars + 1) // 2 + npars + 1),
-                                  dtype=torch.float64, device=dev)
-        self.prior_path = ("kernel" if prior_desc is not None else
-                           "torch" if self.prior is not None else None)
+        self._alloc_buffers(job, nsplit)
+        self._upload(job, guess, psf_host, nsplit)
+        self._lm_init(job)
+        if job.loop_stats and job.arena is None:
+            job.d_ostats = torch.zeros((job.nobj, 2), dtype=torch.float64, device=job.dev)
+        self._prior_record(job)
         # Forward-difference fits of ten and more local parameters (co-elliptical
         # psf fits with 3+ gaussians: cond(J) ~ 1e8 at the solution) take their
         # covariance from a double-double factorisation of the last jacobian's
-        # normal equations (ngmix_lm_precise_cov_batch): the pixel passes leave
-        # the point of every jacobian in d_jacpt.  fitter.precise_cov = False
-        # (NGMIX_LM_NO_PRECISE_COV): the factor the iteration left, as before
-        d_jacpt = None
-        if self.fd and self.nloc >= _lib.LM_PRECISE_MIN_NLOC and \
-                getattr(self, "precise_cov", True) and \
+        # normal equations (ngmix_lm_precise_cov_batch), at the point in d_jacpt
+        job.d_jacpt = None
+        if self.fd and self.nloc >= _lib.LM_PRECISE_MIN_NLOC and self.precise_cov and \
                 not os.environ.get("NGMIX_LM_NO_PRECISE_COV") and self.prior is None:
-            d_jacpt = torch.zeros((nobj, 3, _lib.LM_NPMAX), dtype=torch.float64, device=dev)
-        if self.prior is not None and prior_desc is None:
-            nsplit = 1
-        nsplit = max(1, min(int(nsplit), nobj))
-
-        job.__dict__.update(
-            stamps=stamps, psf=psf, nobj=nobj, npars=npars, nband=nband, ns=ns, npsf=npsf,
-            sobj=sobj, sband=sband, obj_start=obj_start, trivial_map=trivial_map,
-            maxfev=maxfev, d_states=d_states, d_guess=d_guess, d_sobj=d_sobj,
-            d_sband=d_sband, d_start=d_start, d_sums=d_sums, d_status=d_status,
-            d_sstats=d_sstats, d_ostats=d_ostats, d_osums=d_osums, modnum=modnum,
-            prior_desc=prior_desc, loop_stats=loop_stats, nsplit=nsplit, nsum=nsum,
-            d_jacpt=d_jacpt,
-            streaming=streaming, check_every=check_every, ev_init=ev_init,
-            npix_obj=npix_obj, d_npix=d_npix, d_all=d_all, h_all=h_all, arena=arena,
-            batch=stamps._batch(1), chunks=[], useful_rounds=None, ev_post=None,
-            legacy_ev=None, loop_ms_host=0.0)
-        # the host-free loop serves one piece with no prior or the kernel prior;
-        # a torch-evaluated prior sits between the two launches of a round and
-        # pieces on several streams are interleaved by the host: the host-driven
-        # loop (NGMIX_LM_HOST_LOOP selects it for A/B)
-        job.host_loop = (nsplit > 1 or (self.prior is not None and prior_desc is None)
+            job.d_jacpt = torch.zeros((job.nobj, 3, _lib.LM_NPMAX), dtype=torch.float64,
+                                      device=job.dev)
+        torch_prior = self.prior is not None and job.prior_desc is None
+        job.nsplit = 1 if torch_prior else max(1, min(int(nsplit), job.nobj))
+        # the host-free loop serves one piece with no prior or the kernel prior; a
+        # torch-evaluated prior sits between the two launches of a round, pieces on
+        # several streams are interleaved by the host: the host-driven loop
+        job.host_loop = (job.nsplit > 1 or torch_prior
                          or bool(os.environ.get("NGMIX_LM_HOST_LOOP"))
-                         or bool(getattr(self, "host_loop", False)))
+                         or bool(self.host_loop))
+        job.batch = stamps._batch(1)
         self._mark(job, "setup")
         if job.host_loop:
             self._rounds_host_loop(job)
             self._queue_results(job)
-            return job
-        # ---- the whole fit, queued blind: R rounds sized by the last batch's
-        # count, then finalize / pack / downloads.  _collect() finds out
-        # whether R was enough (the rare miss: more rounds, results re-made).
-        hint = getattr(self, "_rounds_hint", None)
+            return
+        # the whole fit, queued blind: rounds sized by the last batch's count, then
+        # the results; _collect() finds out whether they were enough (the rare miss)
+        hint = self._rounds_hint
         first = 4 if hint is None else max(1, min(int(hint), ROUNDS_HINT_CAP))
         self._queue_rounds(job, first)
         self._mark(job, "loop")
         self._queue_results(job)
-        return job
+
+    def _alloc_buffers(self, job, nsplit):
+        """the buffer stage.  Reads nobj, ns, npars, nsum, loop_stats; leaves
+        d_states, d_sums, d_status, d_sstats, d_flat, d_tri, d_rec: for a small
+        batch (SMALL_BATCH) views of one allocation, job.arena holding the bytes of
+        the outputs and their offsets; else separate tensors, arena None and the
+        outputs (out_shapes) left to _finalize_and_pack.  d_ostats comes later."""
+        torch = _torch()
+        dev, nobj, ns, npars = job.dev, job.nobj, job.ns, job.npars
+        shapes = [
+            ("states", (nobj, _lib.LM_STATE_DTYPE.itemsize), torch.uint8),
+            ("sums", (ns, job.nsum), torch.float64),
+            ("status", (ns,), torch.int32),
+            ("sstats", (ns, 2), torch.float64),
+            # the three outputs, contiguous: one download
+            ("flat", (nobj * (2 * npars + _lib.LM_NCOLS),), torch.float64),
+            ("tri", (nobj, npars * (npars + 1) // 2), torch.float64),
+            ("rec", (nobj, 4 + 2 * npars + 2 * npars * npars), torch.float64)]
+        job.arena = job.d_ostats = job.d_flat = job.d_tri = job.d_rec = None
+        job.out_shapes = [shape for _, shape, _ in shapes[4:]]
+        if nobj <= SMALL_BATCH and ns <= 16 * SMALL_BATCH and nsplit <= 1 and \
+                not os.environ.get("NGMIX_LM_NO_ARENA"):
+            abuf, v, off = _carve(torch, dev, shapes)
+            job.arena = {"out": abuf[off["flat"][0]:off["rec"][0] + off["rec"][1]],
+                         "out_off": {k: off[k][0] - off["flat"][0]
+                                     for k in ("flat", "tri", "rec")}}
+            job.d_flat, job.d_tri, job.d_rec = v["flat"], v["tri"], v["rec"]
+        else:
+            # (every row is written by the first round's launch)
+            v = {name: torch.empty(shape, dtype=dt, device=dev)
+                 for name, shape, dt in (shapes[:4] if job.loop_stats else shapes[:3])}
+        job.d_states, job.d_sums, job.d_status = v["states"], v["sums"], v["status"]
+        job.d_sstats = v["sstats"] if job.loop_stats else None
+
+    def _upload(self, job, guess, psf_host, nsplit):
+        """the upload stage: ONE host-to-device copy (~30 us whatever its size)
+        of the guess, the pixel counts, the arena form's zeroed d_ostats, host psf
+        records and, unless stamp i is object i, the maps.  Leaves h_all, d_all and
+        its views d_guess, d_npix, d_ostats, psf, d_sobj, d_sband, d_start."""
+        torch = _torch()
+        nobj, ns = job.nobj, job.ns
+        # 8-byte aligned pieces of one buffer, viewed in their own types
+        u8 = lambda a: a.view(np.uint8).reshape(-1)
+        pieces = [("guess", u8(guess)), ("npix", u8(job.npix_obj))]
+        if job.arena is not None and job.loop_stats:
+            pieces.append(("ostats", np.zeros(16 * nobj, dtype=np.uint8)))
+        if psf_host is not None:
+            pieces.append(("psf", u8(psf_host)))
+        if not job.trivial_map:
+            pad = np.zeros((ns + 1) // 2 * 2 - ns, dtype=np.int32)
+            pieces += [("start", u8(job.obj_start)),
+                       ("sobj", u8(np.concatenate([job.sobj, pad]))),
+                       ("sband", u8(np.concatenate([job.sband, pad])))]
+        # (through pinned memory: a copy from pageable memory makes torch
+        # synchronise the stream, i.e. wait for the previous batch of a pipeline)
+        nbytes = sum(a.size for _, a in pieces)
+        job.h_all = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        np.concatenate([a for _, a in pieces], out=job.h_all.numpy())
+        job.d_all = job.h_all.to(job.dev, non_blocking=True)
+        view, at = {}, 0
+        for name, a in pieces:
+            view[name] = job.d_all[at:at + a.size]
+            at += a.size
+        job.d_guess = view["guess"].view(torch.float64).reshape(nobj, job.npars)
+        job.d_npix = view["npix"].view(torch.int64)
+        if "ostats" in view:
+            job.d_ostats = view["ostats"].view(torch.float64).reshape(nobj, 2)
+        if psf_host is not None:
+            job.psf = GMixBatch(view["psf"].view(torch.float64).reshape(-1, 13), ns, job.npsf)
+        job.d_sobj = job.d_sband = job.d_start = None
+        if not job.trivial_map:
+            job.d_start = view["start"].view(torch.int64)
+            job.d_sobj = view["sobj"].view(torch.int32)[:ns]
+            job.d_sband = view["sband"].view(torch.int32)[:ns]
+        elif nsplit > 1:
+            # stamp i is object i in band 0: the kernels take NULL for the three
+            # maps (as pieces on several streams they need the absolute indices)
+            job.d_sobj = torch.arange(ns, dtype=torch.int32, device=job.dev)
+            job.d_sband = torch.zeros(ns, dtype=torch.int32, device=job.dev)
+            job.d_start = torch.arange(nobj + 1, dtype=torch.int64, device=job.dev)
+
+    def _lm_init(self, job):
+        """the state records at the guess (ngmix_lm_init_batch), with the
+        prior's bounds.  Reads d_states, d_guess, maxfev, ev_init; leaves modnum."""
+        fp, lo, hi = self.fit_pars, None, None
+        if self.prior is not None and getattr(self.prior, "bounds", None) is not None:
+            lo, hi = bounds_arrays(self.prior.bounds, job.npars)
+        _record(job.ev_init, 0, job.stream)
+        _lib.check(_lib.lib().ngmix_lm_init_batch(
+            _dptr(job.d_states), job.nobj, job.npars, _dptr(job.d_guess),
+            float(fp.get("ftol", 1.49012e-8)), float(fp.get("xtol", 1.49012e-8)),
+            float(fp.get("gtol", 0.0)), job.maxfev, float(fp.get("factor", 100.0)),
+            self._lm_mode(),
+            _lib.ptr(lo) if lo is not None else None,
+            _lib.ptr(hi) if hi is not None else None, job.stream),
+            "ngmix_lm_init_batch")
+        _record(job.ev_init, 1, job.stream)
+        job.modnum = get_model_num(self.model)
+        if self.ngauss is not None:
+            job.modnum += 256 * self.ngauss   # the count rides with the model id
+            if job.nband != 1:
+                raise ValueError("coellip fits one band: guess needs %d columns" % self.nloc)
+
+    def _prior_record(self, job):
+        """the prior stage: the record ngmix_lm_prior_sums_batch evaluates,
+        checked against the fit's layout.  Reads npars, nband; leaves prior_desc,
+        d_osums (None for a torch-evaluated prior or none), fitter.prior_path."""
+        nshape = self.nloc - 1
+        desc = None
+        if self.prior is not None and self.device_prior and hasattr(self.prior, "descriptor"):
+            desc = self.prior.descriptor()
+            if desc is not None and nshape != 5 + int(desc["nmid"][0]):
+                raise ValueError("the prior is laid out for %d parameters before the fluxes, "
+                                 "model '%s' has %d" % (5 + int(desc["nmid"][0]),
+                                                        self.model, nshape))
+            if desc is not None and int(desc["nband"][0]) != job.nband:
+                raise ValueError("the prior has %d flux terms, the guess %d bands"
+                                 % (int(desc["nband"][0]), job.nband))
+        job.prior_desc, job.d_osums = desc, None
+        if desc is not None:
+            n = job.npars
+            job.d_osums = _torch().zeros((job.nobj, n * (n + 1) // 2 + n + 1),
+                                         dtype=_torch().float64, device=job.dev)
+        self.prior_path = ("kernel" if desc is not None else
+                           "torch" if self.prior is not None else None)
 
     @staticmethod
     def _job_stream(job):
@@ -643,19 +712,20 @@ class LMBatchFitter(object):
 
     def _lm_mode(self):
         """ngmix_lm_state.mode of this fitter's fits: lmdif, or lmder with the
-        jacobian left out of the trials that are predicted to end the fit
-        (fitter.lazy_jacobian = False or NGMIX_LM_EAGER_JAC: the jacobian with
-        every evaluation; the iterates are the same to the bit either way)"""
+        jacobian left out of the trials predicted to end the fit (lazy_jacobian
+        off: with every evaluation; the same iterates to the bit either way)"""
         if self.fd:
             return _lib.LM_MODE_FD
-        lazy = getattr(self, "lazy_jacobian", True) and \
+        lazy = self.lazy_jacobian and \
             not os.environ.get("NGMIX_LM_EAGER_JAC") and \
             not os.environ.get("NGMIX_LM_JBASIS")
         return _lib.LM_MODE_ANALYTIC_LAZY if lazy else _lib.LM_MODE_ANALYTIC
 
     def _problem(self, job):
-        """the ngmix_lm_problem record of a job (kept alive with it)"""
-        P = _lib.LMProblem()
+        """the ngmix_lm_problem record of a job, made once and kept alive with it"""
+        if job.problem is not None:
+            return job.problem
+        P = job.problem = _lib.LMProblem()
         P.batch = ctypes.pointer(job.batch)
         P.states = job.d_states.data_ptr()
         P.nobj = job.nobj
@@ -682,63 +752,46 @@ class LMBatchFitter(object):
     def _nloc_npars(self, npars):
         """the nloc argument of ngmix_lm_advance_batch carrying the fits'
         parameter count (nloc + 256 npars), which selects the step's kernel: the
-        register form for 6-8 parameters, the team form for 9-14;
-        fitter.advance_hint = False asks for the generic one-thread form
-        (NGMIX_LM_NPARS_GENERIC: what the tests compare the other two with,
-        record by record)"""
-        hint = npars if getattr(self, "advance_hint", True) else _lib.LM_NPARS_GENERIC
+        register form for 6-8 parameters, the team form for 9-14, the generic
+        one-thread form (what the tests compare the two with) without the hint"""
+        hint = npars if self.advance_hint else _lib.LM_NPARS_GENERIC
         return self.nloc + 256 * hint
 
     def _timing_events(self, n):
-        """n hipEvent_t handles when fitter.time_kernels is set (bench.py), else
-        None; released with the fitter"""
-        if not getattr(self, "time_kernels", False):
-            return None
-        pool = self.__dict__.setdefault("_event_pool", _EventPool())
-        return pool.take(n)
-
-    def _record(self, events, i, stream=None):
-        if events is not None:
-            _lib.check(_lib.lib().ngmix_event_record(events[i], stream or _stream()),
-                       "ngmix_event_record")
+        """n hipEvent_t handles of the fitter's pool under time_kernels, else None"""
+        return self._event_pool.take(n) if self.time_kernels else None
 
     def _queue_rounds(self, job, nrounds):
         """nrounds lock-step rounds by one call into the library
         (ngmix_lm_rounds_batch): no host between the launches"""
         torch = _torch()
-        L = _lib.lib()
-        if not hasattr(job, "problem"):
-            job.problem = self._problem(job)
         d_counts = torch.empty(nrounds, dtype=torch.int32, device=job.dev)
         h_counts = torch.empty(nrounds, dtype=torch.int32, pin_memory=True)
         ev = self._timing_events(3 * nrounds)
         span = _HipEvents(2)
         # (the caller holds the device context; the copy of the counts is
         # queued by the library on the same stream)
-        span.record(0, job.stream)
-        _lib.check(L.ngmix_lm_rounds_batch(
-            ctypes.byref(job.problem), nrounds, _dptr(d_counts),
+        _record(span.handles, 0, job.stream)
+        _lib.check(_lib.lib().ngmix_lm_rounds_batch(
+            ctypes.byref(self._problem(job)), nrounds, _dptr(d_counts),
             ctypes.c_void_p(h_counts.data_ptr()), ev, job.stream),
             "ngmix_lm_rounds_batch")
-        span.record(1, job.stream)
-        job.chunks.append((nrounds, d_counts, h_counts, ev, span))
+        _record(span.handles, 1, job.stream)
+        job.chunks.append(_Chunk(nrounds, d_counts, h_counts, ev, span))
 
     def _rounds_done(self, job):
         """after the last queued chunk has run: the count of fits still running"""
-        return int(job.chunks[-1][2][-1])
+        return int(job.chunks[-1].h_counts[-1])
 
     def _collect(self, job):
         """the host's half: wait for the downloads, make sure the rounds queued
         blind were enough (else run more and re-make the results), package"""
-        import time
-        torch = _torch()
         t0 = time.perf_counter()
         job.copied.synchronize()
         t1 = time.perf_counter()
         if not job.host_loop:
-            grow = 2
-            total = sum(c[0] for c in job.chunks)
-            redo = False
+            torch, grow, redo = _torch(), 2, False
+            total = sum(c.nrounds for c in job.chunks)
             while self._rounds_done(job) != 0:
                 if total > 2 * job.maxfev + 5:
                     raise RuntimeError("batched LM did not terminate")
@@ -748,7 +801,7 @@ class LMBatchFitter(object):
                 # chunk records there: the counts read next are this chunk's)
                 with torch.cuda.device(job.dev), torch.cuda.stream(self._job_stream(job)):
                     self._queue_rounds(job, grow)
-                _lib.check(_lib.lib().ngmix_event_synchronize(job.chunks[-1][4].handles[1]),
+                _lib.check(_lib.lib().ngmix_event_synchronize(job.chunks[-1].span.handles[1]),
                            "ngmix_event_synchronize")
                 total += grow
                 grow = min(2 * grow, ROUNDS_HINT_CAP)
@@ -757,14 +810,14 @@ class LMBatchFitter(object):
                     self._queue_results(job)
                 job.copied.synchronize()
             # counts after each round -> the rounds that had fits to advance
-            counts = np.concatenate([c[2].numpy() for c in job.chunks])
+            counts = np.concatenate([c.h_counts.numpy() for c in job.chunks])
             before = np.concatenate([[job.nobj], counts[:-1]])
             job.useful_rounds = int((before > 0).sum())
             self.rounds_launched = int(counts.size)
             self._rounds_hint = job.useful_rounds + 1
             # the device time of the rounds (events around every chunk)
-            self.loop_seconds = sum(c[4].elapsed_ms(0, 1) for c in job.chunks) * 1e-3
-            if job.chunks[0][3] is not None:
+            self.loop_seconds = sum(_elapsed_ms(*c.span.handles) for c in job.chunks) * 1e-3
+            if job.chunks[0].events is not None:
                 self._kernel_times(job, before)
         else:
             self.loop_seconds = job.loop_ms_host * 1e-3
@@ -774,7 +827,7 @@ class LMBatchFitter(object):
         self.rounds = job.useful_rounds
         self.nsplit_used = job.nsplit
         self._d_states = job.d_states
-        if getattr(self, "keep_job", False):
+        if self.keep_job:
             self.last_job = job   # (tests: the device buffers of the batch)
         # (fitter.gmix belongs to the batch whose result is being returned)
         self._fit_ctx = job.fit_ctx
@@ -788,26 +841,13 @@ class LMBatchFitter(object):
 
     def _kernel_times(self, job, before):
         """HIP-event times of every launch of the rounds (time_kernels)"""
-        L = _lib.lib()
-        ms = ctypes.c_float()
-
-        def elapsed(a, b):
-            _lib.check(L.ngmix_event_elapsed_ms(a, b, ctypes.byref(ms)), "elapsed")
-            return float(ms.value)
-        ev_ms, adv_ms = [], []
-        for nr, _, _, ev, _ in job.chunks:
-            for r in range(nr):
-                ev_ms.append(elapsed(ev[3 * r], ev[3 * r + 1]))
-                adv_ms.append(elapsed(ev[3 * r + 1], ev[3 * r + 2]))
-        nstamp_obj = job.ns / float(job.nobj)
-        w = before.astype("f8") * nstamp_obj
+        elapsed = lambda a, b: _elapsed_ms(a, b, "elapsed")
+        rounds = [(c.events, 3 * r) for c in job.chunks for r in range(c.nrounds)]
+        ev_ms = [elapsed(e[i], e[i + 1]) for e, i in rounds]
+        adv_ms = [elapsed(e[i + 1], e[i + 2]) for e, i in rounds]
+        w = before.astype("f8") * (job.ns / float(job.nobj))
         # (the launches that found every fit finished are left out of the mean)
-        live = before > 0
-        self.eval_ms = float(np.mean(np.asarray(ev_ms)[live]))
-        self.eval_ms_total = float(np.sum(ev_ms))
-        self.eval_stamps_total = float(np.sum(w))
-        self.eval_launches = [(float(t), float(x)) for t, x in zip(ev_ms, w)]
-        self.eval_launch_count = int(live.sum())
+        self._eval_times(ev_ms, w, before > 0)
         self.advance_ms_total = float(np.sum(adv_ms))
         self.kernel_ms = {
             "lm_eval": float(np.sum(ev_ms)), "lm_advance": float(np.sum(adv_ms)),
@@ -815,345 +855,311 @@ class LMBatchFitter(object):
             "lm_finalize": elapsed(job.ev_post[0], job.ev_post[1]),
             "lm_pack": elapsed(job.ev_post[1], job.ev_post[2]),
         }
-        pool = self.__dict__.get("_event_pool")
-        if pool is not None:
-            pool.give(job.ev_init)
-            pool.give(job.ev_post)
-            for c in job.chunks:
-                pool.give(c[3])
+        self._event_pool.give(job.ev_init)
+        self._event_pool.give(job.ev_post)
+        for c in job.chunks:
+            self._event_pool.give(c.events)
 
     def _kernel_times_host_loop(self, job):
         ev = job.legacy_ev
-        # per-launch mean, and the whole fit: stamps evaluated / time spent
-        # (a launch whose count was never read -- check_every > 1 -- keeps
-        # the last count known before it)
+        # (a launch whose count was never read -- check_every > 1 -- keeps the
+        # last count known before it)
         last = 0.0
         for rec_ in ev:
             if rec_[2] is None:
                 rec_[2] = last
             last = rec_[2]
-        ms = [a.elapsed_time(b) for a, b, _ in ev]
-        self.eval_ms = float(np.mean(ms))
+        self._eval_times([a.elapsed_time(b) for a, b, _ in ev], [w for _, _, w in ev],
+                         np.ones(len(ev), dtype=bool))
+
+    def _eval_times(self, ms, w, live):
+        """per-launch mean over the live launches, and the whole fit: stamps
+        evaluated / time spent"""
+        self.eval_ms = float(np.mean(np.asarray(ms)[live]))
         self.eval_ms_total = float(np.sum(ms))
-        self.eval_stamps_total = float(np.sum([w for _, _, w in ev]))
-        self.eval_launches = [(float(t), float(w)) for t, (_, _, w) in zip(ms, ev)]
-        self.eval_launch_count = len(ms)
+        self.eval_stamps_total = float(np.sum(w))
+        self.eval_launches = [(float(t), float(x)) for t, x in zip(ms, w)]
+        self.eval_launch_count = int(live.sum())
+
+    def _pieces(self, job):
+        """the batch cut into job.nsplit runs of whole objects, each with its own
+        ngmix_batch record, counter and side stream (no gain measured: DESIGN 3.7)"""
+        torch = _torch()
+        b, nobj, nsplit = job.batch, job.nobj, job.nsplit
+        pieces = []
+        for k in range(nsplit):
+            p = _Piece()
+            p.o_lo, p.o_hi = nobj * k // nsplit, nobj * (k + 1) // nsplit
+            p.s_lo, p.s_hi = int(job.obj_start[p.o_lo]), int(job.obj_start[p.o_hi])
+            p.batch = _lib.Batch()
+            ctypes.memmove(ctypes.byref(p.batch), ctypes.byref(b), ctypes.sizeof(p.batch))
+            p.batch.nstamps = p.s_hi - p.s_lo
+            p.batch.stamps = b.stamps + p.s_lo * _lib.STAMP_DTYPE.itemsize
+            p.batch.jac = b.jac + p.s_lo * _lib.JACOBIAN_DTYPE.itemsize
+            p.stream = self._side_stream(job.dev, 1 + k) if nsplit > 1 else None
+            p.nact = torch.zeros(1, dtype=torch.int32, device=job.dev)
+            p.live, p.active = True, p.o_hi - p.o_lo
+            p.ring = [torch.zeros(1, dtype=torch.int32, pin_memory=True) for _ in range(3)]
+            p.pend, p.launched, p.ev_idx = [], 0, []
+            pieces.append(p)
+        return pieces
 
     def _rounds_host_loop(self, job):
         """the lock-step loop driven from the host, one round at a time (a prior
         evaluated by torch ops between the two launches of a round; pieces of
-        the batch on several streams, fitter.nsplit).  One round is kept in
-        flight ahead of the count being read."""
-        import time
+        the batch on several streams, fitter.nsplit)"""
         torch = _torch()
-        L = _lib.lib()
         dev = job.dev
-        nobj, npars, ns, npsf = job.nobj, job.npars, job.ns, job.npsf
-        psf, obj_start = job.psf, job.obj_start
-        d_states, d_sums, d_status = job.d_states, job.d_sums, job.d_status
-        d_sobj, d_sband, d_start = job.d_sobj, job.d_sband, job.d_start
-        d_sstats, d_ostats, d_osums = job.d_sstats, job.d_ostats, job.d_osums
-        prior_desc, loop_stats, nsum = job.prior_desc, job.loop_stats, job.nsum
-        modnum, maxfev, check_every = job.modnum, job.maxfev, job.check_every
-        b = job.batch
-        # float64 view of the state records: the columns a prior needs
-        fields = _lib.LM_STATE_DTYPE.fields
-        sview = d_states.view(torch.float64)
-
-        def col(name):
-            a = fields[name][1] // 8
-            return sview[:, a:a + npars]
-        # Pieces of the batch on separate streams (fitter.nsplit = k, or the
-        # NGMIX_LM_NSPLIT environment knob): one piece's lm_advance -- one thread
-        # per fit, latency bound -- runs under another piece's pixel pass.
-        # Measured on 100k fits: 6.65 against 6.70 ms for the loop once lm_advance
-        # runs from registers (DESIGN 3.7), so the default is one piece.
-        nsplit = job.nsplit
-        isz = _lib.LM_STATE_DTYPE.itemsize
-        wosum = npars * (npars + 1) // 2 + npars + 1
-
-        def off(t, nbytes):
-            return ctypes.c_void_p(t.data_ptr() + int(nbytes)) if t is not None else None
-        subs = []
-        for k in range(nsplit):
-            o_lo, o_hi = nobj * k // nsplit, nobj * (k + 1) // nsplit
-            s_lo, s_hi = int(obj_start[o_lo]), int(obj_start[o_hi])
-            bk = _lib.Batch()
-            ctypes.memmove(ctypes.byref(bk), ctypes.byref(b), ctypes.sizeof(bk))
-            bk.nstamps = s_hi - s_lo
-            bk.stamps = b.stamps + s_lo * _lib.STAMP_DTYPE.itemsize
-            bk.jac = b.jac + s_lo * _lib.JACOBIAN_DTYPE.itemsize
-            subs.append({
-                "o": (o_lo, o_hi), "s": (s_lo, s_hi), "batch": bk,
-                "stream": self._side_stream(dev, 1 + k) if nsplit > 1 else None,
-                "nact": torch.zeros(1, dtype=torch.int32, device=dev),
-                "live": True, "active": o_hi - o_lo,
-                "ring": [torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                         for _ in range(3)],
-                "pend": [], "launched": 0, "ev_idx": [],
-            })
+        pieces = self._pieces(job)
         rounds = 0
         if not job.streaming:
             torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         # time_kernels: HIP events around every pixel-pass launch (bench.py),
         # with the number of stamps each launch still had to evaluate
-        ev = [] if getattr(self, "time_kernels", False) else None
-        nstamp_obj = ns / float(nobj)
-
-        def enqueue(sub):
-            (o_lo, o_hi), (s_lo, s_hi) = sub["o"], sub["s"]
-            if ev is not None:
-                # (the stamps this launch still has to evaluate are known when
-                # the previous round's counter is read: filled in then)
-                ev.append([torch.cuda.Event(enable_timing=True),
-                           torch.cuda.Event(enable_timing=True),
-                           sub["active"] * nstamp_obj if not sub["launched"] else None])
-                sub["ev_idx"].append(len(ev) - 1)
-                ev[-1][0].record()
-            _lib.check(L.ngmix_lm_eval_batch(
-                ctypes.byref(sub["batch"]), modnum, int(self.fd), _dptr(d_states),
-                off(d_sobj, 4 * s_lo), off(d_sband, 4 * s_lo),
-                off(psf.data, 104 * npsf * s_lo) if psf is not None else None,
-                npsf, off(d_sums, 8 * nsum * s_lo), off(d_status, 4 * s_lo),
-                off(d_sstats, 16 * s_lo), _stream()),
-                "ngmix_lm_eval_batch")
-            if ev is not None:
-                ev[-1][1].record()
-            if prior_desc is not None:
-                # the prior rows at the same trial points (results.py:454)
-                _lib.check(L.ngmix_lm_prior_sums_batch(
-                    off(d_states, isz * o_lo), o_hi - o_lo, _lib.ptr(prior_desc),
-                    STEP_PRIOR, off(d_osums, 8 * wosum * o_lo), _stream()),
-                    "ngmix_lm_prior_sums_batch")
-            elif self.prior is not None:
-                osums_box[0] = prior_normal_sums(
-                    self.prior, col("xt"), col("xstep"), col("hstep"))[0] if self.fd \
-                    else prior_normal_sums(self.prior, col("xt"))[0]
-            osums = d_osums if prior_desc is not None else osums_box[0]
-            # obj_start holds absolute stamp indices: sums / stamp_band stay whole
-            _lib.check(L.ngmix_lm_advance_batch(
-                off(d_states, isz * o_lo), o_hi - o_lo, off(d_start, 8 * o_lo),
-                _dptr(d_sband), _dptr(d_sums), self._nloc_npars(npars),
-                off(osums, 8 * wosum * o_lo) if osums is not None else None,
-                _dptr(sub["nact"]), _dptr(d_sstats) if loop_stats else None,
-                off(d_ostats, 16 * o_lo), _stream()),
-                "ngmix_lm_advance_batch")
-            # the count of fits still running, on its way to the host behind
-            # the round that made it
-            hook = getattr(self, "round_hook", None)
-            if hook is not None:
-                # (tests: the state records after every round of the host loop)
-                hook(job, sub["launched"])
-            h = sub["ring"][sub["launched"] % len(sub["ring"])]
-            h.copy_(sub["nact"], non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            sub["pend"].append((done, h))
-            sub["launched"] += 1
-
-        osums_box = [None]
+        ev = job.legacy_ev = [] if self.time_kernels else None
+        nstamp_obj = job.ns / float(job.nobj)
         with torch.cuda.device(dev):
             main = torch.cuda.current_stream(dev)
-            if nsplit > 1:
+            if job.nsplit > 1:
                 start = torch.cuda.Event()
                 start.record(main)
-                for sub in subs:
-                    sub["stream"].wait_event(start)
-            # One round is kept in flight AHEAD of the counter being read: the
-            # host reads round r's count of running fits (a 4-byte pinned copy
-            # behind that round) while round r + 1 already runs, so the GPU
-            # never waits for the host between rounds.  When the count is zero
-            # the round in flight finds every fit finished and both its kernels
-            # return at once (~30 us, once per call).
-            depth = 1 if check_every == 1 else 0
-            while any(sub["live"] for sub in subs):
-                for sub in subs:
-                    if not sub["live"]:
+                for p in pieces:
+                    p.stream.wait_event(start)
+            # One round is kept in flight AHEAD of the count being read (a 4-byte
+            # pinned copy behind each round): the GPU never waits for the host, and
+            # the last round finds every fit finished and returns at once (~30 us)
+            depth = 1 if job.check_every == 1 else 0
+            while any(p.live for p in pieces):
+                for p in pieces:
+                    if not p.live:
                         continue
-                    with torch.cuda.stream(sub["stream"] or main):
-                        if len(sub["pend"]) > depth and (
-                                sub["launched"] % check_every == 0 or
-                                sub["launched"] > 2 * maxfev):
-                            while len(sub["pend"]) > depth:
-                                done, h = sub["pend"].pop(0)
+                    with torch.cuda.stream(p.stream or main):
+                        if len(p.pend) > depth and (
+                                p.launched % job.check_every == 0 or
+                                p.launched > 2 * job.maxfev):
+                            while len(p.pend) > depth:
+                                done, h = p.pend.pop(0)
                             done.synchronize()
-                            sub["active"] = int(h[0])
+                            p.active = int(h[0])
                             # (that count is what the launch after it evaluates)
-                            k = sub["launched"] - len(sub["pend"])
-                            if ev is not None and k < len(sub["ev_idx"]):
-                                ev[sub["ev_idx"][k]][2] = sub["active"] * nstamp_obj
-                            if sub["active"] == 0:
-                                sub["live"] = False
+                            k = p.launched - len(p.pend)
+                            if ev is not None and k < len(p.ev_idx):
+                                ev[p.ev_idx[k]][2] = p.active * nstamp_obj
+                            if p.active == 0:
+                                p.live = False
                                 continue
-                        enqueue(sub)
+                        self._enqueue_round(job, p)
                 rounds += 1
-                if rounds > 2 * maxfev + 5:
+                if rounds > 2 * job.maxfev + 5:
                     raise RuntimeError("batched LM did not terminate")
             # rounds that had fits to advance (not the one in flight at the end)
-            rounds = max(sub["launched"] - len(sub["pend"]) for sub in subs)
-            if nsplit > 1:
-                for sub in subs:
-                    main.wait_stream(sub["stream"])
+            rounds = max(p.launched - len(p.pend) for p in pieces)
+            if job.nsplit > 1:
+                for p in pieces:
+                    main.wait_stream(p.stream)
         if not job.streaming:
             torch.cuda.synchronize(dev)
         # seconds in the lock-step loop (kernels + one 4-byte readback per round)
         job.loop_ms_host = (time.perf_counter() - t0) * 1e3
         job.useful_rounds = rounds
-        job.legacy_ev = ev
         self._mark(job, "loop")
+
+    def _enqueue_round(self, job, p):
+        """one round of piece p on the current stream: pixel pass, prior rows,
+        step, and the count of running fits on its way to the host behind them"""
+        torch = _torch()
+        L = _lib.lib()
+        n, psf, ev = job.npars, job.psf, job.legacy_ev
+        d_states = job.d_states
+        isz = _lib.LM_STATE_DTYPE.itemsize
+        wosum = n * (n + 1) // 2 + n + 1
+        if ev is not None:
+            # (the stamps this launch still has to evaluate are known when
+            # the previous round's counter is read: filled in then)
+            ev.append([torch.cuda.Event(enable_timing=True),
+                       torch.cuda.Event(enable_timing=True),
+                       p.active * (job.ns / float(job.nobj)) if not p.launched else None])
+            p.ev_idx.append(len(ev) - 1)
+            ev[-1][0].record()
+        _lib.check(L.ngmix_lm_eval_batch(
+            ctypes.byref(p.batch), job.modnum, int(self.fd), _dptr(d_states),
+            _off(job.d_sobj, 4 * p.s_lo), _off(job.d_sband, 4 * p.s_lo),
+            _off(psf.data, 104 * job.npsf * p.s_lo) if psf is not None else None,
+            job.npsf, _off(job.d_sums, 8 * job.nsum * p.s_lo), _off(job.d_status, 4 * p.s_lo),
+            _off(job.d_sstats, 16 * p.s_lo), _stream()),
+            "ngmix_lm_eval_batch")
+        if ev is not None:
+            ev[-1][1].record()
+        osums = None
+        if job.prior_desc is not None:
+            # the prior rows at the same trial points (results.py:454)
+            _lib.check(L.ngmix_lm_prior_sums_batch(
+                _off(d_states, isz * p.o_lo), p.o_hi - p.o_lo, _lib.ptr(job.prior_desc),
+                STEP_PRIOR, _off(job.d_osums, 8 * wosum * p.o_lo), _stream()),
+                "ngmix_lm_prior_sums_batch")
+            osums = job.d_osums
+        elif self.prior is not None:
+            steps = [_state_cols(d_states, c, n) for c in ("xstep", "hstep")] if self.fd else []
+            osums = prior_normal_sums(self.prior, _state_cols(d_states, "xt", n), *steps)[0]
+        # obj_start holds absolute stamp indices: sums / stamp_band stay whole
+        _lib.check(L.ngmix_lm_advance_batch(
+            _off(d_states, isz * p.o_lo), p.o_hi - p.o_lo, _off(job.d_start, 8 * p.o_lo),
+            _dptr(job.d_sband), _dptr(job.d_sums), self._nloc_npars(n),
+            _off(osums, 8 * wosum * p.o_lo), _dptr(p.nact),
+            _dptr(job.d_sstats) if job.loop_stats else None,
+            _off(job.d_ostats, 16 * p.o_lo), _stream()),
+            "ngmix_lm_advance_batch")
+        if self.round_hook is not None:
+            # (tests: the state records after every round of the host loop)
+            self.round_hook(job, p.launched)
+        # the count of fits still running follows the round that made it
+        h = p.ring[p.launched % len(p.ring)]
+        h.copy_(p.nact, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        p.pend.append((done, h))
+        p.launched += 1
 
     def _queue_results(self, job):
         """run_leastsq's packaging, one thread per fit (ngmix_lm_finalize_batch),
-        the statistics / packing kernel and the downloads, all queued"""
+        the statistics / packing kernel and the downloads, all queued.  Leaves
+        h_flat, h_tri, h_cov0 (pinned) and the events copied, cov_copied."""
+        d_ffx = self._prior_ffx(job) if self.prior is not None else None
+        ev_post = self._finalize_and_pack(job, d_ffx)
+        side = self._side_stream(job.dev)   # (made with a fitter's first fit of any size)
+        job.h_flat, job.h_tri, job.h_cov0, job.copied, job.cov_copied = \
+            self._download_arena(job) if job.arena is not None else self._download_side(job, side)
+        self._event_pool.give(job.ev_post)   # (results re-made after a miss)
+        job.ev_post = ev_post
+        self._mark(job, "enqueue_copy")
+
+    def _prior_ffx(self, job):
+        """the part of |f|^2 at the solutions that chi2/dof leaves out, per object
+        (leaves d_prior_lnp when the kernel prior ran): the prior rows
+        (leastsqbound.py:97) and, the reference reserving more slots than
+        PriorSimpleSep fills (results.py:1050-1078, 454-461), the first pixels"""
+        torch = _torch()
+        nobj, dev = job.nobj, job.dev
+        x = _state_cols(job.d_states, "x", job.npars)
+        if job.prior_desc is not None:
+            # one launch at the fits' points (the record the prior kernel
+            # evaluated during the rounds)
+            d_ffx = torch.empty(nobj, dtype=torch.float64, device=dev)
+            job.d_prior_lnp = torch.empty(nobj, dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib().ngmix_lm_prior_finish_batch(
+                _dptr(job.d_states), nobj, _lib.ptr(job.prior_desc), _dptr(d_ffx),
+                _dptr(job.d_prior_lnp), job.stream), "ngmix_lm_prior_finish_batch")
+            nrows = 4 + int(job.prior_desc["nmid"][0]) + int(job.prior_desc["nband"][0])
+        else:
+            rows, bad = self.prior.fill_fdiff_batch(x)
+            d_ffx = torch.where(bad, torch.zeros_like(rows[:, 0]), (rows * rows).sum(dim=1))
+            d_ffx = torch.where(torch.isfinite(d_ffx), d_ffx, torch.zeros_like(d_ffx))
+            nrows = rows.shape[1]
+        nskip = get_lm_n_prior_pars(self.model, job.nband) - nrows
+        if nskip > 0:
+            d_ffx = d_ffx + self._first_pixels_fdiff2(
+                job.stamps, job.psf, x, job.obj_start, job.sband, nskip)
+        return d_ffx.contiguous()
+
+    def _finalize_and_pack(self, job, d_ffx):
+        """the precise covariance where it applies, ngmix_lm_finalize_batch, the
+        statistics where the loop did not carry them, ngmix_lm_pack_batch.
+        Leaves d_cov0, fit_ctx (d_psums); returns the timing events."""
         torch = _torch()
         L = _lib.lib()
-        dev = job.dev
-        stamps, psf = job.stamps, job.psf
-        nobj, n = job.nobj, job.npars
-        obj_start, sband, sobj = job.obj_start, job.sband, job.sobj
-        d_states = job.d_states
-        fields = _lib.LM_STATE_DTYPE.fields
-        sview = d_states.view(torch.float64)
-
-        def col(name):
-            a = fields[name][1] // 8
-            return sview[:, a:a + n]
-        d_npix = job.d_npix
-        width = 4 + 2 * n + 2 * n * n
-        arena = job.arena
-        d_rec = arena["rec"] if arena is not None else \
-            torch.empty((nobj, width), dtype=torch.float64, device=dev)
-        d_ffx = None
-        if self.prior is not None:
-            # chi2/dof is over fdiff[n_prior_pars:] (leastsqbound.py:97): the
-            # prior rows are left out -- and, the reference reserving more
-            # slots than PriorSimpleSep fills (results.py:1050-1078 against
-            # joint_prior.py:86-120) while the pixel rows start right after the
-            # filled ones (results.py:454-461), so are the first pixels
-            job.d_prior_lnp = None
-            if job.prior_desc is not None:
-                # one launch at the fits' points (the record the prior kernel
-                # evaluated during the rounds)
-                d_ffx = torch.empty(nobj, dtype=torch.float64, device=dev)
-                job.d_prior_lnp = torch.empty(nobj, dtype=torch.float64, device=dev)
-                _lib.check(L.ngmix_lm_prior_finish_batch(
-                    _dptr(d_states), nobj, _lib.ptr(job.prior_desc), _dptr(d_ffx),
-                    _dptr(job.d_prior_lnp), job.stream), "ngmix_lm_prior_finish_batch")
-                nrows = 4 + int(job.prior_desc["nmid"][0]) + int(job.prior_desc["nband"][0])
-            else:
-                rows, bad = self.prior.fill_fdiff_batch(col("x"))
-                d_ffx = torch.where(bad, torch.zeros_like(rows[:, 0]),
-                                    (rows * rows).sum(dim=1))
-                d_ffx = torch.where(torch.isfinite(d_ffx), d_ffx, torch.zeros_like(d_ffx))
-                nrows = rows.shape[1]
-            nskip = get_lm_n_prior_pars(self.model, job.nband) - nrows
-            if nskip > 0:
-                d_ffx = d_ffx + self._first_pixels_fdiff2(
-                    stamps, psf, col("x"), obj_start, sband, nskip)
-            d_ffx = d_ffx.contiguous()
+        dev, nobj, n = job.dev, job.nobj, job.npars
+        d_states, d_npix = job.d_states, job.d_npix
+        if job.arena is None:
+            # (here, not in _alloc_buffers: a miss re-makes the results into fresh
+            # buffers while the side stream may still be reading the first ones)
+            job.d_flat, job.d_tri, job.d_rec = (
+                torch.empty(shape, dtype=torch.float64, device=dev) for shape in job.out_shapes)
+        d_rec, d_flat = job.d_rec, job.d_flat
         ev_post = self._timing_events(3)
         if job.d_jacpt is not None and not job.host_loop:
             # R / ipvt of the fits that ended, re-made from double-double normal
             # equations at the point of their last jacobian
-            if not hasattr(job, "problem"):
-                job.problem = self._problem(job)
             job.d_psums = torch.empty((job.ns, 2, job.nsum), dtype=torch.float64, device=dev)
             _lib.check(L.ngmix_lm_precise_cov_batch(
-                ctypes.byref(job.problem), _dptr(job.d_psums), job.stream),
+                ctypes.byref(self._problem(job)), _dptr(job.d_psums), job.stream),
                 "ngmix_lm_precise_cov_batch")
-        if True:
-            self._record(ev_post, 0, job.stream)
-            _lib.check(L.ngmix_lm_finalize_batch(
-                _dptr(d_states), nobj, _dptr(d_npix),
-                _dptr(d_ffx) if d_ffx is not None else None, float(PDEF), float(CDEF),
-                _dptr(d_rec), job.stream), "ngmix_lm_finalize_batch")
-            self._record(ev_post, 1, job.stream)
+        _record(ev_post, 0, job.stream)
+        _lib.check(L.ngmix_lm_finalize_batch(
+            _dptr(d_states), nobj, _dptr(d_npix), _dptr(d_ffx), float(PDEF), float(CDEF),
+            _dptr(d_rec), job.stream), "ngmix_lm_finalize_batch")
+        _record(ev_post, 1, job.stream)
         self._mark(job, "finalize")
-        # Two downloads through pinned memory on a side stream (PyTorch's
-        # caching host allocator: no hipHostMalloc after the first call):
-        #   * the head -- pars, pars_err, flags / nfev / ier / dof / njev and
-        #     the seven statistics columns, 2 n + 12 doubles per fit -- which
-        #     go() waits for;
-        #   * the upper triangle of pars_cov (n (n + 1) / 2 per fit: the matrix
-        #     is symmetric to the bit), which keeps flowing after go() has
-        #     returned and is waited for -- and mirrored -- when pars_cov is
-        #     first read (LMBatchResult lazy key; so are the blocks cut from it).
-        # pars_cov0 stays on the device until it is asked for.
-        c0, c1 = 4 + 2 * n, 4 + 2 * n + n * n
-        job.d_cov0 = d_rec[:, c0:c1]
-        ntri = n * (n + 1) // 2
-        d_tri = arena["tri"] if arena is not None else \
-            torch.empty((nobj, ntri), dtype=torch.float64, device=dev)
-        side = self._side_stream(dev)
+        # pars_cov0 stays on the device until it is asked for
+        job.d_cov0 = d_rec[:, 4 + 2 * n:4 + 2 * n + n * n]
         d_ok = d_rec[:, 0] == 0.0
-        job.fit_ctx = self._fit_ctx = (stamps, psf, sobj, sband, d_rec, d_ok, n)
+        job.fit_ctx = self._fit_ctx = (job.stamps, job.psf, job.sobj, job.sband, d_rec, d_ok, n)
         self._gmix = None
         tot = None
         if not job.loop_stats:
             tot = self._loglike_at_solutions(
-                stamps, psf, sobj, sband, obj_start,
-                prior_lnp=getattr(job, "d_prior_lnp", None)).contiguous()
+                job.stamps, job.psf, job.sobj, job.sband, job.obj_start,
+                prior_lnp=job.d_prior_lnp).contiguous()
         # pars | pars_err rows, then twelve contiguous columns (integers and
         # statistics): one kernel, one download, contiguous host views
-        ncols = _lib.LM_NCOLS
-        d_flat = arena["flat"] if arena is not None else \
-            torch.empty(nobj * (2 * n + ncols), dtype=torch.float64, device=dev)
-        if True:
-            _lib.check(L.ngmix_lm_pack_batch(
-                _dptr(d_states), nobj, n, _dptr(d_rec),
-                _dptr(job.d_ostats) if job.loop_stats else None,
-                _dptr(tot), _dptr(d_npix), _dptr(d_flat),
-                ctypes.c_void_p(d_flat.data_ptr() + 8 * nobj * 2 * n), _dptr(d_tri),
-                job.stream),
-                "ngmix_lm_pack_batch")
-            self._record(ev_post, 2, job.stream)
+        _lib.check(L.ngmix_lm_pack_batch(
+            _dptr(d_states), nobj, n, _dptr(d_rec),
+            _dptr(job.d_ostats) if job.loop_stats else None,
+            _dptr(tot), _dptr(d_npix), _dptr(d_flat),
+            ctypes.c_void_p(d_flat.data_ptr() + 8 * nobj * 2 * n), _dptr(job.d_tri),
+            job.stream),
+            "ngmix_lm_pack_batch")
+        _record(ev_post, 2, job.stream)
         self._mark(job, "pack")
-        if arena is not None:
-            # one download of the three outputs, on the fit's own stream (a
-            # side stream buys nothing when the host waits for all of it)
-            d_out = arena["out"]
-            h_out = torch.empty(d_out.shape, dtype=torch.uint8, pin_memory=True)
-            h_out.copy_(d_out, non_blocking=True)
-            copied = cov_copied = torch.cuda.Event()
-            copied.record()
-            oo = arena["out_off"]
+        return ev_post
 
-            def hview(name, like):
-                nb = like.numel() * 8
-                return h_out[oo[name]:oo[name] + nb].view(torch.float64).reshape(like.shape)
-            h_flat, h_tri = hview("flat", d_flat), hview("tri", d_tri)
-            h_cov0 = hview("rec", d_rec)[:, c0:c1]
-        else:
-            h_flat = torch.empty(d_flat.shape, dtype=torch.float64, pin_memory=True)
-            h_tri = torch.empty((nobj, ntri), dtype=torch.float64, pin_memory=True)
-            self._mark(job, "pinned_alloc")
-            ready = torch.cuda.Event()
-            ready.record()
-            with torch.cuda.stream(side):
-                side.wait_event(ready)
-                h_flat.copy_(d_flat, non_blocking=True)
-                copied = torch.cuda.Event()
-                copied.record()
-                h_tri.copy_(d_tri, non_blocking=True)
-                h_cov0 = None
-                if nobj <= 4096:
-                    # (a small batch: pars_cov0 rides along instead of costing its
-                    # first reader a synchronous download of its own)
-                    h_cov0 = torch.empty((nobj, n * n), dtype=torch.float64,
-                                         pin_memory=True)
-                    h_cov0.copy_(job.d_cov0, non_blocking=True)
-                cov_copied = torch.cuda.Event()
-                cov_copied.record()
-            d_flat.record_stream(side)
-            d_tri.record_stream(side)
-        pool = self.__dict__.get("_event_pool")
-        if pool is not None and job.ev_post is not None:
-            pool.give(job.ev_post)   # (results re-made after a miss)
-        job.ev_post = ev_post
-        job.h_flat, job.h_tri, job.h_cov0 = h_flat, h_tri, h_cov0
-        job.copied, job.cov_copied = copied, cov_copied
-        self._mark(job, "enqueue_copy")
+    def _download_arena(self, job):
+        """one download of the arena's three outputs on the fit's own stream (the
+        host waits for all of it); h_flat, h_tri, h_cov0, copied, cov_copied"""
+        torch = _torch()
+        n = job.npars
+        d_out, oo = job.arena["out"], job.arena["out_off"]
+        h_out = torch.empty(d_out.shape, dtype=torch.uint8, pin_memory=True)
+        h_out.copy_(d_out, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+
+        def hview(name, like):
+            nb = like.numel() * 8
+            return h_out[oo[name]:oo[name] + nb].view(torch.float64).reshape(like.shape)
+        h_cov0 = hview("rec", job.d_rec)[:, 4 + 2 * n:4 + 2 * n + n * n]
+        return hview("flat", job.d_flat), hview("tri", job.d_tri), h_cov0, copied, copied
+
+    def _download_side(self, job, side):
+        """two downloads through pinned memory on the side stream: the head (pars,
+        pars_err, twelve columns), which go() waits for (copied), and the triangle
+        of pars_cov, waited for -- and mirrored -- when pars_cov is first read
+        (cov_copied); returns h_flat, h_tri, h_cov0, copied, cov_copied"""
+        torch = _torch()
+        nobj, n = job.nobj, job.npars
+        d_flat, d_tri = job.d_flat, job.d_tri
+        h_flat = torch.empty(d_flat.shape, dtype=torch.float64, pin_memory=True)
+        h_tri = torch.empty(d_tri.shape, dtype=torch.float64, pin_memory=True)
+        self._mark(job, "pinned_alloc")
+        ready = torch.cuda.Event()
+        ready.record()
+        with torch.cuda.stream(side):
+            side.wait_event(ready)
+            h_flat.copy_(d_flat, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record()
+            h_tri.copy_(d_tri, non_blocking=True)
+            h_cov0 = None
+            if nobj <= 4096:
+                # (a small batch: pars_cov0 rides along instead of costing its
+                # first reader a synchronous download of its own)
+                h_cov0 = torch.empty((nobj, n * n), dtype=torch.float64, pin_memory=True)
+                h_cov0.copy_(job.d_cov0, non_blocking=True)
+            cov_copied = torch.cuda.Event()
+            cov_copied.record()
+        d_flat.record_stream(side)
+        d_tri.record_stream(side)
+        return h_flat, h_tri, h_cov0, copied, cov_copied
 
     def _package(self, job):
         """the result dict over the downloaded block (views, no copies)"""
@@ -1204,15 +1210,9 @@ class LMBatchFitter(object):
             self._fitted_mixtures()
         return self._gmix
 
-    def _nsplit_wanted(self):
-        nsplit = getattr(self, "nsplit", None)
-        if nsplit is None and os.environ.get("NGMIX_LM_NSPLIT"):
-            nsplit = int(os.environ["NGMIX_LM_NSPLIT"])   # A/B knob
-        return 1 if nsplit is None else int(nsplit)
-
     def _side_stream(self, dev, which=0):
         torch = _torch()
-        cache = self.__dict__.setdefault("_side_streams", {})
+        cache = self._side_streams
         key = (dev.type, dev.index, which)
         if key not in cache:
             cache[key] = torch.cuda.Stream(device=dev)

@@ -1139,3 +1139,169 @@ def test_c3_shaped_batch_against_the_reference_fit_by_fit(golden):
         for k in ("lnprob", "chi2per", "s2n"):
             np.testing.assert_allclose(res[k], g[k], rtol=1e-5)
         assert np.array_equal(res["dof"], g["dof"]) and np.array_equal(res["npix"], g["npix"])
+
+
+def _ragged_objects(n, rng, model="exp", nrow=17, ncol=19, epochs=1):
+    """n objects with `epochs` stamps each (the same truth, other noise) on
+    17 x 19 stamps, ragged against the 8 x 8 tiles: images, weights, jacobian
+    record, psf parameters and truth per stamp, guess per object"""
+    scale, noise = 0.263, 0.01
+    pars = np.zeros((n, 6))
+    pars[:, 0:2] = rng.uniform(-0.5, 0.5, size=(n, 2)) * scale
+    pars[:, 2:4] = rng.normal(scale=0.1, size=(n, 2))
+    pars[:, 4] = rng.uniform(0.2, 0.5, size=n)
+    pars[:, 5] = rng.uniform(50.0, 200.0, size=n)
+    guess = pars * rng.uniform(0.9, 1.1, size=pars.shape)
+    guess[:, 0:2] = pars[:, 0:2] + rng.uniform(-0.05, 0.05, size=(n, 2))
+    guess[:, 2:4] = pars[:, 2:4] + rng.uniform(-0.03, 0.03, size=(n, 2))
+    pars = np.repeat(pars, epochs, axis=0)
+    n *= epochs
+    psf_pars = np.tile([0.0, 0.0, 0.0, 0.0, 0.27, 1.0], (n, 1))
+    jac = np.array([(nrow - 1) / 2.0, (ncol - 1) / 2.0, scale, 0.0, 0.0, scale,
+                    scale ** 2, scale])
+    gm0, _ = GMixBatch.from_pars(pars, model)
+    psf, _ = GMixBatch.from_pars(psf_pars, "gauss")
+    gm, _ = gm0.convolve(psf)
+    truth, _ = StampBatch.from_images(np.zeros((n, nrow, ncol)), None, jac).render(gm)
+    images = truth.cpu().numpy().reshape(n, nrow, ncol) + \
+        noise * rng.normal(size=(n, nrow, ncol))
+    weights = np.full((n, nrow, ncol), 1.0 / noise ** 2)
+    return images, weights, jac, psf_pars, pars, guess
+
+
+def _all_keys_equal(a, b):
+    """every key of two results, pars_cov and pars_cov0 included, to the bit"""
+    assert set(a.keys()) == set(b.keys())
+    for key in a.keys():
+        if key != "model":
+            assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=True), key
+
+
+def _test_prior():
+    from ngmix_amd import prior_batch as pb
+    return pb.PriorSimpleSepBatch(pb.GaussianCen(0.0, 0.0, 0.3, 0.3), pb.GPriorBA(0.3),
+                                  pb.TwoSidedErf(-1.0, 0.1, 1.0e3, 1.0),
+                                  [pb.TwoSidedErf(-1.0e3, 1.0, 1.0e5, 10.0)])
+
+
+def test_one_past_the_small_batch_equals_batches_of_64_and_1():
+    """nobj = SMALL_BATCH + 1 takes the separate buffers and the side-stream
+    downloads, 64 objects and one object the single allocation and the single
+    download: the same kernels on the same stamps, so every object's result is
+    the same to the bit whichever batch it was fitted in"""
+    from ngmix_amd.lm_batch import SMALL_BATCH
+    n = SMALL_BATCH + 1
+    images, weights, jac, psf_pars, pars, guess = _ragged_objects(n, np.random.RandomState(91))
+
+    def fit(lo, hi):
+        sb = StampBatch.from_images(images[lo:hi], weights[lo:hi], jac)
+        psf, _ = GMixBatch.from_pars(psf_pars[lo:hi], "gauss")
+        return LMBatchFitter("exp").go(sb, guess[lo:hi], psf=psf)
+    whole, head, tail = fit(0, n), fit(0, SMALL_BATCH), fit(SMALL_BATCH, n)
+    assert np.all(whole["flags"] == 0)
+    assert set(whole.keys()) == set(head.keys()) == set(tail.keys())
+    for key in whole.keys():
+        if key != "model":
+            parts = np.concatenate([np.asarray(head[key]), np.asarray(tail[key])])
+            assert np.array_equal(np.asarray(whole[key]), parts, equal_nan=True), key
+
+
+def test_blind_rounds_too_few_with_the_kernel_prior():
+    """the miss path of _collect() with a prior evaluated in the kernel: one
+    round queued blind (_rounds_hint = 1), so more rounds follow and
+    _queue_results runs again, the prior's finish launch included, against an
+    ample hint that needs neither: every key to the bit"""
+    images, weights, jac, psf_pars, pars, guess = _ragged_objects(20, np.random.RandomState(92))
+    sb = StampBatch.from_images(images, weights, jac)
+    psf, _ = GMixBatch.from_pars(psf_pars, "gauss")
+    ample, short = LMBatchFitter("exp", prior=_test_prior()), \
+        LMBatchFitter("exp", prior=_test_prior())
+    ample._rounds_hint = 64
+    short._rounds_hint = 1
+    a = ample.go(sb, guess, psf=psf)
+    b = short.go(sb, guess, psf=psf)
+    assert ample.prior_path == short.prior_path == "kernel"
+    assert 2 < ample.rounds < 64 and ample.rounds_launched == 64
+    assert short.rounds == ample.rounds and short.rounds_launched > short.rounds
+    assert np.all(a["flags"] == 0)
+    _all_keys_equal(a, b)
+
+
+def test_torch_prior_twice_through_go():
+    """a prior evaluated by torch ops between the launches of a round
+    (device_prior=False: the host-driven loop): the second go() of the same
+    fitter, with the first one's streams and hints, returns the same fit"""
+    images, weights, jac, psf_pars, pars, guess = _ragged_objects(12, np.random.RandomState(93))
+    sb = StampBatch.from_images(images, weights, jac)
+    psf, _ = GMixBatch.from_pars(psf_pars, "gauss")
+    f = LMBatchFitter("exp", prior=_test_prior(), device_prior=False)
+    a = f.go(sb, guess, psf=psf)
+    a.materialize()
+    b = f.go(sb, guess, psf=psf)
+    assert f.prior_path == "torch"
+    assert np.all(a["flags"] == 0)
+    _all_keys_equal(a, b)
+
+
+def test_arena_equals_separate_buffers_two_bands_two_epochs(monkeypatch):
+    """5 objects x 2 bands x 2 epochs on 17 x 19 stamps, with the maps in the
+    upload: the single allocation and single download against
+    NGMIX_LM_NO_ARENA's separate buffers and side-stream downloads"""
+    nobj = 5
+    images, weights, jac, psf_pars, pars, g1 = _ragged_objects(
+        nobj, np.random.RandomState(94), epochs=4)
+    sb = StampBatch.from_images(images, weights, jac)
+    psf, _ = GMixBatch.from_pars(psf_pars, "gauss")
+    sobj = np.repeat(np.arange(nobj), 4).astype(np.int32)
+    sband = np.tile([0, 0, 1, 1], nobj).astype(np.int32)
+    guess = np.concatenate([g1, 1.05 * g1[:, 5:6]], axis=1)
+
+    def run():
+        f = LMBatchFitter("exp")
+        f.keep_job = True
+        return f.go(sb, guess, psf=psf, stamp_obj=sobj, stamp_band=sband).materialize(), \
+            f.last_job.arena is not None
+    a, arena_a = run()
+    monkeypatch.setenv("NGMIX_LM_NO_ARENA", "1")
+    b, arena_b = run()
+    assert arena_a and not arena_b
+    assert np.all(a["flags"] == 0)
+    _all_keys_equal(a, b)
+
+
+def test_go_stream_equals_go_with_noise_images_over_batches_of_three_sizes():
+    """go_stream over batches of 7, 65 and 3 objects (the single allocation,
+    separate buffers, and the allocation again, each queued with the hint the
+    batch before it left) with use_noise_image on, against go() batch by batch
+    on a fitter of its own: every key to the bit"""
+    rng = np.random.RandomState(95)
+    items = []
+    for n in (7, 65, 3):
+        images, weights, jac, psf_pars, pars, guess = _ragged_objects(n, rng)
+        psf, _ = GMixBatch.from_pars(psf_pars, "gauss")
+        noise = list(0.01 * rng.normal(size=images.shape))
+        items.append((StampBatch.from_images(images, weights, jac), guess,
+                      {"psf": psf, "noise": noise}))
+    one = LMBatchFitter("exp", use_noise_image=True)
+    ref = [one.go(sb, g, **kw) for sb, g, kw in items]
+    got = list(LMBatchFitter("exp", use_noise_image=True).go_stream(items))
+    assert len(got) == 3
+    for a, b in zip(ref, got):
+        assert np.all(a["flags"] == 0)
+        _all_keys_equal(a, b)
+
+
+def test_host_loop_in_two_uneven_pieces_equals_one_piece():
+    """the host-driven loop on 5 objects as pieces of 2 and 3 on two streams
+    (separate buffers, explicit maps) against one piece (the single allocation,
+    no maps): every key to the bit"""
+    images, weights, jac, psf_pars, pars, guess = _ragged_objects(5, np.random.RandomState(96))
+    sb = StampBatch.from_images(images, weights, jac)
+    psf, _ = GMixBatch.from_pars(psf_pars, "gauss")
+    whole, pieces = LMBatchFitter("exp"), LMBatchFitter("exp")
+    whole.host_loop, whole.nsplit, pieces.nsplit = True, 1, 2
+    a = whole.go(sb, guess, psf=psf).materialize()
+    b = pieces.go(sb, guess, psf=psf)
+    assert whole.nsplit_used == 1 and pieces.nsplit_used == 2
+    assert np.all(a["flags"] == 0)
+    _all_keys_equal(a, b)

@@ -467,3 +467,46 @@ def test_a_band_the_fit_has_no_flux_for_ends_that_fit_alone(hint):
     others = np.arange(nobj) != 3
     for k in ("flags", "nfev", "ier", "pars", "pars_err"):
         np.testing.assert_array_equal(bad[k][others], clean[k][others], err_msg=k)
+
+
+def test_coellip3_small_batch_equals_a_batch_of_65():
+    """co-elliptical fits with 3 gaussians (10 parameters: the team step and the
+    double-double covariance of ngmix_lm_precise_cov_batch) on 17 x 19 stamps:
+    five objects (three fits that end with flags == 0, two that run out of
+    evaluations) out of the small batch's single allocation against the same
+    five among 65 objects in separate buffers -- every key to the bit"""
+    from ngmix_amd.lm_batch import SMALL_BATCH
+    rng = np.random.RandomState(17)
+    nrow, ncol, n, few, ngauss = 17, 19, SMALL_BATCH + 1, 5, 3
+    jac = ngmix.Jacobian(row=8.0, col=9.0, dvdrow=0.263, dvdcol=0.0, dudrow=0.0, dudcol=0.263)
+    gm = ngmix.GMixModel([0.0, 0.0, 0.02, -0.01, 0.3, 1.0], "turb")
+    im0 = gm.make_image((nrow, ncol), jacobian=jac)
+    images = im0[None] + 2.0e-4 * rng.normal(size=(n, nrow, ncol))
+    weights = np.full((n, nrow, ncol), 1.0 / 2.0e-4 ** 2)
+    T = 0.3 * np.array([0.3, 0.7, 1.5])
+    F = np.array([0.3, 0.45, 0.25])
+    g0 = np.concatenate([[0.0, 0.0, 0.02, -0.01], T, F / F.sum()])
+    guess = g0[None] * rng.uniform(0.9, 1.1, size=(n, g0.size))
+    guess[:, :2] = rng.uniform(-0.01, 0.01, size=(n, 2))
+    pars = {"maxfev": 120, "ftol": 1e-5, "xtol": 1e-5}
+
+    def fit(idx):
+        f = LMBatchFitter("coellip", ngauss=ngauss, fit_pars=pars)
+        f.keep_job = True
+        res = f.go(StampBatch.from_images(images[idx], weights[idx], jac), guess[idx])
+        assert f.last_job.d_jacpt is not None and f.last_job.d_psums is not None
+        assert (f.last_job.arena is not None) == (len(idx) <= SMALL_BATCH)
+        return res
+    _lib.launch_census(reset=True)
+    large = fit(np.arange(n))
+    assert _census_has(_lib.launch_census(reset=True), "lm_advance_team_kernel<")
+    ended, not_ended = np.flatnonzero(large["flags"] == 0), np.flatnonzero(large["flags"] != 0)
+    assert ended.size >= 3 and not_ended.size >= 2
+    idx = np.sort(np.concatenate([ended[:3], not_ended[:2]]))
+    assert idx.size == few
+    small = fit(idx)
+    assert set(small.keys()) == set(large.keys())
+    for k in small.keys():
+        if k != "model":
+            assert np.array_equal(np.asarray(small[k]), np.asarray(large[k])[idx],
+                                  equal_nan=True), k
