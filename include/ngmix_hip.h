@@ -560,6 +560,43 @@ int ngmix_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobi
                        const double *resid, int nrow, int ncol, const int32_t *boxes,
                        const int32_t *items, const int32_t *items_host, int64_t nitems,
                        double *out_mat, double *out_vec, void *stream);
+/* one frame of ngmix_scene_normal_frames: its residual and weight frames
+   (device pointers, nrow x ncol; weight NULL: w = 1) and its band */
+typedef struct {
+    const double *resid;
+    const double *weight;
+    int32_t nrow, ncol;
+    int32_t band;
+    int32_t pad_;
+} ngmix_scene_frame;
+/* the normal equations of a LIST of frames (csrc/scene_normal_frames.hip):
+   ngmix_scene_normal's blocks summed over nframes frames (bands, epochs), each
+   with its own residual, weight and shape.  An object has K = nshape + nband
+   parameters (1 <= K <= 16): its shape parameters, then one flux per band.  In
+   one frame only Kloc = nshape + 1 of them have a non-zero jacobian column
+   (1 <= Kloc <= 8, Kloc <= K): local column j < nshape is global column j, local
+   column nshape is global column nshape + band of that frame.  The
+   per-(frame, object) arrays are indexed f * n + o: gmix (ngauss records each,
+   norms as ngmix_scene_boxes of THAT frame leaves them), jac, boxes (8 each)
+   and tangents ((f * n + o) * ngauss + g, 6, Kloc).  frames: the device table
+   of nframes descriptors.  items as ngmix_scene_normal's; one wave each walks
+   the frames in ascending index: per frame the item's rectangle (box_a, or
+   box_a n box_b, clamped to the frame; an empty one adds nothing) gives that
+   frame's block from an accumulator that starts at zero, which is added to
+   the item's K x K result with plain adds.  out_mat[i] (K x K): F of a self
+   item, symmetric to the bit, or C of a pair item; out_vec[i] (K): g, or
+   zeros.  No atomics; the bits of an item depend on that item and the frame
+   list alone.  frames_host, items_host: NULL, or the caller's host copies,
+   checked before the launch (a frame with nrow * ncol <= 0, a band outside
+   [0, K - nshape) or no residual, and a bad item are refused; the kernel
+   itself skips such a frame and gives such an item zeros). */
+int ngmix_scene_normal_frames(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac,
+                              int64_t n, const double *tangents, int Kloc, int K,
+                              const ngmix_scene_frame *frames,
+                              const ngmix_scene_frame *frames_host, int64_t nframes,
+                              const int32_t *boxes, const int32_t *items,
+                              const int32_t *items_host, int64_t nitems, double *out_mat,
+                              double *out_vec, void *stream);
 /* the block-sparse operator of those blocks (csrc/scene_solve.hip): F_self
    (n, K, K) and F_cross (npairs, K, K) as ngmix_scene_normal wrote them,
    1 <= K <= 8.  Object a's row list is row_ent[2 * e ..] = neighbour, code for e

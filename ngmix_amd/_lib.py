@@ -142,6 +142,13 @@ SIMPLE_SEP_PRIOR_DTYPE = np.dtype([
 ], align=True)
 assert SIMPLE_SEP_PRIOR_DTYPE.itemsize == 288
 
+# ngmix_scene_frame (include/ngmix_hip.h): device pointers as integers
+SCENE_FRAME_DTYPE = np.dtype([
+    ("resid", "u8"), ("weight", "u8"), ("nrow", "i4"), ("ncol", "i4"), ("band", "i4"),
+    ("pad_", "i4"),
+], align=True)
+assert SCENE_FRAME_DTYPE.itemsize == 32
+
 
 class Batch(ctypes.Structure):
     """ngmix_batch: host struct of device pointers"""
@@ -247,6 +254,8 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ngmix_scene_normal": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp,
                                   _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ngmix_scene_normal_frames": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64,
+                                         _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ngmix_scene_block_matvec": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
                                         _vp, _vp]),
     "ngmix_scene_pcg": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp,

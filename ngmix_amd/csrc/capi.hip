@@ -138,6 +138,7 @@ int64_t ngmix_abi_sizeof(const char *type_name)
     NGMIX_SIZEOF_CASE(ngmix_lm_state);
     NGMIX_SIZEOF_CASE(ngmix_simple_sep_prior);
     NGMIX_SIZEOF_CASE(ngmix_lm_problem);
+    NGMIX_SIZEOF_CASE(ngmix_scene_frame);
 #undef NGMIX_SIZEOF_CASE
     return -1;
 }
@@ -644,6 +645,19 @@ int ngmix_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobi
     return launch_scene_normal(gmix, ngauss, jac, n, tangents, K, weight, resid, nrow, ncol,
                                boxes, items, items_host, nitems, out_mat, out_vec,
                                (hipStream_t)stream);
+}
+
+int ngmix_scene_normal_frames(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac,
+                              int64_t n, const double *tangents, int Kloc, int K,
+                              const ngmix_scene_frame *frames,
+                              const ngmix_scene_frame *frames_host, int64_t nframes,
+                              const int32_t *boxes, const int32_t *items,
+                              const int32_t *items_host, int64_t nitems, double *out_mat,
+                              double *out_vec, void *stream)
+{
+    return launch_scene_normal_frames(gmix, ngauss, jac, n, tangents, Kloc, K, frames,
+                                      frames_host, nframes, boxes, items, items_host, nitems,
+                                      out_mat, out_vec, (hipStream_t)stream);
 }
 
 int ngmix_scene_block_matvec(const double *F_self, const double *F_cross, int64_t n,

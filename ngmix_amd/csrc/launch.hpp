@@ -69,6 +69,14 @@ int launch_scene_normal(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacob
                         const double *resid, int nrow, int ncol, const int32_t *boxes,
                         const int32_t *items, const int32_t *items_host, int64_t nitems,
                         double *out_mat, double *out_vec, hipStream_t s);
+// scene_normal_frames.hip
+int launch_scene_normal_frames(const ngmix_gauss2d *gmix, int ngauss, const ngmix_jacobian *jac,
+                               int64_t n, const double *tangents, int Kloc, int K,
+                               const ngmix_scene_frame *frames,
+                               const ngmix_scene_frame *frames_host, int64_t nframes,
+                               const int32_t *boxes, const int32_t *items,
+                               const int32_t *items_host, int64_t nitems, double *out_mat,
+                               double *out_vec, hipStream_t s);
 // scene_solve.hip
 int launch_scene_block_matvec(const double *F_self, const double *F_cross, int64_t n,
                               int64_t npairs, int K, const int64_t *row_start,

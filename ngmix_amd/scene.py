@@ -49,9 +49,21 @@ and the CG updates are HIP, no atomics, and a group's bits depend on that group
 alone.  fit_joint(large_groups="cg") steps the groups that are too large for a
 dense solve with it, instead of with their own blocks only.
 
+    ne = scene.normal_equations_frames(frames, weights, jacobians, pars, "exp", psf=psfs,
+                                       frame_band=[0, 1, 1], prior=prior)
+    res = scene.fit_joint_frames(frames, weights, jacobians, guess, "exp", psf=psfs,
+                                 frame_band=[0, 1, 1], prior=prior)
+
+normal_equations_frames, joint_covariance_frames and fit_joint_frames are the
+same over a LIST of frames (several bands, several epochs per band, each image
+with its own shape, jacobians and psf) and with a prior: pars hold the shape
+parameters and one flux per band (DESIGN.md section 3.18;
+csrc/scene_normal_frames.hip).
+
 torch does the plumbing (the binning of _tile_pairs, the row lists of
 _block_rows, the dense solves of the groups); the pixel work and the sparse
-solve are HIP (csrc/scene.hip, csrc/scene_normal.hip, csrc/scene_solve.hip).
+solve are HIP (csrc/scene.hip, csrc/scene_normal.hip,
+csrc/scene_normal_frames.hip, csrc/scene_solve.hip).
 """
 import numpy as np
 
@@ -59,7 +71,8 @@ from . import _lib
 from .batch import GMixBatch, StampBatch, _dptr, _on_device, _require_cuda, _stream, _torch
 
 __all__ = ["render_scene", "cut_stamps", "cut_deblended_stamps", "fit_deblended",
-           "normal_equations", "joint_covariance", "fit_joint", "solve_normal"]
+           "normal_equations", "joint_covariance", "fit_joint", "solve_normal",
+           "normal_equations_frames", "joint_covariance_frames", "fit_joint_frames"]
 
 TILE_H = 4      # csrc/scene.hip: SCENE_TH, SCENE_TW
 TILE_W = 16
@@ -643,23 +656,46 @@ def _scene_groups(pair_obj, tile_start, n):
     0, 1, ... by their smallest member (an object in no tile is a group of its
     own), and the group of every tile (-1: a tile without objects).
     """
-    pair_obj = np.asarray(pair_obj, dtype=np.int64)
-    tile_start = np.asarray(tile_start, dtype=np.int64)
+    group, tile_group = _scene_groups_frames([(pair_obj, tile_start)], n)
+    return group, tile_group[0]
+
+
+def _tile_chain(pair_obj, tile_start):
+    """the edges (a, b) of a chain through each tile's list, which connects what
+    the tile's n_t^2 pairs connect (host int64 arrays)"""
     E = pair_obj.shape[0]
-    cnt = np.diff(tile_start)
-    # a chain through each tile's list connects what the n_t^2 pairs connect
     same = np.ones(max(E - 1, 0), dtype=bool)
     ends = tile_start[1:-1]
     ends = ends[(ends > 0) & (ends < E)]
     same[ends - 1] = False
     idx = np.nonzero(same)[0]
-    label = _components(n, pair_obj[idx], pair_obj[idx + 1])
+    return pair_obj[idx], pair_obj[idx + 1]
+
+
+def _scene_groups_frames(lists, n):
+    """
+    _scene_groups over several frames: lists = [(pair_obj, tile_start), ...],
+    one (tile -> object) list per frame (host int64 arrays), all over the same
+    n objects.  The groups are the connected components of the UNION of the
+    frames' tile-sharing graphs, numbered by their smallest member.  Returns
+    (group (n,) int64, [tile_group of frame 0, of frame 1, ...]): every tile
+    with objects, in any frame, belongs to exactly one group.
+    """
+    lists = [(np.asarray(po, dtype=np.int64), np.asarray(ts, dtype=np.int64))
+             for po, ts in lists]
+    edges = [_tile_chain(po, ts) for po, ts in lists]
+    label = _components(n, np.concatenate([e[0] for e in edges]),
+                        np.concatenate([e[1] for e in edges]))
     _, group = np.unique(label, return_inverse=True)
     group = group.astype(np.int64).reshape(-1)
-    tile_group = np.full(cnt.shape[0], -1, dtype=np.int64)
-    has = cnt > 0
-    tile_group[has] = group[pair_obj[tile_start[:-1][has]]]
-    return group, tile_group
+    tile_groups = []
+    for po, ts in lists:
+        cnt = np.diff(ts)
+        tile_group = np.full(cnt.shape[0], -1, dtype=np.int64)
+        has = cnt > 0
+        tile_group[has] = group[po[ts[:-1][has]]]
+        tile_groups.append(tile_group)
+    return group, tile_groups
 
 
 def _segment_sums(values, seg, nseg):
@@ -900,15 +936,23 @@ def _joint_model(shape, jac, pars, name, psf, ngauss, max_pairs, tangents):
     rec = torch.where((code != 0).repeat_interleave(G)[:, None], torch.zeros_like(rec), rec)
     gev, status, hb, pair_obj, tile_start = _scene_lists(nrow, ncol, rec, G, n, jac, max_pairs,
                                                          boxes_to_host=True)
+    model = _render_fresh(nrow, ncol, gev, G, jac, pair_obj, tile_start)
+    flag = torch.where(code == 0, status, code)
+    return dict(G=G, rec=rec, dmix=dmix, flag=flag, boxes=hb, pair_obj=pair_obj,
+                tile_start=tile_start, model=model)
+
+
+def _render_fresh(nrow, ncol, gev, G, jac, pair_obj, tile_start):
+    """a fresh frame of _scene_lists' records and lists (render_scene's bits)"""
+    torch = _torch()
+    dev = gev.device
     model = torch.empty((nrow, ncol), dtype=torch.float64, device=dev)
     with _on_device(dev):
         st = _lib.lib().ngmix_scene_render(_dptr(gev), G, _dptr(jac), _dptr(pair_obj),
                                            int(pair_obj.shape[0]), _dptr(tile_start), nrow, ncol,
                                            _dptr(model), 1, _stream())
     _lib.check(st, "ngmix_scene_render")
-    flag = torch.where(code == 0, status, code)
-    return dict(G=G, rec=rec, dmix=dmix, flag=flag, boxes=hb, pair_obj=pair_obj,
-                tile_start=tile_start, model=model)
+    return model
 
 
 def _scene_normal(rec, G, jac, dmix, wframe, resid, boxes_host, items_host):
@@ -1419,30 +1463,70 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
     conjugate-gradient iterations spent on the object's groups, all LM
     iterations together (0 with large_groups="jacobi").
     """
-    from .flags import MAXITER
-    torch = _torch()
-    maxiter = int(maxiter)
-    if maxiter < 1:
-        raise ValueError("fit_joint: maxiter must be at least 1, got %d" % maxiter)
-    if not (float(tol) >= 0.0) or not (float(lambda0) > 0.0):
-        raise ValueError("fit_joint: tol must be >= 0 and lambda0 > 0")
-    if large_groups not in ("jacobi", "cg"):
-        raise ValueError("fit_joint: large_groups must be 'jacobi' or 'cg', got %r"
-                         % (large_groups,))
-    _cg_arguments(cg_tol, cg_maxiter, "fit_joint", "cg_tol", "cg_maxiter")
-    cg = large_groups == "cg"
-    _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
+    kw = _fit_keywords("fit_joint", maxiter, tol, lambda0, max_group, large_groups, cg_tol,
+                       cg_maxiter)
     frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, guess, model,
                                                         psf, "fit_joint")
+    return _fit_loop(_OneFrame(frame, wframe, wpos, jac, name, psf), pars, **kw)
+
+
+def _fit_keywords(who, maxiter, tol, lambda0, max_group, large_groups, cg_tol, cg_maxiter):
+    """fit_joint's keywords, checked on the host; as _fit_loop takes them"""
+    maxiter = int(maxiter)
+    if maxiter < 1:
+        raise ValueError("%s: maxiter must be at least 1, got %d" % (who, maxiter))
+    if not (float(tol) >= 0.0) or not (float(lambda0) > 0.0):
+        raise ValueError("%s: tol must be >= 0 and lambda0 > 0" % who)
+    if large_groups not in ("jacobi", "cg"):
+        raise ValueError("%s: large_groups must be 'jacobi' or 'cg', got %r"
+                         % (who, large_groups))
+    _cg_arguments(cg_tol, cg_maxiter, who, "cg_tol", "cg_maxiter")
+    _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
+    return dict(maxiter=maxiter, tol=float(tol), lambda0=float(lambda0), max_group=max_group,
+                cg=large_groups == "cg", cg_tol=float(cg_tol), cg_maxiter=int(cg_maxiter))
+
+
+class _OneFrame(object):
+    """what _fit_loop asks of fit_joint's problem: one frame, no prior"""
+
+    def __init__(self, frame, wframe, wpos, jac, name, psf):
+        self.frame, self.wframe, self.wpos, self.jac = frame, wframe, wpos, jac
+        self.name, self.psf = name, psf
+        self.shape = (int(frame.shape[0]), int(frame.shape[1]))
+
+    def normal(self, pars):
+        """the normal equations at pars (a _normal result)"""
+        return _normal(self.frame, self.wframe, self.wpos, self.jac, pars, self.name, self.psf,
+                       None, None)
+
+    def trial(self, ne, trial, ngroups):
+        """(chi2 of every group of ne over its current tiles at the trial
+        parameters (host), the trial's status per object)"""
+        jm = _joint_model(self.shape, self.jac, trial, self.name, self.psf, None, None, False)
+        r = self.frame - jm["model"]
+        new = _segment_sums(_tile_sums(r * r * self.wpos).cpu().numpy(), ne["_tile_group"],
+                            ngroups)
+        return new, jm["flag"]
+
+    def chi2(self, ne):
+        """chi2 of the whole problem at ne's parameters, recomputed"""
+        r = self.frame - ne["_model"]
+        return float((r * r * self.wpos).sum())
+
+
+def _fit_loop(problem, pars, maxiter, tol, lambda0, max_group, cg, cg_tol, cg_maxiter):
+    """fit_joint's Levenberg-Marquardt loop, one lambda per group, over a
+    problem that gives normal(pars), trial(ne, trial, ngroups) and chi2(ne)"""
+    from .flags import MAXITER
+    torch = _torch()
     dev = pars.device
     n, K = int(pars.shape[0]), int(pars.shape[1])
-    shape = (int(frame.shape[0]), int(frame.shape[1]))
     lam = np.full(n, float(lambda0))
     conv = np.zeros(n, dtype=bool)
     niter = np.zeros(n, dtype=np.int64)
     cg_iter = np.zeros(n, dtype=np.int64)
     for _ in range(maxiter):
-        ne = _normal(frame, wframe, wpos, jac, pars, name, psf, None, None)
+        ne = problem.normal(pars)
         group = ne["_group"]
         ngroups = int(group.max()) + 1 if n else 0
         ok_obj = ne["status"].cpu().numpy() == 0
@@ -1468,12 +1552,10 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
             cg_iter[big] += sol["cg_iter"].cpu().numpy()[big]
         d_active = torch.from_numpy(active).to(dev)
         trial = torch.where(d_active[:, None], pars + delta, pars)
-        jm = _joint_model(shape, jac, trial, name, psf, None, None, False)
-        r = frame - jm["model"]
-        new = _segment_sums(_tile_sums(r * r * wpos).cpu().numpy(), ne["_tile_group"], ngroups)
+        new, trial_flag = problem.trial(ne, trial, ngroups)
         old = ne["chi2_group"].cpu().numpy()
         refused = np.zeros(ngroups, dtype=bool)
-        np.logical_or.at(refused, group, (jm["flag"].cpu().numpy() != 0) & ok_obj)
+        np.logical_or.at(refused, group, (trial_flag.cpu().numpy() != 0) & ok_obj)
         unsolved = np.zeros(ngroups, dtype=bool)
         np.logical_or.at(unsolved, group, ~solved.cpu().numpy() & ok_obj)
         accept_g = (new < old) & ~refused & ~unsolved
@@ -1499,7 +1581,7 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
         lam = np.where(accept, np.maximum(lam / 10.0, LAMBDA_FLOOR),
                        np.where(active, lam * 10.0, lam))
         conv = conv | (accept & (pred_o <= float(tol)))
-    ne = _normal(frame, wframe, wpos, jac, pars, name, psf, None, None)
+    ne = problem.normal(pars)
     cov = _covariance(ne, max_group)
     group = ne["_group"]
     ngroups = int(group.max()) + 1 if n else 0
@@ -1511,8 +1593,458 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
     pars_cov = cov["pars_cov"].cpu().numpy()
     with np.errstate(invalid="ignore"):
         pars_err = np.sqrt(np.einsum("nii->ni", pars_cov))
-    r = frame - ne["_model"]
     return {"pars": pars.cpu().numpy(), "pars_cov": pars_cov, "pars_err": pars_err,
             "flags": flags, "group": group.copy(), "niter": niter, "converged": conv,
             "joint_status": cov["joint_status"].cpu().numpy() * (2 if cg else 1),
-            "chi2": float((r * r * wpos).sum()), "lambda": lam, "cg_iter": cg_iter}
+            "chi2": problem.chi2(ne), "lambda": lam, "cg_iter": cg_iter}
+
+
+# ------------------------------------- normal equations of many frames (3.18)
+
+FRAMES_KMAX = 16         # csrc/scene_normal_frames.hip: SNF_KMAX
+
+
+def _frames_pairs(pairs, n):
+    """the union of the frames' pair lists [(P_f, 2) int64 tensor, ...] (one
+    device): (P, 2) int64, every pair once, sorted by (a, b)"""
+    torch = _torch()
+    allp = torch.cat([p.reshape(-1, 2) for p in pairs]) if len(pairs) else \
+        torch.zeros((0, 2), dtype=torch.int64)
+    if int(allp.shape[0]) == 0:
+        return allp.to(torch.int64)
+    key = torch.unique(allp[:, 0].to(torch.int64) * int(n) + allp[:, 1].to(torch.int64))
+    a = torch.div(key, int(n), rounding_mode="floor")
+    return torch.stack([a, key - a * int(n)], dim=1)
+
+
+def _frames_arguments(frames, weights, jacobians, pars, model, psf, frame_band, who):
+    """the arguments every call over a list of frames shares, checked on the
+    host before a device is asked for.  Returns (pars tensor (N, K) float64 on
+    the frames' device, model name, frame_band (F,) int64 host array, the
+    weights as a list of F entries)"""
+    from . import autodiff
+    torch = _torch()
+    if not isinstance(frames, (list, tuple)) or len(frames) == 0:
+        raise ValueError("%s: frames must be a non-empty sequence of 2-d device tensors" % who)
+    F = len(frames)
+    for f, fr in enumerate(frames):
+        if not isinstance(fr, torch.Tensor) or fr.ndim != 2:
+            raise ValueError("%s: frame %d must be a 2-d device tensor" % (who, f))
+        if fr.dtype != torch.float64:
+            raise ValueError("%s: frame %d must be float64, got %s" % (who, f, fr.dtype))
+        if fr.shape[0] < 1 or fr.shape[1] < 1:
+            raise ValueError("%s: frame %d needs nrow * ncol > 0, got %r"
+                             % (who, f, tuple(fr.shape)))
+        if fr.device != frames[0].device:
+            raise ValueError("%s: frame %d is on %s, frame 0 on %s"
+                             % (who, f, fr.device, frames[0].device))
+    dev = frames[0].device
+    if isinstance(weights, (list, tuple)):
+        if len(weights) != F:
+            raise ValueError("%s: %d weights for %d frames" % (who, len(weights), F))
+        weights = list(weights)
+    elif isinstance(weights, torch.Tensor) and weights.ndim != 0:
+        raise ValueError("%s: weights must be None, a scalar, or one entry per frame" % who)
+    else:
+        weights = [weights] * F
+    for f, w in enumerate(weights):
+        if isinstance(w, torch.Tensor) and w.ndim != 0:
+            if tuple(w.shape) != tuple(frames[f].shape):
+                raise ValueError("%s: weight %d must be None, a scalar or have the shape of "
+                                 "frame %d, %r" % (who, f, f, tuple(frames[f].shape)))
+            if w.device != dev:
+                raise ValueError("%s: weight %d must be on the frames' device (%s)"
+                                 % (who, f, dev))
+    if isinstance(pars, torch.Tensor):
+        if pars.device != dev:
+            raise ValueError("%s: pars must be on the frames' device (%s)" % (who, dev))
+        p = pars.detach().to(torch.float64)
+    else:
+        p = torch.from_numpy(np.array(pars, dtype=np.float64))
+    if p.ndim != 2:
+        raise ValueError("%s: pars must be (nobj, npars)" % who)
+    n, K = int(p.shape[0]), int(p.shape[1])
+    name = autodiff._model_name(model)
+    if name == "coellip" or name not in autodiff._NLOC:
+        raise ValueError("%s: model '%s' has no [shape, one flux per band] layout: not built"
+                         % (who, name))
+    nshape = autodiff._NLOC[name] - 1
+    if K > FRAMES_KMAX:
+        raise ValueError("%s: at most %d parameters per object, got K = %d"
+                         % (who, FRAMES_KMAX, K))
+    nband = K - nshape
+    if nband < 1:
+        raise ValueError("%s: model '%s' needs %d shape parameters and one flux per band, got "
+                         "K = %d" % (who, name, nshape, K))
+    try:
+        njac = len(jacobians)
+    except TypeError:
+        raise ValueError("%s: jacobians must be a sequence with one entry per frame" % who)
+    if njac != F:
+        raise ValueError("%s: %d jacobian sets for %d frames" % (who, njac, F))
+    for f in range(F):
+        _check_jacobians(jacobians[f], n, "%s: frame %d" % (who, f))
+    if frame_band is None:
+        if F != nband:
+            raise ValueError("%s: frame_band is required when the %d frames are not one per "
+                             "band (nband = %d)" % (who, F, nband))
+        band = np.arange(F, dtype=np.int64)
+    else:
+        if isinstance(frame_band, torch.Tensor):
+            frame_band = frame_band.detach().cpu().numpy()
+        band = np.asarray(frame_band)
+        if band.shape != (F,) or band.dtype.kind not in "iu":
+            raise ValueError("%s: frame_band must be (%d,) integers" % (who, F))
+        band = band.astype(np.int64)
+        for f in range(F):
+            if band[f] < 0 or band[f] >= nband:
+                raise ValueError("%s: frame_band[%d] = %d is outside [0, %d)"
+                                 % (who, f, band[f], nband))
+    if psf is not None:
+        if not isinstance(psf, (list, tuple)) or len(psf) != F:
+            raise ValueError("%s: psf must be None or a sequence with one entry per frame (%d)"
+                             % (who, F))
+        P = None
+        for f, q in enumerate(psf):
+            if isinstance(q, GMixBatch):
+                nq, Pq, qdev = q.n, q.ngauss, q.device
+            elif isinstance(q, torch.Tensor) and q.ndim == 3 and q.shape[2] == 6:
+                nq, Pq, qdev = int(q.shape[0]), int(q.shape[1]), q.device
+            else:
+                raise ValueError("%s: psf[%d]: (nobj, ngauss_psf, 6) tensor or a GMixBatch"
+                                 % (who, f))
+            if nq != n:
+                raise ValueError("%s: psf[%d] must hold one mixture per object (%d), got %d"
+                                 % (who, f, n, nq))
+            if torch.device(qdev) != dev:
+                raise ValueError("%s: psf[%d] must be on the frames' device (%s)"
+                                 % (who, f, dev))
+            if P is not None and Pq != P:
+                raise ValueError("%s: psf[%d] has %d gaussians, psf[0] has %d: P must be the "
+                                 "same in all frames" % (who, f, Pq, P))
+            P = Pq if P is None else P
+    return p, name, band, weights
+
+
+class _Frames(object):
+    """the checked arguments of a call over a list of frames, on the device;
+    what _fit_loop asks of fit_joint_frames' problem"""
+
+    def __init__(self, frames, weights, jacobians, pars, model, psf, frame_band, prior, who):
+        from . import autodiff
+        from .prior_batch import as_batch_prior
+        torch = _torch()
+        pars, self.name, self.band, weights = _frames_arguments(
+            frames, weights, jacobians, pars, model, psf, frame_band, who)
+        self.prior = as_batch_prior(prior)
+        dev = _require_cuda(frames[0].device)
+        self.dev = dev
+        self.pars = pars.to(dev)
+        self.n, self.K = int(pars.shape[0]), int(pars.shape[1])
+        self.F = len(frames)
+        self.nshape = autodiff._NLOC[self.name] - 1
+        self.frames = [fr.detach().contiguous() for fr in frames]
+        self.shapes = [(int(fr.shape[0]), int(fr.shape[1])) for fr in frames]
+        ww = [_weight_frame(fr, w) for fr, w in zip(self.frames, weights)]
+        self.wframes = [w[0] for w in ww]
+        self.wpos = [w[1] for w in ww]
+        self.jacs = [_jacobian_tensor(jacobians[f], self.n, dev) for f in range(self.F)]
+        # the "stamps" of autodiff's layout: object-major, stamp o * F + f
+        self.stamp_obj = np.repeat(np.arange(self.n, dtype=np.int64), self.F)
+        self.stamp_band = np.tile(self.band, self.n)
+        self.psf = None
+        if psf is not None and self.n:
+            per = [autodiff._psf_tensor(q.detach() if isinstance(q, torch.Tensor) else q,
+                                        self.n, dev) for q in psf]
+            self.psf = torch.stack(per, dim=1).reshape(self.n * self.F, -1, 6).contiguous()
+
+    def normal(self, pars):
+        return _normal_frames(self, pars, None, None)
+
+    def trial(self, ne, trial, ngroups):
+        fm = _frames_model(self, trial, None, None, False)
+        new = _frames_chi2_group(self, fm["models"], ne["_tile_group"], ne["_group"], ngroups,
+                                 _prior_ff(self, trial, fm["flag"]))[0]
+        return new, fm["flag"]
+
+    def chi2(self, ne):
+        tot = 0.0
+        for fr, m, w in zip(self.frames, ne["_models"], self.wpos):
+            r = fr - m
+            tot = tot + float((r * r * w).sum())
+        return tot + float(ne["_prior_ff"].sum())
+
+
+def _prior_ff(fs, pars, flag):
+    """the prior's r.r per object at pars (host (N,); 0 without a prior and for
+    a refused object; inf where the prior is out of range)"""
+    if fs.prior is None or fs.n == 0:
+        return np.zeros(fs.n)
+    r0, bad0 = fs.prior.fill_fdiff_batch(pars)
+    ff = (r0 * r0).sum(dim=1)
+    ff = _torch().where(bad0, _torch().full_like(ff, float("inf")), ff)
+    return np.where(flag.cpu().numpy() != 0, 0.0, ff.cpu().numpy())
+
+
+def _frames_chi2_group(fs, models, tile_group, group, ngroups, prior_ff):
+    """(chi2 per group: the fixed-order sum over the frames of the group's
+    per-tile sum w r^2, plus its members' prior r.r in ascending index; the
+    frames' per-tile sums)"""
+    chi2 = np.zeros(ngroups)
+    tile_chi2 = []
+    for f in range(fs.F):
+        r = fs.frames[f] - models[f]
+        t = _tile_sums(r * r * fs.wpos[f]).cpu().numpy()
+        tile_chi2.append(t)
+        chi2 = chi2 + _segment_sums(t, tile_group[f], ngroups)
+    if fs.prior is not None:
+        chi2 = chi2 + _segment_sums(prior_ff, group, ngroups)
+    return chi2, tile_chi2
+
+
+def _frames_model(fs, pars, ngauss, max_pairs, tangents):
+    """the objects at pars in every frame: per frame the gaussian records, the
+    scene lists and the model frame (render_scene's bits); with tangents: and
+    d mixture / d (the frame's Kloc local parameters).  An object refused in
+    any frame is left out of every frame: flag is its first refusal's code, in
+    frame order"""
+    from . import autodiff
+    torch = _torch()
+    dev, n, F = fs.dev, fs.n, fs.F
+    geom = autodiff._SceneGeometry(n * F, dev)
+    if tangents:
+        (_, _, mix, code, _), dmix = autodiff._mixture_tangents(
+            geom, pars, fs.name, fs.psf, fs.stamp_obj, fs.stamp_band, ngauss)
+    else:
+        _, _, mix, code, _ = autodiff._stamp_mixtures(geom, pars, fs.name, fs.psf, fs.stamp_obj,
+                                                      fs.stamp_band, ngauss)
+        dmix = None
+    G = int(mix.shape[1])
+    mix = mix.reshape(n, F, G, 6)
+    code = code.reshape(n, F)
+
+    def lists(f, rec):
+        return _scene_lists(fs.shapes[f][0], fs.shapes[f][1], rec, G, n, fs.jacs[f], max_pairs,
+                            boxes_to_host=True)
+
+    def without(rec, out):
+        # all-zero records, which the norms refuse (as autodiff.scene_render)
+        return torch.where(out.repeat_interleave(G)[:, None], torch.zeros_like(rec), rec)
+
+    recs, sl, flags = [], [], []
+    for f in range(F):
+        rec = without(autodiff._gauss_records(mix[:, f].contiguous(), True), code[:, f] != 0)
+        recs.append(rec)
+        sl.append(lists(f, rec))
+        flags.append(torch.where(code[:, f] == 0, sl[f][1], code[:, f]))
+    flag = torch.zeros(n, dtype=torch.int32, device=dev)
+    for f in range(F):
+        flag = torch.where((flag == 0) & (flags[f] != 0), flags[f], flag)
+    dead = flag != 0
+    if bool(dead.any()):
+        for f in range(F):
+            if bool((dead & (flags[f] == 0)).any()):
+                recs[f] = without(recs[f], dead)
+                sl[f] = lists(f, recs[f])
+    models = [_render_fresh(fs.shapes[f][0], fs.shapes[f][1], sl[f][0], G, fs.jacs[f], sl[f][3],
+                            sl[f][4]) for f in range(F)]
+    A = None
+    if tangents:
+        # the Kloc = nshape + 1 columns that are not zero in frame f
+        cols = np.concatenate([np.tile(np.arange(fs.nshape), (F, 1)),
+                               (fs.nshape + fs.band)[:, None]], axis=1)
+        d5 = dmix.reshape(n, F, G, 6, fs.K)
+        A = torch.stack([d5[:, f][..., torch.from_numpy(cols[f]).to(dev)] for f in range(F)])
+        A = A.contiguous()
+    return dict(G=G, recs=recs, A=A, flag=flag, boxes=[s[2] for s in sl],
+                pair_obj=[s[3] for s in sl], tile_start=[s[4] for s in sl], models=models)
+
+
+def _scene_normal_frames(recs, G, jacs, A, K, wframes, resids, band, boxes_host, items_host):
+    """ngmix_scene_normal_frames over the (nitems, 2) int32 host table: (blocks
+    (nitems, K, K), vectors (nitems, K)).  recs, jacs, wframes (entries may be
+    None), resids, boxes_host: one per frame; A: (F, n, G, 6, Kloc)"""
+    torch = _torch()
+    dev = resids[0].device
+    F, n, Kloc = int(A.shape[0]), int(A.shape[1]), int(A.shape[4])
+    nitems = int(items_host.shape[0])
+    mat = torch.empty((nitems, K, K), dtype=torch.float64, device=dev)
+    vec = torch.empty((nitems, K), dtype=torch.float64, device=dev)
+    items_host = np.ascontiguousarray(items_host, dtype=np.int32)
+    items = torch.from_numpy(items_host).to(dev)
+    boxes = torch.from_numpy(np.ascontiguousarray(np.stack(boxes_host), dtype=np.int32)).to(dev)
+    rec = torch.cat(recs).contiguous()
+    jac = torch.cat(jacs).contiguous()
+    A = A.detach().to(torch.float64).contiguous()
+    table = np.zeros(F, dtype=_lib.SCENE_FRAME_DTYPE)
+    for f in range(F):
+        table[f] = (resids[f].data_ptr(),
+                    wframes[f].data_ptr() if wframes[f] is not None else 0,
+                    int(resids[f].shape[0]), int(resids[f].shape[1]), int(band[f]), 0)
+    d_table = torch.from_numpy(table.view(np.uint8)).to(dev)
+    with _on_device(dev):
+        st = _lib.lib().ngmix_scene_normal_frames(
+            _dptr(rec), G, _dptr(jac), n, _dptr(A), Kloc, K, _dptr(d_table), _lib.ptr(table), F,
+            _dptr(boxes), _dptr(items), _lib.ptr(items_host), nitems, _dptr(mat), _dptr(vec),
+            _stream())
+    _lib.check(st, "ngmix_scene_normal_frames")
+    return mat, vec
+
+
+def _normal_frames(fs, pars, ngauss, max_pairs):
+    """normal_equations_frames on checked arguments; its dict plus what
+    fit_joint_frames reads: _tile_chi2, _tile_group (per frame, host), _group,
+    _models, _prior_ff"""
+    from .prior_batch import prior_normal_sums
+    torch = _torch()
+    dev, n, K, F = fs.dev, fs.n, fs.K, fs.F
+    f64 = dict(dtype=torch.float64, device=dev)
+    if n == 0:
+        models = [torch.zeros_like(fr) for fr in fs.frames]
+        ntiles = [((s[0] + TILE_H - 1) // TILE_H) * ((s[1] + TILE_W - 1) // TILE_W)
+                  for s in fs.shapes]
+        tile_group = [np.full(t, -1, dtype=np.int64) for t in ntiles]
+        _, tile_chi2 = _frames_chi2_group(fs, models, tile_group, np.zeros(0, dtype=np.int64), 0,
+                                          np.zeros(0))
+        return dict(F_self=torch.zeros((0, K, K), **f64), grad=torch.zeros((0, K), **f64),
+                    pairs=torch.zeros((0, 2), dtype=torch.int64, device=dev),
+                    F_cross=torch.zeros((0, K, K), **f64),
+                    group=torch.zeros(0, dtype=torch.int64, device=dev),
+                    chi2_group=torch.zeros(0, **f64),
+                    status=torch.zeros(0, dtype=torch.int32, device=dev),
+                    _tile_chi2=tile_chi2, _tile_group=tile_group,
+                    _group=np.zeros(0, dtype=np.int64), _models=models, _prior_ff=np.zeros(0))
+    fm = _frames_model(fs, pars, ngauss, max_pairs, True)
+    resids = [(fs.frames[f] - fm["models"][f]).contiguous() for f in range(F)]
+    pairs = _frames_pairs(
+        [_scene_pairs(fm["pair_obj"][f], fm["tile_start"][f],
+                      torch.from_numpy(fm["boxes"][f].astype(np.int64)), n, max_pairs)
+         for f in range(F)], n)
+    P = int(pairs.shape[0])
+    group, tile_group = _scene_groups_frames(
+        [(fm["pair_obj"][f].cpu().numpy(), fm["tile_start"][f].cpu().numpy()) for f in range(F)],
+        n)
+    ngroups = int(group.max()) + 1
+    prior_ff = _prior_ff(fs, pars, fm["flag"])
+    chi2_group, tile_chi2 = _frames_chi2_group(fs, fm["models"], tile_group, group, ngroups,
+                                               prior_ff)
+    items = np.empty((n + P, 2), dtype=np.int32)
+    items[:n, 0] = np.arange(n)
+    items[:n, 1] = -1
+    items[n:] = pairs.cpu().numpy()
+    mat, vec = _scene_normal_frames(fm["recs"], fm["G"], fs.jacs, fm["A"], K, fs.wframes, resids,
+                                    fs.band, fm["boxes"], items)
+    F_self, grad = mat[:n], vec[:n]
+    if fs.prior is not None:
+        sums, _ = prior_normal_sums(fs.prior, pars)
+        iu = torch.triu_indices(K, K, device=dev)
+        ntri = int(iu.shape[1])
+        tri = sums[:, :ntri]
+        Pm = pars.new_zeros((n, K, K))
+        Pm[:, iu[0], iu[1]] = tri
+        Pm[:, iu[1], iu[0]] = tri
+        F_self = F_self + Pm
+        grad = grad - sums[:, ntri:ntri + K]
+    bad = fm["flag"] != 0
+    nan = float("nan")
+    F_self = torch.where(bad[:, None, None], torch.full_like(F_self, nan), F_self)
+    grad = torch.where(bad[:, None], torch.full_like(grad, nan), grad)
+    return dict(F_self=F_self, grad=grad, pairs=pairs, F_cross=mat[n:],
+                group=torch.from_numpy(group).to(dev),
+                chi2_group=torch.from_numpy(chi2_group).to(dev), status=fm["flag"],
+                _tile_chi2=tile_chi2, _tile_group=tile_group, _group=group,
+                _models=fm["models"], _prior_ff=prior_ff)
+
+
+def normal_equations_frames(frames, weights, jacobians, pars, model, psf=None, frame_band=None,
+                            prior=None, ngauss=None, max_pairs=None):
+    """
+    normal_equations over a LIST of frames -- several bands, several epochs per
+    band, each image with its own shape, jacobians (WCS, dither) and psf -- and
+    with a prior (csrc/scene_normal_frames.hip).  With
+    r_f = frames[f] - render_scene(objects at pars in frame f) and J_a,f =
+    d model_a,f / d pars_a,
+        F_self[a]  = sum_f sum w J_a,f J_a,f^T     symmetric to the bit
+        grad[a]    = sum_f sum w r_f J_a,f
+        F_cross[p] = sum_f sum w J_a,f J_b,f^T     (a, b) = pairs[p]
+    summed over the frames in ascending index by the one wave that owns the
+    block.  An object whose box misses a frame adds nothing there.
+
+    frames: a sequence of F 2-d float64 device tensors; their shapes may differ
+    weights: None, a scalar, or a sequence of F entries, each None, a scalar or
+        a tensor of that frame's shape
+    jacobians: a sequence of F jacobian sets, each as normal_equations' (one
+        jacobian per object, in that frame's pixel coordinates)
+    pars: (N, nshape + nband) in LMBatchFitter.go's layout: the model's shape
+        parameters, then one flux per band; K = nshape + nband <= 16.
+        'coellip' is refused
+    psf: None, or a sequence of F entries, each a GMixBatch or an (N, P, 6)
+        tensor with one mixture per object; P the same in all frames
+    frame_band: (F,) ints, the band of every frame; default arange(F) when
+        F == nband, otherwise required
+    prior: what autodiff.fisher takes (prior_batch.as_batch_prior): the
+        triangle of its rows' J^T J is added to F_self as autodiff.fisher adds
+        it, J^T r is subtracted from grad (grad is minus half the gradient of
+        chi2 + r_p . r_p), and every member's r_p . r_p is added to its group's
+        chi2_group
+
+    Returns normal_equations' keys with K = nshape + nband: pairs is the union
+    of the frames' pairs, group the connected components of the union of the
+    frames' tile-sharing graphs, chi2_group the fixed-order sum over the frames
+    of the group's per-tile sum w r^2 (plus the prior's).  An object refused in
+    any frame is left out of every frame's model: its status is the code of its
+    first refusal in frame order, its rows are NaN, it is in no pair, and all
+    other objects' bits are those of the catalogue without it.  No atomics: two
+    calls give the same bits.
+    """
+    fs = _Frames(frames, weights, jacobians, pars, model, psf, frame_band, prior,
+                 "normal_equations_frames")
+    return _public(_normal_frames(fs, fs.pars, ngauss, max_pairs))
+
+
+def joint_covariance_frames(frames, weights, jacobians, pars, model, psf=None, frame_band=None,
+                            prior=None, ngauss=None, max_pairs=None, max_group=16):
+    """
+    joint_covariance over a list of frames and with a prior: the blocks of
+    normal_equations_frames, inverted per group by the same bucketed Cholesky.
+    For an isolated object this is autodiff.covariance over one stamp per
+    frame, with the same prior.  Arguments as normal_equations_frames and
+    joint_covariance; returns joint_covariance's keys.
+    """
+    _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
+    fs = _Frames(frames, weights, jacobians, pars, model, psf, frame_band, prior,
+                 "joint_covariance_frames")
+    return _covariance(_normal_frames(fs, fs.pars, ngauss, max_pairs), max_group)
+
+
+def fit_joint_frames(frames, weights, jacobians, guess, model, psf=None, frame_band=None,
+                     prior=None, maxiter=50, tol=1e-6, lambda0=1e-3, max_group=16,
+                     large_groups="jacobi", cg_tol=1e-8, cg_maxiter=200):
+    """
+    fit_joint over a list of frames (bands, epochs) and with a prior: the same
+    Levenberg-Marquardt loop, one lambda per group, over
+    normal_equations_frames.  Per iteration one trial is rendered per frame; a
+    group accepts its step when its chi2 decreases, taken over its current
+    tiles in ALL frames plus its members' prior r . r; a trial where the prior
+    is out of range (r . r = inf) is rejected.
+
+    frames, weights, jacobians, psf, frame_band, prior: as
+        normal_equations_frames; guess: (N, nshape + nband)
+    the other keywords: fit_joint's.  large_groups="cg" goes through
+        solve_normal unchanged, whose blocks hold at most 8 parameters per
+        object: with K > 8 it is refused (ValueError naming K); a wider
+        csrc/scene_solve.hip is not built
+
+    Returns fit_joint's keys; chi2 includes the prior's r . r, and pars_cov is
+    joint_covariance_frames at pars, bit for bit.
+    """
+    kw = _fit_keywords("fit_joint_frames", maxiter, tol, lambda0, max_group, large_groups,
+                       cg_tol, cg_maxiter)
+    K = int(np.shape(guess)[-1]) if np.ndim(guess) == 2 else 0
+    if kw["cg"] and K > NORMAL_KMAX:
+        raise ValueError("fit_joint_frames: large_groups='cg' solves blocks of at most %d "
+                         "parameters per object (scene.solve_normal), got K = %d"
+                         % (NORMAL_KMAX, K))
+    fs = _Frames(frames, weights, jacobians, guess, model, psf, frame_band, prior,
+                 "fit_joint_frames")
+    return _fit_loop(fs, fs.pars, **kw)

@@ -30,8 +30,17 @@ solve_normal at lambda = 1e-3 and tol = 1e-8 end to end with the iterations the
 largest group took, and one fit_joint iteration with large_groups="cg" and with
 "jacobi".
 
+The many-frames leg (--joint-frames; scene.normal_equations_frames,
+scene_normal_frames_kernel): the same scene replicated as
+3 frames in 2 bands (frame_band = [0, 1, 1], K = 7, each frame with noise of its
+own), written to profiles/scene_joint_frames_bench.txt: ngmix_scene_normal_frames
+by events, the parent route for the same blocks by events (one ngmix_scene_normal
+launch per frame over the same item table, each followed by the torch
+scatter-add of its 6 x 6 blocks into the 7 x 7 ones), whether the two agree bit
+for bit, and normal_equations_frames end to end.
+
     python tools/bench_scene.py [--n 30000] [--size 4096] [--out profiles/scene_bench.txt]
-                                [--deblend-only] [--joint-only] [--joint-cg]
+                                [--deblend-only] [--joint-only] [--joint-cg] [--joint-frames]
 """
 import argparse
 import os
@@ -79,6 +88,9 @@ def main():
     ap.add_argument("--joint-cg", action="store_true")
     ap.add_argument("--joint-cg-out",
                     default=os.path.join(ROOT, "profiles", "scene_joint_cg_bench.txt"))
+    ap.add_argument("--joint-frames", action="store_true")
+    ap.add_argument("--joint-frames-out",
+                    default=os.path.join(ROOT, "profiles", "scene_joint_frames_bench.txt"))
     ap.add_argument("--joint-out",
                     default=os.path.join(ROOT, "profiles", "scene_joint_bench.txt"))
     args = ap.parse_args()
@@ -364,6 +376,111 @@ def main():
                    int((res["joint_status"] == 0).sum()), int((res["joint_status"] == 1).sum()),
                    int((res["joint_status"] == 2).sum())))
 
+    def joint_frames_leg():
+        band = [0, 1, 1]
+        F, nshape, K, Kloc = len(band), 5, 7, 6
+        say("joint frames: %d frames of %d x %d, frame_band %s, %d objects, G = %d, K = %d, "
+            "Kloc = %d" % (F, size, size, band, n, G, K, Kloc))
+        clean, _ = scene.render_scene(shape, gm, d_jac)
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(99)
+        frames = [clean + 0.01 * torch.randn(shape, generator=gen, dtype=torch.float64,
+                                             device="cuda") for _ in range(F)]
+        del clean
+        pars7 = torch.cat([d_pars, d_pars[:, 5:6]], dim=1).contiguous()
+        # the lists, the tangents and the item table the call would build
+        fs = scene._Frames(frames, None, [d_jac] * F, pars7, "exp", [d_psf] * F, band, None,
+                           "bench_scene")
+        fm = scene._frames_model(fs, fs.pars, None, None, True)
+        resids = [(fs.frames[f] - fm["models"][f]).contiguous() for f in range(F)]
+        pairs = scene._frames_pairs(
+            [scene._scene_pairs(fm["pair_obj"][f], fm["tile_start"][f],
+                                torch.from_numpy(fm["boxes"][f].astype(np.int64)), n)
+             for f in range(F)], n)
+        P = int(pairs.shape[0])
+        say("joint frames: %d pairs in the union (%.1f per object), %d items" % (P, P / float(n),
+                                                                                 n + P))
+        items = np.empty((n + P, 2), dtype=np.int32)
+        items[:n, 0] = np.arange(n)
+        items[:n, 1] = -1
+        items[n:] = pairs.cpu().numpy()
+        d_items = torch.from_numpy(items).cuda()
+        rec = torch.cat(fm["recs"]).contiguous()
+        jacs = torch.cat(fs.jacs).contiguous()
+        d_boxes = [torch.from_numpy(b).cuda() for b in fm["boxes"]]
+        boxes = torch.stack(d_boxes).contiguous()
+        A = fm["A"].contiguous()
+        table = np.zeros(F, dtype=_lib.SCENE_FRAME_DTYPE)
+        for f in range(F):
+            table[f] = (resids[f].data_ptr(), 0, size, size, band[f], 0)
+        d_table = torch.from_numpy(table.view(np.uint8)).cuda()
+        mat = torch.empty((n + P, K, K), dtype=torch.float64, device="cuda")
+        vec = torch.empty((n + P, K), dtype=torch.float64, device="cuda")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t_kern = []
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize()
+            e0.record()
+            _lib.check(L.ngmix_scene_normal_frames(
+                _dptr(rec), G, _dptr(jacs), n, _dptr(A), Kloc, K, _dptr(d_table), None, F,
+                _dptr(boxes), _dptr(d_items), None, n + P, _dptr(mat), _dptr(vec), _stream()),
+                "scene_normal_frames")
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                t_kern.append(e0.elapsed_time(e1))
+        say("joint frames: ngmix_scene_normal_frames (ms, by events): median %.3f, min %.3f, "
+            "max %.3f; which bound: not established (no counter run was made)"
+            % (np.median(t_kern), min(t_kern), max(t_kern)))
+
+        # the parent route for the same blocks: one launch of the one-band
+        # kernel per frame over the same item table, its 6 x 6 blocks added into
+        # the 7 x 7 ones by torch, in frame order
+        cols = [torch.tensor(list(range(nshape)) + [nshape + b], device="cuda") for b in band]
+        A_f = [A[f].contiguous() for f in range(F)]
+        mat6 = torch.empty((n + P, Kloc, Kloc), dtype=torch.float64, device="cuda")
+        vec6 = torch.empty((n + P, Kloc), dtype=torch.float64, device="cuda")
+        t_par = []
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize()
+            e0.record()
+            mat_p = torch.zeros((n + P, K, K), dtype=torch.float64, device="cuda")
+            vec_p = torch.zeros((n + P, K), dtype=torch.float64, device="cuda")
+            for f in range(F):
+                _lib.check(L.ngmix_scene_normal(
+                    _dptr(fm["recs"][f]), G, _dptr(fs.jacs[f]), n, _dptr(A_f[f]), Kloc, None,
+                    _dptr(resids[f]), size, size, _dptr(d_boxes[f]), _dptr(d_items), None, n + P,
+                    _dptr(mat6), _dptr(vec6), _stream()), "scene_normal")
+                mat_p[:, cols[f][:, None], cols[f][None, :]] += mat6
+                vec_p[:, cols[f]] += vec6
+            e1.record()
+            torch.cuda.synchronize()
+            if rep:
+                t_par.append(e0.elapsed_time(e1))
+        say("joint frames: the parent route, %d launches of ngmix_scene_normal + the torch "
+            "scatter-add (ms, by events): median %.3f, min %.3f, max %.3f"
+            % (F, np.median(t_par), min(t_par), max(t_par)))
+        say("joint frames: the two routes agree bit for bit: blocks %s, vectors %s"
+            % (bool((mat == mat_p).all()), bool((vec == vec_p).all())))
+        del mat_p, vec_p, mat6, vec6
+
+        def new_way():
+            return scene.normal_equations_frames(frames, None, [d_jac] * F, pars7, "exp",
+                                                 psf=[d_psf] * F, frame_band=band)
+
+        timed(new_way)
+        t_new = []
+        for rep in range(args.reps):
+            ne, t = timed(new_way)
+            t_new.append(t)
+        say("joint frames: normal_equations_frames end to end (ms): median %.3f, min %.3f, "
+            "max %.3f; kernel call and normal_equations_frames agree bit for bit: %s"
+            % (np.median(t_new), min(t_new), max(t_new), bool((ne["F_self"] == mat[:n]).all())))
+
+    if args.joint_frames:
+        joint_frames_leg()
+        write("w", args.joint_frames_out)
+        return
     if args.joint_cg:
         joint_cg_leg()
         write("w", args.joint_cg_out)
