@@ -1822,7 +1822,7 @@ int launch_lm_eval(const ngmix_batch *b, int model, int fd, const lm_state *stat
     int ng0, nloc;
     if (model_ngauss_npars(model, ng0, nloc) != 0 || npsf < 0) {
         set_last_error_msg("lm_eval: model must be gauss, turb, exp, dev, bdf, bd or "
-                           "coellip + 256 * ngauss (ngauss <= 3)");
+                           "coellip + 256 * ngauss (ngauss <= 5)");
         return NGMIX_ERR_BAD_ARG;
     }
     model &= 0xff;
@@ -1892,8 +1892,8 @@ int launch_lm_eval(const ngmix_batch *b, int model, int fd, const lm_state *stat
         if (e) linear = e[0] == 'l';
     }
     if (precise && nloc < NGMIX_LM_PRECISE_MIN_NLOC) {
-        // (built for the fits it serves: nine local parameters and up)
-        set_last_error_msg("lm_eval: the precise pass serves nloc >= 9");
+        // (built for the fits it serves: ten local parameters and up)
+        set_last_error_msg("lm_eval: the precise pass serves nloc >= 10");
         return NGMIX_ERR_BAD_ARG;
     }
     static constexpr FdRow rows[] = {
