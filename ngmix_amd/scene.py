@@ -58,7 +58,9 @@ normal_equations_frames, joint_covariance_frames and fit_joint_frames are the
 same over a LIST of frames (several bands, several epochs per band, each image
 with its own shape, jacobians and psf) and with a prior: pars hold the shape
 parameters and one flux per band (DESIGN.md section 3.18;
-csrc/scene_normal_frames.hip).
+csrc/scene_normal_frames.hip).  The one-frame calls above are their case F = 1,
+one band, no prior, on the same code (_Frames.one); only the kernel entry is
+chosen by the case (_scene_normal).
 
 torch does the plumbing (the binning of _tile_pairs, the row lists of
 _block_rows, the dense solves of the groups); the pixel work and the sparse
@@ -582,6 +584,8 @@ def fit_deblended(frame, weight, r_lo, c_lo, nrow, ncol, jacobians, guess, model
 
 
 # ------------------------------------------------ normal equations of a frame
+# (the one-frame API; it runs as the case F = 1, one band, no prior of the
+# frames' code further down: _Frames.one, _frames_model, _normal_frames)
 
 NORMAL_KMAX = 8          # csrc/scene_normal.hip: SN_KT
 LAMBDA_FLOOR = 1.0e-9    # fit_joint: no damping factor goes below this
@@ -913,35 +917,6 @@ def _weight_frame(frame, weight):
     return w, torch.clamp(w, min=0.0)
 
 
-def _joint_model(shape, jac, pars, name, psf, ngauss, max_pairs, tangents):
-    """the objects at pars: mixtures (with tangents: and d mixture / d pars),
-    the scene lists and the model frame (render_scene's bits; a refused object
-    is left out)"""
-    from . import autodiff
-    torch = _torch()
-    nrow, ncol = shape
-    dev = pars.device
-    n = int(pars.shape[0])
-    geom = autodiff._SceneGeometry(n, dev)
-    if tangents:
-        (_, _, mix, code, _), dmix = autodiff._mixture_tangents(geom, pars, name, psf, None, None,
-                                                                ngauss)
-    else:
-        _, _, mix, code, _ = autodiff._stamp_mixtures(geom, pars, name, psf, None, None, ngauss)
-        dmix = None
-    G = int(mix.shape[1])
-    rec = autodiff._gauss_records(mix, True)
-    # an object refused before the kernels is left out: all-zero records, which
-    # the norms refuse (as autodiff.scene_render)
-    rec = torch.where((code != 0).repeat_interleave(G)[:, None], torch.zeros_like(rec), rec)
-    gev, status, hb, pair_obj, tile_start = _scene_lists(nrow, ncol, rec, G, n, jac, max_pairs,
-                                                         boxes_to_host=True)
-    model = _render_fresh(nrow, ncol, gev, G, jac, pair_obj, tile_start)
-    flag = torch.where(code == 0, status, code)
-    return dict(G=G, rec=rec, dmix=dmix, flag=flag, boxes=hb, pair_obj=pair_obj,
-                tile_start=tile_start, model=model)
-
-
 def _render_fresh(nrow, ncol, gev, G, jac, pair_obj, tile_start):
     """a fresh frame of _scene_lists' records and lists (render_scene's bits)"""
     torch = _torch()
@@ -955,91 +930,8 @@ def _render_fresh(nrow, ncol, gev, G, jac, pair_obj, tile_start):
     return model
 
 
-def _scene_normal(rec, G, jac, dmix, wframe, resid, boxes_host, items_host):
-    """ngmix_scene_normal over the (nitems, 2) int32 host table: (blocks
-    (nitems, K, K), vectors (nitems, K))"""
-    torch = _torch()
-    dev = rec.device
-    n, K = int(dmix.shape[0]), int(dmix.shape[3])
-    nitems = int(items_host.shape[0])
-    nrow, ncol = int(resid.shape[0]), int(resid.shape[1])
-    mat = torch.empty((nitems, K, K), dtype=torch.float64, device=dev)
-    vec = torch.empty((nitems, K), dtype=torch.float64, device=dev)
-    items_host = np.ascontiguousarray(items_host, dtype=np.int32)
-    items = torch.from_numpy(items_host).to(dev)
-    boxes = torch.from_numpy(np.ascontiguousarray(boxes_host, dtype=np.int32)).to(dev)
-    A = dmix.detach().to(torch.float64).contiguous()
-    with _on_device(dev):
-        st = _lib.lib().ngmix_scene_normal(
-            _dptr(rec), G, _dptr(jac), n, _dptr(A), K,
-            _dptr(wframe) if wframe is not None else None, _dptr(resid), nrow, ncol,
-            _dptr(boxes), _dptr(items), _lib.ptr(items_host), nitems, _dptr(mat), _dptr(vec),
-            _stream())
-    _lib.check(st, "ngmix_scene_normal")
-    return mat, vec
-
-
-def _normal(frame, wframe, wpos, jac, pars, name, psf, ngauss, max_pairs):
-    """normal_equations on checked arguments; its dict plus what fit_joint
-    reads: tile_chi2 (host), tile_group (host), model"""
-    torch = _torch()
-    dev = pars.device
-    n, K = int(pars.shape[0]), int(pars.shape[1])
-    nrow, ncol = int(frame.shape[0]), int(frame.shape[1])
-    if n == 0:
-        f64 = dict(dtype=torch.float64, device=dev)
-        ntiles = ((nrow + TILE_H - 1) // TILE_H) * ((ncol + TILE_W - 1) // TILE_W)
-        return dict(F_self=torch.zeros((0, K, K), **f64), grad=torch.zeros((0, K), **f64),
-                    pairs=torch.zeros((0, 2), dtype=torch.int64, device=dev),
-                    F_cross=torch.zeros((0, K, K), **f64),
-                    group=torch.zeros(0, dtype=torch.int64, device=dev),
-                    chi2_group=torch.zeros(0, **f64),
-                    status=torch.zeros(0, dtype=torch.int32, device=dev),
-                    _tile_chi2=_tile_sums(frame * frame * wpos).cpu().numpy(),
-                    _tile_group=np.full(ntiles, -1, dtype=np.int64),
-                    _group=np.zeros(0, dtype=np.int64), _model=torch.zeros_like(frame))
-    jm = _joint_model((nrow, ncol), jac, pars, name, psf, ngauss, max_pairs, True)
-    resid = (frame - jm["model"]).contiguous()
-    pairs = _scene_pairs(jm["pair_obj"], jm["tile_start"],
-                         torch.from_numpy(jm["boxes"].astype(np.int64)), n, max_pairs)
-    P = int(pairs.shape[0])
-    group, tile_group = _scene_groups(jm["pair_obj"].cpu().numpy(),
-                                      jm["tile_start"].cpu().numpy(), n)
-    ngroups = int(group.max()) + 1 if n else 0
-    tile_chi2 = _tile_sums(resid * resid * wpos).cpu().numpy()
-    chi2_group = _segment_sums(tile_chi2, tile_group, ngroups)
-    items = np.empty((n + P, 2), dtype=np.int32)
-    items[:n, 0] = np.arange(n)
-    items[:n, 1] = -1
-    items[n:] = pairs.cpu().numpy()
-    if n + P:
-        mat, vec = _scene_normal(jm["rec"], jm["G"], jac, jm["dmix"], wframe, resid, jm["boxes"],
-                                 items)
-    else:
-        mat = torch.zeros((0, K, K), dtype=torch.float64, device=dev)
-        vec = torch.zeros((0, K), dtype=torch.float64, device=dev)
-    bad = jm["flag"] != 0
-    nan = float("nan")
-    F_self = torch.where(bad[:, None, None], torch.full_like(mat[:n], nan), mat[:n])
-    grad = torch.where(bad[:, None], torch.full_like(vec[:n], nan), vec[:n])
-    return dict(F_self=F_self, grad=grad, pairs=pairs, F_cross=mat[n:],
-                group=torch.from_numpy(group).to(dev),
-                chi2_group=torch.from_numpy(chi2_group).to(dev), status=jm["flag"],
-                _tile_chi2=tile_chi2, _tile_group=tile_group, _group=group, _model=jm["model"])
-
-
 def _public(res):
     return {k: v for k, v in res.items() if not k.startswith("_")}
-
-
-def _joint_setup(frame, weight, jacobians, pars, model, psf, who):
-    pars, name = _joint_arguments(frame, weight, jacobians, pars, model, psf, who)
-    dev = _require_cuda(frame.device)
-    pars = pars.to(dev)
-    frame = frame.detach().contiguous()
-    wframe, wpos = _weight_frame(frame, weight)
-    jac = _jacobian_tensor(jacobians, int(pars.shape[0]), dev)
-    return frame, wframe, wpos, jac, pars, name
 
 
 def normal_equations(frame, weight, jacobians, pars, model, psf=None, ngauss=None,
@@ -1073,9 +965,8 @@ def normal_equations(frame, weight, jacobians, pars, model, psf=None, ngauss=Non
     those of the catalogue without it.  No atomics: two calls give the same
     bits (csrc/scene_normal.hip).
     """
-    frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, pars, model,
-                                                        psf, "normal_equations")
-    return _public(_normal(frame, wframe, wpos, jac, pars, name, psf, ngauss, max_pairs))
+    fs = _Frames.one(frame, weight, jacobians, pars, model, psf, "normal_equations")
+    return _public(_normal_frames(fs, fs.pars, ngauss, max_pairs))
 
 
 def _own_inverse(F, bad):
@@ -1087,7 +978,7 @@ def _own_inverse(F, bad):
 
 
 def _covariance(ne, max_group):
-    """joint_covariance from a _normal result"""
+    """joint_covariance from a _normal_frames result"""
     from .flags import LM_SINGULAR_MATRIX
     torch = _torch()
     F = ne["F_self"]
@@ -1132,10 +1023,8 @@ def joint_covariance(frame, weight, jacobians, pars, model, psf=None, ngauss=Non
     group (N,) int64, joint_status (N,) int32 (1: own block only).
     """
     _GroupLayout(np.zeros(0, dtype=np.int64), max_group)
-    frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, pars, model,
-                                                        psf, "joint_covariance")
-    ne = _normal(frame, wframe, wpos, jac, pars, name, psf, ngauss, max_pairs)
-    return _covariance(ne, max_group)
+    fs = _Frames.one(frame, weight, jacobians, pars, model, psf, "joint_covariance")
+    return _covariance(_normal_frames(fs, fs.pars, ngauss, max_pairs), max_group)
 
 
 def _joint_step(ne, layout, lam):
@@ -1465,9 +1354,8 @@ def fit_joint(frame, weight, jacobians, guess, model, psf=None, maxiter=50, tol=
     """
     kw = _fit_keywords("fit_joint", maxiter, tol, lambda0, max_group, large_groups, cg_tol,
                        cg_maxiter)
-    frame, wframe, wpos, jac, pars, name = _joint_setup(frame, weight, jacobians, guess, model,
-                                                        psf, "fit_joint")
-    return _fit_loop(_OneFrame(frame, wframe, wpos, jac, name, psf), pars, **kw)
+    fs = _Frames.one(frame, weight, jacobians, guess, model, psf, "fit_joint")
+    return _fit_loop(fs, fs.pars, **kw)
 
 
 def _fit_keywords(who, maxiter, tol, lambda0, max_group, large_groups, cg_tol, cg_maxiter):
@@ -1486,37 +1374,10 @@ def _fit_keywords(who, maxiter, tol, lambda0, max_group, large_groups, cg_tol, c
                 cg=large_groups == "cg", cg_tol=float(cg_tol), cg_maxiter=int(cg_maxiter))
 
 
-class _OneFrame(object):
-    """what _fit_loop asks of fit_joint's problem: one frame, no prior"""
-
-    def __init__(self, frame, wframe, wpos, jac, name, psf):
-        self.frame, self.wframe, self.wpos, self.jac = frame, wframe, wpos, jac
-        self.name, self.psf = name, psf
-        self.shape = (int(frame.shape[0]), int(frame.shape[1]))
-
-    def normal(self, pars):
-        """the normal equations at pars (a _normal result)"""
-        return _normal(self.frame, self.wframe, self.wpos, self.jac, pars, self.name, self.psf,
-                       None, None)
-
-    def trial(self, ne, trial, ngroups):
-        """(chi2 of every group of ne over its current tiles at the trial
-        parameters (host), the trial's status per object)"""
-        jm = _joint_model(self.shape, self.jac, trial, self.name, self.psf, None, None, False)
-        r = self.frame - jm["model"]
-        new = _segment_sums(_tile_sums(r * r * self.wpos).cpu().numpy(), ne["_tile_group"],
-                            ngroups)
-        return new, jm["flag"]
-
-    def chi2(self, ne):
-        """chi2 of the whole problem at ne's parameters, recomputed"""
-        r = self.frame - ne["_model"]
-        return float((r * r * self.wpos).sum())
-
-
 def _fit_loop(problem, pars, maxiter, tol, lambda0, max_group, cg, cg_tol, cg_maxiter):
     """fit_joint's Levenberg-Marquardt loop, one lambda per group, over a
-    problem that gives normal(pars), trial(ne, trial, ngroups) and chi2(ne)"""
+    problem (_Frames) that gives normal(pars), trial(ne, trial, ngroups) and
+    chi2(ne)"""
     from .flags import MAXITER
     torch = _torch()
     dev = pars.device
@@ -1600,14 +1461,18 @@ def _fit_loop(problem, pars, maxiter, tol, lambda0, max_group, cg, cg_tol, cg_ma
 
 
 # ------------------------------------- normal equations of many frames (3.18)
+# (and, with F = 1, of the one frame of the section above)
 
 FRAMES_KMAX = 16         # csrc/scene_normal_frames.hip: SNF_KMAX
 
 
 def _frames_pairs(pairs, n):
     """the union of the frames' pair lists [(P_f, 2) int64 tensor, ...] (one
-    device): (P, 2) int64, every pair once, sorted by (a, b)"""
+    device): (P, 2) int64, every pair once, sorted by (a, b).  One list is its
+    own union: _scene_pairs gives it unique and sorted"""
     torch = _torch()
+    if len(pairs) == 1:
+        return pairs[0]
     allp = torch.cat([p.reshape(-1, 2) for p in pairs]) if len(pairs) else \
         torch.zeros((0, 2), dtype=torch.int64)
     if int(allp.shape[0]) == 0:
@@ -1727,16 +1592,31 @@ def _frames_arguments(frames, weights, jacobians, pars, model, psf, frame_band, 
 
 
 class _Frames(object):
-    """the checked arguments of a call over a list of frames, on the device;
-    what _fit_loop asks of fit_joint_frames' problem"""
+    """the checked arguments of a joint call, on the device, and what _fit_loop
+    asks of its problem: normal(pars), trial(ne, trial, ngroups) and chi2(ne).
+    The one-frame API (normal_equations, joint_covariance, fit_joint) comes in
+    through one(): it is the case F = 1, band [0], no prior"""
 
     def __init__(self, frames, weights, jacobians, pars, model, psf, frame_band, prior, who):
-        from . import autodiff
         from .prior_batch import as_batch_prior
+        pars, name, band, weights = _frames_arguments(frames, weights, jacobians, pars, model, psf,
+                                                      frame_band, who)
+        self._fill(frames, weights, jacobians, pars, name, psf, band, as_batch_prior(prior))
+
+    @classmethod
+    def one(cls, frame, weight, jacobians, pars, model, psf, who):
+        """the one-frame API's arguments, checked by _joint_arguments (its
+        messages, K <= NORMAL_KMAX and the one-flux rule are that API's)"""
+        pars, name = _joint_arguments(frame, weight, jacobians, pars, model, psf, who)
+        self = cls.__new__(cls)
+        self._fill([frame], [weight], [jacobians], pars, name, None if psf is None else [psf],
+                   np.zeros(1, dtype=np.int64), None)
+        return self
+
+    def _fill(self, frames, weights, jacobians, pars, name, psf, band, prior):
+        from . import autodiff
         torch = _torch()
-        pars, self.name, self.band, weights = _frames_arguments(
-            frames, weights, jacobians, pars, model, psf, frame_band, who)
-        self.prior = as_batch_prior(prior)
+        self.name, self.band, self.prior = name, band, prior
         dev = _require_cuda(frames[0].device)
         self.dev = dev
         self.pars = pars.to(dev)
@@ -1756,14 +1636,17 @@ class _Frames(object):
         if psf is not None and self.n:
             per = [autodiff._psf_tensor(q.detach() if isinstance(q, torch.Tensor) else q,
                                         self.n, dev) for q in psf]
-            self.psf = torch.stack(per, dim=1).reshape(self.n * self.F, -1, 6).contiguous()
+            # (one frame: its tensor as it is, no copy)
+            self.psf = per[0] if self.F == 1 else \
+                torch.stack(per, dim=1).reshape(self.n * self.F, -1, 6).contiguous()
 
     def normal(self, pars):
         return _normal_frames(self, pars, None, None)
 
     def trial(self, ne, trial, ngroups):
         fm = _frames_model(self, trial, None, None, False)
-        new = _frames_chi2_group(self, fm["models"], ne["_tile_group"], ne["_group"], ngroups,
+        resids = [fr - m for fr, m in zip(self.frames, fm["models"])]
+        new = _frames_chi2_group(self, resids, ne["_tile_group"], ne["_group"], ngroups,
                                  _prior_ff(self, trial, fm["flag"]))[0]
         return new, fm["flag"]
 
@@ -1786,14 +1669,14 @@ def _prior_ff(fs, pars, flag):
     return np.where(flag.cpu().numpy() != 0, 0.0, ff.cpu().numpy())
 
 
-def _frames_chi2_group(fs, models, tile_group, group, ngroups, prior_ff):
+def _frames_chi2_group(fs, resids, tile_group, group, ngroups, prior_ff):
     """(chi2 per group: the fixed-order sum over the frames of the group's
-    per-tile sum w r^2, plus its members' prior r.r in ascending index; the
-    frames' per-tile sums)"""
+    per-tile sum w r^2, r = resids[f] = frame f - its model, plus its members'
+    prior r.r in ascending index; the frames' per-tile sums)"""
     chi2 = np.zeros(ngroups)
     tile_chi2 = []
     for f in range(fs.F):
-        r = fs.frames[f] - models[f]
+        r = resids[f]
         t = _tile_sums(r * r * fs.wpos[f]).cpu().numpy()
         tile_chi2.append(t)
         chi2 = chi2 + _segment_sums(t, tile_group[f], ngroups)
@@ -1837,64 +1720,95 @@ def _frames_model(fs, pars, ngauss, max_pairs, tangents):
         recs.append(rec)
         sl.append(lists(f, rec))
         flags.append(torch.where(code[:, f] == 0, sl[f][1], code[:, f]))
-    flag = torch.zeros(n, dtype=torch.int32, device=dev)
-    for f in range(F):
+    flag = flags[0]
+    for f in range(1, F):
         flag = torch.where((flag == 0) & (flags[f] != 0), flags[f], flag)
-    dead = flag != 0
-    if bool(dead.any()):
-        for f in range(F):
-            if bool((dead & (flags[f] == 0)).any()):
-                recs[f] = without(recs[f], dead)
-                sl[f] = lists(f, recs[f])
+    # an object refused in another frame is taken out of this one's lists; with
+    # one frame there is no other, and nothing to read back
+    if F > 1:
+        dead = flag != 0
+        if bool(dead.any()):
+            for f in range(F):
+                if bool((dead & (flags[f] == 0)).any()):
+                    recs[f] = without(recs[f], dead)
+                    sl[f] = lists(f, recs[f])
     models = [_render_fresh(fs.shapes[f][0], fs.shapes[f][1], sl[f][0], G, fs.jacs[f], sl[f][3],
                             sl[f][4]) for f in range(F)]
     A = None
     if tangents:
-        # the Kloc = nshape + 1 columns that are not zero in frame f
-        cols = np.concatenate([np.tile(np.arange(fs.nshape), (F, 1)),
-                               (fs.nshape + fs.band)[:, None]], axis=1)
         d5 = dmix.reshape(n, F, G, 6, fs.K)
-        A = torch.stack([d5[:, f][..., torch.from_numpy(cols[f]).to(dev)] for f in range(F)])
-        A = A.contiguous()
+        if fs.K == fs.nshape + 1:
+            # one band: every column is local in every frame (F = 1: a view)
+            A = d5.permute(1, 0, 2, 3, 4).contiguous()
+        else:
+            # the Kloc = nshape + 1 columns that are not zero in frame f
+            cols = np.concatenate([np.tile(np.arange(fs.nshape), (F, 1)),
+                                   (fs.nshape + fs.band)[:, None]], axis=1)
+            A = torch.stack([d5[:, f][..., torch.from_numpy(cols[f]).to(dev)]
+                             for f in range(F)]).contiguous()
     return dict(G=G, recs=recs, A=A, flag=flag, boxes=[s[2] for s in sl],
                 pair_obj=[s[3] for s in sl], tile_start=[s[4] for s in sl], models=models)
 
 
-def _scene_normal_frames(recs, G, jacs, A, K, wframes, resids, band, boxes_host, items_host):
-    """ngmix_scene_normal_frames over the (nitems, 2) int32 host table: (blocks
-    (nitems, K, K), vectors (nitems, K)).  recs, jacs, wframes (entries may be
-    None), resids, boxes_host: one per frame; A: (F, n, G, 6, Kloc)"""
+def _scene_normal(fs, fm, resids, items_host, one_frame=None):
+    """
+    The blocks (nitems, K, K) and vectors (nitems, K) of the (nitems, 2) int32
+    host item table, from fm = _frames_model(fs, ..., tangents=True) and the
+    frames' residuals: the one place that launches the normal-equation kernels.
+
+    One frame of one band (K == Kloc) goes through ngmix_scene_normal, anything
+    else through ngmix_scene_normal_frames.  There the two give the same bits
+    (scene_normal_frames_kernel adds the one frame's block once into +0, under
+    the identity column map), so the choice is speed only: the one-frame kernel
+    was measured about 6 % faster over the same blocks, at 104 against 136
+    VGPRs.  one_frame: True / False force an entry (the
+    tests hold the two together through it).
+    """
     torch = _torch()
-    dev = resids[0].device
-    F, n, Kloc = int(A.shape[0]), int(A.shape[1]), int(A.shape[4])
+    dev, n, K, F, G = fs.dev, fs.n, fs.K, fs.F, fm["G"]
+    Kloc = fs.nshape + 1
+    if one_frame is None:
+        one_frame = F == 1 and K == Kloc
+    elif one_frame and not (F == 1 and K == Kloc):
+        raise ValueError("scene: ngmix_scene_normal takes one frame of one band")
     nitems = int(items_host.shape[0])
     mat = torch.empty((nitems, K, K), dtype=torch.float64, device=dev)
     vec = torch.empty((nitems, K), dtype=torch.float64, device=dev)
     items_host = np.ascontiguousarray(items_host, dtype=np.int32)
     items = torch.from_numpy(items_host).to(dev)
-    boxes = torch.from_numpy(np.ascontiguousarray(np.stack(boxes_host), dtype=np.int32)).to(dev)
-    rec = torch.cat(recs).contiguous()
-    jac = torch.cat(jacs).contiguous()
-    A = A.detach().to(torch.float64).contiguous()
+    boxes = torch.from_numpy(np.ascontiguousarray(np.stack(fm["boxes"]), dtype=np.int32)).to(dev)
+    L = _lib.lib()
+    if one_frame:
+        w = fs.wframes[0]
+        with _on_device(dev):
+            st = L.ngmix_scene_normal(
+                _dptr(fm["recs"][0]), G, _dptr(fs.jacs[0]), n, _dptr(fm["A"]), K,
+                _dptr(w) if w is not None else None, _dptr(resids[0]), fs.shapes[0][0],
+                fs.shapes[0][1], _dptr(boxes), _dptr(items), _lib.ptr(items_host), nitems,
+                _dptr(mat), _dptr(vec), _stream())
+        _lib.check(st, "ngmix_scene_normal")
+        return mat, vec
+    rec = torch.cat(fm["recs"]).contiguous()
+    jac = torch.cat(fs.jacs).contiguous()
     table = np.zeros(F, dtype=_lib.SCENE_FRAME_DTYPE)
     for f in range(F):
         table[f] = (resids[f].data_ptr(),
-                    wframes[f].data_ptr() if wframes[f] is not None else 0,
-                    int(resids[f].shape[0]), int(resids[f].shape[1]), int(band[f]), 0)
+                    fs.wframes[f].data_ptr() if fs.wframes[f] is not None else 0,
+                    fs.shapes[f][0], fs.shapes[f][1], int(fs.band[f]), 0)
     d_table = torch.from_numpy(table.view(np.uint8)).to(dev)
     with _on_device(dev):
-        st = _lib.lib().ngmix_scene_normal_frames(
-            _dptr(rec), G, _dptr(jac), n, _dptr(A), Kloc, K, _dptr(d_table), _lib.ptr(table), F,
-            _dptr(boxes), _dptr(items), _lib.ptr(items_host), nitems, _dptr(mat), _dptr(vec),
-            _stream())
+        st = L.ngmix_scene_normal_frames(
+            _dptr(rec), G, _dptr(jac), n, _dptr(fm["A"]), Kloc, K, _dptr(d_table),
+            _lib.ptr(table), F, _dptr(boxes), _dptr(items), _lib.ptr(items_host), nitems,
+            _dptr(mat), _dptr(vec), _stream())
     _lib.check(st, "ngmix_scene_normal_frames")
     return mat, vec
 
 
 def _normal_frames(fs, pars, ngauss, max_pairs):
-    """normal_equations_frames on checked arguments; its dict plus what
-    fit_joint_frames reads: _tile_chi2, _tile_group (per frame, host), _group,
-    _models, _prior_ff"""
+    """normal_equations and normal_equations_frames on checked arguments (fs);
+    their dict plus what _fit_loop and _Frames read: _tile_chi2, _tile_group
+    (per frame, host), _group, _models, _prior_ff"""
     from .prior_batch import prior_normal_sums
     torch = _torch()
     dev, n, K, F = fs.dev, fs.n, fs.K, fs.F
@@ -1904,8 +1818,9 @@ def _normal_frames(fs, pars, ngauss, max_pairs):
         ntiles = [((s[0] + TILE_H - 1) // TILE_H) * ((s[1] + TILE_W - 1) // TILE_W)
                   for s in fs.shapes]
         tile_group = [np.full(t, -1, dtype=np.int64) for t in ntiles]
-        _, tile_chi2 = _frames_chi2_group(fs, models, tile_group, np.zeros(0, dtype=np.int64), 0,
-                                          np.zeros(0))
+        # (no model: the residuals are the frames)
+        _, tile_chi2 = _frames_chi2_group(fs, fs.frames, tile_group,
+                                          np.zeros(0, dtype=np.int64), 0, np.zeros(0))
         return dict(F_self=torch.zeros((0, K, K), **f64), grad=torch.zeros((0, K), **f64),
                     pairs=torch.zeros((0, 2), dtype=torch.int64, device=dev),
                     F_cross=torch.zeros((0, K, K), **f64),
@@ -1926,14 +1841,12 @@ def _normal_frames(fs, pars, ngauss, max_pairs):
         n)
     ngroups = int(group.max()) + 1
     prior_ff = _prior_ff(fs, pars, fm["flag"])
-    chi2_group, tile_chi2 = _frames_chi2_group(fs, fm["models"], tile_group, group, ngroups,
-                                               prior_ff)
+    chi2_group, tile_chi2 = _frames_chi2_group(fs, resids, tile_group, group, ngroups, prior_ff)
     items = np.empty((n + P, 2), dtype=np.int32)
     items[:n, 0] = np.arange(n)
     items[:n, 1] = -1
     items[n:] = pairs.cpu().numpy()
-    mat, vec = _scene_normal_frames(fm["recs"], fm["G"], fs.jacs, fm["A"], K, fs.wframes, resids,
-                                    fs.band, fm["boxes"], items)
+    mat, vec = _scene_normal(fs, fm, resids, items)
     F_self, grad = mat[:n], vec[:n]
     if fs.prior is not None:
         sums, _ = prior_normal_sums(fs.prior, pars)

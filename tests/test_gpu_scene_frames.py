@@ -203,24 +203,66 @@ def test_composition_against_the_one_band_kernel(name):
     assert np.abs(got["F_cross"]).max() > 0.0 and np.all(np.isfinite(got["F_self"]))
 
 
+KEYS = ("F_self", "grad", "pairs", "F_cross", "group", "chi2_group", "status")
+
+
+def one_frame_calls(case):
+    """(args, kwargs) of the one-frame API on frame 0 of case, and of the frames
+    API on the list of that one frame: one band, no prior"""
+    pars = case.one_band(0)
+    one = ((case.frames[0], case.d_w[0], case.jac[0], pars, "exp"), dict(psf=case.psf[0]))
+    many = (([case.frames[0]], [case.d_w[0]], [case.jac[0]], pars, "exp"),
+            dict(psf=[case.psf[0]]))
+    return one, many
+
+
 def test_one_frame_one_band_is_normal_equations():
+    """F = 1, nband = 1: ngmix_scene_normal and ngmix_scene_normal_frames give
+    the same bits on the same records, tangents, residual, boxes and item table
+    (the frames kernel adds the one frame's block once into +0, under the
+    identity column map), and the two public calls agree in every key"""
     scene = _scene()
     case = base_case()
-    pars = case.one_band(0)
-    ne1 = scene.normal_equations(case.frames[0], case.d_w[0], case.jac[0], pars, "exp",
-                                 psf=case.psf[0])
-    neF = scene.normal_equations_frames([case.frames[0]], [case.d_w[0]], [case.jac[0]], pars,
-                                        "exp", psf=[case.psf[0]])
-    assert ne1["pairs"].shape[0] >= 2
-    gaps, same = [], True
-    for k in ("F_self", "grad", "F_cross"):
-        a, b = neF[k].cpu().numpy(), ne1[k].cpu().numpy()
-        gaps.append(block_gap(a, b))
-        same = same and np.array_equal(a, b)
-    print("F = 1, nband = 1 against normal_equations: gaps %s, bits equal: %s" % (gaps, same))
-    assert max(gaps) <= 1e-12
-    for k in ("pairs", "group", "chi2_group", "status"):
+    (a1, k1), (aF, kF) = one_frame_calls(case)
+    fs = scene._Frames.one(*(a1 + (k1["psf"], "t")))
+    assert (fs.F, fs.n, fs.K, fs.shapes[0]) == (1, 4, 6, (37, 53))
+    fm = scene._frames_model(fs, fs.pars, None, None, True)
+    assert fm["G"] == 18
+    resids = [(fs.frames[0] - fm["models"][0]).contiguous()]
+    ne1 = scene.normal_equations(*a1, **k1)
+    pairs = ne1["pairs"].cpu().numpy()
+    assert pairs.shape[0] >= 2
+    n = case.n
+    items = np.concatenate([np.stack([np.arange(n), -np.ones(n, dtype=np.int64)], axis=1),
+                            pairs]).astype(np.int32)
+    mat1, vec1 = scene._scene_normal(fs, fm, resids, items, one_frame=True)
+    matF, vecF = scene._scene_normal(fs, fm, resids, items, one_frame=False)
+    assert np.array_equal(matF.cpu().numpy(), mat1.cpu().numpy())
+    assert np.array_equal(vecF.cpu().numpy(), vec1.cpu().numpy())
+    assert np.abs(mat1[n:].cpu().numpy()).max() > 0.0 and np.all(np.isfinite(mat1.cpu().numpy()))
+    neF = scene.normal_equations_frames(*aF, **kF)
+    for k in KEYS:
         assert np.array_equal(neF[k].cpu().numpy(), ne1[k].cpu().numpy()), k
+    assert np.array_equal(ne1["F_self"].cpu().numpy(), mat1[:n].cpu().numpy())
+
+
+@pytest.mark.parametrize("large_groups", ["jacobi", "cg"])
+def test_one_frame_one_band_fit_is_fit_joint(large_groups):
+    """fit_joint is fit_joint_frames over the list of its frame, one band, no
+    prior: every key to the bit.  max_group=1 puts the pairs' groups on the
+    large_groups route"""
+    scene = _scene()
+    (a1, k1), (aF, kF) = one_frame_calls(base_case())
+    kw = dict(maxiter=3, max_group=1, large_groups=large_groups)
+    res1 = scene.fit_joint(*a1, **dict(k1, **kw))
+    resF = scene.fit_joint_frames(*aF, **dict(kF, **kw))
+    assert sorted(res1) == sorted(resF)
+    for k in res1:
+        assert np.array_equal(np.asarray(res1[k]), np.asarray(resF[k]), equal_nan=True), k
+    assert res1["joint_status"].max() == (2 if large_groups == "cg" else 1)
+    assert res1["niter"].max() >= 1
+    if large_groups == "cg":
+        assert res1["cg_iter"].max() >= 1
 
 
 def test_gradient_against_autograd_and_chi2():
@@ -250,9 +292,6 @@ def test_gradient_against_autograd_and_chi2():
     assert ne["chi2_group"].shape == (1,) and abs(tot - chi2) <= 1e-12 * chi2
 
 
-KEYS = ("F_self", "grad", "pairs", "F_cross", "group", "chi2_group", "status")
-
-
 def test_determinism_and_the_item_table():
     scene = _scene()
     case = base_case()
@@ -270,8 +309,7 @@ def test_determinism_and_the_item_table():
     items = np.concatenate([np.stack([np.arange(n), -np.ones(n, dtype=np.int64)], axis=1), pairs])
 
     def run(items):
-        return scene._scene_normal_frames(fm["recs"], fm["G"], fs.jacs, fm["A"], fs.K, fs.wframes,
-                                          resids, fs.band, fm["boxes"], items.astype(np.int32))
+        return scene._scene_normal(fs, fm, resids, items.astype(np.int32))
 
     mat, vec = run(items)
     assert np.array_equal(mat[:n].cpu().numpy(), one["F_self"].cpu().numpy())

@@ -379,9 +379,9 @@ def test_touching_boxes_and_a_shared_tile():
     shape = (24, 24)
     w = weights(shape, seed=8)
     frame = data_frame(shape, jac, pars, "gauss", None, seed=4)
-    jm = scene._joint_model(shape, torch.from_numpy(jac).cuda(), torch.from_numpy(pars).cuda(),
-                            "gauss", None, None, None, False)
-    assert jm["boxes"][:, :4].tolist() == [[7, 13, 7, 13], [13, 19, 13, 19], [7, 13, 0, 6]]
+    fs = scene._Frames.one(frame, None, jac, pars, "gauss", None, "t")
+    fm = scene._frames_model(fs, fs.pars, None, None, False)
+    assert fm["boxes"][0][:, :4].tolist() == [[7, 13, 7, 13], [13, 19, 13, 19], [7, 13, 0, 6]]
     ne = scene.normal_equations(frame, torch.from_numpy(w).cuda(), jac, pars, "gauss")
     assert ne["pairs"].cpu().numpy().tolist() == [[0, 1]]
     assert ne["group"].cpu().numpy().tolist() == [0, 0, 0]
@@ -406,29 +406,26 @@ def test_determinism_permutation_and_isolation():
         assert np.array_equal(one[k].cpu().numpy(), two[k].cpu().numpy()), k
 
     # the item table in another order (and longer): the same bits per item
-    d_jac = torch.from_numpy(jac).cuda()
-    d_pars = torch.from_numpy(pars).cuda()
-    jm = scene._joint_model(SHAPE, d_jac, d_pars, "exp", psf, None, None, True)
-    resid = (frame - jm["model"]).contiguous()
+    fs = scene._Frames.one(frame, d_w, jac, pars, "exp", psf, "t")
+    fm = scene._frames_model(fs, fs.pars, None, None, True)
+    resids = [(frame - fm["models"][0]).contiguous()]
     n = pars.shape[0]
     pairs = one["pairs"].cpu().numpy()
     items = np.concatenate([np.stack([np.arange(n), -np.ones(n, dtype=np.int64)], axis=1), pairs])
-    mat, vec = scene._scene_normal(jm["rec"], jm["G"], d_jac, jm["dmix"], d_w.contiguous(), resid,
-                                   jm["boxes"], items.astype(np.int32))
+    mat, vec = scene._scene_normal(fs, fm, resids, items.astype(np.int32), one_frame=True)
     assert np.array_equal(mat[:n].cpu().numpy(), one["F_self"].cpu().numpy())
     assert np.array_equal(mat[n:].cpu().numpy(), one["F_cross"].cpu().numpy())
     assert np.array_equal(vec[:n].cpu().numpy(), one["grad"].cpu().numpy())
     perm = np.random.RandomState(1).permutation(items.shape[0])
     perm = np.concatenate([perm, perm[:5]])
-    mat2, vec2 = scene._scene_normal(jm["rec"], jm["G"], d_jac, jm["dmix"], d_w.contiguous(),
-                                     resid, jm["boxes"], items[perm].astype(np.int32))
+    mat2, vec2 = scene._scene_normal(fs, fm, resids, items[perm].astype(np.int32), one_frame=True)
     assert np.array_equal(mat2.cpu().numpy(), mat.cpu().numpy()[perm])
     assert np.array_equal(vec2.cpu().numpy(), vec.cpu().numpy()[perm])
     # a bad item is refused on the host copy, before any launch
+    fs.wframes = [None]
     for bad in ([3, 3], [4, 2], [n, -1], [-1, 2], [0, n], [0, -2]):
         with pytest.raises(ValueError, match="scene_normal: item 0"):
-            scene._scene_normal(jm["rec"], jm["G"], d_jac, jm["dmix"], None, resid, jm["boxes"],
-                                np.array([bad], dtype=np.int32))
+            scene._scene_normal(fs, fm, resids, np.array([bad], dtype=np.int32), one_frame=True)
 
     # a refused object: NaN rows for itself, the others as without it
     bad_pars = pars.copy()

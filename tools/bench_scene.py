@@ -223,11 +223,12 @@ def main():
         frame = frame + 0.01 * torch.randn(shape, generator=gen, dtype=torch.float64,
                                            device="cuda")
         # the lists and the item table the call would build
-        jm = scene._joint_model(shape, d_jac, d_pars, "exp", d_psf, None, None, True)
-        hb = jm["boxes"].astype(np.int64)
-        pairs = scene._scene_pairs(jm["pair_obj"], jm["tile_start"], torch.from_numpy(hb), n)
-        group, _ = scene._scene_groups(jm["pair_obj"].cpu().numpy(),
-                                       jm["tile_start"].cpu().numpy(), n)
+        fs = scene._Frames.one(frame, None, d_jac, d_pars, "exp", d_psf, "bench_scene")
+        fm = scene._frames_model(fs, fs.pars, None, None, True)
+        hb = fm["boxes"][0].astype(np.int64)
+        pairs = scene._scene_pairs(fm["pair_obj"][0], fm["tile_start"][0], torch.from_numpy(hb), n)
+        group, _ = scene._scene_groups(fm["pair_obj"][0].cpu().numpy(),
+                                       fm["tile_start"][0].cpu().numpy(), n)
         P = int(pairs.shape[0])
         gsize = np.bincount(group)
         edges = [1, 2, 3, 5, 9, 17, 65, 257, 1025, 1 << 30]
@@ -244,22 +245,22 @@ def main():
         items[:n, 0] = np.arange(n)
         items[:n, 1] = -1
         items[n:] = pairs.cpu().numpy()
-        resid = (frame - jm["model"]).contiguous()
+        resid = (frame - fm["models"][0]).contiguous()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         d_items = torch.from_numpy(items).cuda()
-        d_boxes = torch.from_numpy(jm["boxes"]).cuda()
+        d_boxes = torch.from_numpy(fm["boxes"][0]).cuda()
         K = 6
         mat = torch.empty((n + P, K, K), dtype=torch.float64, device="cuda")
         vec = torch.empty((n + P, K), dtype=torch.float64, device="cuda")
-        A = jm["dmix"].contiguous()
+        A = fm["A"]
         t_kern = []
         for rep in range(args.reps + 1):
             torch.cuda.synchronize()
             e0.record()
             _lib.check(L.ngmix_scene_normal(
-                _dptr(jm["rec"]), G, _dptr(d_jac), n, _dptr(A), K, None, _dptr(resid), size, size,
-                _dptr(d_boxes), _dptr(d_items), None, n + P, _dptr(mat), _dptr(vec), _stream()),
-                "scene_normal")
+                _dptr(fm["recs"][0]), G, _dptr(d_jac), n, _dptr(A), K, None, _dptr(resid), size,
+                size, _dptr(d_boxes), _dptr(d_items), None, n + P, _dptr(mat), _dptr(vec),
+                _stream()), "scene_normal")
             e1.record()
             torch.cuda.synchronize()
             if rep:
@@ -277,7 +278,7 @@ def main():
         r_lo, c_lo = hb[idx, 0], hb[idx, 2]
         wr, wc = hb[idx, 1] - hb[idx, 0] + 1, hb[idx, 3] - hb[idx, 2] + 1
         d_idx = torch.from_numpy(idx).cuda()
-        mix_hit, dmix_hit = mix[d_idx].contiguous(), jm["dmix"][d_idx].contiguous()
+        mix_hit, dmix_hit = mix[d_idx].contiguous(), A[0][d_idx].contiguous()
 
         def long_way():
             sb = scene.cut_stamps(frame, 1.0, r_lo, c_lo, wr, wc, jac[idx])
