@@ -380,6 +380,30 @@ int ngmix_prepsf_sums_batch(const double *kim_re, const double *kim_im, const do
                             const double *fk, const double *wgt, int64_t nstamps, int nmodes,
                             int64_t stride_n, int64_t stride_r, int nrows, int ncols,
                             double df2, double df4, double *out, void *stream);
+/* DEVICE: the spectra of metacalibration images (ngmix/metacal/metacal.py,
+   there through galsim): every stamp deconvolved from its psf stamp, sheared
+   and reconvolved with a round gaussian of width sigma (1 + 2|g|) carrying the
+   psf image's flux, at the modes of the stamp's own FFT grid.  The transform of
+   the samples is evaluated exactly at the sheared frequency q' = J^T A J^-T q of
+   every output mode q; a mode is kept only where |q'_row| < pi and |q'_col| <
+   pi.  images (nstamps, nrow, ncol); noise the same or NULL: a second plane
+   put through the same operation; psf (nstamps, psf_nrow, psf_ncol); jac
+   (nstamps,) the images' jacobians, whose derivatives the psf stamps share;
+   psf_cen (nstamps, 2) the psf stamps' centres; psf_flux, sigma (nstamps,); g
+   (ntypes, 2), or (nstamps, ntypes, 2) with per_stamp_g; g_host: the same
+   shears in HOST memory, checked here (|g| < 1) before anything is launched.
+   spec (nstamps, ntypes, planes, nrow, ncol / 2 + 1) complex128, planes = 2
+   with a noise plane: O^(q) exp(-i q . centre), hermitian on its Nyquist row
+   and column, so that a complex-to-real inverse FFT of shape (nrow, ncol)
+   gives the image about the same centre.  flags (nstamps, ntypes): 1 where a
+   kept mode was not finite (a psf transform of zero); that mode is NaN.  One
+   launch; nstamps <= 0 is a no-op */
+int ngmix_metacal_spectrum_batch(const double *images, const double *noise, const double *psf,
+                                 const ngmix_jacobian *jac, const double *psf_cen,
+                                 const double *psf_flux, const double *sigma, const double *g,
+                                 const double *g_host, int per_stamp_g, int64_t nstamps,
+                                 int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
+                                 double *spec, int32_t *flags, void *stream);
 /* DEVICE: the innermost functions of the fast pixel evaluation over an array
    (fastexp_nb.py): which = 0 fexp = exp5_smooth(x) (:223-265; no range check:
    x in (-15.5, 1.5)), 1 apod_window(chi2) (:97-117), 2 apod_window_deriv(chi2)

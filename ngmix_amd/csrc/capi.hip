@@ -525,6 +525,18 @@ int ngmix_prepsf_sums_batch(const double *kim_re, const double *kim_im, const do
                               (hipStream_t)stream);
 }
 
+int ngmix_metacal_spectrum_batch(const double *images, const double *noise, const double *psf,
+                                 const ngmix_jacobian *jac, const double *psf_cen,
+                                 const double *psf_flux, const double *sigma, const double *g,
+                                 const double *g_host, int per_stamp_g, int64_t nstamps,
+                                 int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
+                                 double *spec, int32_t *flags, void *stream)
+{
+    return launch_metacal_spectrum(images, noise, psf, jac, psf_cen, psf_flux, sigma, g, g_host,
+                                   per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow, psf_ncol,
+                                   spec, flags, (hipStream_t)stream);
+}
+
 int ngmix_fastexp_batch(const double *x, double *out, int64_t n, int which, void *stream)
 {
     return launch_fastexp(x, out, n, which, (hipStream_t)stream);

@@ -36,6 +36,13 @@ int launch_prepsf_sums(const double *kim_re, const double *kim_im, const double 
                        const double *wgt, int64_t nstamps, int M, int64_t stride_n,
                        int64_t stride_r, int R, int C, double df2, double df4, double *out,
                        hipStream_t s);
+// metacal.hip
+int launch_metacal_spectrum(const double *images, const double *noise, const double *psf,
+                            const ngmix_jacobian *jac, const double *psf_cen,
+                            const double *psf_flux, const double *sigma, const double *g,
+                            const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
+                            int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
+                            int32_t *flags, hipStream_t s);
 // loglike_grad.hip
 int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double *out,
                         double *grad, int32_t *status, hipStream_t s);

@@ -1,0 +1,382 @@
+// Metacalibration images (reference: ngmix/metacal/metacal.py, there through
+// galsim): the spectrum of a stamp deconvolved from its psf, sheared and
+// reconvolved with a round gaussian, at the modes of the stamp's own FFT grid.
+//
+// Under a shear the transform of the image is needed at frequencies that are
+// not on the grid.  A stamp is a few thousand samples: their discrete-time
+// Fourier transform is evaluated exactly at the sheared frequency of every
+// output mode -- the band-limited interpolant without an interpolation error
+// -- as a dense sum of modes x pixels terms per stamp.
+//
+// One block per (stamp, shear type).  The stamp, its psf stamp and a noise
+// plane are staged in LDS once; every thread owns output modes of the half
+// plane b <= C/2 (the image is real) and walks ALL pixels in the same order,
+// so every LDS read is one address for the whole wave.  The phase of a pixel
+// is carried by a complex-multiply recurrence along the row, re-seeded from
+// sincos every SEED rows and columns; image, noise and psf share it (the psf
+// up to one factor per mode for its own centre): 4 FMA per pixel for the
+// phase and 2 per pixel and plane for the sums.
+#include "common.hpp"
+#include "device_utils.hpp"
+#include "launch.hpp"
+#include "launch_util.hpp"
+
+#include <string>
+
+namespace ngmix {
+
+namespace {
+
+constexpr int SEED = 16;           // pixels between two sincos seeds of the phase
+constexpr double PI = 3.141592653589793;
+
+struct cplx { double x, y; };
+
+NGMIX_HD cplx cmul(cplx a, cplx b)
+{
+    return {fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x)};
+}
+
+NGMIX_HD cplx cexpi(double phase)
+{
+    double s, c;
+    sincos(phase, &s, &c);
+    return {c, s};
+}
+
+// numpy's complex division (Smith's algorithm, npymath)
+NGMIX_HD cplx cdiv(cplx a, cplx b)
+{
+    const double abs_br = fabs(b.x), abs_bi = fabs(b.y);
+    if (abs_br >= abs_bi) {
+        if (abs_br == 0 && abs_bi == 0) return {a.x / abs_br, a.y / abs_bi};
+        const double rat = b.y / b.x, scl = 1.0 / (b.x + b.y * rat);
+        return {(a.x + a.y * rat) * scl, (a.y - a.x * rat) * scl};
+    }
+    const double rat = b.x / b.y, scl = 1.0 / (b.y + b.x * rat);
+    return {(a.x * rat + a.y) * scl, (a.y * rat - a.x) * scl};
+}
+
+// the integer numerator of fftfreq(n)[i]
+NGMIX_HD int fft_index(int i, int n) { return i < (n + 1) / 2 ? i : i - n; }
+
+// 2 pi fftfreq(n)[i]; the Nyquist entry of an even n is exactly -pi
+NGMIX_HD double grid_freq(int i, int n)
+{
+    return (2.0 * PI) * ((double)fft_index(i, n) / (double)n);
+}
+
+// the stamps of one block: image (R x C), noise (R x C or null), psf (Rp x Cp)
+struct Planes {
+    const double *img, *noise, *psf;
+    int R, C, Rp, Cp;
+};
+
+// sum plane[r, c] exp(-i (qr (r - r0) + qc (c - c0))) for the image, the noise
+// plane and the psf, all about the IMAGE's centre.  Every thread of a block
+// runs the same loops: the bounds depend on the shapes alone.
+template <bool NOISE>
+NGMIX_HD void transforms(const Planes &p, double r0, double c0, double qr, double qc, cplx &si,
+                         cplx &sn, cplx &sp)
+{
+    si = sn = sp = {0.0, 0.0};
+    const cplx zc = cexpi(-qc), zr = cexpi(-qr);
+    const int Rm = p.R > p.Rp ? p.R : p.Rp, Cm = p.C > p.Cp ? p.C : p.Cp;
+    for (int cs = 0; cs < Cm; cs += SEED) {
+        const cplx cseed = cexpi(-qc * ((double)cs - c0));
+        int ni = p.C - cs, np = p.Cp - cs;
+        ni = ni < 0 ? 0 : ni > SEED ? SEED : ni;
+        np = np < 0 ? 0 : np > SEED ? SEED : np;
+        for (int rs = 0; rs < Rm; rs += SEED) {
+            cplx prow = cmul(cexpi(-qr * ((double)rs - r0)), cseed);
+            const int re = rs + SEED < Rm ? rs + SEED : Rm;
+            for (int r = rs; r < re; r++) {
+                const int mi = r < p.R ? ni : 0, mp = r < p.Rp ? np : 0;
+                const int both = mi < mp ? mi : mp;
+                const double *ri = p.img + (int64_t)r * p.C + cs;
+                const double *rn = NOISE ? p.noise + (int64_t)r * p.C + cs : nullptr;
+                const double *rp = p.psf + (int64_t)r * p.Cp + cs;
+                cplx ph = prow;
+                int k = 0;
+                for (; k < both; k++) {
+                    const double vi = ri[k], vp = rp[k];
+                    si.x = fma(vi, ph.x, si.x);
+                    si.y = fma(vi, ph.y, si.y);
+                    if (NOISE) {
+                        const double vn = rn[k];
+                        sn.x = fma(vn, ph.x, sn.x);
+                        sn.y = fma(vn, ph.y, sn.y);
+                    }
+                    sp.x = fma(vp, ph.x, sp.x);
+                    sp.y = fma(vp, ph.y, sp.y);
+                    ph = cmul(ph, zc);
+                }
+                for (; k < mi; k++) {
+                    const double vi = ri[k];
+                    si.x = fma(vi, ph.x, si.x);
+                    si.y = fma(vi, ph.y, si.y);
+                    if (NOISE) {
+                        const double vn = rn[k];
+                        sn.x = fma(vn, ph.x, sn.x);
+                        sn.y = fma(vn, ph.y, sn.y);
+                    }
+                    ph = cmul(ph, zc);
+                }
+                for (; k < mp; k++) {
+                    const double vp = rp[k];
+                    sp.x = fma(vp, ph.x, sp.x);
+                    sp.y = fma(vp, ph.y, sp.y);
+                    ph = cmul(ph, zc);
+                }
+                prow = cmul(prow, zr);
+            }
+        }
+    }
+}
+
+// what a mode needs of its stamp and shear
+struct ModeSetup {
+    double r0, c0, pr0, pc0;       // centres of the image and of the psf
+    double j00, j01, j10, j11;     // J = [[dvdrow, dvdcol], [dudrow, dudcol]]
+    double i00, i01, i10, i11;     // J^-T
+    double d00, d01, d11;          // A - 1 (symmetric), exactly 0 at g = 0
+    double flux, half_sig2;        // sum of the psf image, (sigma_T (1 + 2|g|))^2 / 2
+};
+
+NGMIX_HD ModeSetup mode_setup(const ngmix_jacobian &jac, double pr0, double pc0, double g1,
+                              double g2, double sigma, double flux)
+{
+    ModeSetup m;
+    m.r0 = jac.row0;
+    m.c0 = jac.col0;
+    m.pr0 = pr0;
+    m.pc0 = pc0;
+    m.j00 = jac.dvdrow;
+    m.j01 = jac.dvdcol;
+    m.j10 = jac.dudrow;
+    m.j11 = jac.dudcol;
+    const double det = m.j00 * m.j11 - m.j01 * m.j10;
+    m.i00 = m.j11 / det;
+    m.i01 = -m.j10 / det;
+    m.i10 = -m.j01 / det;
+    m.i11 = m.j00 / det;
+    const double root = sqrt(1.0 - g1 * g1 - g2 * g2);
+    m.d00 = (1.0 - g1) / root - 1.0;
+    m.d01 = g2 / root;
+    m.d11 = (1.0 + g1) / root - 1.0;
+    const double sig = sigma * (1.0 + 2.0 * sqrt(g1 * g1 + g2 * g2));
+    m.half_sig2 = 0.5 * (sig * sig);
+    m.flux = flux;
+    return m;
+}
+
+// O^(q) exp(-i q . centre) of the image (and of the noise plane) at the grid
+// frequency q = (qa, qb): zero outside the band; bad is set when a kept mode
+// is not finite (its value is NaN then, never an infinity)
+template <bool NOISE>
+NGMIX_HD void mode_value(const Planes &p, const ModeSetup &m, double qa, double qb, cplx &oi,
+                         cplx &on, bool &bad)
+{
+    oi = on = {0.0, 0.0};
+    // world frequency (v, u), the sheared one, and back to pixel axes:
+    // q' = q + J^T (A - 1) J^-T q
+    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
+    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
+    const double qr = qa + (m.j00 * dv + m.j10 * du), qc = qb + (m.j01 * dv + m.j11 * du);
+    if (!(fabs(qr) < PI && fabs(qc) < PI)) return;
+    cplx si, sn, sp;
+    transforms<NOISE>(p, m.r0, m.c0, qr, qc, si, sn, sp);
+    // the psf about its own centre
+    sp = cmul(sp, cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
+    const double target = m.flux * exp(-m.half_sig2 * (kv * kv + ku * ku));
+    const cplx shift = cexpi(-(qa * m.r0 + qb * m.c0));
+    cplx o = cdiv(si, sp);
+    oi = cmul(cplx{o.x * target, o.y * target}, shift);
+    bool ok = isfinite(oi.x) && isfinite(oi.y);
+    if (NOISE) {
+        o = cdiv(sn, sp);
+        on = cmul(cplx{o.x * target, o.y * target}, shift);
+        ok = ok && isfinite(on.x) && isfinite(on.y);
+    }
+    if (!ok) {
+        bad = true;
+        oi = on = {NAN, NAN};
+    }
+}
+
+// The real part of the inverse DFT of a full plane F is the inverse of its
+// hermitian part (F[a, b] + conj F[-a, -b]) / 2.  For a mode off the Nyquist
+// row and column the two terms are equal (the transform of a real stamp at
+// -q' is the conjugate of the one at q').  On the Nyquist row / column of an
+// even axis the grid has -pi alone: the partner (-a, -b) sits at another
+// frequency, which is evaluated as a second work item, and the two are
+// averaged.  nyq_items: how many modes of the half plane have such a partner.
+NGMIX_HD int nyq_row_items(int R, int C) { return R % 2 == 0 ? C / 2 + 1 : 0; }
+NGMIX_HD int nyq_col_items(int R, int C) { return C % 2 == 0 ? (R % 2 == 0 ? R - 1 : R) : 0; }
+
+// (a, b) of partner item s
+NGMIX_HD void nyq_item_mode(int s, int R, int C, int &a, int &b)
+{
+    const int nrow = nyq_row_items(R, C);
+    if (s < nrow) {
+        a = R / 2;
+        b = s;
+    } else {
+        const int t = s - nrow;
+        a = (R % 2 == 0 && t >= R / 2) ? t + 1 : t;
+        b = C / 2;
+    }
+}
+
+// the partner item of mode (a, b), or -1
+NGMIX_HD int nyq_item_of(int a, int b, int R, int C)
+{
+    if (R % 2 == 0 && a == R / 2) return b;
+    if (C % 2 == 0 && b == C / 2) return nyq_row_items(R, C) + (R % 2 == 0 && a > R / 2 ? a - 1 : a);
+    return -1;
+}
+
+}  // namespace
+
+size_t metacal_lds_bytes(int R, int C, int Rp, int Cp, bool noise)
+{
+    const size_t planes = (size_t)R * C * (noise ? 2 : 1) + (size_t)Rp * Cp;
+    const size_t items = (size_t)(nyq_row_items(R, C) + nyq_col_items(R, C));
+    return (planes + items * 4 * (noise ? 2 : 1)) * sizeof(double);
+}
+
+// images (N, R, C), noise (N, R, C) with NOISE, psf (N, Rp, Cp); jac (N,): the
+// image's jacobian; psf_cen (N, 2), psf_flux (N,), sigma (N,); g (ng, T, 2)
+// with ng = 1 (one shear per type) or N (a shear per stamp and type).
+// spec (N, T, planes, R, C/2 + 1) complex: the image's spectrum, then the
+// noise plane's; flags (N, T): 1 where a kept mode was not finite.
+template <bool NOISE>
+__global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
+    const double *__restrict__ images, const double *__restrict__ noise,
+    const double *__restrict__ psf, const ngmix_jacobian *__restrict__ jac,
+    const double *__restrict__ psf_cen, const double *__restrict__ psf_flux,
+    const double *__restrict__ sigma, const double *__restrict__ g, int per_stamp_g, int T,
+    int R, int C, int Rp, int Cp, double *__restrict__ spec, int32_t *__restrict__ flags)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t n = blockIdx.x / T;
+    const int t = blockIdx.x % T;
+    const int npix = R * C, nppix = Rp * Cp;
+    constexpr int NPL = NOISE ? 2 : 1;
+
+    double *s_img = (double *)smem;
+    double *s_noise = s_img + npix;
+    double *s_psf = s_img + (size_t)npix * NPL;
+    cplx *s_own = (cplx *)(s_psf + nppix);         // the Nyquist modes' own values
+    const int nitems = nyq_row_items(R, C) + nyq_col_items(R, C);
+    cplx *s_partner = s_own + (size_t)nitems * NPL;
+
+    for (int i = threadIdx.x; i < npix; i += blockDim.x) {
+        s_img[i] = images[n * npix + i];
+        if (NOISE) s_noise[i] = noise[n * npix + i];
+    }
+    for (int i = threadIdx.x; i < nppix; i += blockDim.x) s_psf[i] = psf[n * nppix + i];
+    __syncthreads();
+
+    const Planes planes = {s_img, NOISE ? s_noise : nullptr, s_psf, R, C, Rp, Cp};
+    const double *gt = g + ((per_stamp_g ? n * T : 0) + t) * 2;
+    const ModeSetup m =
+        mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], sigma[n], psf_flux[n]);
+
+    const int Ch = C / 2 + 1;
+    const int nmodes = R * Ch;
+    cplx *out = (cplx *)spec + ((n * T + t) * NPL) * (int64_t)nmodes;
+    bool bad = false;
+    for (int w = threadIdx.x; w < nmodes + nitems; w += blockDim.x) {
+        cplx oi, on;
+        if (w < nmodes) {
+            const int a = w / Ch, b = w % Ch;
+            mode_value<NOISE>(planes, m, grid_freq(a, R), grid_freq(b, C), oi, on, bad);
+            const int s = nyq_item_of(a, b, R, C);
+            if (s < 0) {
+                out[w] = oi;
+                if (NOISE) out[nmodes + w] = on;
+            } else {
+                s_own[s] = oi;
+                if (NOISE) s_own[nitems + s] = on;
+            }
+        } else {
+            const int s = w - nmodes;
+            int a, b;
+            nyq_item_mode(s, R, C, a, b);
+            mode_value<NOISE>(planes, m, grid_freq((R - a) % R, R), grid_freq((C - b) % C, C), oi,
+                              on, bad);
+            s_partner[s] = oi;
+            if (NOISE) s_partner[nitems + s] = on;
+        }
+    }
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    for (int s = threadIdx.x; s < nitems; s += blockDim.x) {
+        int a, b;
+        nyq_item_mode(s, R, C, a, b);
+        for (int pl = 0; pl < NPL; pl++) {
+            const cplx u = s_own[pl * nitems + s], v = s_partner[pl * nitems + s];
+            out[(int64_t)pl * nmodes + a * Ch + b] = {0.5 * (u.x + v.x), 0.5 * (u.y - v.y)};
+        }
+    }
+    if (threadIdx.x == 0) flags[n * T + t] = any_bad;
+}
+
+// g_host: the caller's host copy of g, checked here (|g| < 1) before anything
+// is launched
+int launch_metacal_spectrum(const double *images, const double *noise, const double *psf,
+                            const ngmix_jacobian *jac, const double *psf_cen,
+                            const double *psf_flux, const double *sigma, const double *g,
+                            const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
+                            int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
+                            int32_t *flags, hipStream_t s)
+{
+    if (nstamps <= 0) return NGMIX_OK;
+    if (!images || !psf || !jac || !psf_cen || !psf_flux || !sigma || !g || !g_host || !spec ||
+        !flags) {
+        set_last_error_msg("metacal_spectrum: images, psf, jac, psf_cen, psf_flux, sigma, g, "
+                           "g_host, spec and flags are required");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (ntypes <= 0 || nrow <= 0 || ncol <= 0 || psf_nrow <= 0 || psf_ncol <= 0) {
+        set_last_error_msg("metacal_spectrum: the number of types and the stamp shapes must be "
+                           "positive");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (nstamps * ntypes > 0x7fffffffll) {
+        set_last_error_msg("metacal_spectrum: too many (stamp, type) pairs for one launch");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    const size_t lds = metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr);
+    if (lds > 160 * 1024 || (int64_t)nrow * ncol > 0x7fffff || (int64_t)psf_nrow * psf_ncol > 0x7fffff) {
+        set_last_error_msg("metacal_spectrum: the stamp, its psf stamp and its noise plane do "
+                           "not fit the 160 KB of LDS");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    const int64_t ng = (per_stamp_g ? nstamps : 1) * ntypes;
+    for (int64_t i = 0; i < ng; i++) {
+        const double g1 = g_host[2 * i], g2 = g_host[2 * i + 1];
+        if (!(g1 * g1 + g2 * g2 < 1.0)) {
+            set_last_error_msg(("metacal_spectrum: shear " + std::to_string(i) +
+                                " is not inside the unit circle").c_str());
+            return NGMIX_ERR_BAD_ARG;
+        }
+    }
+    // the block size that leaves the fewest idle work-item slots (the larger on a tie)
+    const int nwork = nrow * (ncol / 2 + 1) + nyq_row_items(nrow, ncol) + nyq_col_items(nrow, ncol);
+    int block = BLOCK, waste = (nwork + BLOCK - 1) / BLOCK * BLOCK;
+    for (int b = BLOCK - WAVE; b >= WAVE; b -= WAVE) {
+        const int slots = (nwork + b - 1) / b * b;
+        if (slots < waste) {
+            waste = slots;
+            block = b;
+        }
+    }
+    const auto k = noise ? kernel(metacal_spectrum_kernel<true>, "metacal_spectrum_kernel<noise>")
+                         : kernel(metacal_spectrum_kernel<false>, "metacal_spectrum_kernel");
+    return launch(k, dim3((unsigned)(nstamps * ntypes)), dim3(block), lds, 48 * 1024, s, images,
+                  noise, psf, jac, psf_cen, psf_flux, sigma, g, per_stamp_g ? 1 : 0, ntypes, nrow,
+                  ncol, psf_nrow, psf_ncol, spec, flags);
+}
+
+}  // namespace ngmix

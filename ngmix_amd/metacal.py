@@ -1,0 +1,472 @@
+"""
+Metacalibration images (reference: ngmix/metacal/): for every stamp the five
+images `noshear, 1p, 1m, 2p, 2m` -- the object deconvolved from its psf,
+sheared, and reconvolved with a slightly larger round gaussian -- as batches
+on the device.
+
+THE INTERPOLANT DIFFERS FROM THE REFERENCE'S.  The reference shears through
+galsim: it interpolates a padded FFT of the stamp (Lanczos-15 in x, quintic in
+k).  Here the discrete-time Fourier transform of the stamp's own samples is
+evaluated exactly at the sheared frequency of every output mode -- the
+band-limited interpolant, with no interpolation error (csrc/metacal.hip;
+DESIGN.md, "metacalibration images", has the definition).  Pixel values and
+random streams are therefore NOT the reference's; signatures, container
+shapes, the target psf of 'fitgauss', the fixnoise recipe and the use made of
+`rng` are.
+
+    MetacalBatch(stamps, psf_stamps, psf='fitgauss', target_sigma=None, rng=None)
+        .get_all(step=0.01, types=None, fixnoise=False, noise=None)
+        .get_obs_galshear(g1, g2)
+    get_all_metacal(obs, psf='fitgauss', step=0.01, types=None, fixnoise=True,
+                    rng=None, use_noise_image=False)
+
+psf='fitgauss' and an explicit target_sigma are served.  psf='gauss',
+'azgauss', 'dilate' and galsim-object psfs are defined through galsim's stepk
+and interpolated images and raise NotImplementedError; so does shearing the
+psf (the `*_psf` types).
+"""
+import numpy as np
+
+from . import _lib
+from .jacobian import Jacobian
+from .observation import Observation, ObsList, MultiBandObsList
+
+__all__ = ["MetacalBatch", "get_all_metacal", "METACAL_TYPES", "METACAL_MINIMAL_TYPES",
+           "METACAL_PSF_FIT_FAILURE", "METACAL_NONFINITE"]
+
+METACAL_MINIMAL_TYPES = ["noshear", "1p", "1m", "2p", "2m"]
+METACAL_TYPES = METACAL_MINIMAL_TYPES
+DEFAULT_STEP = 0.01
+
+# per-stamp flags of the outputs
+METACAL_PSF_FIT_FAILURE = 1     # the adaptive moments of the psf stamp failed
+METACAL_NONFINITE = 2           # a kept mode of the spectrum was not finite
+
+_PSF_FIT_NTRY = 4
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _check_psf_kind(psf):
+    if isinstance(psf, str):
+        if psf == "fitgauss":
+            return
+        if psf in ("gauss", "azgauss", "dilate"):
+            raise NotImplementedError(
+                "metacal psf='%s' is defined through galsim's stepk and interpolated images; "
+                "use psf='fitgauss' or an explicit target_sigma" % psf)
+        raise ValueError("bad metacal psf: '%s'" % psf)
+    raise NotImplementedError(
+        "a galsim object as the metacal psf needs galsim's interpolants; use psf='fitgauss' "
+        "or an explicit target_sigma")
+
+
+def _check_types(types):
+    if types is None:
+        return list(METACAL_MINIMAL_TYPES)
+    types = list(types)
+    for t in types:
+        if isinstance(t, str) and t.endswith("_psf") and t[:-4] in METACAL_MINIMAL_TYPES[1:]:
+            raise NotImplementedError("metacal type '%s': shearing the psf is not served" % t)
+        if t not in METACAL_MINIMAL_TYPES:
+            raise ValueError("bad metacal type: %s" % (t,))
+    return types
+
+
+def _type_shears(types, step):
+    table = {"noshear": (0.0, 0.0), "1p": (step, 0.0), "1m": (-step, 0.0),
+             "2p": (0.0, step), "2m": (0.0, -step)}
+    return np.array([table[t] for t in types], dtype=np.float64).reshape(len(types), 2)
+
+
+def _check_shears(g):
+    if not np.all(g[..., 0] ** 2 + g[..., 1] ** 2 < 1.0):
+        raise ValueError("shears must lie inside the unit circle")
+
+
+def _one_shape(stamps, what):
+    if stamps.n == 0:
+        raise ValueError("%s: an empty batch" % what)
+    nrow, ncol = int(stamps.nrow[0]), int(stamps.ncol[0])
+    if np.any(stamps.nrow != nrow) or np.any(stamps.ncol != ncol) or \
+            np.any(stamps.pix_off != np.arange(stamps.n, dtype=np.int64) * (nrow * ncol)):
+        raise ValueError("%s: all stamps of a batch share one shape" % what)
+    return nrow, ncol
+
+
+def fitgauss_sigma(irr, irc, icc):
+    """
+    The width of the reference's fitgauss target psf (fitgauss_target_psf.py)
+    from the gaussian fitted to the psf: T = irr + icc dilated by
+    _get_ellip_dilation -- the largest eigenvalue of the covariance over T/2,
+    square root, doubled excess, at most 1.1 -- and sigma = sqrt(T dilation / 2).
+    """
+    T = irr + icc
+    with np.errstate(invalid="ignore", divide="ignore"):
+        eig = 0.5 * T + np.sqrt((0.5 * (icc - irr)) ** 2 + irc ** 2)
+        dilation = np.minimum(1.0 + 2.0 * (np.sqrt(eig / (T / 2.0)) - 1.0), 1.1)
+        return np.sqrt(T * dilation / 2.0)
+
+
+class MetacalBatch(object):
+    """
+    stamps, psf_stamps: StampBatch of the images and of their psf images (stamp
+        i of one belongs to stamp i of the other).  All stamps share one shape,
+        the psf stamps share one, possibly another; every stamp has its own
+        jacobian, whose derivatives its psf stamp shares.
+    psf: 'fitgauss' -- the target is the round gaussian of the reference's
+        MetacalFitGaussPSF: adaptive moments of every psf stamp, as one batch
+        (StampBatch.admom, up to four starts), T and e of the fit, the
+        ellipticity dilation, sigma_T = sqrt(T dilation / 2).  A stamp whose
+        moments fail is flagged METACAL_PSF_FIT_FAILURE and its outputs are
+        NaN.  (The reference falls back to an LM fit of a gaussian, then to a
+        stored gmix; that fallback is not made here.)
+    target_sigma: (N,) widths used instead of the fit.
+    rng: np.random.RandomState for the fit's starting points and for the noise
+        fields of fixnoise.
+
+    Every output is resident on the device, ready for bootstrap_batch,
+    LMBatchFitter and the other batch consumers.
+    """
+
+    def __init__(self, stamps, psf_stamps, psf="fitgauss", target_sigma=None, rng=None):
+        if target_sigma is None:
+            _check_psf_kind(psf)
+        from .batch import StampBatch
+        if not isinstance(stamps, StampBatch) or not isinstance(psf_stamps, StampBatch):
+            raise ValueError("stamps and psf_stamps must be StampBatch objects")
+        if stamps.n != psf_stamps.n:
+            raise ValueError("one psf stamp per stamp: %d stamps, %d psf stamps"
+                             % (stamps.n, psf_stamps.n))
+        if stamps.val is None or psf_stamps.val is None:
+            raise ValueError("stamps and psf_stamps must hold pixel data")
+        self.shape = _one_shape(stamps, "stamps")
+        self.psf_shape = _one_shape(psf_stamps, "psf_stamps")
+        self.stamps, self.psf_stamps = stamps, psf_stamps
+        self.n = stamps.n
+        self.device = stamps.device
+        self.rng = rng if rng is not None else np.random.RandomState()
+        torch = _torch()
+        self._psf_cen = psf_stamps.jac[:, 0:2].contiguous()
+        self._psf_flux = psf_stamps.val.reshape(self.n, -1).sum(dim=1).contiguous()
+        self.fit_flags = np.zeros(self.n, dtype=np.int32)
+        if target_sigma is not None:
+            sigma = np.ascontiguousarray(target_sigma, dtype=np.float64)
+            if sigma.shape != (self.n,):
+                raise ValueError("target_sigma must have shape (%d,)" % self.n)
+            if not np.all(sigma > 0):
+                raise ValueError("target_sigma must be positive")
+        else:
+            sigma = self._fit_target_sigma()
+        self.target_sigma = sigma
+        self._sigma = torch.from_numpy(sigma).to(self.device)
+
+    # ------------------------------------------------------------ the psf fit
+    def _fit_target_sigma(self):
+        """adaptive moments of the psf stamps -> sigma_T; fit_flags where they fail"""
+        from .batch import GMixBatch
+        psf = self.psf_stamps
+        scale = psf.jac[:, 7].cpu().numpy()
+        sigma = np.full(self.n, np.nan)
+        todo = np.arange(self.n)
+        for itry in range(_PSF_FIT_NTRY):
+            batch = psf if todo.size == self.n else psf.select(todo)
+            m = todo.size
+            # round starts of two pixels' T, scattered by ten per cent, within
+            # a tenth of a pixel of the jacobian's centre
+            guess = np.zeros((m, 6))
+            guess[:, 0:2] = self.rng.uniform(-0.1, 0.1, size=(m, 2)) * scale[todo, None]
+            guess[:, 4] = 4.0 * scale[todo] ** 2 * (1.0 + self.rng.uniform(-0.1, 0.1, size=m)) \
+                * (1.0 + 0.5 * itry)
+            guess[:, 5] = 1.0
+            wt, _ = GMixBatch.from_pars(guess, "gauss", device=self.device)
+            res, status = batch.admom(wt, no_cov=True)
+            torch = _torch()
+            cols = wt.data[:, 3:6].cpu().numpy()        # irr, irc, icc of the weight
+            # (the int32 flags head the 584-byte records)
+            flags = res[:, 0:1].clone().view(torch.int32)[:, 0].cpu().numpy()
+            status = status.cpu().numpy()
+            s = fitgauss_sigma(cols[:, 0], cols[:, 1], cols[:, 2])
+            ok = (flags == 0) & (status == 0) & np.isfinite(s) & (s > 0)
+            sigma[todo[ok]] = s[ok]
+            todo = todo[~ok]
+            if todo.size == 0:
+                break
+        self.fit_flags[todo] = METACAL_PSF_FIT_FAILURE
+        return sigma
+
+    # ------------------------------------------------------------ the operation
+    def _noise_planes(self, noise):
+        """the (N, R, C) noise stamps on the device: given, or drawn as
+        N(0, 1/sqrt(w)), zero where w = 0 (simobs.simulate_obs with no model)"""
+        torch = _torch()
+        nrow, ncol = self.shape
+        if noise is None:
+            ierr = self.stamps.ierr.reshape(self.n, nrow, ncol).cpu().numpy()
+            with np.errstate(divide="ignore"):
+                sd = np.where(ierr > 0, 1.0 / ierr, 0.0)
+            noise = self.rng.normal(size=sd.shape) * sd
+        if isinstance(noise, torch.Tensor):
+            d = noise.to(device=self.device, dtype=torch.float64)
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float64)).to(self.device)
+        if d.numel() != self.n * nrow * ncol:
+            raise ValueError("noise must hold one %d x %d plane per stamp" % (nrow, ncol))
+        return d.reshape(self.n, nrow, ncol)
+
+    def _run(self, g, per_stamp, noise):
+        """
+        g: (T, 2), or (N, T, 2) with per_stamp; noise: (N, R, C) device tensor
+        or None.  Returns the images (T, N, R, C), the target psf images
+        (T, N, Rp, Cp) and the flags (T, N), all on the device.
+        """
+        torch = _torch()
+        from .batch import _dptr, _stream, _on_device
+        n, (nrow, ncol), (prow, pcol) = self.n, self.shape, self.psf_shape
+        ntypes = g.shape[-2]
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        _check_shears(g)
+        d_g = torch.from_numpy(g).to(self.device)
+        planes = 1 if noise is None else 2
+        d_noise = None
+        if noise is not None:
+            if nrow != ncol:
+                raise ValueError("fixnoise turns the noise stamp by 90 degrees: the stamps "
+                                 "must be square, got %d x %d" % (nrow, ncol))
+            d_noise = torch.rot90(noise, 1, dims=(1, 2)).contiguous()
+        spec = torch.empty((n, ntypes, planes, nrow, ncol // 2 + 1, 2), dtype=torch.float64,
+                           device=self.device)
+        kflags = torch.empty((n, ntypes), dtype=torch.int32, device=self.device)
+        images = self.stamps.val.reshape(n, nrow, ncol)
+        if not images.is_contiguous():
+            images = images.contiguous()
+        with _on_device(self.device):
+            st = _lib.lib().ngmix_metacal_spectrum_batch(
+                _dptr(images), _dptr(d_noise), _dptr(self.psf_stamps.val), _dptr(self.stamps.jac),
+                _dptr(self._psf_cen), _dptr(self._psf_flux), _dptr(self._sigma), _dptr(d_g),
+                _lib.ptr(g), int(per_stamp), n, ntypes, nrow, ncol, prow, pcol, _dptr(spec),
+                _dptr(kflags), _stream())
+        _lib.check(st, "ngmix_metacal_spectrum_batch")
+        # the regular-grid inverse transform (rocFFT); the spectrum is
+        # hermitian on its Nyquist row and column, where a complex-to-real
+        # transform would otherwise drop what does not fit
+        out = torch.fft.irfft2(torch.view_as_complex(spec), s=(nrow, ncol))
+        if noise is not None:
+            out = out[:, :, 0] + torch.rot90(out[:, :, 1], 3, dims=(2, 3))
+        else:
+            out = out[:, :, 0]
+        flags = torch.where(kflags != 0, METACAL_NONFINITE, 0).to(torch.int32) | \
+            torch.from_numpy(self.fit_flags).to(self.device)[:, None]
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
+        out = torch.where(flags[:, :, None, None] != 0, nan, out)
+        out = out.permute(1, 0, 2, 3).contiguous()
+        flags = flags.t().contiguous()
+        psf_images = self._target_psf_images(g, per_stamp)
+        psf_images = torch.where(flags[:, :, None, None] != 0, nan, psf_images)
+        return out, psf_images, flags
+
+    def _psf_jacobians(self):
+        """the psf stamps' jacobians with the centre at the stamp's exact centre"""
+        jac = self.psf_stamps.jac.clone()
+        jac[:, 0] = (self.psf_shape[0] - 1.0) / 2.0
+        jac[:, 1] = (self.psf_shape[1] - 1.0) / 2.0
+        return jac
+
+    def _target_psf_images(self, g, per_stamp):
+        """the round gaussians of width sigma_T (1 + 2|g|) carrying the psf
+        images' flux, on the psf stamps' grid about its centre: (T, N, Rp, Cp)"""
+        torch = _torch()
+        from .batch import StampBatch, GMixBatch
+        n, (prow, pcol) = self.n, self.psf_shape
+        ntypes = g.shape[-2]
+        gabs = np.sqrt(g[..., 0] ** 2 + g[..., 1] ** 2)          # (T,) or (N, T)
+        gabs = np.broadcast_to(gabs.T if per_stamp else gabs[:, None], (ntypes, n))
+        sig = self._sigma[None, :] * torch.from_numpy(1.0 + 2.0 * gabs).to(self.device)
+        bad = ~torch.isfinite(sig)
+        pars = torch.zeros((ntypes * n, 6), dtype=torch.float64, device=self.device)
+        pars[:, 4] = torch.where(bad, torch.ones_like(sig), 2.0 * sig * sig).reshape(-1)
+        pars[:, 5] = self._psf_flux[None, :].expand(ntypes, n).reshape(-1)
+        gm, _ = GMixBatch.from_pars(pars, "gauss", device=self.device)
+        m = ntypes * n
+        geom = StampBatch(None, None, self._psf_jacobians().repeat(ntypes, 1), np.full(m, prow),
+                          np.full(m, pcol), np.arange(m, dtype=np.int64) * (prow * pcol), False)
+        image, _ = geom.render(gm, fast_exp=False, no_skip=True)
+        return image.reshape(ntypes, n, prow, pcol)
+
+    def _stamp_batches(self, images, psf_images, fixnoise):
+        """the StampBatch pair of one type: the input's jacobians and weights
+        (halved by fixnoise), the target psf about its stamp's centre"""
+        from .batch import StampBatch
+        s, p = self.stamps, self.psf_stamps
+        ierr = s.ierr * np.sqrt(0.5) if fixnoise else s.ierr
+        izw = (s.flags & _lib.STAMP_IGNORE_ZERO_WEIGHT) != 0
+        out = StampBatch(images.reshape(-1), ierr, s.jac, s.nrow, s.ncol, s.pix_off, izw,
+                         npix_kept=s.npix_kept,
+                         uniform_ierr=(s.flags & _lib.STAMP_UNIFORM_IERR) != 0)
+        pizw = (p.flags & _lib.STAMP_IGNORE_ZERO_WEIGHT) != 0
+        pout = StampBatch(psf_images.reshape(-1), p.ierr, self._psf_jacobians(), p.nrow, p.ncol,
+                          p.pix_off, pizw, npix_kept=p.npix_kept,
+                          uniform_ierr=(p.flags & _lib.STAMP_UNIFORM_IERR) != 0)
+        return out, pout
+
+    def get_all(self, step=DEFAULT_STEP, types=None, fixnoise=False, noise=None):
+        """
+        {type: {'stamps': StampBatch, 'psf_stamps': StampBatch, 'flags': (N,)
+        int32 array}} for types of METACAL_MINIMAL_TYPES (default: all five),
+        all in one launch; noshear is the same path at g = 0.
+
+        fixnoise: a noise stamp per image -- `noise` ((N, R, C) array or device
+        tensor), or drawn from the weights with the batch's rng -- is turned by
+        rot90(k=1), put through the same operation with the same shear, turned
+        back by k=3 and added; the weight becomes 1 / (1/w + 1/w) where w > 0.
+        Square stamps only.
+        """
+        types = _check_types(types)
+        g = _type_shears(types, float(step))
+        _check_shears(g)
+        if fixnoise and self.shape[0] != self.shape[1]:
+            raise ValueError("fixnoise turns the noise stamp by 90 degrees: the stamps must be "
+                             "square, got %d x %d" % self.shape)
+        planes = self._noise_planes(noise) if fixnoise else None
+        images, psf_images, flags = self._run(g, False, planes)
+        flags = flags.cpu().numpy()
+        out = {}
+        for i, t in enumerate(types):
+            sb, psb = self._stamp_batches(images[i], psf_images[i], fixnoise)
+            out[t] = {"stamps": sb, "psf_stamps": psb, "flags": flags[i]}
+        return out
+
+    def get_obs_galshear(self, g1, g2):
+        """the images sheared by (g1[i], g2[i]), one shear per stamp: a dict
+        as one entry of get_all's"""
+        g = np.stack([np.broadcast_to(np.asarray(g1, dtype=np.float64), (self.n,)),
+                      np.broadcast_to(np.asarray(g2, dtype=np.float64), (self.n,))], axis=1)
+        images, psf_images, flags = self._run(g.reshape(self.n, 1, 2), True, None)
+        sb, psb = self._stamp_batches(images[0], psf_images[0], False)
+        return {"stamps": sb, "psf_stamps": psb, "flags": flags[0].cpu().numpy()}
+
+
+# ---------------------------------------------------------------------------
+# the reference's entry point
+
+def _flatten(obs):
+    """(list of Observations, rebuild(list of new Observations) -> container)"""
+    if isinstance(obs, Observation):
+        return [obs], lambda new: new[0]
+    if isinstance(obs, MultiBandObsList):
+        flat = [o for ol in obs for o in ol]
+        sizes = [len(ol) for ol in obs]
+
+        def rebuild(new):
+            out, at = MultiBandObsList(), 0
+            for m in sizes:
+                ol = ObsList()
+                for o in new[at:at + m]:
+                    ol.append(o)
+                out.append(ol)
+                at += m
+            return out
+        return flat, rebuild
+    if isinstance(obs, ObsList):
+        def rebuild(new):
+            out = ObsList()
+            for o in new:
+                out.append(o)
+            return out
+        return list(obs), rebuild
+    raise ValueError("obs must be Observation, ObsList, or MultiBandObsList")
+
+
+def get_all_metacal(obs, psf="fitgauss", step=DEFAULT_STEP, types=None, fixnoise=True,
+                    rng=None, use_noise_image=False):
+    """
+    The reference's get_all_metacal (ngmix/metacal/convenience.py): a dict
+    {type: container like obs} of metacal Observations.
+
+    obs: Observation, ObsList or MultiBandObsList; every Observation has a psf
+        Observation with the same jacobian derivatives
+    psf: 'fitgauss' (the default here; 'gauss', 'azgauss', 'dilate' and galsim
+        objects raise NotImplementedError: they rest on galsim)
+    fixnoise: add the sheared, rotated noise field and halve the weights
+        (_get_all_metacal_fixnoise); the noise field is obs.noise with
+        use_noise_image, else drawn from the weights with rng
+    rng: required; it also draws the small noise (max / 50000) added to the
+        target psf images, whose weights become (50000 / max)^2
+        (_setup_psf_noise)
+
+    Observations are grouped by image and psf shape; each group runs as one
+    batch on the device.  Pixel values are not the reference's: the interpolant
+    differs (see the top of this module).
+    """
+    _check_psf_kind(psf)
+    types = _check_types(types)
+    flat, rebuild = _flatten(obs)
+    if rng is None:
+        raise ValueError("send an rng to get_all_metacal (psf='fitgauss')")
+    for o in flat:
+        if not o.has_psf():
+            raise ValueError("observation must have a psf observation set")
+        if use_noise_image and fixnoise and not o.has_noise():
+            raise ValueError("obs.noise must be set when use_noise_image=True")
+        if fixnoise and o.image.shape[0] != o.image.shape[1]:
+            raise ValueError("fixnoise needs square images, got %s" % (o.image.shape,))
+        a, b = o.jacobian, o.psf.jacobian
+        if any(getattr(a, k) != getattr(b, k) for k in ("dvdrow", "dvdcol", "dudrow", "dudcol")):
+            raise ValueError("the psf and the observation must have the same jacobian "
+                             "derivatives")
+    from .batch import StampBatch
+    groups = {}
+    for i, o in enumerate(flat):
+        groups.setdefault((o.image.shape, o.psf.image.shape), []).append(i)
+    new = {t: [None] * len(flat) for t in types}
+    for idx in groups.values():
+        sub = [flat[i] for i in idx]
+        mc = MetacalBatch(StampBatch.from_observations(sub),
+                          StampBatch.from_observations([o.psf for o in sub]), psf=psf, rng=rng)
+        noise = None
+        if fixnoise and use_noise_image:
+            noise = np.stack([o.noise for o in sub])
+        res = mc.get_all(step=step, types=types, fixnoise=fixnoise, noise=noise)
+        for t in types:
+            shape, pshape = sub[0].image.shape, sub[0].psf.image.shape
+            ims = res[t]["stamps"].val.reshape((len(sub),) + shape).cpu().numpy()
+            pims = res[t]["psf_stamps"].val.reshape((len(sub),) + pshape).cpu().numpy()
+            for k, i in enumerate(idx):
+                new[t][i] = _make_obs(sub[k], ims[k], pims[k], int(res[t]["flags"][k]),
+                                      fixnoise, rng)
+    return {t: rebuild(new[t]) for t in types}
+
+
+def _make_obs(obs, image, psf_image, flags, fixnoise, rng):
+    """a copy of obs with the metacal image and the target psf (_make_obs,
+    _make_psf_obs and, with fixnoise, _doadd_single_obs of the reference)"""
+    pim = obs.psf.image
+    psf_noise = pim.max() / 50000.0
+    psf_image = psf_image + rng.normal(size=pim.shape, scale=psf_noise)
+    new_psf = obs.psf.copy()
+    with new_psf.writeable():
+        new_psf.image[:, :] = psf_image
+        new_psf.weight[:, :] = pim * 0 + 1.0 / psf_noise ** 2
+    # the centre goes where the target psf was drawn: the stamp's exact centre
+    jac = new_psf.jacobian
+    new_psf.jacobian = Jacobian(row=(pim.shape[0] - 1.0) / 2.0, col=(pim.shape[1] - 1.0) / 2.0,
+                                dvdrow=jac.dvdrow, dvdcol=jac.dvdcol, dudrow=jac.dudrow,
+                                dudcol=jac.dudcol)
+    new = obs.copy()
+    if fixnoise:
+        # (the image before the noise field was added stays on the device: only
+        # the weight's original is kept, as _doadd_single_obs keeps it)
+        new.weight_orig = obs.weight.copy()
+    new.image = image
+    if fixnoise:
+        w = obs.weight
+        halved = np.zeros_like(w)
+        pos = w > 0
+        halved[pos] = 1.0 / (1.0 / w[pos] + 1.0 / w[pos])
+        new.weight = halved
+    new.psf = new_psf
+    new.meta["metacal_flags"] = flags
+    return new

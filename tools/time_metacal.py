@@ -1,0 +1,116 @@
+"""
+Time ngmix_amd.metacal on the device: N stamps of 32 x 32 and of 48 x 48, the
+five metacal types, with and without fixnoise (a given noise plane).
+
+Device events around whole get_all calls and around the spectrum kernel alone
+(the C entry, same arguments), after warm-up runs; the median of the repeats.
+Prints one JSON line per configuration: stamps/s of the whole call, the time
+of the spectrum kernel and of the rest (inverse FFT, psf images, assembly), the
+kernel's FMA rate and its fraction of the derived ceiling.
+
+usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FP64_VECTOR_FMA_PER_S = 78.6e12 / 2      # MI355X vector fp64 peak, FMA = 2 flop
+
+
+def fma_count(dim, planes):
+    """FMAs of the spectrum kernel per stamp and type: every work item (the
+    half plane plus the partners of the Nyquist row and column) walks every
+    pixel: 4 for the phase recurrence, 2 per plane (image, psf, noise)"""
+    items = dim * (dim // 2 + 1) + (dim // 2 + 1) + dim - 1
+    return items * dim * dim * (4 + 2 * planes)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=100000)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    import torch
+    from ngmix_amd import metacal
+    from ngmix_amd.batch import StampBatch
+    assert torch.cuda.is_available(), "time_metacal needs the device"
+    dev = torch.device("cuda", 0)
+    n = args.n
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        times = []
+        for _ in range(args.repeats):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e-3)
+        return float(np.median(times))
+
+    for dim in (32, 48):
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(dim)
+        scale = 0.263
+        r = torch.arange(dim, dtype=torch.float64, device=dev) - (dim - 1) / 2.0
+        cen = torch.rand((n, 2), generator=gen, dtype=torch.float64, device=dev) - 0.5
+        rr = (r[None, :, None] - cen[:, 0, None, None]) * scale
+        cc = (r[None, None, :] - cen[:, 1, None, None]) * scale
+        images = 100.0 * torch.exp(-0.5 * (rr * rr + cc * cc) / 0.35) + \
+            torch.randn((n, dim, dim), generator=gen, dtype=torch.float64, device=dev)
+        rr, cc = r[None, :, None] * scale, r[None, None, :] * scale
+        psfs = torch.exp(-0.5 * (rr * rr + cc * cc) / 0.35 ** 2).expand(n, dim, dim).contiguous()
+        noise = torch.randn((n, dim, dim), generator=gen, dtype=torch.float64, device=dev)
+        jac = np.tile([0.0, 0.0, scale, 0.0, 0.0, scale, scale ** 2, scale], (n, 1))
+        jac[:, 0:2] = (dim - 1) / 2.0 + cen.cpu().numpy()
+        pjac = jac.copy()
+        pjac[:, 0:2] = (dim - 1) / 2.0
+        sb = StampBatch.from_images(images, torch.ones_like(images), jac)
+        psb = StampBatch.from_images(psfs, None, pjac)
+        mc = metacal.MetacalBatch(sb, psb, target_sigma=np.full(n, 0.4))
+        for fixnoise in (False, True):
+            planes = 3 if fixnoise else 2
+            total = timed(lambda: mc.get_all(fixnoise=fixnoise, noise=noise if fixnoise else None))
+            # the kernel alone: _run's launch with the transforms after it stubbed out
+            g = metacal._type_shears(metacal.METACAL_MINIMAL_TYPES, 0.01)
+            kernel = timed(lambda: _spectrum_only(mc, g, noise if fixnoise else None))
+            fma = fma_count(dim, planes) * 5 * n
+            print(json.dumps({
+                "stamp": dim, "n": n, "fixnoise": fixnoise, "types": 5,
+                "stamps_per_s": n / total, "total_ms": total * 1e3,
+                "spectrum_kernel_ms": kernel * 1e3, "rest_ms": (total - kernel) * 1e3,
+                "kernel_fma_per_s": fma / kernel,
+                "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S,
+            }), flush=True)
+
+
+def _spectrum_only(mc, g, noise):
+    import torch
+    from ngmix_amd import _lib
+    from ngmix_amd.batch import _dptr, _stream
+    n, (nrow, ncol), (prow, pcol) = mc.n, mc.shape, mc.psf_shape
+    planes = 1 if noise is None else 2
+    key = ("bufs", planes)
+    if not hasattr(mc, "_time_bufs") or mc._time_bufs[0] != key:
+        mc._time_bufs = (key, torch.empty((n, 5, planes, nrow, ncol // 2 + 1, 2),
+                                          dtype=torch.float64, device=mc.device),
+                         torch.empty((n, 5), dtype=torch.int32, device=mc.device),
+                         torch.from_numpy(g).to(mc.device))
+    _, spec, flags, d_g = mc._time_bufs
+    st = _lib.lib().ngmix_metacal_spectrum_batch(
+        _dptr(mc.stamps.val), _dptr(noise), _dptr(mc.psf_stamps.val), _dptr(mc.stamps.jac),
+        _dptr(mc._psf_cen), _dptr(mc._psf_flux), _dptr(mc._sigma), _dptr(d_g), _lib.ptr(g), 0, n,
+        5, nrow, ncol, prow, pcol, _dptr(spec), _dptr(flags), _stream())
+    _lib.check(st, "ngmix_metacal_spectrum_batch")
+
+
+if __name__ == "__main__":
+    main()
