@@ -404,6 +404,31 @@ int ngmix_metacal_spectrum_batch(const double *images, const double *noise, cons
                                  const double *g_host, int per_stamp_g, int64_t nstamps,
                                  int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
                                  double *spec, int32_t *flags, void *stream);
+/* DEVICE: the noise planes of metacalibration's fixnoise as a pure function of
+   (seed, object id, pixel).  Philox4x32-10 with the standard round constants
+   and Weyl key increments, key = (seed & 0xffffffff, seed >> 32), counter =
+   (id & 0xffffffff, id >> 32, j, 0) for the pair j of un-rotated row-major
+   pixels 2j, 2j + 1 of the stamp.  The output words w0..w3 give u1 = ((w0 >> 5)
+   2^26 + (w1 >> 6) + 1) 2^-53 and u2 likewise from w2, w3, both in (0, 1]; z =
+   sqrt(-2 ln u1) cos(2 pi u2) belongs to pixel 2j and the sine to pixel 2j + 1
+   (a stamp with an odd pixel count drops its last sine).  The value is z /
+   ierr where ierr > 0 and +0.0 elsewhere.  ierr (n, nrow, ncol) as
+   StampBatch.ierr; ids (n) or NULL: id = index; rot_k = 0, or 1 (nrow == ncol
+   only): the value of un-rotated pixel (r, c) is stored where rot90(k=1) of
+   the plane has it, at (ncol - 1 - c, r); out (n, nrow, ncol).
+   NGMIX_ERR_BAD_ARG before any launch for n < 0, a shape that is not positive,
+   rot_k outside {0, 1}, rot_k = 1 on a stamp that is not square, NULL ierr or
+   out with n > 0; n == 0 is a no-op.  One launch, one thread per pair */
+int ngmix_metacal_noise_batch(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
+                              int nrow, int ncol, int rot_k, double *out, void *stream);
+/* HOST twin of ngmix_metacal_noise_batch: the same arguments on host pointers,
+   the same code (csrc/metacal_noise.hpp), the host libm's log and sincos */
+int ngmix_metacal_noise_host(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
+                             int nrow, int ncol, int rot_k, double *out);
+/* HOST: the generator alone: out (n, 4) = Philox4x32-10 of counters (n, 4)
+   under keys (n, 2) */
+int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,
+                             uint32_t *out);
 /* DEVICE: the innermost functions of the fast pixel evaluation over an array
    (fastexp_nb.py): which = 0 fexp = exp5_smooth(x) (:223-265; no range check:
    x in (-15.5, 1.5)), 1 apod_window(chi2) (:97-117), 2 apod_window_deriv(chi2)

@@ -16,6 +16,7 @@
 #include "lm_core.hpp"
 #include "lm_core_reg.hpp"
 #include "launch_iter.hpp"
+#include "metacal_noise.hpp"
 
 namespace ngmix {
 
@@ -535,6 +536,38 @@ int ngmix_metacal_spectrum_batch(const double *images, const double *noise, cons
     return launch_metacal_spectrum(images, noise, psf, jac, psf_cen, psf_flux, sigma, g, g_host,
                                    per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow, psf_ncol,
                                    spec, flags, (hipStream_t)stream);
+}
+
+int ngmix_metacal_noise_batch(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
+                              int nrow, int ncol, int rot_k, double *out, void *stream)
+{
+    return launch_metacal_noise(ierr, ids, seed, n, nrow, ncol, rot_k, out, (hipStream_t)stream);
+}
+
+int ngmix_metacal_noise_host(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
+                             int nrow, int ncol, int rot_k, double *out)
+{
+    bool nothing;
+    const int st =
+        mcnoise::check_args("metacal_noise_host", ierr, n, nrow, ncol, rot_k, out, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    const int npairs = (nrow * ncol + 1) / 2;
+    for (int64_t i = 0; i < n; i++)
+        for (int j = 0; j < npairs; j++)
+            mcnoise::fill_pair(ierr, ids, seed, i, j, nrow, ncol, rot_k, out);
+    return NGMIX_OK;
+}
+
+int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,
+                             uint32_t *out)
+{
+    if (n < 0 || (n > 0 && (!counters || !keys || !out))) return NGMIX_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t *c = counters + 4 * i, *k = keys + 2 * i;
+        const mcnoise::Words x = mcnoise::philox4x32_10(c[0], c[1], c[2], c[3], k[0], k[1]);
+        for (int w = 0; w < 4; w++) out[4 * i + w] = x.w[w];
+    }
+    return NGMIX_OK;
 }
 
 int ngmix_fastexp_batch(const double *x, double *out, int64_t n, int which, void *stream)

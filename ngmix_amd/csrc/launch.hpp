@@ -43,6 +43,9 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
                             const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
                             int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
                             int32_t *flags, hipStream_t s);
+// metacal_noise.hip
+int launch_metacal_noise(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
+                         int nrow, int ncol, int rot_k, double *out, hipStream_t s);
 // loglike_grad.hip
 int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double *out,
                         double *grad, int32_t *status, hipStream_t s);

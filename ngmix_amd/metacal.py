@@ -17,8 +17,23 @@ shapes, the target psf of 'fitgauss', the fixnoise recipe and the use made of
     MetacalBatch(stamps, psf_stamps, psf='fitgauss', target_sigma=None, rng=None)
         .get_all(step=0.01, types=None, fixnoise=False, noise=None)
         .get_obs_galshear(g1, g2)
+        .device_noise(seed, ids=None, rotated=False)
     get_all_metacal(obs, psf='fitgauss', step=0.01, types=None, fixnoise=True,
                     rng=None, use_noise_image=False)
+
+and, from the images to a shear catalogue ("metacal shear
+catalogues"):
+
+    metacal_bootstrap_batch(stamps, psf_stamps, model='gauss', step=0.01, ...,
+                            noise_seed=None, ids=None, ...) -> (resdict, batchdict)
+    shear_response(resdict, step=0.01, key='g') -> {'g', 'R', 'flags'}
+    mean_shear(resp, select=None) -> (2,)
+    metacal_bootstrap(obs, runner, psf_runner=None, ...), MetacalBootstrapper
+    metacal_bootstrap_many(list_of_obs, model='gauss', ...)
+
+With noise_seed the fixnoise field is drawn on the device as a pure function
+of (seed, object id, pixel) (csrc/metacal_noise.hip): the same object gets the
+same field however the catalogue is cut into batches.
 
 psf='fitgauss' and an explicit target_sigma are served.  psf='gauss',
 'azgauss', 'dilate' and galsim-object psfs are defined through galsim's stepk
@@ -32,7 +47,9 @@ from .jacobian import Jacobian
 from .observation import Observation, ObsList, MultiBandObsList
 
 __all__ = ["MetacalBatch", "get_all_metacal", "METACAL_TYPES", "METACAL_MINIMAL_TYPES",
-           "METACAL_PSF_FIT_FAILURE", "METACAL_NONFINITE"]
+           "METACAL_PSF_FIT_FAILURE", "METACAL_NONFINITE", "DeviceNoise",
+           "metacal_bootstrap_batch", "shear_response", "mean_shear", "metacal_bootstrap",
+           "MetacalBootstrapper", "metacal_bootstrap_many"]
 
 METACAL_MINIMAL_TYPES = ["noshear", "1p", "1m", "2p", "2m"]
 METACAL_TYPES = METACAL_MINIMAL_TYPES
@@ -109,6 +126,18 @@ def fitgauss_sigma(irr, irc, icc):
         eig = 0.5 * T + np.sqrt((0.5 * (icc - irr)) ** 2 + irc ** 2)
         dilation = np.minimum(1.0 + 2.0 * (np.sqrt(eig / (T / 2.0)) - 1.0), 1.1)
         return np.sqrt(T * dilation / 2.0)
+
+
+class DeviceNoise(object):
+    """
+    Stands for MetacalBatch.device_noise(seed, ids) as the `noise` of get_all:
+    the planes are drawn straight into the turned layout the spectrum kernel
+    reads, without the copy torch.rot90 makes.  The images are those of the
+    two-step route to the bit.
+    """
+
+    def __init__(self, seed, ids=None):
+        self.seed, self.ids = seed, ids
 
 
 class MetacalBatch(object):
@@ -204,6 +233,8 @@ class MetacalBatch(object):
         N(0, 1/sqrt(w)), zero where w = 0 (simobs.simulate_obs with no model)"""
         torch = _torch()
         nrow, ncol = self.shape
+        if isinstance(noise, DeviceNoise):
+            return noise
         if noise is None:
             ierr = self.stamps.ierr.reshape(self.n, nrow, ncol).cpu().numpy()
             with np.errstate(divide="ignore"):
@@ -217,10 +248,49 @@ class MetacalBatch(object):
             raise ValueError("noise must hold one %d x %d plane per stamp" % (nrow, ncol))
         return d.reshape(self.n, nrow, ncol)
 
+    def device_noise(self, seed, ids=None, rotated=False):
+        """
+        The noise planes of fixnoise drawn on the device, (N, R, C) float64:
+        unit normals of Philox4x32-10 under the key `seed` (0 <= seed < 2^64)
+        and the counter (object id, pixel pair), over the stamps' ierr, +0.0
+        where ierr is not positive (csrc/metacal_noise.hpp).  ids: (N,) int64
+        object ids, default the positions 0 .. N-1.  A stamp's plane depends on
+        (seed, id, ierr) alone, not on the batch it is drawn in.  rotated: the
+        planes as torch.rot90(., 1, dims=(1, 2)) has them (square stamps).
+        """
+        torch = _torch()
+        from .batch import _dptr, _stream, _on_device
+        nrow, ncol = self.shape
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("the noise seed must be in [0, 2^64)")
+        d_ids = None
+        if ids is not None:
+            if isinstance(ids, torch.Tensor):
+                d_ids = ids.to(device=self.device, dtype=torch.int64).contiguous()
+            else:
+                d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
+            if tuple(d_ids.shape) != (self.n,):
+                raise ValueError("ids must have shape (%d,)" % self.n)
+        if rotated and nrow != ncol:
+            raise ValueError("the rotated noise planes need square stamps, got %d x %d"
+                             % (nrow, ncol))
+        ierr = self.stamps.ierr
+        if ierr is None or ierr.numel() != self.n * nrow * ncol:
+            raise ValueError("the stamps hold no per-pixel ierr to draw the noise over")
+        ierr = ierr.reshape(-1).contiguous()
+        out = torch.empty((self.n, nrow, ncol), dtype=torch.float64, device=self.device)
+        with _on_device(self.device):
+            st = _lib.lib().ngmix_metacal_noise_batch(
+                _dptr(ierr), _dptr(d_ids), seed, self.n, nrow, ncol, 1 if rotated else 0,
+                _dptr(out), _stream())
+        _lib.check(st, "ngmix_metacal_noise_batch")
+        return out
+
     def _run(self, g, per_stamp, noise):
         """
-        g: (T, 2), or (N, T, 2) with per_stamp; noise: (N, R, C) device tensor
-        or None.  Returns the images (T, N, R, C), the target psf images
+        g: (T, 2), or (N, T, 2) with per_stamp; noise: (N, R, C) device tensor,
+        a DeviceNoise (drawn here, already turned) or None.  Returns the images (T, N, R, C), the target psf images
         (T, N, Rp, Cp) and the flags (T, N), all on the device.
         """
         torch = _torch()
@@ -236,7 +306,10 @@ class MetacalBatch(object):
             if nrow != ncol:
                 raise ValueError("fixnoise turns the noise stamp by 90 degrees: the stamps "
                                  "must be square, got %d x %d" % (nrow, ncol))
-            d_noise = torch.rot90(noise, 1, dims=(1, 2)).contiguous()
+            if isinstance(noise, DeviceNoise):
+                d_noise = self.device_noise(noise.seed, noise.ids, rotated=True)
+            else:
+                d_noise = torch.rot90(noise, 1, dims=(1, 2)).contiguous()
         spec = torch.empty((n, ntypes, planes, nrow, ncol // 2 + 1, 2), dtype=torch.float64,
                            device=self.device)
         kflags = torch.empty((n, ntypes), dtype=torch.int32, device=self.device)
@@ -470,3 +543,206 @@ def _make_obs(obs, image, psf_image, flags, fixnoise, rng):
     new.psf = new_psf
     new.meta["metacal_flags"] = flags
     return new
+
+
+# ---------------------------------------------------------------------------
+# from the images to a shear catalogue
+
+def metacal_bootstrap_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP, types=None,
+                            fixnoise=True, noise_seed=None, ids=None, psf="fitgauss",
+                            target_sigma=None, rng=None, **bootstrap_kws):
+    """
+    The metacal images of a stamp batch and a bootstrap fit on every type, all
+    on the device: MetacalBatch(stamps, psf_stamps, psf, target_sigma,
+    rng).get_all(step, types, fixnoise, noise), then
+    pipeline.bootstrap_batch(stamps, psf_stamps, model=model, rng=rng,
+    **bootstrap_kws) on each type's pair, in the order of `types`.
+
+    noise_seed: with fixnoise, the noise field is drawn on the device from
+        (noise_seed, ids, pixel) (MetacalBatch.device_noise; ids default to
+        the positions in the batch); None: drawn on the host from rng, as
+        get_all does
+    rng: np.random.RandomState of the psf fits' and the guesses' starting
+        points (and of the host noise draw)
+
+    Returns (resdict, batchdict): resdict[type] is bootstrap_batch's dict with
+    'mcal_flags', the type's metacal flags (N,), added; batchdict is get_all's
+    dict.  A stamp flagged by metacal has NaN images: its psf fit fails, its
+    row comes back with flags = BOOT_PSF_FAILURE and NaN parameters.
+    """
+    from .pipeline import bootstrap_batch
+    for k in ("stamp_obj", "stamp_band"):
+        if bootstrap_kws.get(k) is not None:
+            raise ValueError("metacal_bootstrap_batch fits one stamp per object: no %s" % k)
+    if ids is not None and noise_seed is None:
+        raise ValueError("ids belong to the device noise: send noise_seed too")
+    mc = MetacalBatch(stamps, psf_stamps, psf=psf, target_sigma=target_sigma, rng=rng)
+    noise = None
+    if fixnoise and noise_seed is not None:
+        noise = DeviceNoise(noise_seed, ids)
+    batchdict = mc.get_all(step=step, types=types, fixnoise=fixnoise, noise=noise)
+    resdict = {}
+    for t, d in batchdict.items():
+        res = bootstrap_batch(d["stamps"], d["psf_stamps"], model=model, rng=rng, **bootstrap_kws)
+        res["mcal_flags"] = d["flags"]
+        resdict[t] = res
+    return resdict, batchdict
+
+
+def _response_column(res, key):
+    if key in res:
+        v = res[key]
+    elif key == "g":
+        v = res["pars"][:, 2:4]
+    else:
+        raise ValueError("the fit results have no '%s'" % key)
+    v = np.asarray(v, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 2:
+        raise ValueError("'%s' must be (N, 2), got %s" % (key, v.shape))
+    return v
+
+
+def shear_response(resdict, step=DEFAULT_STEP, key="g"):
+    """
+    The finite-difference shear response of every object from the five fits
+    of metacal_bootstrap_batch (or any dict {type: {key: (N, 2), 'flags': (N,)
+    [, 'mcal_flags': (N,)]}}).
+
+    Returns {'g': (N, 2) noshear's `key`, 'R': (N, 2, 2) with R[:, i, j] =
+    (res[jp][key][:, i] - res[jm][key][:, i]) / (2 step), 'flags': (N,) the OR
+    of the five types' fit flags and metacal flags}; the rows of flagged
+    objects are NaN.
+    """
+    step = float(step)
+    if not step > 0:
+        raise ValueError("step must be positive")
+    missing = [t for t in METACAL_MINIMAL_TYPES if t not in resdict]
+    if missing:
+        raise ValueError("shear_response needs all five types; missing: %s" % (missing,))
+    g0 = _response_column(resdict["noshear"], key)
+    n = g0.shape[0]
+    flags = np.zeros(n, dtype=np.int64)
+    for t in METACAL_MINIMAL_TYPES:
+        res = resdict[t]
+        for k in ("flags", "mcal_flags"):
+            if k in res:
+                f = np.asarray(res[k])
+                if f.shape != (n,):
+                    raise ValueError("type '%s': '%s' must be (%d,)" % (t, k, n))
+                flags |= f.astype(np.int64)
+    R = np.empty((n, 2, 2))
+    for j in (0, 1):
+        p = _response_column(resdict["%dp" % (j + 1)], key)
+        m = _response_column(resdict["%dm" % (j + 1)], key)
+        if p.shape != g0.shape or m.shape != g0.shape:
+            raise ValueError("the five types must hold the same objects")
+        R[:, :, j] = (p - m) / (2.0 * step)
+    g = g0.copy()
+    bad = flags != 0
+    g[bad] = np.nan
+    R[bad] = np.nan
+    return {"g": g, "R": R, "flags": flags}
+
+
+def mean_shear(resp, select=None):
+    """
+    <g> <R>^-1 over the unflagged objects of shear_response's dict -- the
+    solution of <R> gamma = <g> with the 2 x 2 mean response -- and, with
+    `select` (a boolean mask or an index array), over the selected ones of
+    them.  No selection response is applied.
+    """
+    flags = np.asarray(resp["flags"])
+    use = flags == 0
+    if select is not None:
+        sel = np.asarray(select)
+        mask = np.zeros(flags.shape[0], dtype=bool)
+        if sel.dtype == bool:
+            if sel.shape != flags.shape:
+                raise ValueError("select: a mask must have one entry per object")
+            mask = sel
+        else:
+            mask[sel] = True
+        use = use & mask
+    if not use.any():
+        raise ValueError("mean_shear: no unflagged object is selected")
+    return np.linalg.solve(resp["R"][use].mean(axis=0), resp["g"][use].mean(axis=0))
+
+
+def metacal_bootstrap(obs, runner, psf_runner=None, ignore_failed_psf=True, rng=None,
+                      **metacal_kws):
+    """
+    The reference's metacal_bootstrap (ngmix/metacal/bootstrap.py): the metacal
+    observations of get_all_metacal(obs, rng=rng, **metacal_kws), then
+    bootstrap(obs, runner, psf_runner, ignore_failed_psf) on each type.
+
+    Returns (resdict, obsdict), both keyed by the metacal type.  As in the
+    reference, obs.psf.meta['result'] and obs.psf.gmix of the metacal
+    observations may be set by the psf runner.
+    """
+    from .bootstrap import bootstrap
+    obsdict = get_all_metacal(obs=obs, rng=rng, **metacal_kws)
+    resdict = {}
+    for key, tobs in obsdict.items():
+        resdict[key] = bootstrap(obs=tobs, runner=runner, psf_runner=psf_runner,
+                                 ignore_failed_psf=ignore_failed_psf)
+    return resdict, obsdict
+
+
+class MetacalBootstrapper(object):
+    """
+    The reference's MetacalBootstrapper: runner / psf_runner have go(obs=obs);
+    **metacal_kws go to get_all_metacal.
+    """
+
+    def __init__(self, runner, psf_runner, ignore_failed_psf=True, rng=None, **metacal_kws):
+        self.runner = runner
+        self.psf_runner = psf_runner
+        self.ignore_failed_psf = ignore_failed_psf
+        self.metacal_kws = metacal_kws
+        self.rng = rng
+
+    def go(self, obs):
+        return metacal_bootstrap(obs=obs, runner=self.runner, psf_runner=self.psf_runner,
+                                 ignore_failed_psf=self.ignore_failed_psf, rng=self.rng,
+                                 **self.metacal_kws)
+
+    @property
+    def fitter(self):
+        return self.runner.fitter
+
+
+def metacal_bootstrap_many(list_of_obs, model="gauss", rng=None, metacal_kws=None,
+                           **bootstrap_kws):
+    """
+    metacal_bootstrap for a catalogue: list_of_obs is a sequence of Observation
+    / ObsList / MultiBandObsList with psf observations.  The metacal images of
+    all of them are made together (get_all_metacal: one batch per stamp shape)
+    and every type is fitted as one batch (pipeline.bootstrap_many(., model,
+    rng=rng, **bootstrap_kws)).
+
+    Returns a list: element i is the pair (resdict, obsdict) of object i, as
+    metacal_bootstrap returns it -- resdict[type] the object's result dict
+    (flags != 0 and NaN parameters where the reference raises BootPSFFailure),
+    obsdict[type] its metacal observation(s).
+    """
+    from .pipeline import bootstrap_many
+    list_of_obs = list(list_of_obs)
+    if not list_of_obs:
+        return []
+    parts = [_flatten(o) for o in list_of_obs]
+    everything = ObsList()
+    for flat, _ in parts:
+        for o in flat:
+            everything.append(o)
+    obsdict = get_all_metacal(everything, rng=rng, **(metacal_kws or {}))
+    out = [({}, {}) for _ in list_of_obs]
+    for t, tobs in obsdict.items():
+        objs, at = [], 0
+        for flat, rebuild in parts:
+            objs.append(rebuild(list(tobs[at:at + len(flat)])))
+            at += len(flat)
+        many = bootstrap_many(objs, model=model, rng=rng, **bootstrap_kws)
+        for i, o in enumerate(objs):
+            out[i][0][t] = many[i]
+            out[i][1][t] = o
+    return out

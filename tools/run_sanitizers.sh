@@ -29,4 +29,5 @@ cd "$ROOT"
   python -m pytest tests/test_cabi_host.py tests/test_lm_core.py tests/test_oracle_golden.py \
       tests/test_host_logic.py -q -m "not gpu" -p no:cacheprovider \
       -k "not resource_guard and not hazard_guard and not every_declared_symbol and not library_matches_sources" 2>&1 | tail -25
+  make -C "$ROOT/ngmix_amd/csrc" -j4 asan-metacal-noise > /dev/null 2>&1 && "$ROOT/ngmix_amd/metacal_noise_host_asan"
 } | tee "$LOG"

@@ -8,7 +8,11 @@ Prints one JSON line per configuration: stamps/s of the whole call, the time
 of the spectrum kernel and of the rest (inverse FFT, psf images, assembly), the
 kernel's FMA rate and its fraction of the derived ceiling.
 
-usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2]
+--noise times the fixnoise noise field instead: the noise kernel alone
+(csrc/metacal_noise.hip), get_all(fixnoise=True) with the noise drawn on the
+device, and the same with the host draw (numpy normals, scaled and uploaded).
+
+usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2] [--noise]
 """
 import argparse
 import json
@@ -35,6 +39,10 @@ def main():
     ap.add_argument("--n", type=int, default=100000)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--noise", action="store_true",
+                    help="time the fixnoise noise field instead: the noise kernel alone, "
+                         "get_all(fixnoise=True) with device noise, and with the host draw "
+                         "and its upload")
     args = ap.parse_args()
     import torch
     from ngmix_amd import metacal
@@ -75,7 +83,26 @@ def main():
         pjac[:, 0:2] = (dim - 1) / 2.0
         sb = StampBatch.from_images(images, torch.ones_like(images), jac)
         psb = StampBatch.from_images(psfs, None, pjac)
-        mc = metacal.MetacalBatch(sb, psb, target_sigma=np.full(n, 0.4))
+        mc = metacal.MetacalBatch(sb, psb, target_sigma=np.full(n, 0.4),
+                                  rng=np.random.RandomState(dim))
+        if args.noise:
+            # (the kernel reads 8 B and writes 8 B per pixel)
+            kernel = timed(lambda: mc.device_noise(12345))
+            turned = timed(lambda: mc.device_noise(12345, rotated=True))
+            fused = timed(lambda: mc.get_all(fixnoise=True, noise=metacal.DeviceNoise(12345)))
+            two_step = timed(lambda: mc.get_all(fixnoise=True, noise=mc.device_noise(12345)))
+            host = timed(lambda: mc.get_all(fixnoise=True))
+            given = timed(lambda: mc.get_all(fixnoise=True, noise=noise))
+            nbytes = 16.0 * n * dim * dim
+            print(json.dumps({
+                "stamp": dim, "n": n, "noise_kernel_ms": kernel * 1e3,
+                "noise_kernel_rotated_ms": turned * 1e3,
+                "noise_kernel_GB_per_s": nbytes / kernel * 1e-9,
+                "get_all_device_noise_ms": fused * 1e3,
+                "get_all_device_noise_two_step_ms": two_step * 1e3,
+                "get_all_host_draw_ms": host * 1e3, "get_all_given_noise_ms": given * 1e3,
+            }), flush=True)
+            continue
         for fixnoise in (False, True):
             planes = 3 if fixnoise else 2
             total = timed(lambda: mc.get_all(fixnoise=fixnoise, noise=noise if fixnoise else None))
