@@ -425,6 +425,47 @@ int ngmix_metacal_noise_batch(const double *ierr, const int64_t *ids, uint64_t s
    the same code (csrc/metacal_noise.hpp), the host libm's log and sincos */
 int ngmix_metacal_noise_host(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                              int nrow, int ncol, int rot_k, double *out);
+/* DEVICE: the pre-psf Fourier moments (ngmix_prepsf_sums_batch's fourteen sums)
+   of every stamp as sheared BEFORE its psf, for ntypes shears, without making
+   an image: per (stamp, type) the sum over the weight kernel's kept modes k of
+   w(k) K(k) I^(k') / P^(k') at the sheared frequency k' = k + J^T (A - 1) J^-T k
+   (A = [[1 - g1, g2], [g2, 1 + g1]] / sqrt(1 - |g|^2), J the jacobian's
+   derivative matrix; k' = k exactly at g = 0).  I^ is the discrete-time Fourier
+   transform of the stamp's own samples, tapered by edge[r] edge[c] (edge (dim,),
+   NULL: no taper), about cen; P^ that of the psf stamp about psf_cen.  images,
+   weights (n, dim, dim), psf (n, pdim, pdim), cen, psf_cen (n, 2) = (row0,
+   col0); g (ntypes, 2), or (n, ntypes, 2) with per_stamp_g, on the device, and
+   g_host its host copy, checked (|g| < 1) before anything is launched.  The
+   plan of the padded fft_dim x fft_dim transform: mrow, mcol (nmodes,) SIGNED
+   mode numbers (k = 2 pi fftfreq(fft_dim) of them), wgt (nmodes,) 1 or 2, fk
+   (4, nmodes) = fkp, fkc, fkr, fkf.  |P^| <= 1e-5 |sum of the psf| is held at
+   that amplitude; the covariance weight is w pnoise / |P^|^2 with pnoise = (sum
+   of 1 / weight over the positive weights) (fft_dim / dim)^2.  sums (n, ntypes,
+   14): the four sums x fft_dim^-2, then the upper triangle of their covariance
+   x fft_dim^-4; flags (n, ntypes): 1, and the fourteen sums NaN, where a kept
+   mode has |k'_r| >= pi or |k'_c| >= pi, or a sum is not finite.  One block per
+   (stamp, type), fixed summation order: the same bits for every batch size and
+   order.  NGMIX_ERR_BAD_ARG before any launch for n < 0, a count or size that
+   is not positive, derivatives without an inverse, a NULL required pointer with
+   n > 0, a shear outside the unit circle, stamps that do not fit the 160 KB of
+   LDS, n ntypes beyond one grid; n == 0 is a no-op */
+int ngmix_prepsf_shear_sums_batch(
+    const double *images, const double *weights, const double *psf,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags, void *stream);
+/* HOST twin of ngmix_prepsf_shear_sums_batch: the same arguments on host
+   pointers (g is read, g_host checked), the same code (csrc/prepsf_shear.hpp)
+   in the kernel's summation order, the host libm's sincos and hypot */
+int ngmix_prepsf_shear_sums_host(
+    const double *images, const double *weights, const double *psf,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags);
 /* HOST: the generator alone: out (n, 4) = Philox4x32-10 of counters (n, 4)
    under keys (n, 2) */
 int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,

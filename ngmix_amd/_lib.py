@@ -299,6 +299,8 @@ SIGNATURES = {
     "ngmix_metacal_noise_batch": (_i32, [_vp, _vp, ctypes.c_uint64, _i64, _i32, _i32, _i32, _vp,
                                          _vp]),
     "ngmix_metacal_noise_host": (_i32, [_vp, _vp, ctypes.c_uint64, _i64, _i32, _i32, _i32, _vp]),
+    "ngmix_prepsf_shear_sums_batch": (_i32, [_vp] * 8 + [_i32] + [_vp] * 4 + [_i64] + [_i32] * 5 + [_f64] * 4 + [_vp, _vp, _vp]),
+    "ngmix_prepsf_shear_sums_host": (_i32, [_vp] * 8 + [_i32] + [_vp] * 4 + [_i64] + [_i32] * 5 + [_f64] * 4 + [_vp, _vp]),
     "ngmix_philox4x32_10_host": (_i32, [_vp, _vp, _i64, _vp]),
     "ngmix_lm_prior_finish_batch": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "ngmix_first_pixels_fdiff2_batch": (_i32, [_pb, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),

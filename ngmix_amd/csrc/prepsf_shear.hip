@@ -1,0 +1,145 @@
+// Pre-psf Fourier moments of metacalibration's five types without the images
+// (DESIGN.md 3.21): the sums of prepsf.hip with the transforms of the stamp and
+// of its psf stamp taken at the SHEARED frequency of every kept mode of the
+// weight kernel,
+//
+//   M_t = sum_k w(k) K(k) I^(k'_t) / P^(k'_t),   k'_t = k + J^T (A_t - 1) J^-T k
+//
+// (prepsf_shear.hpp has the per-mode text, shared with the host twin).  Under a
+// shear k' is not a product grid, so the separable products of the unsheared
+// measurement do not apply: the transforms are dense sums of modes x pixels
+// terms, as in metacal.hip, over the kernel's modes alone.
+//
+// One block per (stamp, type).  The image -- tapered while it is staged -- and
+// the psf stamp lie in LDS; every thread owns kept modes and walks ALL pixels
+// in the same order, so every LDS read is one address for the whole wave (the
+// recurrence of dtft.hpp).  The fourteen products per mode are summed per
+// thread in the order of the mode list, then over the block in a fixed tree:
+// the results do not depend on the run, the batch's size or its order.  fp64,
+// no atomics.
+#include "common.hpp"
+#include "device_utils.hpp"
+#include "launch.hpp"
+#include "launch_util.hpp"
+#include "prepsf_shear.hpp"
+
+namespace ngmix {
+
+namespace {
+
+using namespace pshear;
+
+// The sums of NV per-thread values over a block of blockDim.x = 64 w threads,
+// valid in thread 0: the shuffle tree of wave_sum in every wave, then the waves
+// in order (host_block_sum of prepsf_shear.hpp is the same order).  scratch:
+// (blockDim.x / 64) * NV doubles of LDS.
+template <int NV>
+__device__ __forceinline__ void block_total(double (&vals)[NV], double *scratch)
+{
+#pragma unroll
+    for (int i = 0; i < NV; i++) vals[i] = wave_sum(vals[i]);
+    const int lane = lane_id(), w = wave_id(), nw = blockDim.x / WAVE;
+    __syncthreads();        // (an earlier round's scratch has been read)
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; i++) scratch[w * NV + i] = vals[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            double s = scratch[i];
+            for (int k = 1; k < nw; k++) s += scratch[k * NV + i];
+            vals[i] = s;
+        }
+    }
+}
+
+}  // namespace
+
+// images, weights (N, dim, dim), psf (N, pdim, pdim), cen, psf_cen (N, 2), edge
+// (dim,) or null, g (ng, T, 2) with ng = 1 or N; the plan: mrow, mcol, wgt
+// (nmodes,), fk (4, nmodes); deriv by value.  sums (N, T, 14), flags (N, T): 1
+// where a kept mode left the band or a sum is not finite (its sums are NaN).
+__global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
+    const double *__restrict__ images, const double *__restrict__ weights,
+    const double *__restrict__ psf, const double *__restrict__ cen,
+    const double *__restrict__ psf_cen, const double *__restrict__ edge,
+    const double *__restrict__ g, int per_stamp_g, const int32_t *__restrict__ mrow,
+    const int32_t *__restrict__ mcol, const double *__restrict__ wgt,
+    const double *__restrict__ fk, int T, int nmodes, int dim, int pdim, int fft_dim, double j00,
+    double j01, double j10, double j11, double *__restrict__ sums, int32_t *__restrict__ flags)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ double s_plane[2];      // the psf's sum, the stamp's total variance
+    const int64_t n = blockIdx.x / T;
+    const int t = blockIdx.x % T;
+    const int npix = dim * dim, nppix = pdim * pdim;
+
+    double *s_img = (double *)smem;
+    double *s_psf = s_img + npix;
+    double *s_red = s_psf + nppix;
+
+    // staging; on the way the two plane sums, strided as the host twin takes them
+    double plane[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < npix; i += blockDim.x) {
+        const double v = images[n * npix + i];
+        s_img[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
+        plane[1] += pixel_var(weights[n * npix + i]);
+    }
+    for (int i = threadIdx.x; i < nppix; i += blockDim.x) {
+        const double v = psf[n * nppix + i];
+        s_psf[i] = v;
+        plane[0] += v;
+    }
+    block_total<2>(plane, s_red);
+    if (threadIdx.x == 0) {
+        s_plane[0] = plane[0];
+        s_plane[1] = plane[1];
+    }
+    __syncthreads();
+
+    const double noise_scale = ((double)fft_dim / (double)dim) * ((double)fft_dim / (double)dim);
+    const double deriv[4] = {j00, j01, j10, j11};
+    const double *gt = g + ((per_stamp_g ? n * T : 0) + t) * 2;
+    const Setup m = setup(cen + 2 * n, psf_cen + 2 * n, deriv, gt[0], gt[1], s_plane[0],
+                          s_plane[1] * noise_scale);
+    const dtft::Planes planes = {s_img, nullptr, s_psf, dim, dim, pdim, pdim};
+
+    double acc[NSUMS];
+#pragma unroll
+    for (int i = 0; i < NSUMS; i++) acc[i] = 0.0;
+    bool out_of_band = false;
+    for (int k = threadIdx.x; k < nmodes; k += blockDim.x)
+        if (!add_mode(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k], fk[nmodes + k],
+                      fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
+            out_of_band = true;
+    const int any_out = __syncthreads_or(out_of_band ? 1 : 0);
+    block_total<NSUMS>(acc, s_red);
+    if (threadIdx.x == 0)
+        flags[n * T + t] = finish(acc, any_out != 0, fft_dim, sums + (n * T + t) * NSUMS) ? 1 : 0;
+}
+
+int launch_prepsf_shear_sums(const double *images, const double *weights, const double *psf,
+                             const double *cen, const double *psf_cen, const double *edge,
+                             const double *g, const double *g_host, int per_stamp_g,
+                             const int32_t *mrow, const int32_t *mcol, const double *wgt,
+                             const double *fk, int64_t n, int ntypes, int nmodes, int dim,
+                             int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow,
+                             double dudcol, double *sums, int32_t *flags, hipStream_t s)
+{
+    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
+    bool nothing;
+    const int st = check_args("prepsf_shear_sums", images, weights, psf, cen, psf_cen, g, g_host,
+                              per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
+                              fft_dim, deriv, sums, flags, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "prepsf_shear.hpp mirrors device_utils.hpp");
+    return launch(kernel(prepsf_shear_sums_kernel, "prepsf_shear_sums_kernel"),
+                  dim3((unsigned)(n * ntypes)), dim3(block_size(nmodes)), lds_bytes(dim, pdim),
+                  48 * 1024, s, images, weights, psf, cen, psf_cen, edge, g, per_stamp_g ? 1 : 0,
+                  mrow, mcol, wgt, fk, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
+                  dudcol, sums, flags);
+}
+
+}  // namespace ngmix

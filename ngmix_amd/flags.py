@@ -22,6 +22,12 @@ EIG_NOTFINITE = 1 << 13
 DIV_ZERO = 1 << 14
 ZERO_DOF = 1 << 15
 
+# not the reference's: set by the sheared pre-psf moments (prepsfmom.py
+# measure_arrays_sheared) in a result's 'flags' and, beside metacal's own bits
+# (metacal.METACAL_PSF_FIT_FAILURE = 1, METACAL_NONFINITE = 2), in its
+# 'mcal_flags' -- above both ranges, so that no existing bit is renumbered
+METACAL_BAND_LIMIT = 1 << 16
+
 EM_RANGE_ERROR = GMIX_RANGE_ERROR
 EM_MAXITER = MAXITER
 BAD_VAR = NONPOS_VAR
@@ -43,6 +49,7 @@ NAME_MAP = {
     EIG_NOTFINITE: 'eigenvalues of covariance cannot be found in LM',
     DIV_ZERO: 'divide by zero',
     ZERO_DOF: 'degrees of freedom for it is zero (no chi^2/dof possible)',
+    METACAL_BAND_LIMIT: 'sheared mode outside the band limit, or sums not finite',
 }
 
 

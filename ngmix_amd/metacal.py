@@ -31,6 +31,12 @@ catalogues"):
     metacal_bootstrap(obs, runner, psf_runner=None, ...), MetacalBootstrapper
     metacal_bootstrap_many(list_of_obs, model='gauss', ...)
 
+and the pre-psf moments of the five types straight from the stamps, without
+the images ("metacal pre-psf moments"; csrc/prepsf_shear.hip):
+
+    metacal_moments_batch(stamps, psf_stamps, measure, step=0.01, types=None) -> resdict
+    metacal_moments_many(list_of_obs, measure, step=0.01, types=None) -> [resdict_i]
+
 With noise_seed the fixnoise field is drawn on the device as a pure function
 of (seed, object id, pixel) (csrc/metacal_noise.hip): the same object gets the
 same field however the catalogue is cut into batches.
@@ -43,13 +49,15 @@ psf (the `*_psf` types).
 import numpy as np
 
 from . import _lib
+from .flags import METACAL_BAND_LIMIT   # a sheared mode of the pre-psf moments left the band
 from .jacobian import Jacobian
 from .observation import Observation, ObsList, MultiBandObsList
 
 __all__ = ["MetacalBatch", "get_all_metacal", "METACAL_TYPES", "METACAL_MINIMAL_TYPES",
            "METACAL_PSF_FIT_FAILURE", "METACAL_NONFINITE", "DeviceNoise",
            "metacal_bootstrap_batch", "shear_response", "mean_shear", "metacal_bootstrap",
-           "MetacalBootstrapper", "metacal_bootstrap_many"]
+           "MetacalBootstrapper", "metacal_bootstrap_many", "METACAL_BAND_LIMIT",
+           "metacal_moments_batch", "metacal_moments_many"]
 
 METACAL_MINIMAL_TYPES = ["noshear", "1p", "1m", "2p", "2m"]
 METACAL_TYPES = METACAL_MINIMAL_TYPES
@@ -58,6 +66,7 @@ DEFAULT_STEP = 0.01
 # per-stamp flags of the outputs
 METACAL_PSF_FIT_FAILURE = 1     # the adaptive moments of the psf stamp failed
 METACAL_NONFINITE = 2           # a kept mode of the spectrum was not finite
+# (METACAL_BAND_LIMIT = 1 << 16 lives in flags.py: it is also ORed into the fit flags)
 
 _PSF_FIT_NTRY = 4
 
@@ -666,6 +675,97 @@ def mean_shear(resp, select=None):
     if not use.any():
         raise ValueError("mean_shear: no unflagged object is selected")
     return np.linalg.solve(resp["R"][use].mean(axis=0), resp["g"][use].mean(axis=0))
+
+
+def _moments_measure(measure):
+    from .prepsfmom import PrePSFMom
+    if not isinstance(measure, PrePSFMom):
+        raise ValueError("measure must be a PGaussMom, KSigmaMom or PrePSFMom instance")
+    return measure
+
+
+def metacal_moments_batch(stamps, psf_stamps, measure, step=DEFAULT_STEP, types=None,
+                          fixnoise=False):
+    """
+    The pre-psf moments (`measure`: a PGaussMom / KSigmaMom / PrePSFMom) of the
+    metacal types of a stamp batch WITHOUT the metacal images: the moment sums
+    are taken in Fourier space at the sheared frequency of every mode the
+    weight kernel keeps (PrePSFMom.go_metacal_batch; the target psf of the
+    image route cancels exactly).
+
+    stamps, psf_stamps: the StampBatch pair of metacal_bootstrap_batch -- one
+    square shape each, one psf stamp per stamp, the same jacobian derivatives
+    for every stamp and its psf stamp.  The weight of a pixel is its ierr^2.
+
+    Returns resdict: {type: make_mom_result_batch dict with 'mcal_flags' (N,)},
+    what shear_response(resdict, step, key='e') and mean_shear take.  fixnoise
+    is not served (NotImplementedError), nor are the `*_psf` types.
+    """
+    from .batch import StampBatch
+    from .prepsfmom import _refuse_fixnoise
+    _moments_measure(measure)
+    _refuse_fixnoise(fixnoise)
+    types = _check_types(types)
+    if not isinstance(stamps, StampBatch) or not isinstance(psf_stamps, StampBatch):
+        raise ValueError("stamps and psf_stamps must be StampBatch objects")
+    if stamps.n != psf_stamps.n:
+        raise ValueError("one psf stamp per stamp: %d stamps, %d psf stamps"
+                         % (stamps.n, psf_stamps.n))
+    if stamps.val is None or psf_stamps.val is None or stamps.ierr is None:
+        raise ValueError("stamps and psf_stamps must hold pixel data")
+    shape, pshape = _one_shape(stamps, "stamps"), _one_shape(psf_stamps, "psf_stamps")
+    if shape[0] != shape[1] or pshape[0] != pshape[1]:
+        raise ValueError("pre-psf moments require square stamps, got %s and %s" % (shape, pshape))
+    n = stamps.n
+    derivs = stamps.jac[:, 2:6].cpu().numpy()
+    if np.any(derivs != derivs[0]) or np.any(psf_stamps.jac[:, 2:6].cpu().numpy() != derivs[0]):
+        raise ValueError("the stamps and their psf stamps must share one set of jacobian "
+                         "derivatives")
+    ierr = stamps.ierr.reshape(n, shape[0], shape[1])
+    return measure.go_metacal_batch(
+        stamps.val.reshape(n, shape[0], shape[1]), ierr * ierr, stamps.jac[:, 0:2],
+        tuple(float(d) for d in derivs[0]), psf_stamps.val.reshape(n, pshape[0], pshape[1]),
+        psf_stamps.jac[:, 0:2], step=step, types=types)
+
+
+def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fixnoise=False):
+    """
+    metacal_moments_batch for a catalogue of Observations (each with a psf
+    Observation of the same jacobian derivatives): grouped by (image size, psf
+    size, derivatives) as PrePSFMom.go_many groups, each group one batch on the
+    device.  Returns a list: element i is object i's {type:
+    moments.make_mom_result dict with 'mcal_flags'}, its 'flags' carrying the
+    metacal flag too.
+    """
+    from .moments import make_mom_result
+    from .prepsfmom import _check_obs_and_get_psf_obs, _refuse_fixnoise
+    _moments_measure(measure)
+    _refuse_fixnoise(fixnoise)
+    types = _check_types(types)
+    list_of_obs = list(list_of_obs)
+    psfs = [_check_obs_and_get_psf_obs(o, False) for o in list_of_obs]
+    groups = {}
+    for i, (o, p) in enumerate(zip(list_of_obs, psfs)):
+        j = o.jacobian
+        key = (o.image.shape[0], p.image.shape[0], j.dvdrow, j.dvdcol, j.dudrow, j.dudcol)
+        groups.setdefault(key, []).append(i)
+    g = _type_shears(types, float(step))
+    out = [None] * len(list_of_obs)
+    for key, idx in groups.items():
+        sub, psub = [list_of_obs[i] for i in idx], [psfs[i] for i in idx]
+        mom, cov, flags, kernels, _ = measure.measure_arrays_sheared(
+            np.stack([o.image for o in sub]), np.stack([o.weight for o in sub]),
+            np.array([[o.jacobian.row0, o.jacobian.col0] for o in sub]), key[2:],
+            np.stack([p.image for p in psub]),
+            np.array([[p.jacobian.row0, p.jacobian.col0] for p in psub]), g)
+        for k, i in enumerate(idx):
+            out[i] = {}
+            for it, t in enumerate(types):
+                res = make_mom_result(mom[k, it], cov[k, it], sums_norm=kernels["fk00"])
+                res["mcal_flags"] = int(flags[k, it])
+                res["flags"] |= int(flags[k, it])
+                out[i][t] = res
+    return out
 
 
 def metacal_bootstrap(obs, runner, psf_runner=None, ignore_failed_psf=True, rng=None,

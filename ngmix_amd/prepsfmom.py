@@ -554,6 +554,156 @@ class PrePSFMom(object):
                 t += 1
         return mom, cov, kernels, target_dim
 
+    # ---- the moments of the object as sheared before the psf
+    def measure_arrays_sheared(self, images, weights, cen, deriv, psf_images, psf_cen, g):
+        """
+        The sums of measure_arrays for every stamp as sheared BEFORE its psf by
+        each of T shears, without making an image: the transforms of the stamp
+        and of its psf stamp are evaluated at the sheared frequency k' = k +
+        J^T (A - 1) J^-T k of every mode k the weight kernel keeps, and summed
+        against the unsheared kernels (csrc/prepsf_shear.hip; one launch, one
+        download).  At g = 0 these are measure_arrays' sums to rounding.
+
+        images, weights, cen, deriv, psf_images, psf_cen: as measure_arrays
+        takes them (device tensors are used where they lie); the psf is
+        required.  g: (T, 2) one shear per type, or (N, T, 2) per stamp and
+        type, inside the unit circle.
+
+        Returns (sums (N, T, 6) = [nan, nan, M+, Mx, Mr, Mf], their covariance
+        (N, T, 6, 6), flags (N, T), the kernels, the padded size).  flags is
+        flags.METACAL_BAND_LIMIT where a kept mode's sheared frequency leaves
+        the band (|k'_r| or |k'_c| >= pi) or a sum is not finite: the fourteen
+        sums of that (stamp, type) are NaN.
+        """
+        from .flags import METACAL_BAND_LIMIT
+        if psf_images is None or psf_cen is None:
+            raise NotImplementedError(
+                "sheared pre-psf moments deconvolve the psf at the sheared frequency: "
+                "no_psf (a pixel in real space) is not served")
+        if self.use_noise_image:
+            raise NotImplementedError(
+                "sheared pre-psf moments take the noise power from the weight map: "
+                "use_noise_image=True is not served")
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        if g.ndim not in (2, 3) or g.shape[-1] != 2 or g.shape[-2] == 0:
+            raise ValueError("g must be (T, 2) or (N, T, 2), got %s" % (g.shape,))
+        if not np.all(g[..., 0] ** 2 + g[..., 1] ** 2 < 1.0):
+            raise ValueError("shears must lie inside the unit circle")
+        n, dim = images.shape[0], images.shape[1]
+        pdim, ntypes = psf_images.shape[1], g.shape[-2]
+        if images.shape[2] != dim or psf_images.shape[2] != pdim:
+            raise ValueError("pre-psf moments require square stamps")
+        if g.ndim == 3 and g.shape[0] != n:
+            raise ValueError("per-stamp shears must be (%d, T, 2), got %s" % (n, g.shape))
+        if psf_images.shape[0] != n:
+            raise ValueError("one psf stamp per stamp: %d stamps, %d psf stamps"
+                             % (n, psf_images.shape[0]))
+        deriv = tuple(float(d) for d in deriv)
+        target_dim = int(max(dim, pdim) * self.pad_factor)
+        mom = np.full((n, ntypes, 6), np.nan)
+        cov = np.zeros((n, ntypes, 6, 6))
+        cov[:, :, 0, 0] = cov[:, :, 1, 1] = 1.0      # (as measure_arrays leaves them)
+        if n == 0:
+            kernels = _kernels(self.kind, target_dim, float(self.fwhm), deriv,
+                               float(self.fwhm_smooth))
+            return mom, cov, np.zeros((0, ntypes), dtype=np.int32), kernels, target_dim
+        torch = _torch()
+        from . import _lib
+        from .batch import _require_cuda, _dptr, _stream
+        dev = _require_cuda(None)
+        kernels = _kernels(self.kind, target_dim, float(self.fwhm), deriv,
+                           float(self.fwhm_smooth))
+        mrow, mcol, wgt, fk = _shear_plan(kernels, target_dim)
+        d_im = _to_device(images, dev).contiguous()
+        d_w = _to_device(weights, dev).contiguous()
+        d_psf = _to_device(psf_images, dev).contiguous()
+        d_cen = _to_device(cen, dev).contiguous()
+        d_pcen = _to_device(psf_cen, dev).contiguous()
+        if tuple(d_w.shape) != tuple(d_im.shape) or tuple(d_cen.shape) != (n, 2) or \
+                tuple(d_pcen.shape) != (n, 2):
+            raise ValueError("weights must have the images' shape, cen and psf_cen (N, 2)")
+        d_edge = None
+        if self.ap_rad > 0:
+            d_edge = torch.from_numpy(_apodization_edge(dim, self.ap_rad)).to(dev)
+        d_g = torch.from_numpy(g).to(dev)
+        d_plan = [torch.from_numpy(a).to(dev) for a in (mrow, mcol, wgt, fk)]
+        d_sums = torch.empty((n, ntypes, 14), dtype=torch.float64, device=dev)
+        d_flags = torch.empty((n, ntypes), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib().ngmix_prepsf_shear_sums_batch(
+                _dptr(d_im), _dptr(d_w), _dptr(d_psf), _dptr(d_cen), _dptr(d_pcen), _dptr(d_edge),
+                _dptr(d_g), _lib.ptr(g), 1 if g.ndim == 3 else 0, _dptr(d_plan[0]),
+                _dptr(d_plan[1]), _dptr(d_plan[2]), _dptr(d_plan[3]), n, ntypes, int(mrow.size),
+                int(dim), int(pdim), target_dim, deriv[0], deriv[1], deriv[2], deriv[3],
+                _dptr(d_sums), _dptr(d_flags), _stream())
+        _lib.check(st, "ngmix_prepsf_shear_sums_batch")
+        # one download: a flagged (stamp, type) is the one whose sums are NaN, all
+        # fourteen (d_flags says the same to callers that stay on the device)
+        sums = d_sums.cpu().numpy()
+        flags = np.where(np.isnan(sums[:, :, 0]), METACAL_BAND_LIMIT, 0).astype(np.int32)
+        mom[:, :, 2:6] = sums[:, :, :4]
+        t = 4
+        for a in range(4):
+            for b in range(a, 4):
+                cov[:, :, 2 + a, 2 + b] = cov[:, :, 2 + b, 2 + a] = sums[:, :, t]
+                t += 1
+        return mom, cov, flags, kernels, target_dim
+
+    def go_metacal_batch(self, images, weights, cen, deriv, psf_images, psf_cen, step=0.01,
+                         types=None, fixnoise=False):
+        """
+        The pre-psf moments of metacalibration's types from the stamps alone
+        (measure_arrays_sheared at the types' shears, no metacal image is
+        made): {type: moments.make_mom_result_batch dict} for types of
+        metacal.METACAL_MINIMAL_TYPES (default: all five), each with
+        'mcal_flags' (N,) added and ORed into 'flags'; the rows of flagged
+        stamps are NaN.  metacal.shear_response(resdict, step, key='e') and
+        metacal.mean_shear take the result as it is.
+
+        fixnoise is not served: moments of noisy stamps carry the noise
+        response.
+        """
+        from .metacal import _check_types, _type_shears
+        from .moments import make_mom_result_batch
+        _refuse_fixnoise(fixnoise)
+        types = _check_types(types)
+        g = _type_shears(types, float(step))
+        mom, cov, flags, kernels, _ = self.measure_arrays_sheared(
+            images, weights, cen, deriv, psf_images, psf_cen, g)
+        out = {}
+        for i, t in enumerate(types):
+            res = make_mom_result_batch(mom[:, i], cov[:, i], sums_norm=kernels["fk00"])
+            res["mcal_flags"] = flags[:, i].copy()
+            res["flags"] = res["flags"] | flags[:, i]
+            out[t] = res
+        return out
+
+
+def _refuse_fixnoise(fixnoise):
+    if fixnoise:
+        raise NotImplementedError(
+            "fixnoise is not served by the sheared pre-psf moments: the turned noise plane is "
+            "deconvolved by the un-turned psf and turned back, which needs a frequency map of "
+            "its own for the plane and another for the psf; moments of noisy stamps carry the "
+            "noise response until then")
+
+
+def _shear_plan(kernels, target_dim):
+    """what the sheared-mode kernel takes of _mode_plan: the SIGNED row and
+    column mode numbers of the kept modes (fftfreq's numerators), their weights
+    (1 or 2) and the four kernels (4, nmodes) = fkp, fkc, fkr, fkf"""
+    plan = _mode_plan(kernels, None)
+    if "shear" not in plan:
+        half = (target_dim + 1) // 2
+
+        def signed(i):
+            return np.where(i < half, i, i - target_dim).astype(np.int32)
+        fk = np.ascontiguousarray(np.stack([kernels[k][plan["keep"]]
+                                            for k in ("fkp", "fkc", "fkr", "fkf")]), dtype="f8")
+        plan["shear"] = (signed(plan["rows"]), signed(plan["cols"]),
+                         np.ascontiguousarray(plan["wgt"], dtype="f8"), fk)
+    return plan["shear"]
+
 
 def _sums_torch(kim_re, kim_im, kpsf_re, kpsf_im, pix, kn_re, kn_im, pnoise_stamp, noise_scale,
                 max_amp, py, px, d_irow, d_icol, fk, wgt, df2, df4):

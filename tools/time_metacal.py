@@ -12,7 +12,13 @@ kernel's FMA rate and its fraction of the derived ceiling.
 (csrc/metacal_noise.hip), get_all(fixnoise=True) with the noise drawn on the
 device, and the same with the host draw (numpy normals, scaled and uploaded).
 
-usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2] [--noise]
+--moments times the pre-psf moments of the five types, PGaussMom(fwhm=2.0):
+the sheared-mode kernel alone (csrc/prepsf_shear.hip), metacal_moments_batch
+end to end, and the two-step route for the same quantities -- get_all(
+fixnoise=False), then measure_arrays on each type's images and target psf
+images.  Prints nmodes, the kept modes of the kernel's plan.
+
+usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2] [--noise | --moments]
 """
 import argparse
 import json
@@ -43,6 +49,9 @@ def main():
                     help="time the fixnoise noise field instead: the noise kernel alone, "
                          "get_all(fixnoise=True) with device noise, and with the host draw "
                          "and its upload")
+    ap.add_argument("--moments", action="store_true",
+                    help="time the pre-psf moments of the five types instead: the sheared-mode "
+                         "kernel alone, metacal_moments_batch, and get_all + measure_arrays")
     args = ap.parse_args()
     import torch
     from ngmix_amd import metacal
@@ -103,6 +112,9 @@ def main():
                 "get_all_host_draw_ms": host * 1e3, "get_all_given_noise_ms": given * 1e3,
             }), flush=True)
             continue
+        if args.moments:
+            print(json.dumps(_moments(mc, sb, psb, dim, scale, timed)), flush=True)
+            continue
         for fixnoise in (False, True):
             planes = 3 if fixnoise else 2
             total = timed(lambda: mc.get_all(fixnoise=fixnoise, noise=noise if fixnoise else None))
@@ -117,6 +129,55 @@ def main():
                 "kernel_fma_per_s": fma / kernel,
                 "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S,
             }), flush=True)
+
+
+def _moments(mc, sb, psb, dim, scale, timed):
+    """the three timings of --moments for one stamp size"""
+    import torch
+    from ngmix_amd import _lib, metacal, prepsfmom
+    from ngmix_amd.batch import _dptr, _stream
+    n, dev = mc.n, mc.device
+    m = prepsfmom.PGaussMom(fwhm=2.0)
+    deriv = (scale, 0.0, 0.0, scale)
+    D = int(dim * m.pad_factor)
+    kernels = prepsfmom._kernels(m.kind, D, float(m.fwhm), deriv, float(m.fwhm_smooth))
+    plan = [torch.from_numpy(a).to(dev) for a in prepsfmom._shear_plan(kernels, D)]
+    nmodes = int(plan[0].numel())
+    g = metacal._type_shears(metacal.METACAL_MINIMAL_TYPES, 0.01)
+    d_g = torch.from_numpy(g).to(dev)
+    edge = torch.from_numpy(prepsfmom._apodization_edge(dim, m.ap_rad)).to(dev)
+    images = sb.val.reshape(n, dim, dim)
+    weights = (sb.ierr * sb.ierr).reshape(n, dim, dim)
+    cen, pcen = sb.jac[:, 0:2].contiguous(), psb.jac[:, 0:2].contiguous()
+    sums = torch.empty((n, 5, 14), dtype=torch.float64, device=dev)
+    flags = torch.empty((n, 5), dtype=torch.int32, device=dev)
+
+    def kernel_only():
+        st = _lib.lib().ngmix_prepsf_shear_sums_batch(
+            _dptr(images), _dptr(weights), _dptr(psb.val), _dptr(cen), _dptr(pcen), _dptr(edge),
+            _dptr(d_g), _lib.ptr(g), 0, _dptr(plan[0]), _dptr(plan[1]), _dptr(plan[2]),
+            _dptr(plan[3]), n, 5, nmodes, dim, dim, D, deriv[0], deriv[1], deriv[2], deriv[3],
+            _dptr(sums), _dptr(flags), _stream())
+        _lib.check(st, "ngmix_prepsf_shear_sums_batch")
+
+    def two_step():
+        both = mc.get_all(fixnoise=False)
+        for t in metacal.METACAL_MINIMAL_TYPES:
+            d = both[t]
+            m.measure_arrays(d["stamps"].val.reshape(n, dim, dim), weights, cen.cpu().numpy(), deriv,
+                             d["psf_stamps"].val.reshape(n, dim, dim),
+                             d["psf_stamps"].jac[:, 0:2].cpu().numpy())
+    kernel = timed(kernel_only)
+    total = timed(lambda: metacal.metacal_moments_batch(sb, psb, m))
+    parent = timed(two_step)
+    # per (stamp, type): every kept mode walks every pixel of the image and the psf
+    fma = float(nmodes) * dim * dim * (4 + 2 * 2) * 5 * n
+    return {"stamp": dim, "n": n, "types": 5, "fft_dim": D, "nmodes": nmodes,
+            "modes_of_the_spectrum_kernel": dim * (dim // 2 + 1) + (dim // 2 + 1) + dim - 1,
+            "shear_sums_kernel_ms": kernel * 1e3, "metacal_moments_batch_ms": total * 1e3,
+            "get_all_then_measure_arrays_ms": parent * 1e3,
+            "kernel_fma_per_s": fma / kernel,
+            "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S}
 
 
 def _spectrum_only(mc, g, noise):
