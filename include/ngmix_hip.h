@@ -316,6 +316,24 @@ typedef struct {
  * every upload -- set when no stamp of the upload is flagged, cleared when one
  * is -- so a caller who wants the diagnostic sets it AFTER the upload */
 #define NGMIX_BATCH_STREAM_IERR 16
+/* every stamp of the batch is max_nrow x max_ncol with max_ngauss > 0 gaussians,
+ * pixels are packed (stamps[i].pix_off == i * max_npix), mixtures stamp-major
+ * (stamps[i].gm_off == i * max_ngauss), nothing is masked (npix_kept ==
+ * max_npix) and all stamps[i].flags are ONE word, which the batch carries in
+ * NGMIX_BATCH_REGULAR_STAMP_FLAGS.  Every field of ngmix_stamp is then a launch
+ * constant or affine in the stamp index, and the fused loglike / fdiff / s2n /
+ * render kernels run instantiations that read no stamp record and ask for the
+ * jacobian, the gaussian records and the first tiles at once (same arithmetic,
+ * bit-identical results).  A fact about the table, established where the
+ * table is built from host arrays, never a guess: ngmix_batch_upload REWRITES
+ * both fields on every upload; a table built elsewhere leaves them clear.  A
+ * launch whose host fields contradict the bit (any_masked, max_nrow * max_ncol
+ * != max_npix, max_ngauss <= 0) is NGMIX_ERR_BAD_ARG. */
+#define NGMIX_BATCH_REGULAR 32
+/* with NGMIX_BATCH_REGULAR: the common stamps[i].flags word (NGMIX_STAMP_*),
+ * shifted left by NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT */
+#define NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT 8
+#define NGMIX_BATCH_REGULAR_STAMP_FLAGS (3 << NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT)
 
 /* A batch of stamps: HOST struct holding DEVICE pointers plus the few host
    facts a launch needs (LDS sizing, tile schedule). */
@@ -345,7 +363,10 @@ typedef struct {
    NGMIX_ERR_BAD_ARG (the reference's GMixFatalError).  The same pass sets
    NGMIX_STAMP_UNIFORM_IERR per stamp, and upload rewrites the batch's
    NGMIX_BATCH_STREAM_IERR bit from it (set: no stamp flagged; a value the
-   caller put there before the upload is lost).  The returned pointer
+   caller put there before the upload is lost), and likewise NGMIX_BATCH_REGULAR
+   with NGMIX_BATCH_REGULAR_STAMP_FLAGS (set: all stamps have one shape and,
+   after the pass, one flag word, none is masked and ngauss > 0; the stamp-major
+   mixture layout is the store's own).  The returned pointer
    is what the *_batch entry points take; release it with ngmix_batch_free. */
 int ngmix_batch_create(ngmix_batch **out, int64_t nstamps, const int32_t *nrow,
                        const int32_t *ncol, int32_t ngauss, int ignore_zero_weight);
@@ -1112,6 +1133,11 @@ int ngmix_event_elapsed_ms(void *start, void *stop, float *ms);
    a silent fall-back to a generic kernel is a performance bug no parity
    test sees. */
 int64_t ngmix_launch_census(char *buf, int64_t buflen, int reset);
+/* ... and how many of the fused pixel-pass launches went to the instantiations
+   for NGMIX_BATCH_REGULAR batches.  (The census counts those under the names of
+   the kernels they stand in for, as it does the streaming kernels.)  reset != 0
+   clears the count afterwards. */
+int64_t ngmix_launch_census_regular(int reset);
 
 /* ======================================================================
  * (4) MULTI-GPU: one process per GPU; objects are sharded by contiguous

@@ -45,6 +45,9 @@ BATCH_EXACT = 2
 BATCH_TRACKED_LOADS = 4
 BATCH_RENDER_OVERWRITE = 8
 BATCH_STREAM_IERR = 16
+BATCH_REGULAR = 32
+BATCH_REGULAR_STAMP_FLAGS_SHIFT = 8
+BATCH_REGULAR_STAMP_FLAGS = 3 << BATCH_REGULAR_STAMP_FLAGS_SHIFT
 
 # ---- record layouts = the reference's numpy dtypes ----
 GAUSS2D_DTYPE = np.dtype([
@@ -310,6 +313,7 @@ SIGNATURES = {
                                       _vp]),
     "ngmix_lm_finalize_batch": (_i32, [_vp, _i64, _vp, _vp, _f64, _f64, _vp, _vp]),
     "ngmix_launch_census": (_i64, [ctypes.c_char_p, _i64, _i32]),
+    "ngmix_launch_census_regular": (_i64, [_i32]),
     "ngmix_lm_pack_batch": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ngmix_lm_rounds_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "ngmix_lm_precise_cov_batch": (_i32, [_vp, _vp, _vp]),
@@ -432,6 +436,12 @@ def launch_census(reset=False):
         name, _, count = line.rpartition("\t")
         out[name] = int(count)
     return out
+
+
+def regular_launches(reset=False):
+    """fused pixel-pass launches that went to the regular-batch kernels
+    (BATCH_REGULAR) so far in this process (ngmix_launch_census_regular)"""
+    return int(lib().ngmix_launch_census_regular(1 if reset else 0))
 
 
 def last_error():

@@ -261,9 +261,21 @@ class StampBatch(object):
         self.tracked_loads = False
         # diagnostic: stream ierr also for the stamps flagged STAMP_UNIFORM_IERR
         self.stream_ierr = False
+        # diagnostic: never launch the regular-batch kernels (BATCH_REGULAR)
+        self.general_kernels = False
         self.max_npix = int(self.npix.max()) if self.n else 0
+        self.max_nrow = int(self.nrow.max()) if self.n else 0
+        self.max_ncol = int(self.ncol.max()) if self.n else 0
         self.total_pix = int(self.npix.sum())
+        # the part of BATCH_REGULAR that the geometry alone decides: one shape,
+        # pixels packed in stamp order
+        self._regular_shape = bool(
+            self.n > 0 and self.max_npix > 0 and
+            np.all(self.nrow == self.max_nrow) and np.all(self.ncol == self.max_ncol) and
+            np.array_equal(self.pix_off,
+                           np.arange(self.n, dtype=np.int64) * self.max_npix))
         self._stamp_tables = {}
+        self._regular_words = {}
         # count kept pixels once (device) so masked stamps are known
         self.npix_kept = self.npix.astype(np.int32).copy()
         if npix_kept is not None:
@@ -562,28 +574,64 @@ class StampBatch(object):
         flat = tab.view(np.int32).reshape(self.n, 8)
         return torch.from_numpy(flat.copy()).to(self.device)
 
-    def stamp_table(self, ngauss):
-        """device ngmix_stamp records for mixtures laid out stamp-major.
-        ngauss: one int (gm_off = i*ngauss) or a per-stamp sequence (ragged,
-        gm_off = running sum); cached per layout"""
+    def _keyed_table(self, ngauss):
+        """(cache key, table) of stamp_table: the key is made once per call"""
         if np.ndim(ngauss) == 0:
             key = int(ngauss)
-            ng = np.full(self.n, key, dtype=np.int64)
         else:
             ng = np.asarray(ngauss, dtype=np.int64)
             assert ng.shape == (self.n,)
             key = tuple(ng.tolist())
         if key not in self._stamp_tables:
+            if np.ndim(ngauss) == 0:
+                ng = np.full(self.n, key, dtype=np.int64)
             gm_off = np.concatenate([[0], np.cumsum(ng)[:-1]]) if self.n else ng
             assert (gm_off[-1] + ng[-1]) < 2 ** 31 if self.n else True
             self._stamp_tables[key] = self._make_table(
                 self.npix_kept, gm_off.astype(np.int32), ng.astype(np.int32))
-        return self._stamp_tables[key]
+        return key, self._stamp_tables[key]
+
+    def stamp_table(self, ngauss):
+        """device ngmix_stamp records for mixtures laid out stamp-major.
+        ngauss: one int (gm_off = i*ngauss) or a per-stamp sequence (ragged,
+        gm_off = running sum); cached per layout"""
+        return self._keyed_table(ngauss)[1]
+
+    def _regular_bits_of(self, key, tab):
+        """regular_bits for a table of _keyed_table"""
+        hit = self._regular_words.get(key)
+        if hit is not None and hit[0] is tab:
+            return hit[1]
+        bits = 0
+        # (a per-stamp ngauss sequence with equal entries is the same layout)
+        ng = key if not isinstance(key, tuple) else \
+            (key[0] if key and len(set(key)) == 1 else 0)
+        if self._regular_shape and ng > 0 and \
+                np.all(self.flags == self.flags[0]) and \
+                np.all(self.npix_kept == self.max_npix):
+            word = int(self.flags[0])
+            if word == word & (_lib.BATCH_REGULAR_STAMP_FLAGS >>
+                               _lib.BATCH_REGULAR_STAMP_FLAGS_SHIFT):
+                bits = _lib.BATCH_REGULAR | (word << _lib.BATCH_REGULAR_STAMP_FLAGS_SHIFT)
+        self._regular_words[key] = (tab, bits)
+        return bits
+
+    def regular_bits(self, ngauss):
+        """
+        the BATCH_REGULAR bits of the stamp table for this mixture layout: set
+        when every stamp has one shape, one flag word and the same ngauss > 0,
+        pixels are packed in stamp order, mixtures stamp-major and nothing is
+        masked -- with the common flag word in BATCH_REGULAR_STAMP_FLAGS; else 0.
+        Found once per cached table, from the host arrays the table is made of.
+        """
+        return self._regular_bits_of(*self._keyed_table(ngauss))
 
     def _batch(self, ngauss, no_skip=False, exact=False):
         b = _lib.Batch()
         b.nstamps = self.n
-        b.stamps = self.stamp_table(ngauss).data_ptr()
+        key, tab = self._keyed_table(ngauss)
+        b.stamps = tab.data_ptr()
+        regular = 0 if self.general_kernels else self._regular_bits_of(key, tab)
         if np.ndim(ngauss) != 0:
             ngauss = int(np.max(ngauss)) if self.n else 0
         b.val = self.val.data_ptr() if self.val is not None else None
@@ -592,9 +640,9 @@ class StampBatch(object):
         b.max_ngauss = ngauss
         b.max_npix = self.max_npix
         b.any_masked = int(self.any_masked)
-        b.max_nrow = int(self.nrow.max()) if self.n else 0
-        b.max_ncol = int(self.ncol.max()) if self.n else 0
-        b.flags = (_lib.BATCH_NO_SKIP if no_skip else 0) | \
+        b.max_nrow = self.max_nrow
+        b.max_ncol = self.max_ncol
+        b.flags = regular | (_lib.BATCH_NO_SKIP if no_skip else 0) | \
             (_lib.BATCH_EXACT if exact else 0) | \
             (_lib.BATCH_TRACKED_LOADS if self.tracked_loads else 0) | \
             (_lib.BATCH_STREAM_IERR if self.stream_ierr or not self.any_uniform else 0)

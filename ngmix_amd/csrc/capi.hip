@@ -39,6 +39,17 @@ void census(const char *kernel)
     g_census[kernel] += 1;
 }
 
+// launches of the regular-batch instantiations (NGMIX_BATCH_REGULAR): they are
+// counted in the census under the names of the kernels they stand in for, and
+// here on top
+static long long g_census_regular = 0;
+
+void census_regular()
+{
+    std::lock_guard<std::mutex> lock(g_census_mutex);
+    g_census_regular += 1;
+}
+
 // grow-only device scratch, one set per host thread AND per device: after
 // ngmix_set_device(other) on the same thread the seam forms must not reuse
 // pointers that belong to the previous device
@@ -1040,6 +1051,14 @@ int64_t ngmix_launch_census(char *buf, int64_t buflen, int reset)
         buf[n] = 0;
     }
     return (int64_t)text.size() + 1;
+}
+
+int64_t ngmix_launch_census_regular(int reset)
+{
+    std::lock_guard<std::mutex> lock(g_census_mutex);
+    const long long n = g_census_regular;
+    if (reset) g_census_regular = 0;
+    return n;
 }
 
 }  // extern "C"

@@ -426,6 +426,8 @@ void set_last_error_msg(const char *msg);
 // silent fall-back to a generic kernel is a performance bug no parity test
 // sees).  A mutex-protected map; a few hundred nanoseconds per launch.
 void census(const char *kernel);
+// ... and, on top, that it was a regular-batch instantiation (pixpass.hip)
+void census_regular();
 }  // namespace ngmix
 
 #define NGMIX_HIP_CHECK(expr)                                   \

@@ -75,9 +75,11 @@ static size_t lds_bytes(int max_ngauss, int nchunks_cap, int tile_cap = 0)
 // them when gmix[0].norm_set == 0, stopping at the first failure; gaussians
 // before the failing one keep their fresh norms).  Also stages the exp table.
 // Returns the status for the stamp (uniform across the work-group).
-template <int NT = BLOCK>
+// KNOWN: the caller has read gm[0].norm_set already and says in `need_known`
+// whether the norms are to be set (the regular-batch kernels).
+template <int NT = BLOCK, bool KNOWN = false>
 __device__ __forceinline__ int lazy_norms(const LdsLayout &L, ngmix_gauss2d *gm,
-                                          int ng)
+                                          int ng, bool need_known = false)
 {
     const int tid = threadIdx.x;
     if (tid < 16) L.tab[tid] = c_exp_table[tid];
@@ -88,7 +90,7 @@ __device__ __forceinline__ int lazy_norms(const LdsLayout &L, ngmix_gauss2d *gm,
         L.ctl[3] = 1;        // all chi2 forms positive definite (fused kernel)
     }
     __syncthreads();
-    const bool need = ng > 0 && gm[0].norm_set == 0;
+    const bool need = KNOWN ? need_known : (ng > 0 && gm[0].norm_set == 0);
     if (need) {
         for (int g = tid; g < ng; g += NT) {
             ngmix_gauss2d t = gm[g];
@@ -823,13 +825,31 @@ __device__ __forceinline__ void wave_tiles(
 // every pixel and is launched as the LS = false kernel: the plain loop, the
 // early request, no union of the boxes -- the launcher picks by that flag, and
 // the LS kernel does not look at it.
-template <int OP, bool MASKED, int TW, bool NG8, bool LS = (OP == OP_RENDER_FAST), bool UE = true>
+//
+// REG: the kernel of a batch with NGMIX_BATCH_REGULAR.  Every field of the
+// stamp record is then a kernel argument or affine in blockIdx.x: no record is
+// read, and the loads that the general kernel issues one memory round trip
+// after another -- the record, then gm[0].norm_set and the first tiles, then
+// the gaussian records -- are all issued at the top: the jacobian, lane g's
+// gaussian record (norm_set arrives inside record 0) and the early request of
+// the first four tiles, at byte offsets that follow from the shape alone.
+// Everything after that is the general kernel's text on the same numbers.
+struct RegularShape {
+    int nrow, ncol;      // every stamp's shape
+    unsigned ntx_magic;  // ceil(2^32 / ntx) for ntx >= 2, 0 for ntx == 1: T / ntx
+                         // = umulhi(T, magic), exact while T * ntx < 2^32
+};
+
+template <int OP, bool MASKED, int TW, bool NG8, bool LS = (OP == OP_RENDER_FAST), bool UE = true,
+          bool REG = false>
 __device__ __forceinline__ void pixpass_wave_body(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
-    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap,
+    const RegularShape rs)
 {
+    static_assert(!REG || !MASKED, "a regular batch has no masked stamp");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LdsLayout L = carve(smem, max_ngauss, nchunks_cap, tile_cap);
     GaussFused *gf = (GaussFused *)L.gl;
@@ -837,11 +857,28 @@ __device__ __forceinline__ void pixpass_wave_body(
     TileEnt *te = (TileEnt *)L.tb;
 
     const int s = blockIdx.x;
-    const ngmix_stamp st = stamps[s];
+    ngmix_stamp st;
+    if (REG) {
+        // (no_skip bits 3-4: the batch's common stamp flag word)
+        static_assert(NGMIX_STAMP_IGNORE_ZERO_WEIGHT == 1, "the flag word below");
+        st.nrow = rs.nrow;
+        st.ncol = rs.ncol;
+        st.pix_off = (int64_t)s * (rs.nrow * rs.ncol);
+        st.gm_off = 0;  // (not used: gm below, in 64 bits)
+        st.ngauss = max_ngauss;
+        st.flags = (no_skip >> 3) & 3;
+        st.npix_kept = rs.nrow * rs.ncol;
+    } else {
+        st = stamps[s];
+    }
     const ngmix_jacobian jac = jacs[s];
     const int nrow = st.nrow, ncol = st.ncol, ng = st.ngauss;
     const int npix = nrow * ncol;
-    ngmix_gauss2d *gm = gmix + st.gm_off;
+    ngmix_gauss2d *gm = REG ? gmix + (int64_t)s * max_ngauss : gmix + st.gm_off;
+    // REG: lane g's gaussian record, asked for before anything else (lanes past
+    // the last gaussian ask for the last one: no branch, one more cached line)
+    ngmix_gauss2d t0 = {};
+    if (REG) t0 = gm[threadIdx.x < (unsigned)ng ? (int)threadIdx.x : ng - 1];
     const double *sval = val + st.pix_off;
     const double *sierr = ierr + st.pix_off;
     const bool izw = (st.flags & NGMIX_STAMP_IGNORE_ZERO_WEIGHT) != 0;
@@ -867,10 +904,51 @@ __device__ __forceinline__ void pixpass_wave_body(
     const int ntx = (ncol + TW - 1) / TW;
     const int nty = (nrow + TH - 1) / TH;
     const int ntiles = ntx * nty;
+
+    // REG: the early request of the first four tiles is issued here, at once,
+    // behind the jacobian and the gaussian records -- the text of the general
+    // kernel's request below, with the offsets of tiles 0..3 computed from the
+    // shape on the scalar unit (row-major over ntx tiles per band, as stage 1
+    // writes them into te[]) instead of read from te[]
+    // (straight into the look-ahead registers: a register with an untracked load
+    // in flight must never be copied)
+    double pv[FUSED_PF], pe[FUSED_PF];
+#pragma unroll
+    for (int t = 0; t < FUSED_PF; t++) {
+        pv[t] = 0.0;
+        pe[t] = 0.0;
+    }
+    if constexpr (REG && !LS) {
+        const int rkeep = (OP == OP_RENDER_FAST) ? (((no_skip >> 2) & 1) - 1) : -1;
+        if ((nrow % TH) == 0 && (ncol % TW) == 0 && !(no_skip & 2)) {
+            const unsigned lane_off = (unsigned)((lane / TW) * ncol + lane % TW) * 8u;
+            int r0 = 0, c0 = 0;
+#pragma unroll
+            for (int t = 0; t < FUSED_PF; t++) {
+                // (a tile past the last one is issued with EXEC = 0, whatever its offset)
+                const int on = __builtin_amdgcn_readfirstlane(-(int)(t < ntiles));
+                const unsigned off = lane_off + (unsigned)((r0 * ncol + c0) * 8);
+                if (kNeedsVal) gload_f64_if(pv[t], (const char *)sval, off, on);
+                if (OP != OP_RENDER_FAST)
+                    gload_f64_if(pe[t], (const char *)sierr, off & (unsigned)ie_on, on);
+                if (OP == OP_RENDER_FAST)
+                    gload_f64_if(pv[t], (const char *)(out + st.pix_off), off, on & rkeep);
+                c0 += TW;
+                if (c0 >= ncol) {
+                    c0 = 0;
+                    r0 += TH;
+                }
+            }
+        }
+    }
+
     for (int T = lane; T < ntiles + FUSED_SENTINELS; T += WAVE) {
         TileEnt e;
         if (T < ntiles) {
-            const int ty = T / ntx, tx = T - ty * ntx;
+            // (REG: the division by the launch constant ntx is a multiplication)
+            const int ty = !REG ? T / ntx
+                                : (rs.ntx_magic ? (int)__umulhi((unsigned)T, rs.ntx_magic) : T);
+            const int tx = T - ty * ntx;
             e.r0 = ty * TH;
             e.c0 = tx * TW;
             const double rd = (double)e.r0 - jac.row0, cd = (double)e.c0 - jac.col0;
@@ -904,18 +982,12 @@ __device__ __forceinline__ void pixpass_wave_body(
     // ---- request the first tiles now: they fly while the gaussians are staged
     // (no_skip bit 1 = NGMIX_BATCH_TRACKED_LOADS: the compiler-tracked path)
     const bool full = (nrow % TH) == 0 && (ncol % TW) == 0 && !(no_skip & 2);
-    double pv[FUSED_PF], pe[FUSED_PF];
-#pragma unroll
-    for (int t = 0; t < FUSED_PF; t++) {
-        pv[t] = 0.0;
-        pe[t] = 0.0;
-    }
     // (not the line-skipping render's: it asks only for the lines that the union
     // of the boxes reaches, which exists after stage 2; wave_tiles requests them.
     // An overwriting render issues them here with EXEC = 0.  Keeping this
     // early request unmasked would read the stamp's first four tiles, rows 0-4,
     // which are the lines most often out of reach)
-    if (full && ng > 0 && ntiles > 0 && !LS) {
+    if (!REG && full && ng > 0 && ntiles > 0 && !LS) {
         const unsigned lane_off = (unsigned)((lane / TW) * ncol + lane % TW) * 8u;
 #pragma unroll
         for (int t = 0; t < FUSED_PF; t++) {
@@ -934,7 +1006,15 @@ __device__ __forceinline__ void pixpass_wave_body(
 
     // ---- stage 2: norms (lazily, as the reference) and gaussian records
     const bool overwrite = OP == OP_RENDER_FAST && !LS && (no_skip & 4);
-    const int stcode = lazy_norms<WAVE>(L, gm, ng);
+    // REG: gm[0].norm_set came with lane 0's record.  When the norms have to be
+    // set the general sequence runs, and the records asked for at the top are
+    // stale: they are read again
+    bool need_norms = false;
+    if (REG)
+        need_norms = __builtin_amdgcn_readfirstlane(
+                         (int)((unsigned long long)t0.norm_set >> 32) | (int)t0.norm_set) == 0;
+    const int stcode = REG ? lazy_norms<WAVE, true>(L, gm, ng, need_norms)
+                           : lazy_norms<WAVE>(L, gm, ng);
     if (stcode != NGMIX_OK || (overwrite && ng == 0)) {
         // the look-ahead registers are dead on this path and the compiler may
         // reuse them: not before their loads have landed
@@ -950,9 +1030,17 @@ __device__ __forceinline__ void pixpass_wave_body(
     }
     // the fused evaluator indexes the table by n = round(chi2/2): exp(-n)
     if (lane < 16) L.tab[lane] = c_exp_table[15 - lane];
-    const double row0 = ng > 0 ? gm[0].row : 0.0, col0 = ng > 0 ? gm[0].col : 0.0;
+    if (REG && need_norms) t0 = gm[lane < ng ? lane : ng - 1];
+    // (REG: record 0 is lane 0's)
+    auto first_lane = [](double x) {
+        return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)),
+                                __builtin_amdgcn_readfirstlane(__double2loint(x)));
+    };
+    const double row0 = REG ? first_lane(t0.row) : (ng > 0 ? gm[0].row : 0.0);
+    const double col0 = REG ? first_lane(t0.col) : (ng > 0 ? gm[0].col : 0.0);
     for (int g = lane; g < ng; g += WAVE) {
-        const ngmix_gauss2d t = gm[g];
+        // (REG: the first round stages the records that are already in registers)
+        const ngmix_gauss2d t = (REG && g == lane) ? t0 : gm[g];
         GaussFused r;
         r.a = 0.5 * t.dcc;   // exact scalings: y == 0.5 * chi2 bit for bit
         r.b = 0.5 * t.drr;
@@ -1063,71 +1151,79 @@ __device__ __forceinline__ void pixpass_wave_body(
     }
 }
 
-template <int OP, bool MASKED, int TW, bool NG8>
+template <int OP, bool MASKED, int TW, bool NG8, bool REG = false>
 __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
-    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap,
+    const RegularShape rs)
 {
-    pixpass_wave_body<OP, MASKED, TW, NG8>(stamps, val, ierr, jacs, gmix, out, out_start, status,
-                                      max_ngauss, nchunks_cap, no_skip, tile_cap);
+    pixpass_wave_body<OP, MASKED, TW, NG8, (OP == OP_RENDER_FAST), true, REG>(
+        stamps, val, ierr, jacs, gmix, out, out_start, status, max_ngauss, nchunks_cap, no_skip,
+        tile_cap, rs);
 }
 
 // the render that overwrites (writes every pixel, reads none): no line skip
-template <int OP, bool MASKED, int TW, bool NG8>
+template <int OP, bool MASKED, int TW, bool NG8, bool REG = false>
 __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_plain(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
-    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap,
+    const RegularShape rs)
 {
-    pixpass_wave_body<OP, MASKED, TW, NG8, false>(stamps, val, ierr, jacs, gmix, out, out_start,
-                                             status, max_ngauss, nchunks_cap, no_skip, tile_cap);
+    pixpass_wave_body<OP, MASKED, TW, NG8, false, true, REG>(
+        stamps, val, ierr, jacs, gmix, out, out_start, status, max_ngauss, nchunks_cap, no_skip,
+        tile_cap, rs);
 }
 
 // get_loglike at seven waves per SIMD: its body fits 72 VGPRs without spilling
 // (the boxes re-read at each ballot, the window in the form that needs no VGPR constant), and
 // with instruction issue and memory both ~80 % busy one more resident wave per
 // SIMD is what overlaps them better
-template <int OP, bool MASKED, int TW, bool NG8>
+template <int OP, bool MASKED, int TW, bool NG8, bool REG = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7)))
 void pixpass_wave_kernel7(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
-    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap,
+    const RegularShape rs)
 {
-    pixpass_wave_body<OP, MASKED, TW, NG8>(stamps, val, ierr, jacs, gmix, out, out_start, status,
-                                      max_ngauss, nchunks_cap, no_skip, tile_cap);
+    pixpass_wave_body<OP, MASKED, TW, NG8, (OP == OP_RENDER_FAST), true, REG>(
+        stamps, val, ierr, jacs, gmix, out, out_start, status, max_ngauss, nchunks_cap, no_skip,
+        tile_cap, rs);
 }
 
 // loglike / fdiff / s2n of a batch in which no stamp is flagged
 // NGMIX_STAMP_UNIFORM_IERR (or with NGMIX_BATCH_STREAM_IERR): every weight map
 // is streamed, and the kernel carries nothing of the other path
-template <int OP, bool MASKED, int TW, bool NG8>
+template <int OP, bool MASKED, int TW, bool NG8, bool REG = false>
 __global__ __launch_bounds__(WAVE) void pixpass_wave_kernel_stream(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
-    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap,
+    const RegularShape rs)
 {
-    pixpass_wave_body<OP, MASKED, TW, NG8, false, false>(stamps, val, ierr, jacs, gmix, out,
-                                                    out_start, status, max_ngauss,
-                                                    nchunks_cap, no_skip, tile_cap);
+    pixpass_wave_body<OP, MASKED, TW, NG8, false, false, REG>(
+        stamps, val, ierr, jacs, gmix, out, out_start, status, max_ngauss, nchunks_cap, no_skip,
+        tile_cap, rs);
 }
 
-template <int OP, bool MASKED, int TW, bool NG8>
+template <int OP, bool MASKED, int TW, bool NG8, bool REG = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7)))
 void pixpass_wave_kernel7_stream(
     const ngmix_stamp *__restrict__ stamps, const double *__restrict__ val,
     const double *__restrict__ ierr, const ngmix_jacobian *__restrict__ jacs,
     ngmix_gauss2d *gmix, double *out, const int64_t *__restrict__ out_start,
-    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap)
+    int32_t *status, int max_ngauss, int nchunks_cap, int no_skip, int tile_cap,
+    const RegularShape rs)
 {
-    pixpass_wave_body<OP, MASKED, TW, NG8, false, false>(stamps, val, ierr, jacs, gmix, out,
-                                                    out_start, status, max_ngauss,
-                                                    nchunks_cap, no_skip, tile_cap);
+    pixpass_wave_body<OP, MASKED, TW, NG8, false, false, REG>(
+        stamps, val, ierr, jacs, gmix, out, out_start, status, max_ngauss, nchunks_cap, no_skip,
+        tile_cap, rs);
 }
 
 // ---------------------------------------------------------------- launchers
@@ -1163,41 +1259,50 @@ static auto pick_grid_kernel(bool k4)
 // that no generic kernel served the workload.)
 using WaveKernel = decltype(kernel(pixpass_wave_kernel<OP_LOGLIKE, false, 8, false>, ""));
 
-template <int FOP, int TW, bool NG8>
+// REG: the instantiations for NGMIX_BATCH_REGULAR batches (never masked), under
+// the same census names.
+template <int FOP, int TW, bool NG8, bool REG>
 static WaveKernel pick_wave_kernel_ng(bool masked, bool seven, bool stream, bool overwrite)
 {
+    // (REG: the masked kernels do not exist; `masked` is false, the launcher checks)
+    constexpr bool M = !REG;
     if constexpr (FOP == OP_LOGLIKE) {
         constexpr const char *n7 = "pixpass_wave_kernel7<loglike>";
         if (seven && stream)
-            return masked ? kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, true, 8, NG8>, n7)
-                          : kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8, NG8>, n7);
+            return masked ? kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, M, 8, NG8, REG>, n7)
+                          : kernel(pixpass_wave_kernel7_stream<OP_LOGLIKE, false, 8, NG8, REG>, n7);
         if (seven)
-            return masked ? kernel(pixpass_wave_kernel7<OP_LOGLIKE, true, 8, NG8>, n7)
-                          : kernel(pixpass_wave_kernel7<OP_LOGLIKE, false, 8, NG8>, n7);
+            return masked ? kernel(pixpass_wave_kernel7<OP_LOGLIKE, M, 8, NG8, REG>, n7)
+                          : kernel(pixpass_wave_kernel7<OP_LOGLIKE, false, 8, NG8, REG>, n7);
     }
     constexpr const char *n = FOP == OP_LOGLIKE ? "pixpass_wave_kernel<loglike>"
                               : FOP == OP_FDIFF ? "pixpass_wave_kernel<fdiff>"
                               : FOP == OP_S2N   ? "pixpass_wave_kernel<s2n>"
                                                 : "pixpass_wave_kernel<render>";
     if constexpr (FOP == OP_RENDER_FAST) {
-        if (overwrite) return kernel(pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16, NG8>, n);
+        if (overwrite)
+            return kernel(pixpass_wave_kernel_plain<OP_RENDER_FAST, false, 16, NG8, REG>, n);
     } else {
         if (stream)
-            return masked ? kernel(pixpass_wave_kernel_stream<FOP, true, TW, NG8>, n)
-                          : kernel(pixpass_wave_kernel_stream<FOP, false, TW, NG8>, n);
+            return masked ? kernel(pixpass_wave_kernel_stream<FOP, M, TW, NG8, REG>, n)
+                          : kernel(pixpass_wave_kernel_stream<FOP, false, TW, NG8, REG>, n);
     }
-    return masked ? kernel(pixpass_wave_kernel<FOP, true, TW, NG8>, n)
-                  : kernel(pixpass_wave_kernel<FOP, false, TW, NG8>, n);
+    return masked ? kernel(pixpass_wave_kernel<FOP, M, TW, NG8, REG>, n)
+                  : kernel(pixpass_wave_kernel<FOP, false, TW, NG8, REG>, n);
 }
 
 // ng8: no stamp of the batch has more than 8 gaussians -- the kernels whose pair
 // loop is unrolled over the gaussian index (wave_tiles, NG8)
 template <int FOP, int TW>
 static WaveKernel pick_wave_kernel(bool masked, bool seven, bool stream, bool overwrite,
-                                   bool ng8)
+                                   bool ng8, bool regular)
 {
-    return ng8 ? pick_wave_kernel_ng<FOP, TW, true>(masked, seven, stream, overwrite)
-               : pick_wave_kernel_ng<FOP, TW, false>(masked, seven, stream, overwrite);
+    // (regular: only with ng8 -- the generic pair loop has no regular form, it
+    // measured slower than the general kernel on C5; the launcher knows)
+    if (regular && ng8)
+        return pick_wave_kernel_ng<FOP, TW, true, true>(false, seven, stream, overwrite);
+    return ng8 ? pick_wave_kernel_ng<FOP, TW, true, false>(masked, seven, stream, overwrite)
+               : pick_wave_kernel_ng<FOP, TW, false, false>(masked, seven, stream, overwrite);
 }
 
 template <int OP>
@@ -1236,19 +1341,46 @@ static int launch_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
                       status, max_ng, nchunks_cap, no_skip & 5);
     constexpr int FOP = (OP == OP_RENDER_EXACT) ? OP_RENDER_FAST : OP;
     static const bool six_waves = getenv("NGMIX_LOGLIKE_6WAVES") != nullptr;   // A/B knob
+    // NGMIX_BATCH_REGULAR: a fact the builder of the table established; the host
+    // fields of the batch must not contradict it
+    // Only the kernels of small mixtures (max_ngauss <= 8) have a regular form:
+    // with the generic pair loop it was slower than the general kernel (C5).
+    const bool flagged = (b->flags & NGMIX_BATCH_REGULAR) != 0;
+    const bool regular = flagged && max_ng <= 8;
+    RegularShape rs = {0, 0, 0u};
+    int no_skip_k = no_skip;
+    if (flagged) {
+        if (b->any_masked || b->max_ngauss <= 0 || b->max_nrow <= 0 || b->max_ncol <= 0 ||
+            (int64_t)b->max_nrow * b->max_ncol != b->max_npix) {
+            set_last_error_msg("NGMIX_BATCH_REGULAR on a batch whose any_masked, max_ngauss or "
+                               "max_nrow * max_ncol != max_npix contradict it");
+            return NGMIX_ERR_BAD_ARG;
+        }
+        const unsigned ntx = (unsigned)((b->max_ncol + TW - 1) / TW);
+        rs.nrow = b->max_nrow;
+        rs.ncol = b->max_ncol;
+        // (T < FUSED_TILE_CAP + FUSED_SENTINELS and ntx <= FUSED_TILE_CAP: T * ntx < 2^32)
+        rs.ntx_magic = ntx >= 2 ? (unsigned)(((1ull << 32) + ntx - 1) / ntx) : 0u;
+        // the common stamp flag word rides in bits 3-4 of the kernel's no_skip
+        static_assert((NGMIX_BATCH_REGULAR_STAMP_FLAGS >> NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT) == 3,
+                      "two bits");
+        no_skip_k |= ((b->flags & NGMIX_BATCH_REGULAR_STAMP_FLAGS) >>
+                      NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT) << 3;
+    }
     // zero-weight pixels only matter to the kernels that read ierr; every map is
     // streamed when no stamp of the batch has a uniform weight map (the caller
     // says so with NGMIX_BATCH_STREAM_IERR, which is also the diagnostic)
     const WaveKernel k = pick_wave_kernel<FOP, TW>(
         b->any_masked && FOP != OP_RENDER_FAST, !six_waves,
-        (b->flags & NGMIX_BATCH_STREAM_IERR) != 0, (no_skip & 4) != 0, max_ng <= 8);
+        (b->flags & NGMIX_BATCH_STREAM_IERR) != 0, (no_skip & 4) != 0, max_ng <= 8, regular);
     const size_t flds = lds_bytes(max_ng, nchunks_cap, a_tc);
     if (flds > 160 * 1024) {
         set_last_error_msg("stamp needs more than 160 KiB of LDS");
         return NGMIX_ERR_BAD_ARG;
     }
+    if (regular) census_regular();
     return launch(k, grid, dim3(WAVE), flds, 64 * 1024, s, b->stamps, b->val, b->ierr, b->jac,
-                  gmix, out, out_start, status, max_ng, nchunks_cap, no_skip, a_tc);
+                  gmix, out, out_start, status, max_ng, nchunks_cap, no_skip_k, a_tc, rs);
 }
 
 int launch_loglike_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,

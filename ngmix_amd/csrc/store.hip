@@ -190,6 +190,9 @@ int ngmix_batch_upload(ngmix_batch *b, const double *images, const double *weigh
     const size_t pixbytes = (size_t)s->total_pix * sizeof(double);
     const size_t n = (size_t)b->nstamps;
     if (n == 0) return NGMIX_OK;
+    // (a fact about the table of THIS upload, established at the end: an upload
+    // that fails on the way must not leave the previous one's claim behind)
+    b->flags &= ~(NGMIX_BATCH_REGULAR | NGMIX_BATCH_REGULAR_STAMP_FLAGS);
     NGMIX_HIP_CHECK(hipMemcpyAsync(s->d_val, images, pixbytes, hipMemcpyHostToDevice, q));
     NGMIX_HIP_CHECK(hipMemcpyAsync(s->d_jac, jac, n * sizeof(ngmix_jacobian),
                                    hipMemcpyHostToDevice, q));
@@ -238,6 +241,24 @@ int ngmix_batch_upload(ngmix_batch *b, const double *images, const double *weigh
     // path serve the batch (a caller's own NGMIX_BATCH_STREAM_IERR is set after
     // the upload, like the other diagnostics)
     b->flags = (b->flags & ~NGMIX_BATCH_STREAM_IERR) | (uniform ? 0 : NGMIX_BATCH_STREAM_IERR);
+    // NGMIX_BATCH_REGULAR, from the table of this upload: one shape, one flag
+    // word, nothing masked (pix_off and gm_off are then i * npix and i * ngauss
+    // by construction, ngmix_batch_create)
+    bool regular = b->max_ngauss > 0 && !masked &&
+                   (int64_t)b->max_nrow * b->max_ncol == b->max_npix;
+    const int32_t word = s->host_stamps[0].flags;
+    for (size_t i = 0; i < n && regular; i++) {
+        const ngmix_stamp &st = s->host_stamps[i];
+        regular = st.nrow == b->max_nrow && st.ncol == b->max_ncol && st.flags == word &&
+                  st.ngauss == b->max_ngauss && st.npix_kept == b->max_npix &&
+                  st.pix_off == (int64_t)i * b->max_npix &&
+                  st.gm_off == (int64_t)i * b->max_ngauss;
+    }
+    // (the bits were cleared at the top)
+    constexpr int32_t kWordMask =
+        NGMIX_BATCH_REGULAR_STAMP_FLAGS >> NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT;
+    if (regular && (word & ~kWordMask) == 0)
+        b->flags |= NGMIX_BATCH_REGULAR | (word << NGMIX_BATCH_REGULAR_STAMP_FLAGS_SHIFT);
     return NGMIX_OK;
 }
 

@@ -896,6 +896,9 @@ class LMBatchFitter(object):
             p.batch.nstamps = p.s_hi - p.s_lo
             p.batch.stamps = b.stamps + p.s_lo * _lib.STAMP_DTYPE.itemsize
             p.batch.jac = b.jac + p.s_lo * _lib.JACOBIAN_DTYPE.itemsize
+            # (val, ierr and the mixtures keep their bases: pix_off and gm_off of a
+            # piece's table are not i * npix, i * ngauss -- the piece is not regular)
+            p.batch.flags &= ~(_lib.BATCH_REGULAR | _lib.BATCH_REGULAR_STAMP_FLAGS)
             p.stream = self._side_stream(job.dev, 1 + k) if nsplit > 1 else None
             p.nact = torch.zeros(1, dtype=torch.int32, device=job.dev)
             p.live, p.active = True, p.o_hi - p.o_lo
