@@ -1,5 +1,9 @@
 """
-ctypes binding of libngmix_hip.so (include/ngmix_hip.h).
+ctypes binding of libngmix_hip.so.  The argument lists are not restated here:
+SIGNATURES is read at import from the prototypes of include/ngmix_hip.h
+(parse_header), which refuses a type it has no ctypes type for.  The constants
+and the record layouts below are written by hand and held to the header and to
+the library by tests/test_cabi_host.py.
 
 The HIP library IS the product: there is no CPU fallback.  If the shared
 object is missing we try to build it in-tree with hipcc (same image on the
@@ -7,6 +11,7 @@ GPU box); if that fails, importing any compute entry point raises.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -196,133 +201,82 @@ class LMProblem(ctypes.Structure):
     ]
 
 
-_vp = ctypes.c_void_p
-_i64 = ctypes.c_int64
-_i32 = ctypes.c_int
-_f64 = ctypes.c_double
-_sz = ctypes.c_size_t
-_pd = ctypes.POINTER(ctypes.c_double)
-_pb = ctypes.POINTER(Batch)
-
-# name -> (restype, argtypes); every symbol include/ngmix_hip.h declares
-SIGNATURES = {
-    "ngmix_version": (ctypes.c_char_p, []),
-    "ngmix_last_error": (ctypes.c_char_p, []),
-    "ngmix_device_count": (_i32, []),
-    "ngmix_set_device": (_i32, [_i32]),
-    "ngmix_device_malloc": (_i32, [ctypes.POINTER(_vp), _sz]),
-    "ngmix_device_free": (_i32, [_vp]),
-    "ngmix_memcpy_h2d": (_i32, [_vp, _vp, _sz, _vp]),
-    "ngmix_memcpy_d2h": (_i32, [_vp, _vp, _sz, _vp]),
-    "ngmix_memset_device": (_i32, [_vp, _i32, _sz, _vp]),
-    "ngmix_stream_synchronize": (_i32, [_vp]),
-    # seam forms
-    "ngmix_set_norms": (_i32, [_vp, _i64]),
-    "ngmix_fill_model": (_i32, [_vp, _i64, _i32, _vp, _i64]),
-    "ngmix_fill_cm": (_i32, [_vp, _f64, _f64, _f64, _vp]),
-    "ngmix_get_cm_Tfactor": (_i32, [_f64, _f64, _pd]),
-    "ngmix_g1g2_to_e1e2": (_i32, [_f64, _f64, _pd, _pd]),
-    "ngmix_convolve_fill": (_i32, [_vp, _vp, _i64, _vp, _i64]),
-    "ngmix_jacobian_get_vu": (None, [_vp, _f64, _f64, _pd, _pd]),
-    "ngmix_jacobian_get_rowcol": (_i32, [_vp, _f64, _f64, _pd, _pd]),
-    "ngmix_fill_pixels": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i32]),
-    "ngmix_fill_coords": (_i32, [_vp, _i64, _i64, _vp]),
-    "ngmix_render": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32]),
-    "ngmix_get_loglike": (_i32, [_vp, _i64, _vp, _i64, _pd, _pd, _pd,
-                                 ctypes.POINTER(_i64)]),
-    "ngmix_fill_fdiff": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64]),
-    "ngmix_get_model_s2n_sum": (_i32, [_vp, _i64, _vp, _i64, _pd]),
-    "ngmix_get_weighted_sums": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _f64]),
-    "ngmix_admom": (_i32, [_vp, _vp, _vp, _i64, _vp]),
-    "ngmix_em_run": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64,
-                            _vp, _i32, ctypes.POINTER(ctypes.c_int32), _pd, _pd]),
-    "ngmix_deriv_images": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    # batch forms
-    "ngmix_weight_to_ierr_batch": (_i32, [_vp, _vp, _i64, _vp]),
-    "ngmix_count_kept_batch": (_i32, [_vp, _i64, _vp, _vp]),
-    "ngmix_template_sums_batch": (_i32, [_vp, _vp, _vp, _vp, _vp]),
-    "ngmix_fill_model_batch": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp,
-                                      _vp, _vp]),
-    "ngmix_convolve_fill_batch": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp,
-                                         _vp]),
-    "ngmix_set_norms_batch": (_i32, [_vp, _i32, _i64, _vp, _vp]),
-    "ngmix_loglike_batch": (_i32, [_pb, _vp, _vp, _vp, _vp]),
-    "ngmix_loglike_grad_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
-    "ngmix_render_vjp_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "ngmix_fisher_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
-    "ngmix_scene_boxes": (_i32, [_vp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "ngmix_scene_render": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp]),
-    "ngmix_frame_gather": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
-    "ngmix_scene_cut_minus": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp,
-                                     _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
-    "ngmix_scene_normal": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _vp,
-                                  _vp, _vp, _i64, _vp, _vp, _vp]),
-    "ngmix_scene_normal_frames": (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64,
-                                         _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "ngmix_scene_block_matvec": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
-                                        _vp, _vp]),
-    "ngmix_scene_pcg": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                               _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                               _f64, _i32, _i32, _vp]),
-    "ngmix_fill_fdiff_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
-    "ngmix_render_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _vp]),
-    "ngmix_model_s2n_sum_batch": (_i32, [_pb, _vp, _vp, _vp, _vp]),
-    "ngmix_weighted_sums_batch": (_i32, [_pb, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "ngmix_admom_batch": (_i32, [_vp, _pb, _vp, _vp, _vp, _vp]),
-    "ngmix_em_batch": (_i32, [_i32, _vp, _pb, _vp, _i32, _vp, _i32, _vp, _vp,
-                              _i32, _vp, _vp, _vp]),
-    "ngmix_deriv_images_batch": (_i32, [_pb, _vp, _vp, _vp, _vp, _vp]),
-    "ngmix_noise_cov_blocks_batch": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32,
-                                            _i32, _vp, _vp]),
-    "ngmix_noise_cov_finish_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32,
-                                            _i32, _vp, _vp]),
-    # library-owned stamp store and the RCCL gather of result records
-    "ngmix_batch_create": (_i32, [ctypes.POINTER(_pb), _i64, _vp, _vp, _i32, _i32]),
-    "ngmix_batch_upload": (_i32, [_pb, _vp, _vp, _vp, _vp]),
-    "ngmix_batch_npix_kept": (_i32, [_pb, _vp]),
-    "ngmix_batch_free": (_i32, [_pb]),
-    "ngmix_comm_unique_id": (_i32, [_vp]),
-    "ngmix_comm_init_rank": (_i32, [ctypes.POINTER(_vp), _i32, _vp, _i32]),
-    "ngmix_comm_destroy": (_i32, [_vp]),
-    "ngmix_allgather_results": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp]),
-    # batched Levenberg-Marquardt
-    "ngmix_abi_sizeof": (_i64, [ctypes.c_char_p]),
-    "ngmix_lm_init": (_i32, [_vp, _i64, _i32, _vp, _f64, _f64, _f64, _i32, _f64, _i32,
-                              _vp, _vp]),
-    "ngmix_lm_init_batch": (_i32, [_vp, _i64, _i32, _vp, _f64, _f64, _f64, _i32, _f64,
-                                    _i32, _vp, _vp, _vp]),
-    "ngmix_lm_prior_sums_batch": (_i32, [_vp, _i64, _vp, _f64, _vp, _vp]),
-    "ngmix_simple_sep_prior_eval": (_i32, [_vp, _vp, _vp, _vp]),
-    "ngmix_lm_advance_host": (_i64, [_vp, _i64, _vp, _vp, _vp]),
-    "ngmix_lm_prior_sums_host": (_i32, [_vp, _i64, _vp, _f64, _vp]),
-    "ngmix_fastexp_batch": (_i32, [_vp, _vp, _i64, _i32, _vp]),
-    "ngmix_prepsf_sums_batch": (_i32, [_vp] * 8 + [_f64] + [_vp] * 7 + [_i64, _i32, _i64, _i64, _i32,
-                                                               _i32, _f64, _f64, _vp, _vp]),
-    "ngmix_metacal_spectrum_batch": (_i32, [_vp] * 9 + [_i32, _i64] + [_i32] * 5 + [_vp, _vp, _vp]),
-    "ngmix_metacal_noise_batch": (_i32, [_vp, _vp, ctypes.c_uint64, _i64, _i32, _i32, _i32, _vp,
-                                         _vp]),
-    "ngmix_metacal_noise_host": (_i32, [_vp, _vp, ctypes.c_uint64, _i64, _i32, _i32, _i32, _vp]),
-    "ngmix_prepsf_shear_sums_batch": (_i32, [_vp] * 8 + [_i32] + [_vp] * 4 + [_i64] + [_i32] * 5 + [_f64] * 4 + [_vp, _vp, _vp]),
-    "ngmix_prepsf_shear_sums_host": (_i32, [_vp] * 8 + [_i32] + [_vp] * 4 + [_i64] + [_i32] * 5 + [_f64] * 4 + [_vp, _vp]),
-    "ngmix_philox4x32_10_host": (_i32, [_vp, _vp, _i64, _vp]),
-    "ngmix_lm_prior_finish_batch": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
-    "ngmix_first_pixels_fdiff2_batch": (_i32, [_pb, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
-    "ngmix_lm_eval_batch": (_i32, [_pb, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
-                                   _vp, _vp, _vp]),
-    "ngmix_lm_advance_batch": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
-                                      _vp]),
-    "ngmix_lm_finalize_batch": (_i32, [_vp, _i64, _vp, _vp, _f64, _f64, _vp, _vp]),
-    "ngmix_launch_census": (_i64, [ctypes.c_char_p, _i64, _i32]),
-    "ngmix_launch_census_regular": (_i64, [_i32]),
-    "ngmix_lm_pack_batch": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ngmix_lm_rounds_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
-    "ngmix_lm_precise_cov_batch": (_i32, [_vp, _vp, _vp]),
-    "ngmix_events_create": (_i32, [_i32, _vp]),
-    "ngmix_events_destroy": (_i32, [_i32, _vp]),
-    "ngmix_event_record": (_i32, [_vp, _vp]),
-    "ngmix_event_synchronize": (_i32, [_vp]),
-    "ngmix_event_elapsed_ms": (_i32, [_vp, _vp, _vp]),
+_SCALARS = {
+    "int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64,
+    "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
 }
+
+
+def _ctype(decl, where, named):
+    """the ctypes type of one C parameter (named) or return type: the type map
+    of DESIGN.md section 1, and an error for everything outside it"""
+    tokens = re.findall(r"\w+|\S", decl)
+    const = "const" in tokens[:tokens.index("*")] if "*" in tokens else False
+    tokens = [t for t in tokens if t != "const"]
+    base, depth = (tokens[0] if tokens else ""), 0
+    while tokens[1 + depth:2 + depth] == ["*"]:
+        depth += 1
+    rest = tokens[1 + depth:]
+    if not re.fullmatch(r"[A-Za-z_]\w*", base) or len(rest) > named or \
+            (rest and not re.fullmatch(r"[A-Za-z_]\w*", rest[0])):
+        raise TypeError("%s: cannot read '%s'" % (where, " ".join(decl.split())))
+    if depth == 0:
+        if base == "void" and not named:
+            return None
+        if base not in _SCALARS:
+            raise TypeError("%s: no ctypes type for '%s' in '%s'"
+                            % (where, base, " ".join(decl.split())))
+        return _SCALARS[base]
+    if base == "char" and depth == 1 and const:
+        return ctypes.c_char_p
+    if base == "ngmix_batch" and depth <= 2:
+        t = ctypes.POINTER(Batch)
+        return t if depth == 1 else ctypes.POINTER(t)
+    return ctypes.c_void_p
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every `ngmix_*` function the header text
+    declares.  Serves include/ngmix_hip.h, not C: comments, preprocessor lines,
+    typedefs and the extern "C" braces are dropped, and whatever remains must
+    be a prototype whose every type is in the type map"""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r"\btypedef\b[^;{]*(\{[^}]*\})?[^;{}]*;", " ", text)
+    text = re.sub(r'\bextern\s+"C"\s*\{', " ", text)
+    decls = text.split(";")
+    if decls.pop().strip() not in ("", "}"):
+        raise TypeError("header ends inside a declaration")
+    table = {}
+    for decl in decls:
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(ngmix_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        if m is None:
+            raise TypeError("not a prototype: '%s'" % " ".join(decl.split()))
+        ret, name, params = m.groups()
+        if "(" in params or ")" in params:
+            raise TypeError("%s: function pointer parameter" % name)
+        if name in table:
+            raise TypeError("%s: declared twice" % name)
+        params = [] if params.strip() == "void" else params.split(",")
+        table[name] = (_ctype(ret, name + ": return type", False),
+                       [_ctype(p, "%s: parameter %d" % (name, i + 1), True)
+                        for i, p in enumerate(params)])
+    return table
+
+
+def _read_header():
+    path = os.path.join(os.path.dirname(_HERE), "include", "ngmix_hip.h")
+    try:
+        with open(path) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise ImportError("ngmix_amd needs the C ABI's declaration, %s: %s" % (path, e))
+
+
+# name -> (restype, argtypes) of every entry point, read from the declaration
+# itself: include/ngmix_hip.h is the only place an argument list is written
+SIGNATURES = _read_header()
 LM_NCOLS = 12
 
 

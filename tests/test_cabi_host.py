@@ -39,6 +39,133 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert b"gfx950" in L.ngmix_version()
 
 
+def test_bindings_read_from_the_header_are_exact():
+    """_lib.SIGNATURES is parsed from include/ngmix_hip.h; these rows are written
+    out by hand from the same prototypes and cover every line of the type map"""
+    i32, i64, u64 = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
+    f64, vp, cp, sz = ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
+    pb = ctypes.POINTER(_lib.Batch)
+    expected = {
+        "ngmix_version": (cp, []),
+        "ngmix_abi_sizeof": (i64, [cp]),
+        "ngmix_jacobian_get_vu": (None, [vp, f64, f64, vp, vp]),
+        "ngmix_device_malloc": (i32, [vp, sz]),
+        "ngmix_batch_create": (i32, [ctypes.POINTER(pb), i64, vp, vp, i32, i32]),
+        "ngmix_loglike_batch": (i32, [pb, vp, vp, vp, vp]),
+        "ngmix_batch_upload": (i32, [pb, vp, vp, vp, vp]),
+        "ngmix_metacal_noise_batch": (i32, [vp, vp, u64, i64, i32, i32, i32, vp, vp]),
+        "ngmix_prepsf_shear_sums_batch": (i32, [
+            vp, vp, vp, vp, vp, vp, vp, vp,     # images .. g_host
+            i32,                                # per_stamp_g
+            vp, vp, vp, vp,                     # mrow, mcol, wgt, fk
+            i64,                                # n
+            i32, i32, i32, i32, i32,            # ntypes, nmodes, dim, pdim, fft_dim
+            f64, f64, f64, f64,                 # dvdrow, dvdcol, dudrow, dudcol
+            vp, vp, vp]),                       # sums, flags, stream
+        "ngmix_scene_pcg": (i32, [
+            vp, vp,                             # F_self, F_cross
+            i64, i64, i32,                      # n, npairs, K
+            vp, vp, i64,                        # row_start, row_ent, nent
+            vp, vp, vp, vp, vp,                 # lam, Minv, g, obj_group, seg_order
+            i64, vp, i64,                       # nseg, seg_start, ngroups
+            vp, vp, vp, vp, vp, vp, vp, vp,     # x, r, p, z, q, part, gscal, grec
+            f64, i32, i32, vp]),                # tol, init, niter, stream
+        "ngmix_lm_init": (i32, [vp, i64, i32, vp, f64, f64, f64, i32, f64, i32, vp, vp]),
+        "ngmix_launch_census": (i64, [vp, i64, i32]),
+    }
+    assert len(expected["ngmix_prepsf_shear_sums_batch"][1]) == 26
+    assert len(expected["ngmix_scene_pcg"][1]) == 28
+    for name, row in expected.items():
+        assert _lib.SIGNATURES[name] == row, name
+
+
+@pytest.mark.parametrize("what, decl", [
+    ("an unknown type name", "int ngmix_probe(int n, float x);"),
+    ("an unknown return type", "unsigned ngmix_probe(int n);"),
+    ("a struct by value", "int ngmix_probe(int n, ngmix_jacobian jac);"),
+    ("a struct by value, with the keyword", "int ngmix_probe(int n, struct ngmix_batch b);"),
+    ("an array", "int ngmix_probe(int n, double x[4]);"),
+    ("an ellipsis", "int ngmix_probe(const char *fmt, ...);"),
+    ("a function pointer", "int ngmix_probe(int n, int (*cb)(int));"),
+    ("a void parameter beside others", "int ngmix_probe(int n, void);"),
+])
+def test_header_parser_refuses_what_it_does_not_know(what, decl):
+    with pytest.raises(TypeError, match="ngmix_probe"):
+        _lib.parse_header("typedef struct { double a; } ngmix_jacobian;\n" + decl)
+
+
+def test_header_parser_reads_the_forms_the_header_uses():
+    text = """
+    #ifdef __cplusplus
+    extern "C" {
+    #endif
+    #define NGMIX_PROBE_BYTES(n) (8 * (n))  /* int ngmix_not_this(void); */
+    typedef struct {
+        int32_t a; /* int ngmix_nor_this(void); */
+        double b[3];
+    } ngmix_rec;
+    typedef struct { double u, v; } ngmix_pair;
+    // int ngmix_nor_that(void);
+    int ngmix_split(const ngmix_rec *rec,
+                    int64_t n, /* a comment
+                                  over two lines; with a semicolon */
+                    double const *x, double *const y,
+                    size_t nbytes);
+    const char *ngmix_name(void);
+    void ngmix_none(void);
+    int64_t ngmix_count(char const *name, char *buf, const ngmix_batch *b, ngmix_batch **out,
+                        void **p, const int32_t *q, uint64_t seed, int32_t k, int flag);
+    #ifdef __cplusplus
+    }
+    #endif
+    """
+    i32, i64, vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+    pb = ctypes.POINTER(_lib.Batch)
+    assert _lib.parse_header(text) == {
+        "ngmix_split": (i32, [vp, i64, vp, vp, ctypes.c_size_t]),
+        "ngmix_name": (ctypes.c_char_p, []),
+        "ngmix_none": (None, []),
+        "ngmix_count": (i64, [ctypes.c_char_p, vp, pb, ctypes.POINTER(pb), vp, vp,
+                              ctypes.c_uint64, i32, i32]),
+    }
+    # what is left over is refused, not skipped
+    with pytest.raises(TypeError):
+        _lib.parse_header("int ngmix_a(void); int x")
+    with pytest.raises(TypeError):
+        _lib.parse_header("static inline int ngmix_a(void) { return 0; }")
+    with pytest.raises(TypeError, match="ngmix_a"):
+        _lib.parse_header("int ngmix_a(void); int ngmix_a(int n);")
+
+
+def test_constants_match_the_header():
+    """every #define NGMIX_<NAME> <value> of the header that _lib restates as
+    <NAME> has the header's value"""
+    header = open(os.path.join(ROOT, "include", "ngmix_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    values, compared, unread = {}, [], []
+    for name, rhs in re.findall(r"^[ \t]*#[ \t]*define[ \t]+NGMIX_(\w+)[ \t]+(\S[^\n]*)$", header,
+                                flags=re.M):            # NAME( is a function-like macro
+        expr = re.sub(r"\bNGMIX_(\w+)\b",
+                      lambda m: str(values[m.group(1)]) if m.group(1) in values else m.group(0),
+                      rhs)
+        if re.fullmatch(r"(?:[0-9 ()|-]|<<)+", expr):
+            values[name] = eval(expr, {"__builtins__": {}})
+        elif hasattr(_lib, name):
+            unread.append(name)
+            continue
+        if hasattr(_lib, name) and name in values:
+            assert getattr(_lib, name) == values[name], name
+            compared.append(name)
+    assert len(compared) >= 30, compared
+    for name in ("OK", "ERR_HIP", "ERR_BAD_ARG", "BATCH_REGULAR_STAMP_FLAGS", "LM_NPMAX",
+                 "PRIOR_MAXBAND", "LM_NCOLS"):
+        assert name in compared
+    assert values["ERR_HIP"] == -100 and values["BATCH_REGULAR_STAMP_FLAGS"] == 0x300
+    # the one restated constant whose right-hand side is a function-like macro:
+    # NGMIX_LM_NSUMS(6) = 6 * 7 / 2 + 6 + 1
+    assert unread == ["LM_NSUM"] and _lib.LM_NSUM == 6 * 7 // 2 + 6 + 1
+
+
 def test_struct_layouts_match_reference():
     """SURVEY.md 8b, measured from the reference's dtypes"""
     d = _lib.GAUSS2D_DTYPE
