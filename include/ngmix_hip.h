@@ -487,6 +487,38 @@ int ngmix_prepsf_shear_sums_host(
     const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags);
+/* DEVICE: ngmix_prepsf_shear_sums_batch with the fixnoise term of
+   metacalibration in the sums: besides the stamp, the noise plane N that is
+   turned by 90 degrees, deconvolved by the UN-turned psf, sheared and turned
+   back, without making an image and with no target psf.  noise_turned (n, dim,
+   dim): the planes ALREADY in rot90(k=1) layout, N'[i, j] = N[j, dim - 1 - i]
+   (what ngmix_metacal_noise_batch writes with rot_k = 1), tapered by the same
+   edge.  Per kept mode k = (k_r, k_c): q = (-k_c, k_r), q' = q + J^T (A - 1)
+   J^-T q, F^(k) = N'^(q') / P^(q') exp(-i (q_r (r0 + c0 - (dim - 1)) + q_c (c0
+   - r0))) with N'^ about cen = (r0, c0), P^ about psf_cen and under the same
+   floor; the four sums gain w fk Re F^(k) and the covariance sums become fk_a
+   fk_b w pnoise (1 / |P^(k')|^2 + 1 / |P^(q')|^2): two independent fields of
+   the weight map's variance.  flags: 1, all fourteen sums NaN, also where a
+   kept mode has |q'_r| >= pi or |q'_c| >= pi, or a noise pixel is not finite.
+   Every other argument, the order of summation and the refusals are those of
+   ngmix_prepsf_shear_sums_batch; refused too: NULL noise_turned with n > 0,
+   and the three planes not fitting the 160 KB of LDS.  n == 0 is a no-op */
+int ngmix_prepsf_shear_fixnoise_sums_batch(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags, void *stream);
+/* HOST twin of ngmix_prepsf_shear_fixnoise_sums_batch: the same arguments on
+   host pointers, the same code in the kernel's summation order */
+int ngmix_prepsf_shear_fixnoise_sums_host(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags);
 /* HOST: the generator alone: out (n, 4) = Philox4x32-10 of counters (n, 4)
    under keys (n, 2) */
 int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,

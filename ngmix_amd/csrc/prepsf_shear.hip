@@ -17,6 +17,10 @@
 // thread in the order of the mode list, then over the block in a fixed tree:
 // the results do not depend on the run, the batch's size or its order.  fp64,
 // no atomics.
+//
+// NOISE (fixnoise): a third plane in LDS, the noise plane in its
+// turned layout, tapered while staged; after the image term every mode takes
+// add_noise_mode's term from it at the turned, sheared frequency.
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "launch.hpp"
@@ -61,6 +65,12 @@ __device__ __forceinline__ void block_total(double (&vals)[NV], double *scratch)
 // (dim,) or null, g (ng, T, 2) with ng = 1 or N; the plan: mrow, mcol, wgt
 // (nmodes,), fk (4, nmodes); deriv by value.  sums (N, T, 14), flags (N, T): 1
 // where a kept mode left the band or a sum is not finite (its sums are NaN).
+// NOISE: noise_turned (N, dim, dim), rot90(k=1) of the noise planes; else unread.
+// It is the LAST argument: the others keep their places in the argument
+// segment, and the scalar loads and registers of the NOISE = false form stay
+// those of the kernel before the noise form existed (the scalar file is full:
+// with the pointer among the first arguments that form ran 3 to 6 % slower).
+template <bool NOISE>
 __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const double *__restrict__ images, const double *__restrict__ weights,
     const double *__restrict__ psf, const double *__restrict__ cen,
@@ -68,7 +78,8 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const double *__restrict__ g, int per_stamp_g, const int32_t *__restrict__ mrow,
     const int32_t *__restrict__ mcol, const double *__restrict__ wgt,
     const double *__restrict__ fk, int T, int nmodes, int dim, int pdim, int fft_dim, double j00,
-    double j01, double j10, double j11, double *__restrict__ sums, int32_t *__restrict__ flags)
+    double j01, double j10, double j11, double *__restrict__ sums, int32_t *__restrict__ flags,
+    const double *__restrict__ noise_turned)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ double s_plane[2];      // the psf's sum, the stamp's total variance
@@ -77,7 +88,8 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const int npix = dim * dim, nppix = pdim * pdim;
 
     double *s_img = (double *)smem;
-    double *s_psf = s_img + npix;
+    double *s_noise = s_img + npix;
+    double *s_psf = s_noise + (NOISE ? npix : 0);
     double *s_red = s_psf + nppix;
 
     // staging; on the way the two plane sums, strided as the host twin takes them
@@ -87,6 +99,11 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
         s_img[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
         plane[1] += pixel_var(weights[n * npix + i]);
     }
+    if (NOISE)
+        for (int i = threadIdx.x; i < npix; i += blockDim.x) {
+            const double v = noise_turned[n * npix + i];
+            s_noise[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
+        }
     for (int i = threadIdx.x; i < nppix; i += blockDim.x) {
         const double v = psf[n * nppix + i];
         s_psf[i] = v;
@@ -105,20 +122,53 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const Setup m = setup(cen + 2 * n, psf_cen + 2 * n, deriv, gt[0], gt[1], s_plane[0],
                           s_plane[1] * noise_scale);
     const dtft::Planes planes = {s_img, nullptr, s_psf, dim, dim, pdim, pdim};
+    const dtft::Planes nplanes = {s_noise, nullptr, s_psf, dim, dim, pdim, pdim};
 
     double acc[NSUMS];
 #pragma unroll
     for (int i = 0; i < NSUMS; i++) acc[i] = 0.0;
     bool out_of_band = false;
-    for (int k = threadIdx.x; k < nmodes; k += blockDim.x)
+    for (int k = threadIdx.x; k < nmodes; k += blockDim.x) {
         if (!add_mode(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k], fk[nmodes + k],
                       fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
             out_of_band = true;
+        if (NOISE && !add_noise_mode(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k], fk[k],
+                                     fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
+            out_of_band = true;
+    }
     const int any_out = __syncthreads_or(out_of_band ? 1 : 0);
     block_total<NSUMS>(acc, s_red);
     if (threadIdx.x == 0)
         flags[n * T + t] = finish(acc, any_out != 0, fft_dim, sums + (n * T + t) * NSUMS) ? 1 : 0;
 }
+
+namespace {
+
+// both entries: each launches its own instantiation
+int launch_sums(const char *who, bool with_noise, const double *images, const double *weights,
+                const double *psf, const double *noise_turned, const double *cen,
+                const double *psf_cen, const double *edge, const double *g, const double *g_host,
+                int per_stamp_g, const int32_t *mrow, const int32_t *mcol, const double *wgt,
+                const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+                int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
+                double *sums, int32_t *flags, hipStream_t s)
+{
+    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
+    bool nothing;
+    const int st = check_args(who, images, weights, psf, cen, psf_cen, g, g_host, per_stamp_g,
+                              mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, deriv,
+                              sums, flags, nothing, with_noise, noise_turned);
+    if (st != NGMIX_OK || nothing) return st;
+    static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "prepsf_shear.hpp mirrors device_utils.hpp");
+    const auto k = with_noise ? kernel(prepsf_shear_sums_kernel<true>, "prepsf_shear_sums_kernel<1>")
+                              : kernel(prepsf_shear_sums_kernel<false>, "prepsf_shear_sums_kernel");
+    return launch(k, dim3((unsigned)(n * ntypes)), dim3(block_size(nmodes)),
+                  lds_bytes(dim, pdim, with_noise), 48 * 1024, s, images, weights, psf, cen, psf_cen,
+                  edge, g, per_stamp_g ? 1 : 0, mrow, mcol, wgt, fk, ntypes, nmodes, dim, pdim,
+                  fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, noise_turned);
+}
+
+}  // namespace
 
 int launch_prepsf_shear_sums(const double *images, const double *weights, const double *psf,
                              const double *cen, const double *psf_cen, const double *edge,
@@ -128,18 +178,22 @@ int launch_prepsf_shear_sums(const double *images, const double *weights, const 
                              int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow,
                              double dudcol, double *sums, int32_t *flags, hipStream_t s)
 {
-    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
-    bool nothing;
-    const int st = check_args("prepsf_shear_sums", images, weights, psf, cen, psf_cen, g, g_host,
-                              per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
-                              fft_dim, deriv, sums, flags, nothing);
-    if (st != NGMIX_OK || nothing) return st;
-    static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "prepsf_shear.hpp mirrors device_utils.hpp");
-    return launch(kernel(prepsf_shear_sums_kernel, "prepsf_shear_sums_kernel"),
-                  dim3((unsigned)(n * ntypes)), dim3(block_size(nmodes)), lds_bytes(dim, pdim),
-                  48 * 1024, s, images, weights, psf, cen, psf_cen, edge, g, per_stamp_g ? 1 : 0,
-                  mrow, mcol, wgt, fk, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
-                  dudcol, sums, flags);
+    return launch_sums("prepsf_shear_sums", false, images, weights, psf, nullptr, cen, psf_cen,
+                       edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim,
+                       pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, s);
+}
+
+int launch_prepsf_shear_fixnoise_sums(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags, hipStream_t s)
+{
+    return launch_sums("prepsf_shear_fixnoise_sums", true, images, weights, psf, noise_turned, cen,
+                       psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
+                       nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, s);
 }
 
 }  // namespace ngmix

@@ -9,6 +9,15 @@
 // over the kernel's kept modes k alone; I^ and P^ are the discrete-time
 // Fourier transforms of the tapered stamp and of the psf stamp (dtft.hpp), each
 // about its own centre.
+//
+// With fixnoise (ngmix_prepsf_shear_fixnoise_sums_*) every mode
+// also takes the term of the noise plane N that is turned by 90 degrees,
+// deconvolved by the un-turned psf, sheared and turned back: with N' =
+// rot90(N), q = (-k_c, k_r) and q' its sheared frequency,
+//
+//   F^(k) = N'^(q') / P^(q') exp(-i (q_r (r0 + c0 - (n - 1)) + q_c (c0 - r0)))
+//
+// (add_noise_mode); no target psf enters.
 #pragma once
 #include <string>
 #include <vector>
@@ -113,6 +122,55 @@ NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int 
     return true;
 }
 
+// What fixnoise adds to the sums of the kept mode (a, b) after add_mode: the
+// moment terms of the turned-back noise field and the variance it brings.  p:
+// the TAPERED noise plane in its turned layout rot90(N, k=1) (as the image of
+// the planes) and the psf; n: the stamp's side.  The plane is read at the
+// sheared image q' of the turned frequency q = (-k_c, k_r), about the image's
+// centre; turning back by rot90(k=3) moves that centre to (n - 1 - c0, r0),
+// which is the closing phase.  false, and nothing added, when q' leaves the band.
+NGMIX_HD bool add_noise_mode(const dtft::Planes &p, const Setup &m, int a, int b, int D, int n,
+                             double wgt, double fp, double fc, double fr, double ff,
+                             double (&acc)[NSUMS])
+{
+    const double qa = -mode_freq(b, D), qb = mode_freq(a, D);
+    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
+    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
+    const double qr = qa + (m.j00 * dv + m.j10 * du), qc = qb + (m.j01 * dv + m.j11 * du);
+    if (!(fabs(qr) < dtft::PI && fabs(qc) < dtft::PI)) return false;
+    cplx sn, unused, sp;
+    dtft::transforms<false>(p, m.r0, m.c0, qr, qc, sn, unused, sp);
+    sp = dtft::cmul(sp, dtft::cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
+    const double amp = hypot(sp.x, sp.y);
+    if (amp <= m.min_amp) {
+        if (amp != 0.0) {
+            sp = {sp.x / amp * m.min_amp, sp.y / amp * m.min_amp};
+        } else {
+            sp = {m.min_amp, 0.0};
+        }
+    }
+    const cplx back =
+        dtft::cexpi(-(qa * (m.r0 + m.c0 - (double)(n - 1)) + qb * (m.c0 - m.r0)));
+    const cplx k = dtft::cmul(dtft::cdiv(sn, sp), back);
+    const double w = wgt * m.pnoise / (sp.x * sp.x + sp.y * sp.y);
+    const double kr = wgt * k.x;
+    acc[0] += kr * fp;
+    acc[1] += kr * fc;
+    acc[2] += kr * fr;
+    acc[3] += kr * ff;
+    acc[4] += fp * fp * w;
+    acc[5] += fp * fc * w;
+    acc[6] += fp * fr * w;
+    acc[7] += fp * ff * w;
+    acc[8] += fc * fc * w;
+    acc[9] += fc * fr * w;
+    acc[10] += fc * ff * w;
+    acc[11] += fr * fr * w;
+    acc[12] += fr * ff * w;
+    acc[13] += ff * ff * w;
+    return true;
+}
+
 // the fourteen sums of one (stamp, type) from the block's totals: scaled, or
 // all NaN (and true) when a mode left the band or a sum is not finite
 NGMIX_HD bool finish(const double (&tot)[NSUMS], bool out_of_band, int D, double *out)
@@ -128,10 +186,12 @@ NGMIX_HD bool finish(const double (&tot)[NSUMS], bool out_of_band, int D, double
     return bad;
 }
 
-// bytes of LDS of one block: the tapered image, the psf, one row of sums per wave
-inline size_t lds_bytes(int dim, int pdim)
+// bytes of LDS of one block: the tapered image, with fixnoise the tapered noise
+// plane, the psf, one row of sums per wave
+inline size_t lds_bytes(int dim, int pdim, bool noise = false)
 {
-    return ((size_t)dim * dim + (size_t)pdim * pdim + (MAX_BLOCK / LANES) * NSUMS) * sizeof(double);
+    return ((size_t)dim * dim * (noise ? 2 : 1) + (size_t)pdim * pdim +
+            (MAX_BLOCK / LANES) * NSUMS) * sizeof(double);
 }
 
 // the block size that leaves the fewest idle mode slots (the larger on a tie)
@@ -148,14 +208,16 @@ inline int block_size(int nmodes)
     return block;
 }
 
-// the refusals shared by the launcher and the host twin; nothing: n == 0
+// the refusals shared by the launchers and the host twins; nothing: n == 0.
+// with_noise: the fixnoise entries, which need noise_turned and its room in LDS
 inline int check_args(const char *who, const double *images, const double *weights,
                       const double *psf, const double *cen, const double *psf_cen,
                       const double *g, const double *g_host, int per_stamp_g,
                       const int32_t *mrow, const int32_t *mcol, const double *wgt,
                       const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
                       int fft_dim, const double *deriv, const double *sums, const int32_t *flags,
-                      bool &nothing)
+                      bool &nothing, bool with_noise = false,
+                      const double *noise_turned = nullptr)
 {
     nothing = false;
     std::string why;
@@ -170,8 +232,10 @@ inline int check_args(const char *who, const double *images, const double *weigh
              !wgt || !fk || !sums || !flags)
         why = "images, weights, psf, cen, psf_cen, g, g_host, mrow, mcol, wgt, fk, sums and "
               "flags are required";
-    else if (dim > 0x7fff || pdim > 0x7fff || lds_bytes(dim, pdim) > LDS_LIMIT)
-        why = "the stamp and its psf stamp do not fit the 160 KB of LDS";
+    else if (with_noise && !noise_turned) why = "noise_turned is required";
+    else if (dim > 0x7fff || pdim > 0x7fff || lds_bytes(dim, pdim, with_noise) > LDS_LIMIT)
+        why = with_noise ? "the stamp, its noise plane and its psf stamp do not fit the 160 KB of LDS"
+                         : "the stamp and its psf stamp do not fit the 160 KB of LDS";
     else if (n * ntypes > 0x7fffffffll) why = "too many (stamp, type) pairs for one launch";
     else {
         const int64_t ng = (per_stamp_g ? n : 1) * ntypes;
@@ -217,8 +281,10 @@ inline double host_plane_sum(const double *plane, int count, int block, double *
     return host_block_sum(part, block);
 }
 
+// noise_turned: null (the sums of the stamps alone), or the planes of fixnoise
 inline int run_host(const double *images, const double *weights, const double *psf,
-                    const double *cen, const double *psf_cen, const double *edge,
+                    const double *noise_turned, const double *cen, const double *psf_cen,
+                    const double *edge,
                     const double *g, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
                     const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
                     int dim, int pdim, int fft_dim, const double *deriv, double *sums,
@@ -226,16 +292,23 @@ inline int run_host(const double *images, const double *weights, const double *p
 {
     const int npix = dim * dim, nppix = pdim * pdim, block = block_size(nmodes);
     const double noise_scale = ((double)fft_dim / (double)dim) * ((double)fft_dim / (double)dim);
-    std::vector<double> tapered_v(npix), part_v((size_t)block * NSUMS);
-    double *tapered = tapered_v.data(), *part = part_v.data();
+    std::vector<double> tapered_v(npix), noise_v(noise_turned ? npix : 0),
+        part_v((size_t)block * NSUMS);
+    double *tapered = tapered_v.data(), *tnoise = noise_v.data(), *part = part_v.data();
     for (int64_t i = 0; i < n; i++) {
         const double *im = images + i * npix, *ps = psf + i * nppix;
         for (int p = 0; p < npix; p++)
             tapered[p] = edge ? edge[p / dim] * edge[p % dim] * im[p] : im[p];
+        if (noise_turned) {
+            const double *nz = noise_turned + i * npix;
+            for (int p = 0; p < npix; p++)
+                tnoise[p] = edge ? edge[p / dim] * edge[p % dim] * nz[p] : nz[p];
+        }
         const double psf_sum =
             host_plane_sum(ps, nppix, block, part, [](double v) { return v; });
         const double var = host_plane_sum(weights + i * npix, npix, block, part, pixel_var);
         const dtft::Planes planes = {tapered, nullptr, ps, dim, dim, pdim, pdim};
+        const dtft::Planes nplanes = {tnoise, nullptr, ps, dim, dim, pdim, pdim};
         for (int t = 0; t < ntypes; t++) {
             const double *gt = g + ((per_stamp_g ? i * ntypes : 0) + t) * 2;
             const Setup m =
@@ -243,10 +316,16 @@ inline int run_host(const double *images, const double *weights, const double *p
             bool out_of_band = false;
             for (int th = 0; th < block; th++) {
                 double acc[NSUMS] = {0.0};
-                for (int k = th; k < nmodes; k += block)
+                for (int k = th; k < nmodes; k += block) {
                     if (!add_mode(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k],
                                   fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
                         out_of_band = true;
+                    if (noise_turned &&
+                        !add_noise_mode(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k], fk[k],
+                                        fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k],
+                                        acc))
+                        out_of_band = true;
+                }
                 for (int s = 0; s < NSUMS; s++) part[(size_t)s * block + th] = acc[s];
             }
             double tot[NSUMS];

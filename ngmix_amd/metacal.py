@@ -34,8 +34,14 @@ catalogues"):
 and the pre-psf moments of the five types straight from the stamps, without
 the images ("metacal pre-psf moments"; csrc/prepsf_shear.hip):
 
-    metacal_moments_batch(stamps, psf_stamps, measure, step=0.01, types=None) -> resdict
-    metacal_moments_many(list_of_obs, measure, step=0.01, types=None) -> [resdict_i]
+    metacal_moments_batch(stamps, psf_stamps, measure, step=0.01, types=None,
+                          fixnoise=False, noise=None, noise_seed=None, ids=None) -> resdict
+    metacal_moments_many(list_of_obs, measure, step=0.01, types=None, fixnoise=False,
+                         noise_seed=None, ids=None, use_noise_image=False) -> [resdict_i]
+
+Moments of noisy stamps carry the noise response; fixnoise=True with noise_seed
+(or noise) sums the cancelling term of the turned, deconvolved, sheared noise
+field with them (DESIGN.md, "fixnoise for the pre-psf moments").
 
 With noise_seed the fixnoise field is drawn on the device as a pure function
 of (seed, object id, pixel) (csrc/metacal_noise.hip): the same object gets the
@@ -685,7 +691,7 @@ def _moments_measure(measure):
 
 
 def metacal_moments_batch(stamps, psf_stamps, measure, step=DEFAULT_STEP, types=None,
-                          fixnoise=False):
+                          fixnoise=False, noise=None, noise_seed=None, ids=None):
     """
     The pre-psf moments (`measure`: a PGaussMom / KSigmaMom / PrePSFMom) of the
     metacal types of a stamp batch WITHOUT the metacal images: the moment sums
@@ -698,13 +704,27 @@ def metacal_moments_batch(stamps, psf_stamps, measure, step=DEFAULT_STEP, types=
     for every stamp and its psf stamp.  The weight of a pixel is its ierr^2.
 
     Returns resdict: {type: make_mom_result_batch dict with 'mcal_flags' (N,)},
-    what shear_response(resdict, step, key='e') and mean_shear take.  fixnoise
-    is not served (NotImplementedError), nor are the `*_psf` types.
+    what shear_response(resdict, step, key='e') and mean_shear take.  The
+    `*_psf` types are not served.
+
+    fixnoise: sum the term of metacalibration's noise field -- turned by 90
+        degrees, deconvolved by the un-turned psf, sheared, turned back -- with
+        the moments, and the variance it brings with the covariance (DESIGN.md
+        3.22).  The field comes from one of
+    noise_seed: drawn on the device from (noise_seed, ids, pixel) over the
+        batch's ierr, straight into the turned layout (ids (N,) object ids,
+        default the positions in the batch): a stamp's field does not depend on
+        how the catalogue is cut into batches;
+    noise: (N, dim, dim) un-turned planes, numpy or device tensor, or a
+        DeviceNoise.
+    fixnoise=True with neither raises NotImplementedError (the host draw from
+    an rng is not served); a noise source with fixnoise=False, or both, is a
+    ValueError.
     """
     from .batch import StampBatch
-    from .prepsfmom import _refuse_fixnoise
+    from .prepsfmom import _fixnoise_source
+    noise = _fixnoise_source(fixnoise, noise, noise_seed, ids)
     _moments_measure(measure)
-    _refuse_fixnoise(fixnoise)
     types = _check_types(types)
     if not isinstance(stamps, StampBatch) or not isinstance(psf_stamps, StampBatch):
         raise ValueError("stamps and psf_stamps must be StampBatch objects")
@@ -725,10 +745,12 @@ def metacal_moments_batch(stamps, psf_stamps, measure, step=DEFAULT_STEP, types=
     return measure.go_metacal_batch(
         stamps.val.reshape(n, shape[0], shape[1]), ierr * ierr, stamps.jac[:, 0:2],
         tuple(float(d) for d in derivs[0]), psf_stamps.val.reshape(n, pshape[0], pshape[1]),
-        psf_stamps.jac[:, 0:2], step=step, types=types)
+        psf_stamps.jac[:, 0:2], step=step, types=types, fixnoise=fixnoise, noise=noise,
+        noise_ierr=ierr if isinstance(noise, DeviceNoise) else None)
 
 
-def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fixnoise=False):
+def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fixnoise=False,
+                         noise_seed=None, ids=None, use_noise_image=False):
     """
     metacal_moments_batch for a catalogue of Observations (each with a psf
     Observation of the same jacobian derivatives): grouped by (image size, psf
@@ -736,13 +758,27 @@ def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fi
     device.  Returns a list: element i is object i's {type:
     moments.make_mom_result dict with 'mcal_flags'}, its 'flags' carrying the
     metacal flag too.
+
+    fixnoise, as in metacal_moments_batch, with the field of every object from
+    noise_seed: drawn on the device from (noise_seed, ids, pixel) over
+        sqrt(weight) where weight > 0 (ids: one per observation, default the
+        positions in the list), or
+    use_noise_image: each observation's own ob.noise, as get_all_metacal takes it.
     """
     from .moments import make_mom_result
-    from .prepsfmom import _check_obs_and_get_psf_obs, _refuse_fixnoise
+    from .prepsfmom import _check_obs_and_get_psf_obs, _fixnoise_source
+    seeded = _fixnoise_source(fixnoise, None, noise_seed, ids, use_noise_image)
     _moments_measure(measure)
-    _refuse_fixnoise(fixnoise)
     types = _check_types(types)
     list_of_obs = list(list_of_obs)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if ids.shape != (len(list_of_obs),):
+            raise ValueError("ids must have shape (%d,)" % len(list_of_obs))
+    if use_noise_image:
+        for o in list_of_obs:
+            if not o.has_noise():
+                raise ValueError("use_noise_image=True: every observation needs a noise image")
     psfs = [_check_obs_and_get_psf_obs(o, False) for o in list_of_obs]
     groups = {}
     for i, (o, p) in enumerate(zip(list_of_obs, psfs)):
@@ -753,11 +789,17 @@ def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fi
     out = [None] * len(list_of_obs)
     for key, idx in groups.items():
         sub, psub = [list_of_obs[i] for i in idx], [psfs[i] for i in idx]
+        noise = None
+        if use_noise_image:
+            noise = np.stack([o.noise for o in sub])
+        elif seeded is not None:
+            noise = DeviceNoise(seeded.seed, np.asarray(idx, dtype=np.int64) if ids is None
+                                else ids[idx])
         mom, cov, flags, kernels, _ = measure.measure_arrays_sheared(
             np.stack([o.image for o in sub]), np.stack([o.weight for o in sub]),
             np.array([[o.jacobian.row0, o.jacobian.col0] for o in sub]), key[2:],
             np.stack([p.image for p in psub]),
-            np.array([[p.jacobian.row0, p.jacobian.col0] for p in psub]), g)
+            np.array([[p.jacobian.row0, p.jacobian.col0] for p in psub]), g, noise=noise)
         for k, i in enumerate(idx):
             out[i] = {}
             for it, t in enumerate(types):

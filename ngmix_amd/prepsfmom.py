@@ -555,7 +555,8 @@ class PrePSFMom(object):
         return mom, cov, kernels, target_dim
 
     # ---- the moments of the object as sheared before the psf
-    def measure_arrays_sheared(self, images, weights, cen, deriv, psf_images, psf_cen, g):
+    def measure_arrays_sheared(self, images, weights, cen, deriv, psf_images, psf_cen, g,
+                               noise=None, noise_ierr=None):
         """
         The sums of measure_arrays for every stamp as sheared BEFORE its psf by
         each of T shears, without making an image: the transforms of the stamp
@@ -568,6 +569,18 @@ class PrePSFMom(object):
         takes them (device tensors are used where they lie); the psf is
         required.  g: (T, 2) one shear per type, or (N, T, 2) per stamp and
         type, inside the unit circle.
+
+        noise: the noise field of metacalibration's fixnoise,
+        or None for the sums of the stamps alone.  (N, dim, dim) UN-turned
+        planes, numpy or device tensor, turned with torch.rot90 on the device;
+        or a metacal.DeviceNoise: drawn on the device straight into the turned
+        layout from (seed, id, pixel) over noise_ierr ((N, dim, dim), default
+        sqrt(weight) where weight > 0).  Every mode then also takes the term of
+        the plane as turned, deconvolved by the un-turned psf, sheared and
+        turned back (csrc/prepsf_shear.hpp, add_noise_mode), and the
+        covariance sums those of two independent fields of the weight map's
+        variance; a kept mode whose turned, sheared frequency leaves the band,
+        or a noise pixel that is not finite, flags its (stamp, type) as well.
 
         Returns (sums (N, T, 6) = [nan, nan, M+, Mx, Mr, Mf], their covariance
         (N, T, 6, 6), flags (N, T), the kernels, the padded size).  flags is
@@ -630,13 +643,21 @@ class PrePSFMom(object):
         d_sums = torch.empty((n, ntypes, 14), dtype=torch.float64, device=dev)
         d_flags = torch.empty((n, ntypes), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            st = _lib.lib().ngmix_prepsf_shear_sums_batch(
-                _dptr(d_im), _dptr(d_w), _dptr(d_psf), _dptr(d_cen), _dptr(d_pcen), _dptr(d_edge),
-                _dptr(d_g), _lib.ptr(g), 1 if g.ndim == 3 else 0, _dptr(d_plan[0]),
-                _dptr(d_plan[1]), _dptr(d_plan[2]), _dptr(d_plan[3]), n, ntypes, int(mrow.size),
-                int(dim), int(pdim), target_dim, deriv[0], deriv[1], deriv[2], deriv[3],
-                _dptr(d_sums), _dptr(d_flags), _stream())
-        _lib.check(st, "ngmix_prepsf_shear_sums_batch")
+            head = (_dptr(d_im), _dptr(d_w), _dptr(d_psf))
+            rest = (_dptr(d_cen), _dptr(d_pcen), _dptr(d_edge),
+                    _dptr(d_g), _lib.ptr(g), 1 if g.ndim == 3 else 0, _dptr(d_plan[0]),
+                    _dptr(d_plan[1]), _dptr(d_plan[2]), _dptr(d_plan[3]), n, ntypes, int(mrow.size),
+                    int(dim), int(pdim), target_dim, deriv[0], deriv[1], deriv[2], deriv[3],
+                    _dptr(d_sums), _dptr(d_flags), _stream())
+            if noise is None:
+                entry = "ngmix_prepsf_shear_sums_batch"
+                st = _lib.lib().ngmix_prepsf_shear_sums_batch(*(head + rest))
+            else:
+                entry = "ngmix_prepsf_shear_fixnoise_sums_batch"
+                d_noise = _turned_noise(noise, noise_ierr, d_w, n, dim, dev)
+                st = _lib.lib().ngmix_prepsf_shear_fixnoise_sums_batch(
+                    *(head + (_dptr(d_noise),) + rest))
+        _lib.check(st, entry)
         # one download: a flagged (stamp, type) is the one whose sums are NaN, all
         # fourteen (d_flags says the same to callers that stay on the device)
         sums = d_sums.cpu().numpy()
@@ -650,7 +671,8 @@ class PrePSFMom(object):
         return mom, cov, flags, kernels, target_dim
 
     def go_metacal_batch(self, images, weights, cen, deriv, psf_images, psf_cen, step=0.01,
-                         types=None, fixnoise=False):
+                         types=None, fixnoise=False, noise=None, noise_seed=None, ids=None,
+                         noise_ierr=None):
         """
         The pre-psf moments of metacalibration's types from the stamps alone
         (measure_arrays_sheared at the types' shears, no metacal image is
@@ -660,16 +682,23 @@ class PrePSFMom(object):
         stamps are NaN.  metacal.shear_response(resdict, step, key='e') and
         metacal.mean_shear take the result as it is.
 
-        fixnoise is not served: moments of noisy stamps carry the noise
-        response.
+        fixnoise: the moments of noisy stamps carry the noise
+        response; with fixnoise=True the term of the turned, deconvolved,
+        sheared noise field that cancels it is summed with them.  The field is
+        `noise` ((N, dim, dim) un-turned planes, or a metacal.DeviceNoise) or
+        is drawn on the device from (noise_seed, ids, pixel) over noise_ierr
+        (default sqrt(weight) where weight > 0; ids default to the positions).
+        Without either, fixnoise=True is not served (NotImplementedError): the
+        host draw from an rng is not made here.
         """
         from .metacal import _check_types, _type_shears
         from .moments import make_mom_result_batch
-        _refuse_fixnoise(fixnoise)
+        noise = _fixnoise_source(fixnoise, noise, noise_seed, ids)
         types = _check_types(types)
         g = _type_shears(types, float(step))
         mom, cov, flags, kernels, _ = self.measure_arrays_sheared(
-            images, weights, cen, deriv, psf_images, psf_cen, g)
+            images, weights, cen, deriv, psf_images, psf_cen, g, noise=noise,
+            noise_ierr=noise_ierr)
         out = {}
         for i, t in enumerate(types):
             res = make_mom_result_batch(mom[:, i], cov[:, i], sums_norm=kernels["fk00"])
@@ -679,13 +708,68 @@ class PrePSFMom(object):
         return out
 
 
-def _refuse_fixnoise(fixnoise):
-    if fixnoise:
+def _fixnoise_source(fixnoise, noise, noise_seed, ids, use_noise_image=False):
+    """the rules of the fixnoise keywords, before any other argument is looked
+    at; returns what measure_arrays_sheared takes as `noise` (None, the planes,
+    or a metacal.DeviceNoise); with use_noise_image the caller supplies the
+    planes"""
+    given = noise is not None or noise_seed is not None or bool(use_noise_image)
+    if fixnoise and not given:
         raise NotImplementedError(
-            "fixnoise is not served by the sheared pre-psf moments: the turned noise plane is "
-            "deconvolved by the un-turned psf and turned back, which needs a frequency map of "
-            "its own for the plane and another for the psf; moments of noisy stamps carry the "
-            "noise response until then")
+            "fixnoise=True needs a noise field: send noise_seed (drawn on the device), noise "
+            "(planes or a metacal.DeviceNoise) or, for observations, use_noise_image=True; the "
+            "host draw from an rng is not served by the sheared pre-psf moments")
+    if given and not fixnoise:
+        raise ValueError("a noise field was sent with fixnoise=False: send fixnoise=True too")
+    if (noise is not None) + (noise_seed is not None) + bool(use_noise_image) > 1:
+        raise ValueError("send one noise source: noise, noise_seed or use_noise_image")
+    if ids is not None and noise_seed is None:
+        raise ValueError("ids belong to the device noise: send noise_seed too")
+    if noise_seed is not None:
+        from .metacal import DeviceNoise
+        return DeviceNoise(noise_seed, ids)
+    return noise
+
+
+def _turned_noise(noise, ierr, d_w, n, dim, dev):
+    """the (N, dim, dim) noise planes of fixnoise on the device in the layout
+    torch.rot90(., 1, dims=(1, 2)) gives them: planes that were sent are turned
+    there; a metacal.DeviceNoise is drawn straight into that layout
+    (ngmix_metacal_noise_batch, rot_k = 1) over ierr, or over sqrt(weight)
+    where the weight d_w is positive"""
+    torch = _torch()
+    from . import _lib
+    from .batch import _dptr, _stream
+    from .metacal import DeviceNoise
+    if not isinstance(noise, DeviceNoise):
+        d = _to_device(noise, dev)
+        if tuple(d.shape) != (n, dim, dim):
+            raise ValueError("noise must hold one %d x %d plane per stamp, got %s"
+                             % (dim, dim, tuple(d.shape)))
+        return torch.rot90(d, 1, dims=(1, 2)).contiguous()
+    seed = int(noise.seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("the noise seed must be in [0, 2^64)")
+    d_ids = None
+    if noise.ids is not None:
+        if isinstance(noise.ids, torch.Tensor):
+            d_ids = noise.ids.to(device=dev, dtype=torch.int64).contiguous()
+        else:
+            d_ids = torch.from_numpy(np.ascontiguousarray(noise.ids, dtype=np.int64)).to(dev)
+        if tuple(d_ids.shape) != (n,):
+            raise ValueError("ids must have shape (%d,)" % n)
+    if ierr is None:
+        d_ierr = torch.sqrt(torch.clamp(d_w, min=0.0))
+    else:
+        d_ierr = _to_device(ierr, dev)
+        if d_ierr.numel() != n * dim * dim:
+            raise ValueError("noise_ierr must hold one %d x %d plane per stamp" % (dim, dim))
+    d_ierr = d_ierr.reshape(-1).contiguous()
+    out = torch.empty((n, dim, dim), dtype=torch.float64, device=dev)
+    st = _lib.lib().ngmix_metacal_noise_batch(_dptr(d_ierr), _dptr(d_ids), seed, n, dim, dim, 1,
+                                              _dptr(out), _stream())
+    _lib.check(st, "ngmix_metacal_noise_batch")
+    return out
 
 
 def _shear_plan(kernels, target_dim):

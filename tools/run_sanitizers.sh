@@ -31,4 +31,5 @@ cd "$ROOT"
       -k "not resource_guard and not hazard_guard and not every_declared_symbol and not library_matches_sources" 2>&1 | tail -25
   make -C "$ROOT/ngmix_amd/csrc" -j4 asan-metacal-noise > /dev/null 2>&1 && "$ROOT/ngmix_amd/metacal_noise_host_asan"
   make -C "$ROOT/ngmix_amd/csrc" -j4 asan-prepsf-shear > /dev/null 2>&1 && "$ROOT/ngmix_amd/prepsf_shear_host_asan"
+  make -C "$ROOT/ngmix_amd/csrc" -j4 asan-prepsf-shear-noise > /dev/null 2>&1 && "$ROOT/ngmix_amd/prepsf_shear_noise_host_asan"
 } | tee "$LOG"

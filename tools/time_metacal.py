@@ -16,9 +16,13 @@ device, and the same with the host draw (numpy normals, scaled and uploaded).
 the sheared-mode kernel alone (csrc/prepsf_shear.hip), metacal_moments_batch
 end to end, and the two-step route for the same quantities -- get_all(
 fixnoise=False), then measure_arrays on each type's images and target psf
-images.  Prints nmodes, the kept modes of the kernel's plan.
+images.  Prints nmodes, the kept modes of the kernel's plan, and the smallest
+and largest of the repeats beside every median.  With --fixnoise also the
+fixnoise form: its kernel alone on a turned noise plane, and
+metacal_moments_batch(fixnoise=True, noise_seed=...) end to end.
 
-usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2] [--noise | --moments]
+usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2]
+                                    [--noise | --moments [--fixnoise]]
 """
 import argparse
 import json
@@ -52,6 +56,9 @@ def main():
     ap.add_argument("--moments", action="store_true",
                     help="time the pre-psf moments of the five types instead: the sheared-mode "
                          "kernel alone, metacal_moments_batch, and get_all + measure_arrays")
+    ap.add_argument("--fixnoise", action="store_true",
+                    help="with --moments: also the fixnoise kernel alone and "
+                         "metacal_moments_batch(fixnoise=True, noise_seed=...)")
     args = ap.parse_args()
     import torch
     from ngmix_amd import metacal
@@ -71,6 +78,7 @@ def main():
             b.record()
             b.synchronize()
             times.append(a.elapsed_time(b) * 1e-3)
+        timed.spread = (float(min(times)), float(max(times)))
         return float(np.median(times))
 
     for dim in (32, 48):
@@ -113,7 +121,7 @@ def main():
             }), flush=True)
             continue
         if args.moments:
-            print(json.dumps(_moments(mc, sb, psb, dim, scale, timed)), flush=True)
+            print(json.dumps(_moments(mc, sb, psb, dim, scale, timed, args.fixnoise)), flush=True)
             continue
         for fixnoise in (False, True):
             planes = 3 if fixnoise else 2
@@ -131,8 +139,9 @@ def main():
             }), flush=True)
 
 
-def _moments(mc, sb, psb, dim, scale, timed):
-    """the three timings of --moments for one stamp size"""
+def _moments(mc, sb, psb, dim, scale, timed, fixnoise=False):
+    """the three timings of --moments for one stamp size, and with fixnoise the
+    two of the fixnoise form"""
     import torch
     from ngmix_amd import _lib, metacal, prepsfmom
     from ngmix_amd.batch import _dptr, _stream
@@ -167,17 +176,48 @@ def _moments(mc, sb, psb, dim, scale, timed):
             m.measure_arrays(d["stamps"].val.reshape(n, dim, dim), weights, cen.cpu().numpy(), deriv,
                              d["psf_stamps"].val.reshape(n, dim, dim),
                              d["psf_stamps"].jac[:, 0:2].cpu().numpy())
+    def spread_ms():
+        return [t * 1e3 for t in timed.spread]
     kernel = timed(kernel_only)
+    kernel_spread = spread_ms()
     total = timed(lambda: metacal.metacal_moments_batch(sb, psb, m))
+    total_spread = spread_ms()
     parent = timed(two_step)
     # per (stamp, type): every kept mode walks every pixel of the image and the psf
     fma = float(nmodes) * dim * dim * (4 + 2 * 2) * 5 * n
-    return {"stamp": dim, "n": n, "types": 5, "fft_dim": D, "nmodes": nmodes,
-            "modes_of_the_spectrum_kernel": dim * (dim // 2 + 1) + (dim // 2 + 1) + dim - 1,
-            "shear_sums_kernel_ms": kernel * 1e3, "metacal_moments_batch_ms": total * 1e3,
-            "get_all_then_measure_arrays_ms": parent * 1e3,
-            "kernel_fma_per_s": fma / kernel,
-            "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S}
+    out = {"stamp": dim, "n": n, "types": 5, "fft_dim": D, "nmodes": nmodes,
+           "modes_of_the_spectrum_kernel": dim * (dim // 2 + 1) + (dim // 2 + 1) + dim - 1,
+           "shear_sums_kernel_ms": kernel * 1e3, "shear_sums_kernel_min_max_ms": kernel_spread,
+           "metacal_moments_batch_ms": total * 1e3,
+           "metacal_moments_batch_min_max_ms": total_spread,
+           "get_all_then_measure_arrays_ms": parent * 1e3,
+           "kernel_fma_per_s": fma / kernel,
+           "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S}
+    if not fixnoise:
+        return out
+    turned = mc.device_noise(12345, rotated=True)
+
+    def fixnoise_kernel_only():
+        st = _lib.lib().ngmix_prepsf_shear_fixnoise_sums_batch(
+            _dptr(images), _dptr(weights), _dptr(psb.val), _dptr(turned), _dptr(cen), _dptr(pcen),
+            _dptr(edge), _dptr(d_g), _lib.ptr(g), 0, _dptr(plan[0]), _dptr(plan[1]),
+            _dptr(plan[2]), _dptr(plan[3]), n, 5, nmodes, dim, dim, D, deriv[0], deriv[1],
+            deriv[2], deriv[3], _dptr(sums), _dptr(flags), _stream())
+        _lib.check(st, "ngmix_prepsf_shear_fixnoise_sums_batch")
+    fkernel = timed(fixnoise_kernel_only)
+    fkernel_spread = spread_ms()
+    ftotal = timed(lambda: metacal.metacal_moments_batch(sb, psb, m, fixnoise=True,
+                                                         noise_seed=12345))
+    # a second pass of the phase recurrence, over the noise plane and the psf
+    out.update({"fixnoise_sums_kernel_ms": fkernel * 1e3,
+                "fixnoise_sums_kernel_min_max_ms": fkernel_spread,
+                "fixnoise_kernel_over_plain_kernel": fkernel / kernel,
+                "metacal_moments_batch_fixnoise_ms": ftotal * 1e3,
+                "metacal_moments_batch_fixnoise_min_max_ms": spread_ms(),
+                "fixnoise_kernel_fma_per_s": 2 * fma / fkernel,
+                "fixnoise_fraction_of_fp64_vector_fma_peak":
+                    2 * fma / fkernel / FP64_VECTOR_FMA_PER_S})
+    return out
 
 
 def _spectrum_only(mc, g, noise):
