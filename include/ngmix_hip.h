@@ -425,6 +425,50 @@ int ngmix_metacal_spectrum_batch(const double *images, const double *noise, cons
                                  const double *g_host, int per_stamp_g, int64_t nstamps,
                                  int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
                                  double *spec, int32_t *flags, void *stream);
+/* DEVICE: ngmix_metacal_spectrum_batch with the psf stamp's own dilated (and,
+   for the psf-sheared types, sheared) image as the reconvolution target
+   (ngmix/metacal/metacal.py: the Metacal base class, get_obs_galshear and
+   get_obs_psfshear; there through galsim).  Beside its shear g every (stamp,
+   type) has a dilation d >= 1 and a kind: 0, the image is sheared, or 1, the
+   psf is.  With S(g) q = q + J^T (A - 1) J^-T q and Pi(q) = sinc(q_row / 2)
+   sinc(q_col / 2) the transform of the pixel, the image is read at q' and the
+   target at q_t:  kind 0: q' = S(g) q, q_t = d q;  kind 1: q' = q, q_t = d S(g) q.
+   T^(q) = P^(q_t) / Pi(q_t) Pi(q), P^ the psf stamp's transform about psf_cen,
+   and O^(q) = I^(q') / P^(q') T^(q); a mode is kept only where all four of
+   |q'_row|, |q'_col|, |q_t,row|, |q_t,col| are < pi: the dilated psf is zero
+   beyond its band, never extrapolated.  images, noise, psf, jac, psf_cen, g,
+   g_host, per_stamp_g, spec and flags as in ngmix_metacal_spectrum_batch; dil
+   (ntypes,) and kind (ntypes,) int32, or (nstamps, ntypes) with per_stamp_g, on
+   the device; dil_host, kind_host: the same in HOST memory.
+   NGMIX_ERR_BAD_ARG before any launch for a NULL required pointer (all but
+   noise), a count or shape that is not positive, |g| >= 1, a dilation below 1
+   or not finite, a kind outside {0, 1}, nstamps ntypes beyond one grid, planes
+   that do not fit the 160 KB of LDS.  One launch; nstamps <= 0 is a no-op */
+int ngmix_metacal_dilate_spectrum_batch(const double *images, const double *noise,
+                                        const double *psf, const ngmix_jacobian *jac,
+                                        const double *psf_cen, const double *g, const double *dil,
+                                        const int32_t *kind, const double *g_host,
+                                        const double *dil_host, const int32_t *kind_host,
+                                        int per_stamp_g, int64_t nstamps, int ntypes, int nrow,
+                                        int ncol, int psf_nrow, int psf_ncol, double *spec,
+                                        int32_t *flags, void *stream);
+/* DEVICE: the target psf of ngmix_metacal_dilate_spectrum_batch on the PSF
+   stamp's own grid q_p: spec (nstamps, ntypes, psf_nrow, psf_ncol / 2 + 1)
+   complex128 = T^(q_p) exp(-i q_p . psf_cen), kept where |q_t,row| < pi and
+   |q_t,col| < pi, hermitian on its Nyquist row and column: a complex-to-real
+   inverse FFT of shape (psf_nrow, psf_ncol) gives the target psf image about
+   the psf stamp's own centre.  At g = 0, d = 1 that is the psf stamp without
+   the Nyquist row and column of its transform.  jac (nstamps,): jacobians
+   whose derivatives are the psf stamps' (the centres are read from psf_cen);
+   the other arguments, the refusals and flags (nstamps, ntypes) as above */
+int ngmix_metacal_dilate_psf_spectrum_batch(const double *psf, const ngmix_jacobian *jac,
+                                            const double *psf_cen, const double *g,
+                                            const double *dil, const int32_t *kind,
+                                            const double *g_host, const double *dil_host,
+                                            const int32_t *kind_host, int per_stamp_g,
+                                            int64_t nstamps, int ntypes, int psf_nrow,
+                                            int psf_ncol, double *spec, int32_t *flags,
+                                            void *stream);
 /* DEVICE: the noise planes of metacalibration's fixnoise as a pure function of
    (seed, object id, pixel).  Philox4x32-10 with the standard round constants
    and Weyl key increments, key = (seed & 0xffffffff, seed >> 32), counter =

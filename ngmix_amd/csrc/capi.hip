@@ -550,6 +550,36 @@ int ngmix_metacal_spectrum_batch(const double *images, const double *noise, cons
                                    spec, flags, (hipStream_t)stream);
 }
 
+int ngmix_metacal_dilate_spectrum_batch(const double *images, const double *noise,
+                                        const double *psf, const ngmix_jacobian *jac,
+                                        const double *psf_cen, const double *g, const double *dil,
+                                        const int32_t *kind, const double *g_host,
+                                        const double *dil_host, const int32_t *kind_host,
+                                        int per_stamp_g, int64_t nstamps, int ntypes, int nrow,
+                                        int ncol, int psf_nrow, int psf_ncol, double *spec,
+                                        int32_t *flags, void *stream)
+{
+    return launch_metacal_dilate_spectrum(images, noise, psf, jac, psf_cen, g, dil, kind, g_host,
+                                          dil_host, kind_host, per_stamp_g, nstamps, ntypes, nrow,
+                                          ncol, psf_nrow, psf_ncol, spec, flags, false,
+                                          (hipStream_t)stream);
+}
+
+int ngmix_metacal_dilate_psf_spectrum_batch(const double *psf, const ngmix_jacobian *jac,
+                                            const double *psf_cen, const double *g,
+                                            const double *dil, const int32_t *kind,
+                                            const double *g_host, const double *dil_host,
+                                            const int32_t *kind_host, int per_stamp_g,
+                                            int64_t nstamps, int ntypes, int psf_nrow,
+                                            int psf_ncol, double *spec, int32_t *flags,
+                                            void *stream)
+{
+    return launch_metacal_dilate_spectrum(nullptr, nullptr, psf, jac, psf_cen, g, dil, kind, g_host,
+                                          dil_host, kind_host, per_stamp_g, nstamps, ntypes,
+                                          psf_nrow, psf_ncol, psf_nrow, psf_ncol, spec, flags, true,
+                                          (hipStream_t)stream);
+}
+
 int ngmix_metacal_noise_batch(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                               int nrow, int ncol, int rot_k, double *out, void *stream)
 {

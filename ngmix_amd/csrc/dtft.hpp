@@ -111,5 +111,36 @@ NGMIX_HD void transforms(const Planes &p, double r0, double c0, double qr, doubl
     }
 }
 
+// sum plane[r, c] exp(-i (qr (r - r0) + qc (c - c0))) of ONE R x C plane about
+// its own centre, with a recurrence of its own: for a plane that is wanted at
+// another frequency than the planes of transforms() (the dilated target psf of
+// metacal.hip).  4 + 2 FMA per pixel; the same seeds every SEED rows and columns.
+NGMIX_HD cplx transform_one(const double *plane, int R, int C, double r0, double c0, double qr,
+                            double qc)
+{
+    cplx s = {0.0, 0.0};
+    const cplx zc = cexpi(-qc), zr = cexpi(-qr);
+    for (int cs = 0; cs < C; cs += SEED) {
+        const cplx cseed = cexpi(-qc * ((double)cs - c0));
+        const int nc = C - cs > SEED ? SEED : C - cs;
+        for (int rs = 0; rs < R; rs += SEED) {
+            cplx prow = cmul(cexpi(-qr * ((double)rs - r0)), cseed);
+            const int re = rs + SEED < R ? rs + SEED : R;
+            for (int r = rs; r < re; r++) {
+                const double *row = plane + (int64_t)r * C + cs;
+                cplx ph = prow;
+                for (int k = 0; k < nc; k++) {
+                    const double v = row[k];
+                    s.x = fma(v, ph.x, s.x);
+                    s.y = fma(v, ph.y, s.y);
+                    ph = cmul(ph, zc);
+                }
+                prow = cmul(prow, zr);
+            }
+        }
+    }
+    return s;
+}
+
 }  // namespace dtft
 }  // namespace ngmix

@@ -43,6 +43,13 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
                             const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
                             int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
                             int32_t *flags, hipStream_t s);
+int launch_metacal_dilate_spectrum(const double *images, const double *noise, const double *psf,
+                                   const ngmix_jacobian *jac, const double *psf_cen,
+                                   const double *g, const double *dil, const int32_t *kind,
+                                   const double *g_host, const double *dil_host,
+                                   const int32_t *kind_host, int per_stamp_g, int64_t nstamps,
+                                   int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
+                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s);
 // metacal_noise.hip
 int launch_metacal_noise(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                          int nrow, int ncol, int rot_k, double *out, hipStream_t s);

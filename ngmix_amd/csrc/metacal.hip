@@ -15,12 +15,21 @@
 // is carried by the recurrence of dtft.hpp (shared with prepsf_shear.hip);
 // image, noise and psf share it (the psf up to one factor per mode for its own
 // centre): 4 FMA per pixel for the phase and 2 per pixel and plane for the sums.
+//
+// A second target (TARGET_DILATE): the psf stamp's own
+// transform, deconvolved from the pixel, dilated -- and, for the psf-sheared
+// types, sheared -- and reconvolved with the pixel.  It is the psf plane's
+// transform at one more frequency per mode, with a recurrence of its own over
+// the psf pixels (dtft.hpp, transform_one): (4 + 2) Rp Cp more FMA per mode.
+// TARGET_DILATE_PSF is the same target alone, at the modes of the PSF stamp's
+// grid: the target psf image.
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "dtft.hpp"
 #include "launch.hpp"
 #include "launch_util.hpp"
 
+#include <cmath>
 #include <string>
 
 namespace ngmix {
@@ -28,6 +37,27 @@ namespace ngmix {
 namespace {
 
 using namespace dtft;   // cplx, cmul, cexpi, cdiv, Planes, transforms, SEED, PI
+
+// the reconvolution target of a spectrum kernel, and what it reads beside g
+enum { TARGET_GAUSS = 0, TARGET_DILATE = 1, TARGET_DILATE_PSF = 2 };
+
+// The two arrays a target reads: psf_flux and sigma (N,) of the round gaussian;
+// of the dilated psf the dilation d >= 1 and the kind (0: the image is sheared,
+// 1: the psf is), (ng, T) like g.  The second array's element type:
+template <int TARGET>
+struct SecondArg {
+    using type = int32_t;
+};
+template <>
+struct SecondArg<TARGET_GAUSS> {
+    using type = double;
+};
+
+// dilation and kind of one (stamp, type)
+struct DilateSetup {
+    double dil;
+    bool shear_psf;
+};
 
 // the integer numerator of fftfreq(n)[i]
 NGMIX_HD int fft_index(int i, int n) { return i < (n + 1) / 2 ? i : i - n; }
@@ -74,14 +104,71 @@ NGMIX_HD ModeSetup mode_setup(const ngmix_jacobian &jac, double pr0, double pc0,
     return m;
 }
 
+// sinc(x) = sin x / x
+NGMIX_HD double sinc(double x) { return x == 0.0 ? 1.0 : sin(x) / x; }
+
+// the transform of the pixel, a unit square in pixel coordinates
+NGMIX_HD double pixel_ft(double qr, double qc) { return sinc(0.5 * qr) * sinc(0.5 * qc); }
+
+// The same with the dilated psf as the target.  S(g) q = q +
+// J^T (A - 1) J^-T q; the image is read at q' and the psf, about its own
+// centre, at q' and at q_t:
+//   the image is sheared:  q' = S(g) q,  q_t = d q
+//   the psf is sheared:    q' = q,       q_t = d S(g) q
+// T^(q) = P^(q_t) / Pi(q_t) Pi(q), O^(q) = I^(q') / P^(q') T^(q); a mode is
+// kept only where q' and q_t are strictly inside the band (|Pi(q_t)| >= (2 /
+// pi)^2 there).  PSF_ONLY: T^(q) exp(-i q . psf centre) alone, q a mode of the
+// psf stamp's grid, kept where q_t is inside the band.
+template <bool NOISE, bool PSF_ONLY>
+NGMIX_HD void dilate_mode_value(const Planes &p, const ModeSetup &m, const DilateSetup &ds,
+                                double qa, double qb, cplx &oi, cplx &on, bool &bad)
+{
+    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
+    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
+    const double sr = qa + (m.j00 * dv + m.j10 * du), sc = qb + (m.j01 * dv + m.j11 * du);
+    const double qr = ds.shear_psf ? qa : sr, qc = ds.shear_psf ? qb : sc;
+    const double tr = ds.dil * (ds.shear_psf ? sr : qa), tc = ds.dil * (ds.shear_psf ? sc : qb);
+    if (!(fabs(tr) < PI && fabs(tc) < PI)) return;
+    if (!PSF_ONLY && !(fabs(qr) < PI && fabs(qc) < PI)) return;
+    const cplx pt = transform_one(p.psf, p.Rp, p.Cp, m.pr0, m.pc0, tr, tc);
+    const double pix = pixel_ft(qa, qb) / pixel_ft(tr, tc);
+    const cplx target = {pt.x * pix, pt.y * pix};
+    if (PSF_ONLY) {
+        oi = cmul(target, cexpi(-(qa * m.pr0 + qb * m.pc0)));
+        if (!(isfinite(oi.x) && isfinite(oi.y))) {
+            bad = true;
+            oi = {NAN, NAN};
+        }
+        return;
+    }
+    cplx si, sn, sp;
+    transforms<NOISE>(p, m.r0, m.c0, qr, qc, si, sn, sp);
+    sp = cmul(sp, cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
+    const cplx shift = cexpi(-(qa * m.r0 + qb * m.c0));
+    oi = cmul(cmul(cdiv(si, sp), target), shift);
+    bool ok = isfinite(oi.x) && isfinite(oi.y);
+    if (NOISE) {
+        on = cmul(cmul(cdiv(sn, sp), target), shift);
+        ok = ok && isfinite(on.x) && isfinite(on.y);
+    }
+    if (!ok) {
+        bad = true;
+        oi = on = {NAN, NAN};
+    }
+}
+
 // O^(q) exp(-i q . centre) of the image (and of the noise plane) at the grid
 // frequency q = (qa, qb): zero outside the band; bad is set when a kept mode
 // is not finite (its value is NaN then, never an infinity)
-template <bool NOISE>
-NGMIX_HD void mode_value(const Planes &p, const ModeSetup &m, double qa, double qb, cplx &oi,
-                         cplx &on, bool &bad)
+template <bool NOISE, int TARGET>
+NGMIX_HD void mode_value(const Planes &p, const ModeSetup &m, const DilateSetup &ds, double qa,
+                         double qb, cplx &oi, cplx &on, bool &bad)
 {
     oi = on = {0.0, 0.0};
+    if constexpr (TARGET != TARGET_GAUSS) {
+        dilate_mode_value<NOISE, TARGET == TARGET_DILATE_PSF>(p, m, ds, qa, qb, oi, on, bad);
+        return;
+    }
     // world frequency (v, u), the sheared one, and back to pixel axes:
     // q' = q + J^T (A - 1) J^-T q
     const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
@@ -149,23 +236,34 @@ size_t metacal_lds_bytes(int R, int C, int Rp, int Cp, bool noise)
     return (planes + items * 4 * (noise ? 2 : 1)) * sizeof(double);
 }
 
+// TARGET_DILATE_PSF: the psf stamp alone, the Nyquist items of its own grid
+size_t metacal_psf_lds_bytes(int Rp, int Cp)
+{
+    const size_t items = (size_t)(nyq_row_items(Rp, Cp) + nyq_col_items(Rp, Cp));
+    return ((size_t)Rp * Cp + items * 4) * sizeof(double);
+}
+
 // images (N, R, C), noise (N, R, C) with NOISE, psf (N, Rp, Cp); jac (N,): the
-// image's jacobian; psf_cen (N, 2), psf_flux (N,), sigma (N,); g (ng, T, 2)
+// image's jacobian; psf_cen (N, 2); psf_flux (N,), sigma (N,) of TARGET_GAUSS,
+// in their place dil and kind (ng, T) of the dilated psf; g (ng, T, 2)
 // with ng = 1 (one shear per type) or N (a shear per stamp and type).
 // spec (N, T, planes, R, C/2 + 1) complex: the image's spectrum, then the
 // noise plane's; flags (N, T): 1 where a kept mode was not finite.
-template <bool NOISE>
+// TARGET_DILATE_PSF: no image and no noise plane, (R, C) = (Rp, Cp) is the psf
+// stamp's grid and spec the target psf's spectrum on it.
+template <bool NOISE, int TARGET>
 __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
     const double *__restrict__ images, const double *__restrict__ noise,
     const double *__restrict__ psf, const ngmix_jacobian *__restrict__ jac,
-    const double *__restrict__ psf_cen, const double *__restrict__ psf_flux,
-    const double *__restrict__ sigma, const double *__restrict__ g, int per_stamp_g, int T,
+    const double *__restrict__ psf_cen, const double *__restrict__ flux_or_dil,
+    const typename SecondArg<TARGET>::type *__restrict__ sigma_or_kind,
+    const double *__restrict__ g, int per_stamp_g, int T,
     int R, int C, int Rp, int Cp, double *__restrict__ spec, int32_t *__restrict__ flags)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t n = blockIdx.x / T;
     const int t = blockIdx.x % T;
-    const int npix = R * C, nppix = Rp * Cp;
+    const int npix = TARGET == TARGET_DILATE_PSF ? 0 : R * C, nppix = Rp * Cp;
     constexpr int NPL = NOISE ? 2 : 1;
 
     double *s_img = (double *)smem;
@@ -183,9 +281,17 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
     __syncthreads();
 
     const Planes planes = {s_img, NOISE ? s_noise : nullptr, s_psf, R, C, Rp, Cp};
-    const double *gt = g + ((per_stamp_g ? n * T : 0) + t) * 2;
-    const ModeSetup m =
-        mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], sigma[n], psf_flux[n]);
+    const int64_t gi = (per_stamp_g ? n * T : 0) + t;
+    const double *gt = g + gi * 2;
+    ModeSetup m;
+    DilateSetup ds = {1.0, false};
+    if constexpr (TARGET == TARGET_GAUSS) {
+        m = mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], sigma_or_kind[n],
+                       flux_or_dil[n]);
+    } else {
+        m = mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], 0.0, 0.0);
+        ds = {flux_or_dil[gi], sigma_or_kind[gi] != 0};
+    }
 
     const int Ch = C / 2 + 1;
     const int nmodes = R * Ch;
@@ -195,7 +301,8 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
         cplx oi, on;
         if (w < nmodes) {
             const int a = w / Ch, b = w % Ch;
-            mode_value<NOISE>(planes, m, grid_freq(a, R), grid_freq(b, C), oi, on, bad);
+            mode_value<NOISE, TARGET>(planes, m, ds, grid_freq(a, R), grid_freq(b, C), oi, on,
+                                      bad);
             const int s = nyq_item_of(a, b, R, C);
             if (s < 0) {
                 out[w] = oi;
@@ -208,8 +315,8 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
             const int s = w - nmodes;
             int a, b;
             nyq_item_mode(s, R, C, a, b);
-            mode_value<NOISE>(planes, m, grid_freq((R - a) % R, R), grid_freq((C - b) % C, C), oi,
-                              on, bad);
+            mode_value<NOISE, TARGET>(planes, m, ds, grid_freq((R - a) % R, R),
+                                      grid_freq((C - b) % C, C), oi, on, bad);
             s_partner[s] = oi;
             if (NOISE) s_partner[nitems + s] = on;
         }
@@ -224,6 +331,21 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
         }
     }
     if (threadIdx.x == 0) flags[n * T + t] = any_bad;
+}
+
+// the block size that leaves the fewest idle work-item slots (the larger on a tie)
+static int spectrum_block(int nrow, int ncol)
+{
+    const int nwork = nrow * (ncol / 2 + 1) + nyq_row_items(nrow, ncol) + nyq_col_items(nrow, ncol);
+    int block = BLOCK, waste = (nwork + BLOCK - 1) / BLOCK * BLOCK;
+    for (int b = BLOCK - WAVE; b >= WAVE; b -= WAVE) {
+        const int slots = (nwork + b - 1) / b * b;
+        if (slots < waste) {
+            waste = slots;
+            block = b;
+        }
+    }
+    return block;
 }
 
 // g_host: the caller's host copy of g, checked here (|g| < 1) before anything
@@ -266,21 +388,75 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
             return NGMIX_ERR_BAD_ARG;
         }
     }
-    // the block size that leaves the fewest idle work-item slots (the larger on a tie)
-    const int nwork = nrow * (ncol / 2 + 1) + nyq_row_items(nrow, ncol) + nyq_col_items(nrow, ncol);
-    int block = BLOCK, waste = (nwork + BLOCK - 1) / BLOCK * BLOCK;
-    for (int b = BLOCK - WAVE; b >= WAVE; b -= WAVE) {
-        const int slots = (nwork + b - 1) / b * b;
-        if (slots < waste) {
-            waste = slots;
-            block = b;
-        }
+    const auto k = noise ? kernel(metacal_spectrum_kernel<true, TARGET_GAUSS>,
+                                  "metacal_spectrum_kernel<noise>")
+                         : kernel(metacal_spectrum_kernel<false, TARGET_GAUSS>,
+                                  "metacal_spectrum_kernel");
+    return launch(k, dim3((unsigned)(nstamps * ntypes)), dim3(spectrum_block(nrow, ncol)), lds,
+                  48 * 1024, s, images, noise, psf, jac, psf_cen, psf_flux, sigma, g,
+                  per_stamp_g ? 1 : 0, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags);
+}
+
+// The dilated psf as the target (psf_only: its own spectrum on the psf stamp's
+// grid; images, noise, nrow and ncol are not looked at then).  g_host, dil_host,
+// kind_host: the caller's host copies, checked here (|g| < 1, d >= 1 and finite,
+// kind 0 or 1) before anything is launched
+int launch_metacal_dilate_spectrum(const double *images, const double *noise, const double *psf,
+                                   const ngmix_jacobian *jac, const double *psf_cen,
+                                   const double *g, const double *dil, const int32_t *kind,
+                                   const double *g_host, const double *dil_host,
+                                   const int32_t *kind_host, int per_stamp_g, int64_t nstamps,
+                                   int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
+                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s)
+{
+    const std::string who = psf_only ? "metacal_dilate_psf_spectrum" : "metacal_dilate_spectrum";
+    const auto refuse = [&who](const std::string &what) {
+        set_last_error_msg((who + ": " + what).c_str());
+        return NGMIX_ERR_BAD_ARG;
+    };
+    if (nstamps <= 0) return NGMIX_OK;
+    if (psf_only) {
+        images = noise = nullptr;
+        nrow = psf_nrow;
+        ncol = psf_ncol;
+    } else if (!images) {
+        return refuse("images is required");
     }
-    const auto k = noise ? kernel(metacal_spectrum_kernel<true>, "metacal_spectrum_kernel<noise>")
-                         : kernel(metacal_spectrum_kernel<false>, "metacal_spectrum_kernel");
-    return launch(k, dim3((unsigned)(nstamps * ntypes)), dim3(block), lds, 48 * 1024, s, images,
-                  noise, psf, jac, psf_cen, psf_flux, sigma, g, per_stamp_g ? 1 : 0, ntypes, nrow,
-                  ncol, psf_nrow, psf_ncol, spec, flags);
+    if (!psf || !jac || !psf_cen || !g || !dil || !kind || !g_host || !dil_host || !kind_host ||
+        !spec || !flags)
+        return refuse("psf, jac, psf_cen, g, dil, kind, g_host, dil_host, kind_host, spec and "
+                      "flags are required");
+    if (ntypes <= 0 || nrow <= 0 || ncol <= 0 || psf_nrow <= 0 || psf_ncol <= 0)
+        return refuse("the number of types and the stamp shapes must be positive");
+    if (nstamps * ntypes > 0x7fffffffll) return refuse("too many (stamp, type) pairs for one launch");
+    const size_t lds = psf_only ? metacal_psf_lds_bytes(psf_nrow, psf_ncol)
+                                : metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr);
+    if (lds > 160 * 1024 || (int64_t)nrow * ncol > 0x7fffff ||
+        (int64_t)psf_nrow * psf_ncol > 0x7fffff)
+        return refuse("the stamp, its psf stamp and its noise plane do not fit the 160 KB of LDS");
+    const int64_t ng = (per_stamp_g ? nstamps : 1) * ntypes;
+    for (int64_t i = 0; i < ng; i++) {
+        const double g1 = g_host[2 * i], g2 = g_host[2 * i + 1];
+        if (!(g1 * g1 + g2 * g2 < 1.0))
+            return refuse("shear " + std::to_string(i) + " is not inside the unit circle");
+        if (!(dil_host[i] >= 1.0 && std::isfinite(dil_host[i])))
+            return refuse("dilation " + std::to_string(i) + " is not a finite number >= 1");
+        if (kind_host[i] != 0 && kind_host[i] != 1)
+            return refuse("kind " + std::to_string(i) + " is neither 0 (image) nor 1 (psf)");
+    }
+    const dim3 grid((unsigned)(nstamps * ntypes)), block(spectrum_block(nrow, ncol));
+    const int per = per_stamp_g ? 1 : 0;
+    if (psf_only)
+        return launch(kernel(metacal_spectrum_kernel<false, TARGET_DILATE_PSF>,
+                             "metacal_spectrum_kernel<dilate psf>"),
+                      grid, block, lds, 48 * 1024, s, images, noise, psf, jac, psf_cen, dil, kind, g,
+                      per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags);
+    const auto k = noise ? kernel(metacal_spectrum_kernel<true, TARGET_DILATE>,
+                                  "metacal_spectrum_kernel<noise, dilate>")
+                         : kernel(metacal_spectrum_kernel<false, TARGET_DILATE>,
+                                  "metacal_spectrum_kernel<dilate>");
+    return launch(k, grid, block, lds, 48 * 1024, s, images, noise, psf, jac, psf_cen, dil, kind, g,
+                  per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags);
 }
 
 }  // namespace ngmix

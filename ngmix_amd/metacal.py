@@ -17,6 +17,7 @@ shapes, the target psf of 'fitgauss', the fixnoise recipe and the use made of
     MetacalBatch(stamps, psf_stamps, psf='fitgauss', target_sigma=None, rng=None)
         .get_all(step=0.01, types=None, fixnoise=False, noise=None)
         .get_obs_galshear(g1, g2)
+        .get_obs_psfshear(g1, g2)              (psf='dilate-exact')
         .device_noise(seed, ids=None, rotated=False)
     get_all_metacal(obs, psf='fitgauss', step=0.01, types=None, fixnoise=True,
                     rng=None, use_noise_image=False)
@@ -26,10 +27,11 @@ catalogues"):
 
     metacal_bootstrap_batch(stamps, psf_stamps, model='gauss', step=0.01, ...,
                             noise_seed=None, ids=None, ...) -> (resdict, batchdict)
-    shear_response(resdict, step=0.01, key='g') -> {'g', 'R', 'flags'}
-    mean_shear(resp, select=None) -> (2,)
+    shear_response(resdict, step=0.01, key='g') -> {'g', 'R', 'flags'[, 'Rpsf']}
+    mean_shear(resp, select=None, psf_g=None) -> (2,)
     metacal_bootstrap(obs, runner, psf_runner=None, ...), MetacalBootstrapper
     metacal_bootstrap_many(list_of_obs, model='gauss', ...)
+    (psf= and types= go through all of them to MetacalBatch / get_all_metacal)
 
 and the pre-psf moments of the five types straight from the stamps, without
 the images ("metacal pre-psf moments"; csrc/prepsf_shear.hip):
@@ -47,10 +49,23 @@ With noise_seed the fixnoise field is drawn on the device as a pure function
 of (seed, object id, pixel) (csrc/metacal_noise.hip): the same object gets the
 same field however the catalogue is cut into batches.
 
-psf='fitgauss' and an explicit target_sigma are served.  psf='gauss',
-'azgauss', 'dilate' and galsim-object psfs are defined through galsim's stepk
-and interpolated images and raise NotImplementedError; so does shearing the
-psf (the `*_psf` types).
+psf='fitgauss' and an explicit target_sigma are served: a round gaussian
+target, the five types.  psf='dilate-exact' is the reference's Metacal base
+class (its psf='dilate') under this module's interpolant: the target is the psf
+stamp's own image, deconvolved from the pixel, dilated by 1 + 2|g| and
+reconvolved with the pixel -- the psf stamp's transform at one more frequency
+per mode, nothing fitted, no METACAL_PSF_FIT_FAILURE ("the psf's own
+dilated, sheared image as target").  Under it, and under it alone, get_all
+takes all nine METACAL_TYPES: for `1p_psf, 1m_psf, 2p_psf, 2m_psf` the image is
+left alone and the target psf is dilated and sheared (get_obs_psfshear), and
+
+    shear_response(resdict) -> {..., 'Rpsf'}   with the four `*_psf` types
+    mean_shear(resp, psf_g=(N, 2))             <R> gamma = <g> - <Rpsf psf_g>
+
+psf='gauss', 'azgauss', 'dilate' and galsim-object psfs are defined through
+galsim's stepk and interpolated images and raise NotImplementedError; so does
+shearing the psf (the `*_psf` types) under every psf but 'dilate-exact', and in
+the pre-psf moments, which have no target psf to shear.
 """
 import numpy as np
 
@@ -66,8 +81,10 @@ __all__ = ["MetacalBatch", "get_all_metacal", "METACAL_TYPES", "METACAL_MINIMAL_
            "metacal_moments_batch", "metacal_moments_many"]
 
 METACAL_MINIMAL_TYPES = ["noshear", "1p", "1m", "2p", "2m"]
-METACAL_TYPES = METACAL_MINIMAL_TYPES
+METACAL_PSF_TYPES = ["1p_psf", "1m_psf", "2p_psf", "2m_psf"]
+METACAL_TYPES = METACAL_MINIMAL_TYPES + METACAL_PSF_TYPES     # all served by psf='dilate-exact'
 DEFAULT_STEP = 0.01
+DILATE_EXACT = "dilate-exact"
 
 # per-stamp flags of the outputs
 METACAL_PSF_FIT_FAILURE = 1     # the adaptive moments of the psf stamp failed
@@ -84,25 +101,37 @@ def _torch():
 
 def _check_psf_kind(psf):
     if isinstance(psf, str):
-        if psf == "fitgauss":
+        if psf in ("fitgauss", DILATE_EXACT):
             return
         if psf in ("gauss", "azgauss", "dilate"):
             raise NotImplementedError(
                 "metacal psf='%s' is defined through galsim's stepk and interpolated images; "
-                "use psf='fitgauss' or an explicit target_sigma" % psf)
+                "use psf='fitgauss', psf='dilate-exact' or an explicit target_sigma" % psf)
         raise ValueError("bad metacal psf: '%s'" % psf)
     raise NotImplementedError(
-        "a galsim object as the metacal psf needs galsim's interpolants; use psf='fitgauss' "
-        "or an explicit target_sigma")
+        "a galsim object as the metacal psf needs galsim's interpolants; use psf='fitgauss', "
+        "psf='dilate-exact' or an explicit target_sigma")
 
 
-def _check_types(types):
+def _check_types(types, psf="fitgauss"):
+    """the list of types; the `*_psf` types only under psf='dilate-exact' (psf
+    None: the pre-psf moments, which have no target psf)"""
     if types is None:
         return list(METACAL_MINIMAL_TYPES)
     types = list(types)
+    dilate = isinstance(psf, str) and psf == DILATE_EXACT
     for t in types:
-        if isinstance(t, str) and t.endswith("_psf") and t[:-4] in METACAL_MINIMAL_TYPES[1:]:
-            raise NotImplementedError("metacal type '%s': shearing the psf is not served" % t)
+        if isinstance(t, str) and t in METACAL_PSF_TYPES:
+            if dilate:
+                continue
+            if psf is None:
+                raise NotImplementedError(
+                    "metacal type '%s': shearing the psf is not served by the pre-psf moments, "
+                    "which have no target psf to shear; the images of psf='dilate-exact' "
+                    "serve it" % t)
+            raise NotImplementedError(
+                "metacal type '%s': shearing the psf is not served under this psf; "
+                "psf='dilate-exact' serves it" % t)
         if t not in METACAL_MINIMAL_TYPES:
             raise ValueError("bad metacal type: %s" % (t,))
     return types
@@ -111,7 +140,13 @@ def _check_types(types):
 def _type_shears(types, step):
     table = {"noshear": (0.0, 0.0), "1p": (step, 0.0), "1m": (-step, 0.0),
              "2p": (0.0, step), "2m": (0.0, -step)}
-    return np.array([table[t] for t in types], dtype=np.float64).reshape(len(types), 2)
+    return np.array([table[t[:-4] if t.endswith("_psf") else t] for t in types],
+                    dtype=np.float64).reshape(len(types), 2)
+
+
+def _type_kinds(types):
+    """1 where the type shears the psf, 0 where it shears the image"""
+    return np.array([1 if t in METACAL_PSF_TYPES else 0 for t in types], dtype=np.int32)
 
 
 def _check_shears(g):
@@ -168,7 +203,15 @@ class MetacalBatch(object):
         moments fail is flagged METACAL_PSF_FIT_FAILURE and its outputs are
         NaN.  (The reference falls back to an LM fit of a gaussian, then to a
         stored gmix; that fallback is not made here.)
-    target_sigma: (N,) widths used instead of the fit.
+        'dilate-exact' -- the target is the psf stamp's own image, deconvolved
+        from the pixel, dilated (and, in the `*_psf` types and
+        get_obs_psfshear, sheared) and reconvolved with the pixel: the
+        reference's Metacal base class.  Nothing is fitted: fit_flags stay
+        zero and target_sigma is None.  get_all gives every type, noshear
+        included, the dilation 1 + 2 step; the per-stamp calls 1 + 2|g|.  The
+        output psf stamps keep the input psf stamps' jacobians and centres.
+    target_sigma: (N,) widths used instead of the fit (a ValueError with
+        psf='dilate-exact').
     rng: np.random.RandomState for the fit's starting points and for the noise
         fields of fixnoise.
 
@@ -177,6 +220,9 @@ class MetacalBatch(object):
     """
 
     def __init__(self, stamps, psf_stamps, psf="fitgauss", target_sigma=None, rng=None):
+        self.dilate = isinstance(psf, str) and psf == DILATE_EXACT
+        if self.dilate and target_sigma is not None:
+            raise ValueError("psf='dilate-exact' has no gaussian target: do not send target_sigma")
         if target_sigma is None:
             _check_psf_kind(psf)
         from .batch import StampBatch
@@ -197,6 +243,9 @@ class MetacalBatch(object):
         self._psf_cen = psf_stamps.jac[:, 0:2].contiguous()
         self._psf_flux = psf_stamps.val.reshape(self.n, -1).sum(dim=1).contiguous()
         self.fit_flags = np.zeros(self.n, dtype=np.int32)
+        if self.dilate:
+            self.target_sigma = self._sigma = None
+            return
         if target_sigma is not None:
             sigma = np.ascontiguousarray(target_sigma, dtype=np.float64)
             if sigma.shape != (self.n,):
@@ -302,11 +351,13 @@ class MetacalBatch(object):
         _lib.check(st, "ngmix_metacal_noise_batch")
         return out
 
-    def _run(self, g, per_stamp, noise):
+    def _run(self, g, per_stamp, noise, dil=None, kind=None):
         """
         g: (T, 2), or (N, T, 2) with per_stamp; noise: (N, R, C) device tensor,
-        a DeviceNoise (drawn here, already turned) or None.  Returns the images (T, N, R, C), the target psf images
-        (T, N, Rp, Cp) and the flags (T, N), all on the device.
+        a DeviceNoise (drawn here, already turned) or None.  With
+        psf='dilate-exact', dil (float64) and kind (int32: 1 where the psf is
+        sheared), both (T,) or (N, T).  Returns the images (T, N, R, C), the
+        target psf images (T, N, Rp, Cp) and the flags (T, N), all on the device.
         """
         torch = _torch()
         from .batch import _dptr, _stream, _on_device
@@ -315,6 +366,13 @@ class MetacalBatch(object):
         g = np.ascontiguousarray(g, dtype=np.float64)
         _check_shears(g)
         d_g = torch.from_numpy(g).to(self.device)
+        if self.dilate:
+            dil = np.ascontiguousarray(dil, dtype=np.float64)
+            kind = np.ascontiguousarray(kind, dtype=np.int32)
+            if dil.shape != g.shape[:-1] or kind.shape != g.shape[:-1]:
+                raise ValueError("one dilation and one kind per shear")
+            d_dil, d_kind = torch.from_numpy(dil).to(self.device), \
+                torch.from_numpy(kind).to(self.device)
         planes = 1 if noise is None else 2
         d_noise = None
         if noise is not None:
@@ -331,13 +389,33 @@ class MetacalBatch(object):
         images = self.stamps.val.reshape(n, nrow, ncol)
         if not images.is_contiguous():
             images = images.contiguous()
-        with _on_device(self.device):
-            st = _lib.lib().ngmix_metacal_spectrum_batch(
-                _dptr(images), _dptr(d_noise), _dptr(self.psf_stamps.val), _dptr(self.stamps.jac),
-                _dptr(self._psf_cen), _dptr(self._psf_flux), _dptr(self._sigma), _dptr(d_g),
-                _lib.ptr(g), int(per_stamp), n, ntypes, nrow, ncol, prow, pcol, _dptr(spec),
-                _dptr(kflags), _stream())
-        _lib.check(st, "ngmix_metacal_spectrum_batch")
+        if self.dilate:
+            pspec = torch.empty((n, ntypes, prow, pcol // 2 + 1, 2), dtype=torch.float64,
+                                device=self.device)
+            pflags = torch.empty((n, ntypes), dtype=torch.int32, device=self.device)
+            with _on_device(self.device):
+                L = _lib.lib()
+                st = L.ngmix_metacal_dilate_spectrum_batch(
+                    _dptr(images), _dptr(d_noise), _dptr(self.psf_stamps.val),
+                    _dptr(self.stamps.jac), _dptr(self._psf_cen), _dptr(d_g), _dptr(d_dil),
+                    _dptr(d_kind), _lib.ptr(g), _lib.ptr(dil), _lib.ptr(kind), int(per_stamp), n,
+                    ntypes, nrow, ncol, prow, pcol, _dptr(spec), _dptr(kflags), _stream())
+                _lib.check(st, "ngmix_metacal_dilate_spectrum_batch")
+                st = L.ngmix_metacal_dilate_psf_spectrum_batch(
+                    _dptr(self.psf_stamps.val), _dptr(self.psf_stamps.jac), _dptr(self._psf_cen),
+                    _dptr(d_g), _dptr(d_dil), _dptr(d_kind), _lib.ptr(g), _lib.ptr(dil),
+                    _lib.ptr(kind), int(per_stamp), n, ntypes, prow, pcol, _dptr(pspec),
+                    _dptr(pflags), _stream())
+                _lib.check(st, "ngmix_metacal_dilate_psf_spectrum_batch")
+            kflags = kflags | pflags
+        else:
+            with _on_device(self.device):
+                st = _lib.lib().ngmix_metacal_spectrum_batch(
+                    _dptr(images), _dptr(d_noise), _dptr(self.psf_stamps.val),
+                    _dptr(self.stamps.jac), _dptr(self._psf_cen), _dptr(self._psf_flux),
+                    _dptr(self._sigma), _dptr(d_g), _lib.ptr(g), int(per_stamp), n, ntypes, nrow,
+                    ncol, prow, pcol, _dptr(spec), _dptr(kflags), _stream())
+            _lib.check(st, "ngmix_metacal_spectrum_batch")
         # the regular-grid inverse transform (rocFFT); the spectrum is
         # hermitian on its Nyquist row and column, where a complex-to-real
         # transform would otherwise drop what does not fit
@@ -352,7 +430,12 @@ class MetacalBatch(object):
         out = torch.where(flags[:, :, None, None] != 0, nan, out)
         out = out.permute(1, 0, 2, 3).contiguous()
         flags = flags.t().contiguous()
-        psf_images = self._target_psf_images(g, per_stamp)
+        if self.dilate:
+            # (the same inverse transform on the psf stamps' own grid)
+            psf_images = torch.fft.irfft2(torch.view_as_complex(pspec), s=(prow, pcol))
+            psf_images = psf_images.permute(1, 0, 2, 3).contiguous()
+        else:
+            psf_images = self._target_psf_images(g, per_stamp)
         psf_images = torch.where(flags[:, :, None, None] != 0, nan, psf_images)
         return out, psf_images, flags
 
@@ -395,7 +478,9 @@ class MetacalBatch(object):
                          npix_kept=s.npix_kept,
                          uniform_ierr=(s.flags & _lib.STAMP_UNIFORM_IERR) != 0)
         pizw = (p.flags & _lib.STAMP_IGNORE_ZERO_WEIGHT) != 0
-        pout = StampBatch(psf_images.reshape(-1), p.ierr, self._psf_jacobians(), p.nrow, p.ncol,
+        # (the dilated psf stays where the psf stamp has it: the base class's _make_psf_obs)
+        pjac = p.jac if self.dilate else self._psf_jacobians()
+        pout = StampBatch(psf_images.reshape(-1), p.ierr, pjac, p.nrow, p.ncol,
                           p.pix_off, pizw, npix_kept=p.npix_kept,
                           uniform_ierr=(p.flags & _lib.STAMP_UNIFORM_IERR) != 0)
         return out, pout
@@ -404,7 +489,10 @@ class MetacalBatch(object):
         """
         {type: {'stamps': StampBatch, 'psf_stamps': StampBatch, 'flags': (N,)
         int32 array}} for types of METACAL_MINIMAL_TYPES (default: all five),
-        all in one launch; noshear is the same path at g = 0.
+        all in one launch; noshear is the same path at g = 0.  With
+        psf='dilate-exact' the types of METACAL_TYPES, the four `*_psf` too (the
+        default stays the five); every type, noshear included, has the target
+        psf dilated by 1 + 2 step, as the reference draws noshear with 1p's psf.
 
         fixnoise: a noise stamp per image -- `noise` ((N, R, C) array or device
         tensor), or drawn from the weights with the batch's rng -- is turned by
@@ -412,14 +500,18 @@ class MetacalBatch(object):
         back by k=3 and added; the weight becomes 1 / (1/w + 1/w) where w > 0.
         Square stamps only.
         """
-        types = _check_types(types)
+        types = _check_types(types, DILATE_EXACT if self.dilate else "fitgauss")
         g = _type_shears(types, float(step))
         _check_shears(g)
         if fixnoise and self.shape[0] != self.shape[1]:
             raise ValueError("fixnoise turns the noise stamp by 90 degrees: the stamps must be "
                              "square, got %d x %d" % self.shape)
         planes = self._noise_planes(noise) if fixnoise else None
-        images, psf_images, flags = self._run(g, False, planes)
+        if self.dilate:
+            dil = np.full(len(types), 1.0 + 2.0 * abs(float(step)))
+            images, psf_images, flags = self._run(g, False, planes, dil, _type_kinds(types))
+        else:
+            images, psf_images, flags = self._run(g, False, planes)
         flags = flags.cpu().numpy()
         out = {}
         for i, t in enumerate(types):
@@ -430,9 +522,28 @@ class MetacalBatch(object):
     def get_obs_galshear(self, g1, g2):
         """the images sheared by (g1[i], g2[i]), one shear per stamp: a dict
         as one entry of get_all's"""
+        return self._per_stamp_shear(g1, g2, 0)
+
+    def get_obs_psfshear(self, g1, g2):
+        """psf='dilate-exact': the images left unsheared and reconvolved with
+        the psf dilated by 1 + 2|g| and sheared by (g1[i], g2[i]), one shear
+        per stamp (the reference's Metacal.get_obs_psfshear): a dict as one
+        entry of get_all's"""
+        if not self.dilate:
+            raise NotImplementedError("get_obs_psfshear: shearing the psf is not served under "
+                                      "this psf; psf='dilate-exact' serves it")
+        return self._per_stamp_shear(g1, g2, 1)
+
+    def _per_stamp_shear(self, g1, g2, kind):
         g = np.stack([np.broadcast_to(np.asarray(g1, dtype=np.float64), (self.n,)),
                       np.broadcast_to(np.asarray(g2, dtype=np.float64), (self.n,))], axis=1)
-        images, psf_images, flags = self._run(g.reshape(self.n, 1, 2), True, None)
+        g = g.reshape(self.n, 1, 2)
+        if self.dilate:
+            dil = 1.0 + 2.0 * np.sqrt(g[..., 0] ** 2 + g[..., 1] ** 2)
+            images, psf_images, flags = self._run(g, True, None, dil,
+                                                  np.full((self.n, 1), kind, dtype=np.int32))
+        else:
+            images, psf_images, flags = self._run(g, True, None)
         sb, psb = self._stamp_batches(images[0], psf_images[0], False)
         return {"stamps": sb, "psf_stamps": psb, "flags": flags[0].cpu().numpy()}
 
@@ -476,7 +587,11 @@ def get_all_metacal(obs, psf="fitgauss", step=DEFAULT_STEP, types=None, fixnoise
 
     obs: Observation, ObsList or MultiBandObsList; every Observation has a psf
         Observation with the same jacobian derivatives
-    psf: 'fitgauss' (the default here; 'gauss', 'azgauss', 'dilate' and galsim
+    psf: 'fitgauss' (the default here), or 'dilate-exact': the psf's own
+        dilated image as the target (MetacalBatch), which also serves the
+        `*_psf` types; its psf observations get the new image and keep their
+        jacobian and weight, no psf noise is added, and rng is needed only to
+        draw a fixnoise field.  ('gauss', 'azgauss', 'dilate' and galsim
         objects raise NotImplementedError: they rest on galsim)
     fixnoise: add the sheared, rotated noise field and halve the weights
         (_get_all_metacal_fixnoise); the noise field is obs.noise with
@@ -490,9 +605,13 @@ def get_all_metacal(obs, psf="fitgauss", step=DEFAULT_STEP, types=None, fixnoise
     differs (see the top of this module).
     """
     _check_psf_kind(psf)
-    types = _check_types(types)
+    types = _check_types(types, psf)
     flat, rebuild = _flatten(obs)
-    if rng is None:
+    dilate = psf == DILATE_EXACT
+    if rng is None and dilate and fixnoise and not use_noise_image:
+        raise ValueError("send an rng to get_all_metacal: psf='dilate-exact' draws the "
+                         "fixnoise field with it")
+    if rng is None and not dilate:
         raise ValueError("send an rng to get_all_metacal (psf='fitgauss')")
     for o in flat:
         if not o.has_psf():
@@ -524,25 +643,32 @@ def get_all_metacal(obs, psf="fitgauss", step=DEFAULT_STEP, types=None, fixnoise
             pims = res[t]["psf_stamps"].val.reshape((len(sub),) + pshape).cpu().numpy()
             for k, i in enumerate(idx):
                 new[t][i] = _make_obs(sub[k], ims[k], pims[k], int(res[t]["flags"][k]),
-                                      fixnoise, rng)
+                                      fixnoise, rng, dilate)
     return {t: rebuild(new[t]) for t in types}
 
 
-def _make_obs(obs, image, psf_image, flags, fixnoise, rng):
+def _make_obs(obs, image, psf_image, flags, fixnoise, rng, dilate=False):
     """a copy of obs with the metacal image and the target psf (_make_obs,
-    _make_psf_obs and, with fixnoise, _doadd_single_obs of the reference)"""
+    _make_psf_obs and, with fixnoise, _doadd_single_obs of the reference);
+    dilate: the base class's psf observation -- the new image, the psf's own
+    jacobian and weight, no noise added"""
     pim = obs.psf.image
-    psf_noise = pim.max() / 50000.0
-    psf_image = psf_image + rng.normal(size=pim.shape, scale=psf_noise)
     new_psf = obs.psf.copy()
-    with new_psf.writeable():
-        new_psf.image[:, :] = psf_image
-        new_psf.weight[:, :] = pim * 0 + 1.0 / psf_noise ** 2
-    # the centre goes where the target psf was drawn: the stamp's exact centre
-    jac = new_psf.jacobian
-    new_psf.jacobian = Jacobian(row=(pim.shape[0] - 1.0) / 2.0, col=(pim.shape[1] - 1.0) / 2.0,
-                                dvdrow=jac.dvdrow, dvdcol=jac.dvdcol, dudrow=jac.dudrow,
-                                dudcol=jac.dudcol)
+    if dilate:
+        with new_psf.writeable():
+            new_psf.image[:, :] = psf_image
+    else:
+        psf_noise = pim.max() / 50000.0
+        psf_image = psf_image + rng.normal(size=pim.shape, scale=psf_noise)
+        with new_psf.writeable():
+            new_psf.image[:, :] = psf_image
+            new_psf.weight[:, :] = pim * 0 + 1.0 / psf_noise ** 2
+        # the centre goes where the target psf was drawn: the stamp's exact centre
+        jac = new_psf.jacobian
+        new_psf.jacobian = Jacobian(row=(pim.shape[0] - 1.0) / 2.0,
+                                    col=(pim.shape[1] - 1.0) / 2.0,
+                                    dvdrow=jac.dvdrow, dvdcol=jac.dvdcol, dudrow=jac.dudrow,
+                                    dudcol=jac.dudcol)
     new = obs.copy()
     if fixnoise:
         # (the image before the noise field was added stays on the device: only
@@ -579,6 +705,8 @@ def metacal_bootstrap_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP
         get_all does
     rng: np.random.RandomState of the psf fits' and the guesses' starting
         points (and of the host noise draw)
+    psf, types: as MetacalBatch and get_all take them; psf='dilate-exact' with
+        types=METACAL_TYPES gives the nine fits shear_response makes 'Rpsf' of
 
     Returns (resdict, batchdict): resdict[type] is bootstrap_batch's dict with
     'mcal_flags', the type's metacal flags (N,), added; batchdict is get_all's
@@ -627,6 +755,12 @@ def shear_response(resdict, step=DEFAULT_STEP, key="g"):
     (res[jp][key][:, i] - res[jm][key][:, i]) / (2 step), 'flags': (N,) the OR
     of the five types' fit flags and metacal flags}; the rows of flagged
     objects are NaN.
+
+    When resdict also holds all four of `1p_psf, 1m_psf, 2p_psf, 2m_psf`
+    (psf='dilate-exact'), the dict has 'Rpsf' too, the psf response (N, 2, 2)
+    with Rpsf[:, i, j] = (res[jp_psf][key][:, i] - res[jm_psf][key][:, i]) /
+    (2 step), and their flags are ORed in.  With fewer of them the dict is the
+    one above.
     """
     step = float(step)
     if not step > 0:
@@ -637,14 +771,17 @@ def shear_response(resdict, step=DEFAULT_STEP, key="g"):
     g0 = _response_column(resdict["noshear"], key)
     n = g0.shape[0]
     flags = np.zeros(n, dtype=np.int64)
-    for t in METACAL_MINIMAL_TYPES:
+
+    def _or_flags(t):
         res = resdict[t]
         for k in ("flags", "mcal_flags"):
             if k in res:
                 f = np.asarray(res[k])
                 if f.shape != (n,):
                     raise ValueError("type '%s': '%s' must be (%d,)" % (t, k, n))
-                flags |= f.astype(np.int64)
+                flags[:] |= f.astype(np.int64)
+    for t in METACAL_MINIMAL_TYPES:
+        _or_flags(t)
     R = np.empty((n, 2, 2))
     for j in (0, 1):
         p = _response_column(resdict["%dp" % (j + 1)], key)
@@ -652,20 +789,47 @@ def shear_response(resdict, step=DEFAULT_STEP, key="g"):
         if p.shape != g0.shape or m.shape != g0.shape:
             raise ValueError("the five types must hold the same objects")
         R[:, :, j] = (p - m) / (2.0 * step)
+    Rpsf = None
+    if all(t in resdict for t in METACAL_PSF_TYPES):
+        for t in METACAL_PSF_TYPES:
+            _or_flags(t)
+        Rpsf = np.empty((n, 2, 2))
+        for j in (0, 1):
+            p = _response_column(resdict["%dp_psf" % (j + 1)], key)
+            m = _response_column(resdict["%dm_psf" % (j + 1)], key)
+            if p.shape != g0.shape or m.shape != g0.shape:
+                raise ValueError("the psf-sheared types must hold the same objects")
+            Rpsf[:, :, j] = (p - m) / (2.0 * step)
     g = g0.copy()
     bad = flags != 0
     g[bad] = np.nan
     R[bad] = np.nan
-    return {"g": g, "R": R, "flags": flags}
+    out = {"g": g, "R": R, "flags": flags}
+    if Rpsf is not None:
+        Rpsf[bad] = np.nan
+        out["Rpsf"] = Rpsf
+    return out
 
 
-def mean_shear(resp, select=None):
+def mean_shear(resp, select=None, psf_g=None):
     """
     <g> <R>^-1 over the unflagged objects of shear_response's dict -- the
     solution of <R> gamma = <g> with the 2 x 2 mean response -- and, with
     `select` (a boolean mask or an index array), over the selected ones of
     them.  No selection response is applied.
+
+    psf_g: (N, 2) psf shapes; with the psf response 'Rpsf' of the dict (the
+    four `*_psf` types, psf='dilate-exact') the psf leakage is taken out first:
+    <R> gamma = <g> - <Rpsf psf_g> over the same objects.  A ValueError
+    without 'Rpsf'.
     """
+    if psf_g is not None:
+        if "Rpsf" not in resp:
+            raise ValueError("mean_shear: psf_g needs the psf response 'Rpsf' of the four "
+                             "`*_psf` types (psf='dilate-exact')")
+        psf_g = np.asarray(psf_g, dtype=np.float64)
+        if psf_g.shape != np.asarray(resp["g"]).shape:
+            raise ValueError("psf_g must be (N, 2), got %s" % (psf_g.shape,))
     flags = np.asarray(resp["flags"])
     use = flags == 0
     if select is not None:
@@ -680,7 +844,10 @@ def mean_shear(resp, select=None):
         use = use & mask
     if not use.any():
         raise ValueError("mean_shear: no unflagged object is selected")
-    return np.linalg.solve(resp["R"][use].mean(axis=0), resp["g"][use].mean(axis=0))
+    rhs = resp["g"][use].mean(axis=0)
+    if psf_g is not None:
+        rhs = rhs - np.einsum("nij,nj->ni", resp["Rpsf"][use], psf_g[use]).mean(axis=0)
+    return np.linalg.solve(resp["R"][use].mean(axis=0), rhs)
 
 
 def _moments_measure(measure):
@@ -725,7 +892,7 @@ def metacal_moments_batch(stamps, psf_stamps, measure, step=DEFAULT_STEP, types=
     from .prepsfmom import _fixnoise_source
     noise = _fixnoise_source(fixnoise, noise, noise_seed, ids)
     _moments_measure(measure)
-    types = _check_types(types)
+    types = _check_types(types, None)
     if not isinstance(stamps, StampBatch) or not isinstance(psf_stamps, StampBatch):
         raise ValueError("stamps and psf_stamps must be StampBatch objects")
     if stamps.n != psf_stamps.n:
@@ -769,7 +936,7 @@ def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fi
     from .prepsfmom import _check_obs_and_get_psf_obs, _fixnoise_source
     seeded = _fixnoise_source(fixnoise, None, noise_seed, ids, use_noise_image)
     _moments_measure(measure)
-    types = _check_types(types)
+    types = _check_types(types, None)
     list_of_obs = list(list_of_obs)
     if ids is not None:
         ids = np.ascontiguousarray(ids, dtype=np.int64)

@@ -694,7 +694,7 @@ class PrePSFMom(object):
         from .metacal import _check_types, _type_shears
         from .moments import make_mom_result_batch
         noise = _fixnoise_source(fixnoise, noise, noise_seed, ids)
-        types = _check_types(types)
+        types = _check_types(types, None)
         g = _type_shears(types, float(step))
         mom, cov, flags, kernels, _ = self.measure_arrays_sheared(
             images, weights, cen, deriv, psf_images, psf_cen, g, noise=noise,

@@ -21,8 +21,16 @@ and largest of the repeats beside every median.  With --fixnoise also the
 fixnoise form: its kernel alone on a turned noise plane, and
 metacal_moments_batch(fixnoise=True, noise_seed=...) end to end.
 
+--psf dilate-exact adds, after every row of the gaussian target and in the same
+run, the rows of psf='dilate-exact'  with the five and with the
+nine types: whole get_all calls, the two spectrum kernels alone (the images',
+and the target psf's on the psf stamp's grid), and the image kernel's FMA rate
+by the count of 3.19 plus (4 + 2) Rp Cp per work item for the psf's second
+transform.
+
 usage: python tools/time_metacal.py [--n 100000] [--repeats 7] [--warmup 2]
-                                    [--noise | --moments [--fixnoise]]
+                                    [--noise | --moments [--fixnoise] |
+                                     --psf dilate-exact]
 """
 import argparse
 import json
@@ -44,6 +52,13 @@ def fma_count(dim, planes):
     return items * dim * dim * (4 + 2 * planes)
 
 
+def dilate_fma_count(dim, pdim, planes):
+    """fma_count plus the psf plane's transform at the target frequency, with a
+    recurrence of its own: (4 + 2) Rp Cp per work item"""
+    items = dim * (dim // 2 + 1) + (dim // 2 + 1) + dim - 1
+    return fma_count(dim, planes) + items * pdim * pdim * (4 + 2)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=100000)
@@ -59,6 +74,10 @@ def main():
     ap.add_argument("--fixnoise", action="store_true",
                     help="with --moments: also the fixnoise kernel alone and "
                          "metacal_moments_batch(fixnoise=True, noise_seed=...)")
+    ap.add_argument("--psf", choices=["fitgauss", "dilate-exact"], default="fitgauss",
+                    help="dilate-exact: after each row of the gaussian target, the same "
+                         "configuration with the psf's own dilated image as the target, five "
+                         "and nine types")
     args = ap.parse_args()
     import torch
     from ngmix_amd import metacal
@@ -137,6 +156,24 @@ def main():
                 "kernel_fma_per_s": fma / kernel,
                 "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S,
             }), flush=True)
+            if args.psf != "dilate-exact":
+                continue
+            md = metacal.MetacalBatch(sb, psb, psf="dilate-exact", rng=np.random.RandomState(dim))
+            for types in (metacal.METACAL_MINIMAL_TYPES, metacal.METACAL_TYPES):
+                nt = len(types)
+                total = timed(lambda: md.get_all(types=types, fixnoise=fixnoise,
+                                                 noise=noise if fixnoise else None))
+                kernel = timed(lambda: _dilate_spectrum_only(md, types, noise if fixnoise else None,
+                                                             False))
+                pkernel = timed(lambda: _dilate_spectrum_only(md, types, None, True))
+                fma = dilate_fma_count(dim, dim, planes) * nt * n
+                print(json.dumps({
+                    "psf": "dilate-exact", "stamp": dim, "n": n, "fixnoise": fixnoise,
+                    "types": nt, "stamps_per_s": n / total, "total_ms": total * 1e3,
+                    "spectrum_kernel_ms": kernel * 1e3, "psf_spectrum_kernel_ms": pkernel * 1e3,
+                    "rest_ms": (total - kernel - pkernel) * 1e3, "kernel_fma_per_s": fma / kernel,
+                    "fraction_of_fp64_vector_fma_peak": fma / kernel / FP64_VECTOR_FMA_PER_S,
+                }), flush=True)
 
 
 def _moments(mc, sb, psb, dim, scale, timed, fixnoise=False):
@@ -238,6 +275,40 @@ def _spectrum_only(mc, g, noise):
         _dptr(mc._psf_cen), _dptr(mc._psf_flux), _dptr(mc._sigma), _dptr(d_g), _lib.ptr(g), 0, n,
         5, nrow, ncol, prow, pcol, _dptr(spec), _dptr(flags), _stream())
     _lib.check(st, "ngmix_metacal_spectrum_batch")
+
+
+def _dilate_spectrum_only(mc, types, noise, psf_only):
+    """the launch of MetacalBatch._run for psf='dilate-exact': the images' spectra,
+    or with psf_only the target psf's on the psf stamp's grid"""
+    import torch
+    from ngmix_amd import _lib, metacal
+    from ngmix_amd.batch import _dptr, _stream
+    n, (nrow, ncol), (prow, pcol) = mc.n, mc.shape, mc.psf_shape
+    nt = len(types)
+    planes = 1 if noise is None else 2
+    key = ("dilate", nt, planes, psf_only)
+    if not hasattr(mc, "_time_bufs") or mc._time_bufs[0] != key:
+        g = metacal._type_shears(types, 0.01)
+        dil = np.full(nt, 1.02)
+        kind = metacal._type_kinds(types)
+        shape = (n, nt, prow, pcol // 2 + 1, 2) if psf_only else \
+            (n, nt, planes, nrow, ncol // 2 + 1, 2)
+        mc._time_bufs = (key, torch.empty(shape, dtype=torch.float64, device=mc.device),
+                         torch.empty((n, nt), dtype=torch.int32, device=mc.device), (g, dil, kind),
+                         [torch.from_numpy(a).to(mc.device) for a in (g, dil, kind)])
+    _, spec, flags, (g, dil, kind), (d_g, d_dil, d_kind) = mc._time_bufs
+    L = _lib.lib()
+    if psf_only:
+        st = L.ngmix_metacal_dilate_psf_spectrum_batch(
+            _dptr(mc.psf_stamps.val), _dptr(mc.psf_stamps.jac), _dptr(mc._psf_cen), _dptr(d_g),
+            _dptr(d_dil), _dptr(d_kind), _lib.ptr(g), _lib.ptr(dil), _lib.ptr(kind), 0, n, nt, prow,
+            pcol, _dptr(spec), _dptr(flags), _stream())
+    else:
+        st = L.ngmix_metacal_dilate_spectrum_batch(
+            _dptr(mc.stamps.val), _dptr(noise), _dptr(mc.psf_stamps.val), _dptr(mc.stamps.jac),
+            _dptr(mc._psf_cen), _dptr(d_g), _dptr(d_dil), _dptr(d_kind), _lib.ptr(g), _lib.ptr(dil),
+            _lib.ptr(kind), 0, n, nt, nrow, ncol, prow, pcol, _dptr(spec), _dptr(flags), _stream())
+    _lib.check(st, "ngmix_metacal_dilate_spectrum_batch")
 
 
 if __name__ == "__main__":
