@@ -7,8 +7,16 @@
 //
 // One work-group per stamp.  Both are compute-bound: the stamp
 // is read from HBM once and the iteration runs on chip.
+//
+// Adaptive moments has two kernel bodies here -- streaming (admom_list_kernel,
+// admom_grid_kernel<256, 0>) and register-resident (every other
+// admom_grid_kernel<NT, PPT>) -- which own the pixel passes, the reductions
+// and the covariance.  What is decided from the sums (admom(), deweight_moments
+// and the effect of clear_result on the record) is admom_step.hpp's, one text
+// that both bodies call.
 #include <stdio.h>
 
+#include "admom_step.hpp"
 #include "iter_common.hpp"
 #include "launch_iter.hpp"
 #include "launch_util.hpp"
@@ -686,65 +694,20 @@ int launch_weighted_sums_list(const ngmix_gauss2d *wt, int ng,
 // once, after the loop, for the weight and centre of the last moments pass
 // executed -- the same per-pixel terms the reference's last pass adds, so the
 // result record is the same while the hot loop does ~1/3 of the flops.
-// Scalar iteration logic (admom_nb.py:33-108) runs on thread 0 out of LDS.
+// The scalar iteration logic (admom_nb.py:33-108) is admom_step.hpp's, ONE text
+// for both bodies below: here thread 0 runs it on the state in LDS.
 
 struct AdmomShared {
     double tab[16];
     double red_scratch[NWAVES * 64];  // sized for the widest work-group
     double red_out[64];
-    ngmix_gauss2d wt;       // current weight
+    AdmomState st;          // thread 0's; st.wt is read by all between barriers
     ngmix_gauss2d wt_used;  // weight of the last moments pass
-    ngmix_admom_result res;
-    int stop;       // loop exit requested
-    int status;     // C-ABI status (range error / zero division)
-    int mom_ran;    // a moments pass has been executed
-    int res_is_mom; // res.sums currently hold a moments pass
+    double sums[7], wsum;   // of the last pass
+    int npix;
+    int stop;               // thread 0's verdict: the loop ends
     int iscratch[NWAVES + 4];
 };
-
-// clear_result, admom_nb.py:229-239
-__device__ __forceinline__ void admom_clear(ngmix_admom_result &r)
-{
-    r.npix = 0;
-    r.wsum = 0.0;
-    for (int i = 0; i < 7; i++) r.sums[i] = 0.0;
-    for (int i = 0; i < 49; i++) r.sums_cov[i] = 0.0;
-    for (int i = 0; i < 6; i++) r.pars[i] = NAN;
-    r.rho4 = NAN;
-}
-
-// deweight_moments, admom_nb.py:178-226
-__device__ __forceinline__ void admom_deweight(ngmix_gauss2d &wt, double Irr,
-                                               double Irc, double Icc,
-                                               ngmix_admom_result &res)
-{
-    const double detm = Irr * Icc - Irc * Irc;
-    if (detm <= LOW_DETVAL) {
-        res.flags = NGMIX_FLAG_LOW_DET;
-        return;
-    }
-    const double Wrr = wt.irr, Wrc = wt.irc, Wcc = wt.icc;
-    const double detw = Wrr * Wcc - Wrc * Wrc;
-    if (detw <= LOW_DETVAL) {
-        res.flags = NGMIX_FLAG_LOW_DET;
-        return;
-    }
-    const double idetw = 1.0 / detw;
-    const double idetm = 1.0 / detm;
-    const double Nrr = Icc * idetm - Wcc * idetw;
-    const double Ncc = Irr * idetm - Wrr * idetw;
-    const double Nrc = -Irc * idetm + Wrc * idetw;
-    const double detn = Nrr * Ncc - Nrc * Nrc;
-    if (detn <= LOW_DETVAL) {
-        res.flags = NGMIX_FLAG_LOW_DET;
-        return;
-    }
-    const double idetn = 1. / detn;
-    wt.irr = Ncc * idetn;
-    wt.icc = Nrr * idetn;
-    wt.irc = -Nrc * idetn;
-    wt.det = wt.irr * wt.icc - wt.irc * wt.irc;
-}
 
 // NT threads cooperate on one stamp (64, 128 or 256: fewer waves mean fewer
 // reduction instructions and no cross-wave barriers, more waves mean fewer
@@ -771,40 +734,21 @@ __device__ __forceinline__ void admom_body(const Src &src,
     const int has_zero = group_max_int<NT>(my_zero, sh.iscratch);
 
     if (tid < 16) sh.tab[tid] = c_exp_table_m[tid];
-    if (tid == 0) {
-        sh.wt = wt_io[0];
-        sh.res = res_io[0];
-        sh.stop = 0;
-        sh.status = NGMIX_OK;
-        sh.mom_ran = 0;
-        sh.res_is_mom = 0;
-    }
+    if (tid == 0) admom_start(sh.st, wt_io[0], res_io[0].flags);
     __syncthreads();
 
-    const double roworig = sh.wt.row, colorig = sh.wt.col;
-    double e1old = NAN, e2old = NAN, Told = NAN;  // used by thread 0 only
+    const ngmix_gauss2d &wt = sh.st.wt;
     int iter_index = -1;
 
     for (int it = 0; it < conf.maxiter; it++) {
         iter_index = it;
-        if (tid == 0) {
-            if (sh.wt.det < LOW_DETVAL) {
-                sh.res.flags = NGMIX_FLAG_LOW_DET;
-                sh.stop = 1;
-            } else {
-                const int st = gauss_set_norm(sh.wt);
-                if (st) {  // GMixRangeError("T too low") escapes admom()
-                    sh.status = st;
-                    sh.stop = 1;
-                }
-            }
-        }
+        if (tid == 0) sh.stop = admom_begin_iter(sh.st);
         __syncthreads();
         if (sh.stop) break;
 
         // ---- centroid pass (admom_censums, admom_nb.py:111-128)
         {
-            const EvalGauss e = make_eval(sh.wt);
+            const EvalGauss e = make_eval(wt);
             double a[4] = {0.0, 0.0, 0.0, 0.0};
             cache.for_each(src, [&](double v, double u, double area, double val,
                                     double, int) {
@@ -818,36 +762,19 @@ __device__ __forceinline__ void admom_body(const Src &src,
             group_sum<NT, 4>(a, sh.red_scratch, sh.red_out);
         }
         if (tid == 0) {
-            ngmix_admom_result &res = sh.res;
-            admom_clear(res);
-            sh.res_is_mom = 0;
-            res.npix = (int32_t)sh.red_out[3];
-            res.sums[0] = sh.red_out[0];
-            res.sums[1] = sh.red_out[1];
-            res.sums[5] = sh.red_out[2];
-            if (res.sums[5] <= 0.0) {
-                res.flags = NGMIX_FLAG_NONPOS_FLUX;
-                sh.stop = 1;
-            } else {
-                sh.wt.row = res.sums[0] / res.sums[5];
-                sh.wt.col = res.sums[1] / res.sums[5];
-                if (fabs(sh.wt.row - roworig) > conf.shiftmax ||
-                    fabs(sh.wt.col - colorig) > conf.shiftmax) {
-                    res.flags = NGMIX_FLAG_CEN_SHIFT;
-                    sh.stop = 1;
-                } else if (has_zero) {
-                    sh.status = NGMIX_ERR_ZERO_DIV;
-                    sh.stop = 1;
-                }
-            }
+            sh.npix = (int32_t)sh.red_out[3];
+            sh.sums[0] = sh.red_out[0];
+            sh.sums[1] = sh.red_out[1];
+            sh.sums[5] = sh.red_out[2];
+            sh.stop = admom_after_censums(sh.st, conf, sh.sums, has_zero != 0);
         }
         __syncthreads();
         if (sh.stop) break;
 
         // ---- moments pass without the covariance (admom_momsums, :131-175)
         {
-            const EvalGauss e = make_eval(sh.wt);
-            const double vcen = sh.wt.row, ucen = sh.wt.col;
+            const EvalGauss e = make_eval(wt);
+            const double vcen = wt.row, ucen = wt.col;
             double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
             cache.for_each(src, [&](double v, double u, double area, double val,
                                     double, int) {
@@ -869,64 +796,21 @@ __device__ __forceinline__ void admom_body(const Src &src,
             group_sum<NT, 9>(a, sh.red_scratch, sh.red_out);
         }
         if (tid == 0) {
-            ngmix_admom_result &res = sh.res;
-            admom_clear(res);
-            for (int i = 0; i < 7; i++) res.sums[i] = sh.red_out[i];
-            res.wsum = sh.red_out[7];
-            res.npix = (int32_t)sh.red_out[8];
-            sh.wt_used = sh.wt;
-            sh.mom_ran = 1;
-            sh.res_is_mom = 1;
-
-            if (res.sums[5] <= 0.0) {
-                res.flags = NGMIX_FLAG_NONPOS_FLUX;
-                sh.stop = 1;
-            } else {
-                const double finv = 1.0 / res.sums[5];
-                const double M1 = res.sums[2] * finv;
-                const double M2 = res.sums[3] * finv;
-                const double T = res.sums[4] * finv;
-                const double Irr = 0.5 * (T - M1);
-                const double Icc = 0.5 * (T + M1);
-                const double Irc = 0.5 * M2;
-                if (T <= 0.0) {
-                    res.flags = NGMIX_FLAG_NONPOS_SIZE;
-                    sh.stop = 1;
-                } else {
-                    const double e1 = (Icc - Irr) / T;
-                    const double e2 = 2 * Irc / T;
-                    if ((fabs(e1 - e1old) < conf.etol) &&
-                        (fabs(e2 - e2old) < conf.etol) &&
-                        (fabs(T / Told - 1.) < conf.Ttol)) {
-                        res.pars[0] = sh.wt.row;
-                        res.pars[1] = sh.wt.col;
-                        res.pars[2] = sh.wt.icc - sh.wt.irr;
-                        res.pars[3] = 2.0 * sh.wt.irc;
-                        res.pars[4] = sh.wt.icc + sh.wt.irr;
-                        res.pars[5] = 1.0;
-                        res.rho4 = res.sums[6] / res.sums[5];
-                        sh.stop = 1;
-                    } else {
-                        if (!conf.cenonly) {
-                            admom_deweight(sh.wt, Irr, Irc, Icc, res);
-                            if (res.flags != 0) sh.stop = 1;
-                        }
-                        e1old = e1;
-                        e2old = e2;
-                        Told = T;
-                    }
-                }
-            }
+            for (int i = 0; i < 7; i++) sh.sums[i] = sh.red_out[i];
+            sh.wsum = sh.red_out[7];
+            sh.npix = (int32_t)sh.red_out[8];
+            sh.wt_used = wt;  // (the verdict deweights it)
+            sh.stop = admom_after_momsums(sh.st, conf, sh.sums);
         }
         __syncthreads();
         if (sh.stop) break;
     }
 
     // ---- the covariance of the last moments pass, and the F scratch
-    if (sh.mom_ran) {
+    if (sh.st.mom_ran) {
         const EvalGauss e = make_eval(sh.wt_used);
         const double vcen = sh.wt_used.row, ucen = sh.wt_used.col;
-        const bool want_cov = sh.res_is_mom != 0 && sh.status == NGMIX_OK && !conf.no_cov;
+        const bool want_cov = admom_want_cov(sh.st, conf);
         double c[49];
 #pragma unroll
         for (int i = 0; i < 49; i++) c[i] = 0.0;
@@ -945,7 +829,7 @@ __device__ __forceinline__ void admom_body(const Src &src,
             F[6] = chi2 * chi2;
             if (p == last_pos) {
 #pragma unroll
-                for (int i = 0; i < 7; i++) sh.res.F[i] = F[i];
+                for (int i = 0; i < 7; i++) res_io[0].F[i] = F[i];
             }
             if (want_cov) {
                 const double weight = gauss_eval_fast(e, v, u, area, sh.tab);
@@ -972,7 +856,7 @@ __device__ __forceinline__ void admom_body(const Src &src,
                 if (tid == 0) {
                     for (int k = 0; k < 13; k++)
                         if (slab * 13 + k < 49)
-                            sh.res.sums_cov[slab * 13 + k] = sh.red_out[k];
+                            res_io[0].sums_cov[slab * 13 + k] = sh.red_out[k];
                 }
                 __syncthreads();
             }
@@ -981,13 +865,10 @@ __device__ __forceinline__ void admom_body(const Src &src,
     __syncthreads();
 
     if (tid == 0) {
-        // admom_nb.py:105-108.  With maxiter <= 0 the reference's loop
-        // variable is undefined; numiter = 0 is used (=> MAXITER if 0 == maxiter)
-        sh.res.numiter = iter_index + 1;
-        if (sh.res.numiter == conf.maxiter) sh.res.flags = NGMIX_FLAG_MAXITER;
-        res_io[0] = sh.res;
-        wt_io[0] = sh.wt;
-        if (status) *status = sh.status;
+        const int numiter = admom_numiter(sh.st, conf, iter_index);
+        admom_record(sh.st, conf, numiter, sh.npix, sh.wsum, sh.sums, res_io[0]);
+        wt_io[0] = wt;
+        if (status) *status = sh.st.status;
     }
 }
 
@@ -1165,30 +1046,19 @@ __device__ __forceinline__ void admom_fused_body(const GridSrc &src,
     const double area = src.area;
     int phase = 0;
 
-    // ---- uniform iteration state, replicated in every lane
-    ngmix_gauss2d wt = wt_io[0];
-    const double roworig = wt.row, colorig = wt.col;
-    double e1old = NAN, e2old = NAN, Told = NAN;
-    int flags = res_io[0].flags, st = NGMIX_OK;
-    int last_kind = 0;  // 0: no pass ran, 1: centroid pass, 2: moments pass
-    bool mom_ran = false;
+    // ---- uniform iteration state (admom_step.hpp), replicated in every lane:
+    // each verdict is the same in all of them, and branched on as a scalar
+    AdmomState state;
+    admom_start(state, wt_io[0], res_io[0].flags);
+    const ngmix_gauss2d &wt = state.wt;
     int iter_index = -1;
     double sums[7] = {0, 0, 0, 0, 0, 0, 0}, wsum = 0.0;
-    double pars[6] = {NAN, NAN, NAN, NAN, NAN, NAN}, rho4 = NAN;
     double used_row = 0, used_col = 0, used_dcc = 0, used_drr = 0, used_drc2 = 0,
            used_pa = 0;
 
     for (int it = 0; it < conf.maxiter; it++) {
         iter_index = it;
-        if (NGMIX_UNIFORM(wt.det < LOW_DETVAL)) {  // admom_nb.py:40-42
-            flags = NGMIX_FLAG_LOW_DET;
-            break;
-        }
-        const int sn = gauss_set_norm(wt);
-        if (NGMIX_UNIFORM(sn != 0)) {  // GMixRangeError escapes admom()
-            st = sn;
-            break;
-        }
+        if (NGMIX_UNIFORM(admom_begin_iter(state))) break;
         const double dcc = wt.dcc, drr = wt.drr, mdrc2 = -2.0 * wt.drc;
         const double pa = wt.pnorm * area;
 
@@ -1217,29 +1087,11 @@ __device__ __forceinline__ void admom_fused_body(const GridSrc &src,
                 if (ALLCHUNKS) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]));
             }
             group_total<NT, 3>(a, sh.slots, phase);
-            last_kind = 1;
-#pragma unroll
-            for (int i = 0; i < 6; i++) pars[i] = NAN;
-            rho4 = NAN;
             sums[0] = a[0];
             sums[1] = a[1];
             sums[5] = a[2];
         }
-        if (NGMIX_UNIFORM(sums[5] <= 0.0)) {
-            flags = NGMIX_FLAG_NONPOS_FLUX;
-            break;
-        }
-        wt.row = sums[0] / sums[5];
-        wt.col = sums[1] / sums[5];
-        if (NGMIX_UNIFORM(fabs(wt.row - roworig) > conf.shiftmax ||
-                          fabs(wt.col - colorig) > conf.shiftmax)) {
-            flags = NGMIX_FLAG_CEN_SHIFT;
-            break;
-        }
-        if (has_zero) {
-            st = NGMIX_ERR_ZERO_DIV;
-            break;
-        }
+        if (NGMIX_UNIFORM(admom_after_censums(state, conf, sums, has_zero != 0))) break;
 
         // ---- moments pass without the covariance (admom_momsums, :131-175)
         {
@@ -1276,8 +1128,6 @@ __device__ __forceinline__ void admom_fused_body(const GridSrc &src,
                                       "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
             }
             group_total<NT, 8>(a, sh.slots, phase);
-            last_kind = 2;
-            mom_ran = true;
 #pragma unroll
             for (int i = 0; i < 7; i++) sums[i] = a[i];
             wsum = a[7];
@@ -1288,80 +1138,18 @@ __device__ __forceinline__ void admom_fused_body(const GridSrc &src,
             used_drc2 = mdrc2;
             used_pa = pa;
         }
-        if (NGMIX_UNIFORM(sums[5] <= 0.0)) {
-            flags = NGMIX_FLAG_NONPOS_FLUX;
-            break;
-        }
-        {
-            const double finv = 1.0 / sums[5];
-            const double M1 = sums[2] * finv;
-            const double M2 = sums[3] * finv;
-            const double T = sums[4] * finv;
-            const double Irr = 0.5 * (T - M1);
-            const double Icc = 0.5 * (T + M1);
-            const double Irc = 0.5 * M2;
-            if (NGMIX_UNIFORM(T <= 0.0)) {
-                flags = NGMIX_FLAG_NONPOS_SIZE;
-                break;
-            }
-            const double e1 = (Icc - Irr) / T;
-            const double e2 = 2 * Irc / T;
-            if (NGMIX_UNIFORM((fabs(e1 - e1old) < conf.etol) &&
-                              (fabs(e2 - e2old) < conf.etol) &&
-                              (fabs(T / Told - 1.) < conf.Ttol))) {
-                pars[0] = wt.row;
-                pars[1] = wt.col;
-                pars[2] = wt.icc - wt.irr;
-                pars[3] = 2.0 * wt.irc;
-                pars[4] = wt.icc + wt.irr;
-                pars[5] = 1.0;
-                rho4 = sums[6] / sums[5];
-                break;
-            }
-            if (!conf.cenonly) {
-                // deweight_moments, admom_nb.py:178-226
-                const double detm = Irr * Icc - Irc * Irc;
-                if (NGMIX_UNIFORM(detm <= LOW_DETVAL)) {
-                    flags = NGMIX_FLAG_LOW_DET;
-                    break;
-                }
-                const double Wrr = wt.irr, Wrc = wt.irc, Wcc = wt.icc;
-                const double detw = Wrr * Wcc - Wrc * Wrc;
-                if (NGMIX_UNIFORM(detw <= LOW_DETVAL)) {
-                    flags = NGMIX_FLAG_LOW_DET;
-                    break;
-                }
-                const double idetw = 1.0 / detw;
-                const double idetm = 1.0 / detm;
-                const double Nrr = Icc * idetm - Wcc * idetw;
-                const double Ncc = Irr * idetm - Wrr * idetw;
-                const double Nrc = -Irc * idetm + Wrc * idetw;
-                const double detn = Nrr * Ncc - Nrc * Nrc;
-                if (NGMIX_UNIFORM(detn <= LOW_DETVAL)) {
-                    flags = NGMIX_FLAG_LOW_DET;
-                    break;
-                }
-                const double idetn = 1. / detn;
-                wt.irr = Ncc * idetn;
-                wt.icc = Nrr * idetn;
-                wt.irc = -Nrc * idetn;
-                wt.det = wt.irr * wt.icc - wt.irc * wt.irc;
-            }
-            e1old = e1;
-            e2old = e2;
-            Told = T;
-        }
+        if (NGMIX_UNIFORM(admom_after_momsums(state, conf, sums))) break;
     }
 
     // ---- covariance of the last moments pass (admom_nb.py:168-175) and the
     // F scratch of its last pixel.  sums_cov[i,j] and [j,i] differ in the
     // reference only by the rounding of (w2var*F[i])*F[j] vs (w2var*F[j])*F[i];
     // one triangle is accumulated and mirrored.
-    const bool want_cov = last_kind == 2 && st == NGMIX_OK && !conf.no_cov;
+    const bool want_cov = admom_want_cov(state, conf);
     double c[28];
 #pragma unroll
     for (int i = 0; i < 28; i++) c[i] = 0.0;
-    if (mom_ran) {
+    if (state.mom_ran) {
 #pragma unroll
         for (int k = 0; k < PPT; k++) {
             if (!ALLCHUNKS && k >= nchunk) break;
@@ -1410,36 +1198,22 @@ __device__ __forceinline__ void admom_fused_body(const GridSrc &src,
     }
 
     if (tid == 0) {
-        ngmix_admom_result *r = res_io;
-        // admom_nb.py:105-108; maxiter <= 0 leaves the loop variable undefined
-        // in the reference, numiter = 0 here
-        const int numiter = iter_index + 1;
-        if (numiter == conf.maxiter) flags = NGMIX_FLAG_MAXITER;
-        r->flags = flags;
-        r->numiter = numiter;
-        if (last_kind != 0) {
-            r->npix = npix;
-            r->wsum = last_kind == 2 ? wsum : 0.0;
-#pragma unroll
-            for (int i = 0; i < 7; i++)
-                r->sums[i] = (last_kind == 2 || i == 0 || i == 1 || i == 5) ? sums[i] : 0.0;
+        const int numiter = admom_numiter(state, conf, iter_index);
+        admom_record(state, conf, numiter, npix, wsum, sums, res_io[0]);
+        if (want_cov) {
             int idx = 0;
 #pragma unroll
             for (int i = 0; i < 7; i++) {
 #pragma unroll
                 for (int j = i; j < 7; j++) {
-                    const double x = want_cov ? c[idx] : 0.0;
-                    r->sums_cov[i * 7 + j] = x;
-                    r->sums_cov[j * 7 + i] = x;
+                    res_io[0].sums_cov[i * 7 + j] = c[idx];
+                    res_io[0].sums_cov[j * 7 + i] = c[idx];
                     idx++;
                 }
             }
-#pragma unroll
-            for (int i = 0; i < 6; i++) r->pars[i] = pars[i];
-            r->rho4 = rho4;
         }
         wt_io[0] = wt;
-        if (status) *status = st;
+        if (status) *status = state.status;
     }
 }
 

@@ -236,6 +236,196 @@ def test_admom_errors():
     assert st == 0 and res["numiter"][0] == 0 and res["flags"][0] == 32
 
 
+# Every way out of admom's loop (csrc/admom_step.hpp), as
+# name: (conf overrides, the flags and the status the ORACLE must give).
+ADMOM_EXITS = {
+    "converged": ({}, 0, 0),
+    "cenonly": ({"cenonly": True}, 0, 0),
+    "maxiter": ({"maxiter": 3}, 32, 0),
+    "maxiter0": ({"maxiter": 0}, 32, 0),
+    "low_det_entry": ({}, 16, 0),
+    "nonpos_flux_cen": ({}, 4, 0),
+    "cen_shift": ({"shiftmax": 0.1}, 2, 0),
+    "zero_div": ({}, 0, _lib.ERR_ZERO_DIV),
+    "low_det_deweight": ({}, 16, 0),
+    "nonpos_size": ({}, 8, 0),
+    "nonpos_flux_mom": ({"shiftmax": 1.0e9}, 4, 0),
+    # the caller's record comes with flags set: nothing clears them, and the test
+    # after deweight_moments (admom_nb.py:98) ends the loop on them at once
+    "stale_flags": ({}, 1, 0),
+}
+ADMOM_EXIT_CONF = {"maxiter": 200, "shiftmax": 5.0, "etol": 1.0e-5, "Ttol": 1.0e-3,
+                   "cenonly": False}
+# (id, stamp shape, NGMIX_ADMOM_NT, the kernel the census must name, ALLCHUNKS):
+# the shapes sit at the lower edge of each row of launch_admom_grid
+ADMOM_EXIT_FORMS = [
+    ("seam", (13, 15), None, None, None),
+    ("64x8", (13, 15), None, "admom_grid_kernel<64, 8>", False),
+    ("64x8-allchunks", (19, 21), None, "admom_grid_kernel<64, 8>", True),
+    ("64x16", (19, 27), None, "admom_grid_kernel<64, 16>", False),
+    ("64x16-allchunks", (29, 29), None, "admom_grid_kernel<64, 16>", True),
+    ("128x8", (13, 15), 128, "admom_grid_kernel<128, 8>", False),   # (only when forced)
+    ("128x16", (25, 41), None, "admom_grid_kernel<128, 16>", False),
+    ("64x36", (41, 50), None, "admom_grid_kernel<64, 36>", True),
+    ("128x32", (48, 49), None, "admom_grid_kernel<128, 32>", True),
+    ("256x0", (64, 65), None, "admom_grid_kernel<256, 0>", False),
+]
+_ADMOM_EXIT_INPUTS = {}
+
+
+def _admom_exit_inputs(shape):
+    """per exit: image, weight map, ignore_zero_weight, the guess (row, col,
+    irr, icc), the conf and the oracle's (status, record, weight) -- built once
+    per shape, on the host alone"""
+    if shape in _ADMOM_EXIT_INPUTS:
+        return _ADMOM_EXIT_INPUTS[shape]
+    from oracle import oracle as ora
+    nrow, ncol = shape
+    scale = 0.263
+    rc, cc = (nrow - 1) // 2, (ncol - 1) // 2    # v = u = 0 AT this pixel
+    jac = np.array([rc, cc, scale, 0.0, 0.0, scale, scale ** 2, scale])
+    r, c = np.mgrid[0:nrow, 0:ncol]
+    v, u = (r - (rc + 0.3)) * scale, (c - (cc - 0.2)) * scale
+    irr, icc = 0.5 * 0.35 * 0.8, 0.5 * 0.35 * 1.2
+    gal = 40.0 * scale ** 2 * np.exp(-0.5 * (v * v / irr + u * u / icc)) / (
+        2 * np.pi * np.sqrt(irr * icc))
+    gal = gal + 0.003 * np.random.RandomState(nrow * 100 + ncol).normal(size=shape)
+    w = np.full(shape, 1.0 / 0.003 ** 2)
+    g = (0.0, 0.0, 0.1925, 0.1925)
+    wz = w.copy()
+    wz[rc + 1, cc - 1] = 0.0
+    # flux on the line v = 0 alone: Irr and Irc are exact zeros, detm = 0 (a flat
+    # image does not do it: its fit converges)
+    line = np.zeros(shape)
+    line[rc] = gal[rc]
+    # a positive core inside a negative ring: sum w I > 0 > sum w I r^2
+    ring = np.zeros(shape)
+    ring[rc, cc] = 1.0
+    for dr, dc in ((2, 0), (-2, 0), (0, 2), (0, -2)):
+        ring[rc + dr, cc + dc] = -0.3
+    # +1 and -0.999 about the centre: a tiny positive flux throws the centroid
+    # 2000 pixels out, and no pixel is inside the weight's cut from there
+    pair = np.zeros(shape)
+    pair[rc, cc + 1], pair[rc, cc - 1] = 1.0, -0.999
+    inputs = {
+        "converged": (gal, w, True, g), "cenonly": (gal, w, True, g),
+        "maxiter": (gal, w, True, g), "maxiter0": (gal, w, True, g),
+        "low_det_entry": (gal, w, True, (0.0, 0.0, 1.0e-101, 1.0e-101)),
+        "nonpos_flux_cen": (-gal, w, True, g),
+        "cen_shift": (gal, w, True, (2.5 * scale, -2.0 * scale, g[2], g[3])),
+        "zero_div": (gal, wz, False, g),
+        "low_det_deweight": (line, w, True, g),
+        "nonpos_size": (ring, w, True, g),
+        "nonpos_flux_mom": (pair, w, True, g), "stale_flags": (gal, w, True, g),
+    }
+    j = np.zeros(1, dtype=ora.JACOBIAN_DTYPE)
+    j[0] = tuple(jac)
+    out = {}
+    for name, (over, flags, status) in ADMOM_EXITS.items():
+        im, wmap, izw, guess = inputs[name]
+        conf = dict(ADMOM_EXIT_CONF, **over)
+        oconf = np.zeros(1, dtype=ora.ADMOM_CONF_DTYPE)
+        for k, x in conf.items():
+            oconf[k] = x
+        wt = np.zeros(1, dtype=_lib.GAUSS2D_DTYPE)
+        wt["p"] = 1.0
+        wt["row"], wt["col"], wt["irr"], wt["icc"] = guess
+        wt["det"] = wt["irr"] * wt["icc"]
+        owt = conv_rec(wt, ora.GAUSS2D_DTYPE)
+        ref = np.zeros(1, dtype=ora.ADMOM_RESULT_DTYPE)
+        ref["flags"] = flags_in = 1 if name == "stale_flags" else 0
+        st = ora.admom(oconf, owt, ora.make_pixels(im, wmap, j, izw), ref)
+        # the input reaches the exit it is meant for, in the oracle
+        assert (st, ref["flags"][0]) == (status, flags), (shape, name, st, ref["flags"][0])
+        assert name != "stale_flags" or ref["numiter"][0] == 1
+        out[name] = dict(image=im, weight=wmap, izw=izw, wt=wt, conf=conf, st=st, ref=ref,
+                         ref_wt=owt, flags_in=flags_in)
+    for a in [x for case in out.values() for x in (case["image"], case["weight"], case["wt"])]:
+        a.setflags(write=False)
+    _ADMOM_EXIT_INPUTS[shape] = (jac, j, out)
+    return _ADMOM_EXIT_INPUTS[shape]
+
+
+def _check_admom_exit(what, st, res, wt, case):
+    assert st == case["st"], what
+    if case["st"] != 0:
+        # the reference raises in the middle of a pass: its record is not a
+        # result.  The status word, the flags and the new centre are
+        assert res["flags"][0] == case["ref"]["flags"][0], what
+        for f in ("row", "col"):
+            close(wt[f], case["ref_wt"][f], scale=1.0, err_msg=what + " wt " + f)
+        return
+    _check_admom(what, res, wt, case["ref"], case["ref_wt"])
+
+
+@pytest.mark.parametrize("form", ADMOM_EXIT_FORMS, ids=[f[0] for f in ADMOM_EXIT_FORMS])
+def test_admom_every_exit_every_form(form, monkeypatch):
+    """every exit of admom's loop through every kernel that runs it -- the
+    seam's list kernel, each register-resident admom_grid_kernel<NT, PPT> with
+    its pixel loops unrolled (ALLCHUNKS) and not, the streaming <256, 0> --
+    against the CPU oracle: the iteration step is one text (admom_step.hpp)
+    that two kernel bodies call, and the golden cases that fail reach only one
+    variant.  The exits: converged, cenonly converged, MAXITER, maxiter = 0,
+    LOW_DET at entry, NONPOS_FLUX after the centroid pass, CEN_SHIFT,
+    ERR_ZERO_DIV (a listed pixel of zero weight), LOW_DET from
+    deweight_moments, NONPOS_SIZE and NONPOS_FLUX after the moments pass: all
+    eleven are reached, none is left out; and a twelfth, the flags that the
+    caller's record came with, which the reference tests after
+    deweight_moments (before the step was one text the register form did not).  The oracle's flags and status are
+    asserted to be the intended exit before a kernel is compared with it
+    (_check_admom: flags, numiter, npix exact, the record to 1e-10; after
+    ERR_ZERO_DIV, where the reference has raised, the status, the flags and
+    the centre)."""
+    import torch
+    from ngmix_amd.batch import StampBatch, GMixBatch, records_to_numpy
+    from oracle import oracle as ora
+    fid, shape, nt, kernel, allchunks = form
+    jac, j, cases = _admom_exit_inputs(shape)
+    if kernel is None:
+        L = _lib.lib()
+        for name, case in cases.items():
+            conf = np.zeros(1, dtype=_lib.ADMOM_CONF_DTYPE)
+            for k, x in case["conf"].items():
+                conf[k] = x
+            pixels = as_pixels(ora.make_pixels(case["image"], case["weight"], j, case["izw"]))
+            wt = case["wt"].copy()
+            res = np.zeros(1, dtype=_lib.ADMOM_RESULT_DTYPE)
+            res["flags"] = case["flags_in"]
+            st = L.ngmix_admom(_lib.ptr(conf), _lib.ptr(wt), _lib.ptr(pixels), pixels.size,
+                               _lib.ptr(res))
+            _check_admom_exit("seam " + name, st, res, wt[0], case)
+        return
+    if nt:
+        monkeypatch.setenv("NGMIX_ADMOM_NT", str(nt))
+    else:
+        monkeypatch.delenv("NGMIX_ADMOM_NT", raising=False)
+    # (admom_grid_kernel's own rule for the unrolled pixel loops)
+    npix, (knt, ppt) = shape[0] * shape[1], [int(x) for x in kernel[18:-1].split(",")]
+    assert allchunks == (ppt > 16 or (knt == 64 and (npix + 63) // 64 * 8 >= ppt * 7))
+    # one launch per conf, over the stamps that share it
+    groups = {}
+    for name, case in cases.items():
+        groups.setdefault(tuple(sorted(case["conf"].items())), []).append(name)
+    for names in groups.values():
+        sb = StampBatch.from_arrays([cases[n]["image"] for n in names],
+                                    [cases[n]["weight"] for n in names], [jac] * len(names),
+                                    [cases[n]["izw"] for n in names])
+        wt = GMixBatch.from_numpy(np.stack([cases[n]["wt"] for n in names]))
+        rec = np.zeros(len(names), dtype=_lib.ADMOM_RESULT_DTYPE)
+        rec["flags"] = [cases[n]["flags_in"] for n in names]
+        res = torch.from_numpy(rec.view(np.float64).reshape(len(names), 73)).cuda()
+        _lib.launch_census(reset=True)
+        res, status = sb.admom(wt, res=res, **cases[names[0]]["conf"])
+        seen = _lib.launch_census(reset=True)
+        assert seen == {kernel: 1}, (fid, seen)
+        res = records_to_numpy(res, _lib.ADMOM_RESULT_DTYPE)
+        status = status.cpu().numpy()
+        wt_out = wt.to_numpy()
+        for i, name in enumerate(names):
+            _check_admom_exit("%s %s" % (fid, name), int(status[i]), res[i:i + 1], wt_out[i],
+                              cases[name])
+
+
 # ----------------------------------------------------------------------- em
 def _check_em(name, numiter, frac, sky, gm, conv, g, label=""):
     assert numiter == int(g[name + "_numiter"]), name
