@@ -1192,6 +1192,85 @@ int ngmix_lm_rounds_batch(const ngmix_lm_problem *problem, int nrounds,
 #define NGMIX_LM_PRECISE_MIN_NLOC 10
 int ngmix_lm_precise_cov_batch(const ngmix_lm_problem *problem, double *psums,
                                void *stream);
+
+/* ----------------------------------------------------------------------
+ * Fourier-space profile fits.  The reference's GalsimFitter /
+ * GalsimSpergelFitter fit the exact profile to a k-space observation that
+ * galsim draws; here the observation is the transform of the stamp's OWN
+ * samples (the rfft2 half plane times the centre phase), the psf enters as
+ * the transform of its own stamp, and the same lock-step LM driver runs: the
+ * evaluation below produces the per-stamp normal-equation sums that
+ * ngmix_lm_advance_batch consumes.  The pixel values of such an observation
+ * are not galsim's (no interpolant, no stepk grid), and the weight is the
+ * Parseval weight, twice the reference's.
+ *   model   'gauss'   Phi = exp(-s/2),          r0 = r50 / sqrt(2 ln 2)
+ *           'exp'     Phi = (1 + s)^(-3/2),     r0 = r50 / 1.6783469900166605
+ *           'spergel' Phi = (1 + s)^(-(1 + nu)), r0 = r50 / c_nu
+ *   parameters [cen1, cen2, g1, g2, r50, F_band...] (nloc = 6), 'spergel'
+ *   [cen1, cen2, g1, g2, r50, nu, F_band...] (nloc = 7)
+ * ---------------------------------------------------------------------- */
+#define NGMIX_KFIT_GAUSS 0
+#define NGMIX_KFIT_EXP 1
+#define NGMIX_KFIT_SPERGEL 2
+#define NGMIX_ERR_NOT_FINITE 8 /* a non-finite transform on a kept mode (per-stamp status) */
+/* HOST: c_nu = r50 / r0 of the Spergel profile and its derivative, from the
+   committed Chebyshev table (csrc/spergel_hlr.hpp; 1e-12 relative); returns
+   NGMIX_ERR_G_RANGE outside nu in [-0.85, 4] and leaves c, dc_dnu untouched */
+int ngmix_spergel_hlr(double nu, double *c, double *dc_dnu);
+/* DEVICE: every stamp of every running fit at its object's trial point
+   states[obj].xt.  dhat, phat: (nstamps, R, C/2+1, 2) interleaved complex128,
+   16-byte aligned -- the stamp's transform about its jacobian centre and the
+   psf stamp's about its own centre divided by its sum (phat NULL: no psf);
+   wbar (nstamps,): the largest weight of each stamp; jac (nstamps,): only the
+   four derivatives are read.  sums: (nstamps, NGMIX_LM_NSUMS(nloc)) in the
+   layout of ngmix_lm_eval_batch; status (may be NULL): NGMIX_ERR_G_RANGE where
+   g >= 1, r50 < 1e-4 or nu is outside [-0.85, 4], NGMIX_ERR_NOT_FINITE where
+   a kept mode of dhat or phat is not finite -- the sums then carry ff = +inf;
+   stamp_stats (may be NULL): (nstamps, 2) = sum w Re(M^ D^*), sum w |M^|^2.
+   The stamps of a finished fit are skipped and their sums left as they are.
+   The analytic jacobian comes with every evaluation (states in
+   NGMIX_LM_MODE_ANALYTIC; a state's fonly is not read). */
+int ngmix_kfit_eval_batch(const double *dhat, const double *phat, const double *wbar,
+                          const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                          int model, const ngmix_lm_state *states,
+                          const int32_t *stamp_obj, const int32_t *stamp_band,
+                          double *sums, int32_t *status, double *stamp_stats,
+                          void *stream);
+/* HOST: the same for arrays in host memory -- the text the kernel runs, the
+   same order of sums */
+int ngmix_kfit_eval_host(const double *dhat, const double *phat, const double *wbar,
+                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                         int model, const ngmix_lm_state *states,
+                         const int32_t *stamp_obj, const int32_t *stamp_band,
+                         double *sums, int32_t *status, double *stamp_stats);
+/* DEVICE: ngmix_lm_rounds_batch with the evaluation above in place of the
+   pixel pass: per round ngmix_kfit_eval_batch, ngmix_lm_prior_sums_batch (when
+   `prior` is set) and ngmix_lm_advance_batch; counts, counts_host and events
+   as there.  The members are the arguments of those entry points. */
+typedef struct {
+    const double *dhat;              /* (nstamps, nrow, ncol/2+1, 2) */
+    const double *phat;              /* the same shape, or NULL */
+    const double *wbar;              /* (nstamps,) */
+    const ngmix_jacobian *jac;       /* (nstamps,) */
+    int64_t nstamps;
+    ngmix_lm_state *states;          /* device, nobj records */
+    int64_t nobj;
+    const int32_t *stamp_obj;        /* (nstamps,) or NULL */
+    const int32_t *stamp_band;       /* (nstamps,) or NULL */
+    const int64_t *obj_start;        /* (nobj + 1,) or NULL */
+    double *sums;                    /* (nstamps, NGMIX_LM_NSUMS(nloc)) */
+    int32_t *status;                 /* (nstamps,) or NULL */
+    double *stamp_stats;             /* (nstamps, 2) or NULL */
+    double *obj_stats;               /* (nobj, 2) or NULL */
+    const ngmix_simple_sep_prior *prior; /* HOST record or NULL */
+    double *obj_sums;                /* (nobj, NGMIX_LM_NSUMS(npars)) or NULL */
+    double prior_step;               /* step_rel of ngmix_lm_prior_sums_batch */
+    int32_t nrow, ncol, model;
+    int32_t nloc_npars;              /* nloc + 256 * npars, as ngmix_lm_advance_batch */
+} ngmix_kfit_problem;
+int ngmix_kfit_rounds_batch(const ngmix_kfit_problem *problem, int nrounds,
+                            int32_t *counts, int32_t *counts_host, void **events,
+                            void *stream);
 /* HOST: n timing events (hipEvent_t) for ngmix_lm_rounds_batch / to record
    on a stream; elapsed milliseconds between two recorded events (both must
    have completed: synchronise the stream or the later event first) */

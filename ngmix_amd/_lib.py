@@ -201,6 +201,40 @@ class LMProblem(ctypes.Structure):
     ]
 
 
+KFIT_GAUSS = 0
+KFIT_EXP = 1
+KFIT_SPERGEL = 2
+ERR_NOT_FINITE = 8
+
+
+class KFitProblem(ctypes.Structure):
+    """ngmix_kfit_problem: the arguments of one lock-step round of a
+    Fourier-space fit (ngmix_kfit_rounds_batch)"""
+    _fields_ = [
+        ("dhat", ctypes.c_void_p),
+        ("phat", ctypes.c_void_p),
+        ("wbar", ctypes.c_void_p),
+        ("jac", ctypes.c_void_p),
+        ("nstamps", ctypes.c_int64),
+        ("states", ctypes.c_void_p),
+        ("nobj", ctypes.c_int64),
+        ("stamp_obj", ctypes.c_void_p),
+        ("stamp_band", ctypes.c_void_p),
+        ("obj_start", ctypes.c_void_p),
+        ("sums", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("stamp_stats", ctypes.c_void_p),
+        ("obj_stats", ctypes.c_void_p),
+        ("prior", ctypes.c_void_p),
+        ("obj_sums", ctypes.c_void_p),
+        ("prior_step", ctypes.c_double),
+        ("nrow", ctypes.c_int32),
+        ("ncol", ctypes.c_int32),
+        ("model", ctypes.c_int32),
+        ("nloc_npars", ctypes.c_int32),
+    ]
+
+
 _SCALARS = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64,
     "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "double": ctypes.c_double,

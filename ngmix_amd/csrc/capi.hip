@@ -18,6 +18,7 @@
 #include "launch_iter.hpp"
 #include "metacal_noise.hpp"
 #include "prepsf_shear.hpp"
+#include "kfit.hpp"
 
 namespace ngmix {
 
@@ -151,6 +152,7 @@ int64_t ngmix_abi_sizeof(const char *type_name)
     NGMIX_SIZEOF_CASE(ngmix_lm_state);
     NGMIX_SIZEOF_CASE(ngmix_simple_sep_prior);
     NGMIX_SIZEOF_CASE(ngmix_lm_problem);
+    NGMIX_SIZEOF_CASE(ngmix_kfit_problem);
     NGMIX_SIZEOF_CASE(ngmix_scene_frame);
 #undef NGMIX_SIZEOF_CASE
     return -1;
@@ -1053,6 +1055,51 @@ int ngmix_lm_rounds_batch(const ngmix_lm_problem *problem, int nrounds, int32_t 
 int ngmix_lm_precise_cov_batch(const ngmix_lm_problem *problem, double *psums, void *stream)
 {
     return launch_lm_precise_cov(problem, psums, (hipStream_t)stream);
+}
+
+int ngmix_spergel_hlr(double nu, double *c, double *dc_dnu)
+{
+    if (!c || !dc_dnu) return NGMIX_ERR_BAD_ARG;
+    return spergel_hlr(nu, *c, *dc_dnu) ? NGMIX_OK : NGMIX_ERR_G_RANGE;
+}
+
+int ngmix_kfit_eval_batch(const double *dhat, const double *phat, const double *wbar,
+                          const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                          const ngmix_lm_state *states, const int32_t *stamp_obj,
+                          const int32_t *stamp_band, double *sums, int32_t *status,
+                          double *stamp_stats, void *stream)
+{
+    return launch_kfit_eval(dhat, phat, wbar, jac, R, C, nstamps, model, states, stamp_obj,
+                            stamp_band, sums, status, stamp_stats, (hipStream_t)stream);
+}
+
+int ngmix_kfit_eval_host(const double *dhat, const double *phat, const double *wbar,
+                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                         const ngmix_lm_state *states, const int32_t *stamp_obj,
+                         const int32_t *stamp_band, double *sums, int32_t *status,
+                         double *stamp_stats)
+{
+    bool nothing;
+    const int st = kfit::check_args("kfit_eval_host", dhat, wbar, jac, R, C, nstamps, model,
+                                    states, sums, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    if (model == NGMIX_KFIT_GAUSS)
+        kfit::host_eval<NGMIX_KFIT_GAUSS>(dhat, phat, wbar, jac, R, C, nstamps, states, stamp_obj,
+                                          stamp_band, sums, status, stamp_stats);
+    else if (model == NGMIX_KFIT_EXP)
+        kfit::host_eval<NGMIX_KFIT_EXP>(dhat, phat, wbar, jac, R, C, nstamps, states, stamp_obj,
+                                        stamp_band, sums, status, stamp_stats);
+    else
+        kfit::host_eval<NGMIX_KFIT_SPERGEL>(dhat, phat, wbar, jac, R, C, nstamps, states,
+                                            stamp_obj, stamp_band, sums, status, stamp_stats);
+    return NGMIX_OK;
+}
+
+int ngmix_kfit_rounds_batch(const ngmix_kfit_problem *problem, int nrounds, int32_t *counts,
+                            int32_t *counts_host, void **events, void *stream)
+{
+    return launch_kfit_rounds(problem, nrounds, counts, counts_host, events,
+                              (hipStream_t)stream);
 }
 
 int ngmix_events_create(int n, void **events)

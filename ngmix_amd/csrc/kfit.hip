@@ -1,0 +1,173 @@
+// kfit.hip -- Fourier-space profile fits: the evaluation kernel
+// of the lock-step LM driver for 'gauss', 'exp' and 'spergel' fitted to the
+// transform of a stamp's own samples, and the rounds that queue it.
+//
+//   kfit_eval_kernel<MODEL>  one WAVE per stamp, four stamps per block: the
+//       lanes stride over the stored modes of the stamp's rfft2 half plane,
+//       load D^ and P^n as 16-byte pairs (consecutive lanes, consecutive
+//       pairs), evaluate the model and its analytic jacobian at the object's
+//       trial point in registers (kfit.hpp has the per-mode text, shared with
+//       the host twin) and accumulate the stamp's normal equations; the lanes
+//       are summed in the fixed tree of wave_sum.  No LDS, no atomics, fp64: a
+//       stamp's sums do not depend on the batch around it or on the launch.
+//
+// The step that consumes the sums is ngmix_lm_advance_batch as it stands: the
+// layout is that of lm_eval_kernel (lmfit.hip), a finished fit is skipped and
+// its sums are left as they are.
+#include "device_utils.hpp"
+#include "kfit.hpp"
+#include "launch.hpp"
+#include "launch_util.hpp"
+
+namespace ngmix {
+
+namespace {
+constexpr int KFIT_STAMPS_PER_BLOCK = BLOCK / WAVE;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(BLOCK) void kfit_eval_kernel(
+    const double2 *__restrict__ dhat, const double2 *__restrict__ phat,
+    const double *__restrict__ wbar, const ngmix_jacobian *__restrict__ jacs, int R, int C,
+    int64_t nstamps, const ngmix_lm_state *__restrict__ states,
+    const int32_t *__restrict__ stamp_obj, const int32_t *__restrict__ stamp_band,
+    double *__restrict__ sums, int32_t *__restrict__ status, double *__restrict__ stamp_stats)
+{
+    using T = kfit::Traits<MODEL>;
+    static_assert(kfit::LANES == WAVE, "kfit.hpp mirrors device_utils.hpp");
+    const int64_t s = (int64_t)blockIdx.x * KFIT_STAMPS_PER_BLOCK + wave_id();
+    if (s >= nstamps) return;
+    const int lane = lane_id();
+    const int obj = stamp_obj ? stamp_obj[s] : (int)s;
+    const ngmix_lm_state &state = states[obj];
+    if (state.phase == NGMIX_LM_PHASE_DONE) return;   // this object has finished
+    const int band = stamp_band ? stamp_band[s] : 0;
+    double p[T::NLOC];
+#pragma unroll
+    for (int k = 0; k < T::NLOC - 1; k++) p[k] = state.xt[k];
+    p[T::NLOC - 1] = state.xt[T::NLOC - 1 + band];
+    double *out = sums + (size_t)s * T::NSUMS;
+    double *stats = stamp_stats ? stamp_stats + 2 * (size_t)s : nullptr;
+
+    const kfit::Setup m = kfit::setup<MODEL>(p, jacs[s], wbar[s], R, C);
+    if (m.bad) {   // (uniform over the wave)
+        if (lane == 0) {
+            kfit::write_refused(T::NSUMS, out, stats);
+            if (status) status[s] = NGMIX_ERR_G_RANGE;
+        }
+        return;
+    }
+
+    const int CH = C / 2 + 1, nm = R * CH;
+    const double2 *D = dhat + (size_t)s * nm;
+    const double2 *P = phat ? phat + (size_t)s * nm : nullptr;
+    double acc[T::NACC];
+#pragma unroll
+    for (int k = 0; k < T::NACC; k++) acc[k] = 0.0;
+    bool notfinite = false;
+    for (int i = lane; i < nm; i += WAVE) {
+        const int a = i / CH, b = i - a * CH;
+        const double mult = kfit::mode_mult(a, b, R, C);
+        if (mult == 0.0) continue;
+        const double2 d = D[i];
+        double2 q = make_double2(1.0, 0.0);
+        if (P) q = P[i];
+        if (!isfinite(d.x + d.y + q.x + q.y)) notfinite = true;
+        kfit::add_mode<MODEL>(m, a, b, R, mult, d.x, d.y, q.x, q.y, acc);
+    }
+#pragma unroll
+    for (int k = 0; k < T::NACC; k++) acc[k] = wave_sum(acc[k]);
+    const bool any_notfinite = __ballot(notfinite) != 0ull;
+    if (lane == 0) {
+        if (any_notfinite) {
+            kfit::write_refused(T::NSUMS, out, stats);
+            if (status) status[s] = NGMIX_ERR_NOT_FINITE;
+        } else {
+            kfit::write_sums<MODEL>(acc, m.flux, out, stats);
+            if (status) status[s] = NGMIX_OK;
+        }
+    }
+}
+
+int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
+                     const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                     const ngmix_lm_state *states, const int32_t *stamp_obj,
+                     const int32_t *stamp_band, double *sums, int32_t *status,
+                     double *stamp_stats, hipStream_t s)
+{
+    bool nothing;
+    const int st = kfit::check_args("kfit_eval", dhat, wbar, jac, R, C, nstamps, model, states,
+                                    sums, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    if (((uintptr_t)dhat | (uintptr_t)phat) & 15) {
+        set_last_error_msg("kfit_eval: dhat and phat must be 16-byte aligned");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    struct Row {
+        int model;
+        decltype(kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS>, "")) k;
+    };
+    static constexpr Row rows[] = {
+        {NGMIX_KFIT_GAUSS, kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS>, "kfit_eval_kernel<gauss>")},
+        {NGMIX_KFIT_EXP, kernel(kfit_eval_kernel<NGMIX_KFIT_EXP>, "kfit_eval_kernel<exp>")},
+        {NGMIX_KFIT_SPERGEL,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_SPERGEL>, "kfit_eval_kernel<spergel>")},
+    };
+    const auto k = find_kernel(rows, [&](const Row &q) { return q.model == model; });
+    const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
+    return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
+                  (const double2 *)phat, wbar, jac, R, C, nstamps, states, stamp_obj, stamp_band,
+                  sums, status, stamp_stats);
+}
+
+// launch_lm_rounds (lmfit.hip) with the k-space evaluation in place of the
+// pixel pass: nrounds x {kfit eval, prior rows, lmder step} queued by one host
+// call, the same counts / counts_host / events contract
+int launch_kfit_rounds(const ngmix_kfit_problem *p, int nrounds, int32_t *counts,
+                       int32_t *counts_host, void **events, hipStream_t s)
+{
+    if (!p || !p->states || !p->sums || nrounds < 0) {
+        set_last_error_msg("kfit_rounds: problem, states and sums are required");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (counts_host && !counts) {
+        set_last_error_msg("kfit_rounds: counts_host needs counts");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (p->prior && !p->obj_sums) {
+        set_last_error_msg("kfit_rounds: a prior needs obj_sums");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    const int nloc = kfit::model_nloc(p->model);
+    if (nloc == 0 || (p->nloc_npars & 0xff) != nloc) {
+        set_last_error_msg("kfit_rounds: nloc_npars does not carry the model's nloc");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (nrounds == 0 || p->nobj <= 0) return NGMIX_OK;
+    if (counts)
+        NGMIX_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)nrounds * sizeof(int32_t), s));
+    for (int r = 0; r < nrounds; r++) {
+        if (events) NGMIX_HIP_CHECK(hipEventRecord((hipEvent_t)events[3 * r], s));
+        int rc = launch_kfit_eval(p->dhat, p->phat, p->wbar, p->jac, p->nrow, p->ncol,
+                                  p->nstamps, p->model, p->states, p->stamp_obj, p->stamp_band,
+                                  p->sums, p->status, p->stamp_stats, s);
+        if (rc != NGMIX_OK) return rc;
+        if (events) NGMIX_HIP_CHECK(hipEventRecord((hipEvent_t)events[3 * r + 1], s));
+        if (p->prior) {
+            rc = launch_lm_prior_sums(p->states, p->nobj, p->prior, p->prior_step, p->obj_sums,
+                                      s);
+            if (rc != NGMIX_OK) return rc;
+        }
+        rc = launch_lm_advance(p->states, p->nobj, p->obj_start, p->stamp_band, p->sums,
+                               p->nloc_npars, p->obj_sums, counts ? counts + r : nullptr,
+                               p->stamp_stats, p->obj_stats, s, false);
+        if (rc != NGMIX_OK) return rc;
+        if (events) NGMIX_HIP_CHECK(hipEventRecord((hipEvent_t)events[3 * r + 2], s));
+    }
+    if (counts_host)
+        NGMIX_HIP_CHECK(hipMemcpyAsync(counts_host, counts, (size_t)nrounds * sizeof(int32_t),
+                                       hipMemcpyDeviceToHost, s));
+    return NGMIX_OK;
+}
+
+}  // namespace ngmix

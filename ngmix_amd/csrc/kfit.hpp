@@ -1,0 +1,320 @@
+// kfit.hpp -- Fourier-space profile fits: the per-stamp set-up
+// and the per-mode text of kfit_eval_kernel, shared with its host twin.
+//
+// A stamp's residual rows are sqrt(w) Re (M^ - D^) and sqrt(w) Im (M^ - D^) of
+// every stored mode of its rfft2 half plane, with
+//
+//   M^(q) = F Phi(s) exp(-i (k_v cen1 + k_u cen2)) P^n(q),
+//   (k_v, k_u) = J^-T q,
+//   s = r0^2 [((1 + g1) k_u + g2 k_v)^2 + (g2 k_u + (1 - g1) k_v)^2] / (1 - g^2)
+//
+// and Phi = exp(-s/2) | (1 + s)^-3/2 | (1 + s)^-(1 + nu).  With G = exp(-i theta)
+// P^n the model is A G for a REAL A, and so is every derivative with respect to
+// g1, g2, r50, nu and F: column j is alpha_j G.  The two centre columns are
+// -i k_v A G and -i k_u A G, a quarter turn from G: their products with the
+// other columns vanish mode by mode, so
+//
+//   (J^T J)[cen_a][cen_b] = sum w k_a k_b A^2 |G|^2
+//   (J^T J)[cen_a][j]     = 0                          j = g1 .. F
+//   (J^T J)[i][j]         = sum w alpha_i alpha_j |G|^2
+//   (J^T f)[cen_a]        = sum w k_a A (Im G Re f - Re G Im f)
+//   (J^T f)[j]            = sum w alpha_j (Re G Re f + Im G Im f)
+//
+// which are 20 (nloc = 6) or 26 (nloc = 7) running sums per lane instead of 28
+// or 36.  The modes of a stamp go to the 64 lanes of a wave in the order of the
+// stored plane, lane l taking modes l, l + 64, ..; the lanes are then summed in
+// the tree of wave_sum.  host_eval below walks the same order.
+#pragma once
+
+#include <math.h>
+#include <stdio.h>
+
+#include <vector>
+
+#include "common.hpp"
+#include "spergel_hlr.hpp"
+
+namespace ngmix {
+namespace kfit {
+
+constexpr int LANES = 64;                 // device_utils.hpp: WAVE
+constexpr double R50_MIN = 1.0e-4;        // the reference's lower limit of r50
+constexpr double TWO_PI = 6.283185307179586;
+// r50 / r0: sqrt(2 ln 2) for the gaussian, c_0.5 for the exponential
+constexpr double HLR_GAUSS = 1.1774100225154747;
+constexpr double HLR_EXP = 1.6783469900166605;
+
+template <int MODEL>
+struct Traits {
+    static constexpr int NLOC = MODEL == NGMIX_KFIT_SPERGEL ? 7 : 6;
+    static constexpr int NA = NLOC - 2;                       // g1, g2, r50, (nu,) F
+    static constexpr int NTRI = NA * (NA + 1) / 2;
+    // cen-cen (3) | alpha alpha triangle | cen J^T f (2) | alpha J^T f | f.f
+    static constexpr int NACC = 3 + NTRI + 2 + NA + 1;
+    static constexpr int NSUMS = NGMIX_LM_NSUMS(NLOC);
+};
+
+// what is the same for every mode of a stamp at one trial point
+struct Setup {
+    double kvr, kvc, kur, kuc;   // J^-T: k_v = kvr q_r + kvc q_c, k_u = kur q_r + kuc q_c
+    double cen1, cen2, g1, g2, flux, nu;
+    double opg1, omg1;           // 1 + g1, 1 - g1
+    double iD;                   // 1 / (1 - g^2)
+    double r0sq;                 // r0^2
+    double ds_scale;             // 2 r0^2 / (1 - g^2)
+    double dlns_dr50;            // 2 / r50
+    double dlns_dnu;             // -2 c'_nu / c_nu
+    double onepnu;               // 1 + nu
+    double wscale;               // wbar / (R C)
+    double qr_unit, qc_unit;     // 2 pi / R, 2 pi / C
+    bool bad;                    // out of range at the trial point
+};
+
+// p: the stamp's nloc local parameters [cen1, cen2, g1, g2, r50, (nu,) F]
+template <int MODEL>
+NGMIX_HD Setup setup(const double *p, const ngmix_jacobian &jac, double wbar, int R, int C)
+{
+    Setup m;
+    const double det = jac.dvdrow * jac.dudcol - jac.dvdcol * jac.dudrow;
+    const double idet = 1.0 / det;
+    m.kvr = jac.dudcol * idet;
+    m.kvc = -jac.dudrow * idet;
+    m.kur = -jac.dvdcol * idet;
+    m.kuc = jac.dvdrow * idet;
+    m.cen1 = p[0];
+    m.cen2 = p[1];
+    m.g1 = p[2];
+    m.g2 = p[3];
+    const double r50 = p[4];
+    m.nu = MODEL == NGMIX_KFIT_SPERGEL ? p[5] : 0.5;
+    m.flux = p[Traits<MODEL>::NLOC - 1];
+    const double gsq = m.g1 * m.g1 + m.g2 * m.g2;
+    // (negated tests: a NaN parameter is out of range)
+    m.bad = !(gsq < 1.0) || !(r50 >= R50_MIN) || !(fabs(det) > 0.0);
+    double c = MODEL == NGMIX_KFIT_GAUSS ? HLR_GAUSS : HLR_EXP, dc = 0.0;
+    if (MODEL == NGMIX_KFIT_SPERGEL && !spergel_hlr(m.nu, c, dc)) m.bad = true;
+    m.opg1 = 1.0 + m.g1;
+    m.omg1 = 1.0 - m.g1;
+    m.iD = 1.0 / (1.0 - gsq);
+    const double r0 = r50 / c;
+    m.r0sq = r0 * r0;
+    m.ds_scale = 2.0 * m.r0sq * m.iD;
+    m.dlns_dr50 = 2.0 / r50;
+    m.dlns_dnu = -2.0 * dc / c;
+    m.onepnu = 1.0 + m.nu;
+    m.wscale = wbar / ((double)R * (double)C);
+    m.qr_unit = TWO_PI / (double)R;
+    m.qc_unit = TWO_PI / (double)C;
+    return m;
+}
+
+// the Parseval multiplicity of stored mode (a, b): 0 on the Nyquist row and
+// column, 1 on the column b = 0, 2 elsewhere
+NGMIX_HD double mode_mult(int a, int b, int R, int C)
+{
+    if ((R % 2 == 0 && 2 * a == R) || (C % 2 == 0 && 2 * b == C)) return 0.0;
+    return b == 0 ? 1.0 : 2.0;
+}
+
+// one kept mode's terms of the running sums; (dr, di) = D^, (pr, pi) = P^n
+template <int MODEL>
+NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double mult, double dr, double di,
+                       double pr, double pi, double (&acc)[Traits<MODEL>::NACC])
+{
+    constexpr int NA = Traits<MODEL>::NA, NTRI = Traits<MODEL>::NTRI;
+    const double qr = m.qr_unit * (double)(2 * a < R ? a : a - R);   // fftfreq
+    const double qc = m.qc_unit * (double)b;
+    const double kv = fma(m.kvr, qr, m.kvc * qc);
+    const double ku = fma(m.kur, qr, m.kuc * qc);
+    const double ea = fma(m.opg1, ku, m.g2 * kv);
+    const double eb = fma(m.g2, ku, m.omg1 * kv);
+    const double t = fma(ea, ea, eb * eb);          // s = r0^2 t / (1 - g^2)
+    const double s = m.r0sq * (t * m.iD);
+    // Phi and dPhi/ds
+    double phi, dphi, lnu = 0.0;
+    if (MODEL == NGMIX_KFIT_GAUSS) {
+        phi = exp(-0.5 * s);
+        dphi = -0.5 * phi;
+    } else if (MODEL == NGMIX_KFIT_EXP) {
+        const double u = 1.0 + s;
+        phi = 1.0 / (u * sqrt(u));
+        dphi = -1.5 * phi / u;
+    } else {
+        const double u = 1.0 + s;
+        lnu = log1p(s);
+        phi = exp(-m.onepnu * lnu);
+        dphi = -m.onepnu * phi / u;
+    }
+    // G = exp(-i theta) P^n
+    const double theta = fma(kv, m.cen1, ku * m.cen2);
+    double sn, cs;
+    sincos(theta, &sn, &cs);
+    const double gr = fma(cs, pr, sn * pi);
+    const double gi = fma(cs, pi, -(sn * pr));
+    // alpha_j: g1, g2, r50, (nu,) F
+    double al[NA];
+    const double fd = m.flux * dphi;       // d A / d s
+    const double tD = t * m.iD;
+    al[0] = fd * (m.ds_scale * (fma(ea, ku, -(eb * kv)) + m.g1 * tD));
+    al[1] = fd * (m.ds_scale * (fma(ea, kv, eb * ku) + m.g2 * tD));
+    al[2] = fd * (s * m.dlns_dr50);
+    if (MODEL == NGMIX_KFIT_SPERGEL)
+        al[3] = fma(fd, s * m.dlns_dnu, -(m.flux * (lnu * phi)));
+    al[NA - 1] = phi;
+    const double A = m.flux * al[NA - 1];
+    const double fr = fma(A, gr, -dr), fi = fma(A, gi, -di);
+    const double w = m.wscale * mult;
+    const double gg = w * fma(gr, gr, gi * gi);
+    const double gf = w * fma(gr, fr, gi * fi);
+    const double cf = (w * A) * fma(gi, fr, -(gr * fi));
+    const double aa = (A * A) * gg;
+    acc[0] = fma(kv * kv, aa, acc[0]);
+    acc[1] = fma(kv * ku, aa, acc[1]);
+    acc[2] = fma(ku * ku, aa, acc[2]);
+    int k = 3;
+#pragma unroll
+    for (int i = 0; i < NA; i++) {
+        const double ai = al[i] * gg;
+#pragma unroll
+        for (int j = i; j < NA; j++) {
+            acc[k] = fma(ai, al[j], acc[k]);
+            k++;
+        }
+    }
+    acc[3 + NTRI] = fma(kv, cf, acc[3 + NTRI]);
+    acc[4 + NTRI] = fma(ku, cf, acc[4 + NTRI]);
+#pragma unroll
+    for (int i = 0; i < NA; i++) acc[5 + NTRI + i] = fma(al[i], gf, acc[5 + NTRI + i]);
+    acc[5 + NTRI + NA] = fma(w, fma(fr, fr, fi * fi), acc[5 + NTRI + NA]);
+}
+
+// the stamp's sums in the layout ngmix_lm_advance_batch reads -- J^T J upper
+// triangle | J^T f | f.f over the nloc local parameters -- from the reduced
+// running sums, and the two statistics: sum w Re(M^ D^*) = sum w |M^|^2 -
+// sum w Re(M^ f*) and sum w |M^|^2, both from the flux column (M^ = F alpha_F G)
+template <int MODEL>
+NGMIX_HD void write_sums(const double (&acc)[Traits<MODEL>::NACC], double flux, double *out,
+                         double *stats)
+{
+    constexpr int NLOC = Traits<MODEL>::NLOC, NA = Traits<MODEL>::NA,
+                  NTRI = Traits<MODEL>::NTRI;
+    int k = 0, ka = 3;
+    for (int i = 0; i < NLOC; i++)
+        for (int j = i; j < NLOC; j++) {
+            double v = 0.0;
+            if (j < 2) v = acc[i + j];            // (0,0) (0,1) (1,1)
+            else if (i >= 2) v = acc[ka++];
+            out[k++] = v;
+        }
+    for (int i = 0; i < NLOC; i++) out[k++] = acc[3 + NTRI + i];
+    out[k] = acc[5 + NTRI + NA];
+    if (stats) {
+        const double mm = flux * flux * acc[3 + NTRI - 1];          // (F, F)
+        stats[0] = mm - flux * acc[5 + NTRI + NA - 1];
+        stats[1] = mm;
+    }
+}
+
+// a stamp that cannot be evaluated: the reference's LOWVAL residuals
+NGMIX_HD void write_refused(int nsums, double *out, double *stats)
+{
+    for (int k = 0; k < nsums - 1; k++) out[k] = 0.0;
+    out[nsums - 1] = INFINITY;
+    if (stats) {
+        stats[0] = 0.0;
+        stats[1] = 0.0;
+    }
+}
+
+inline int model_nloc(int model)
+{
+    return model == NGMIX_KFIT_GAUSS || model == NGMIX_KFIT_EXP ? 6
+           : model == NGMIX_KFIT_SPERGEL                        ? 7
+                                                                : 0;
+}
+
+// the argument checks of ngmix_kfit_eval_batch and its host twin; nothing: a
+// legal call with no stamps
+inline int check_args(const char *who, const double *dhat, const double *wbar,
+                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                      const ngmix_lm_state *states, const double *sums, bool &nothing)
+{
+    nothing = false;
+    const char *why = nullptr;
+    if (nstamps < 0) why = "nstamps must not be negative";
+    else if (model_nloc(model) == 0) why = "model must be NGMIX_KFIT_GAUSS, _EXP or _SPERGEL";
+    else if (R < 1 || C < 1 || R > 0x7fff || C > 0x7fff) why = "the stamp shape must be 1..32767";
+    else if (nstamps == 0) nothing = true;
+    else if (!dhat || !wbar || !jac || !states || !sums)
+        why = "dhat, wbar, jac, states and sums are required";
+    else if (nstamps > 0x7fffffffll) why = "too many stamps for one launch";
+    if (!why) return NGMIX_OK;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    set_last_error_msg(msg);
+    return NGMIX_ERR_BAD_ARG;
+}
+
+// the host twin of kfit_eval_kernel: the same text, the same order of sums
+template <int MODEL>
+inline void host_eval(const double *dhat, const double *phat, const double *wbar,
+                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                      const ngmix_lm_state *states, const int32_t *stamp_obj,
+                      const int32_t *stamp_band, double *sums, int32_t *status,
+                      double *stamp_stats)
+{
+    constexpr int NLOC = Traits<MODEL>::NLOC, NACC = Traits<MODEL>::NACC,
+                  NSUMS = Traits<MODEL>::NSUMS;
+    const int CH = C / 2 + 1, nm = R * CH;
+    std::vector<double> part((size_t)LANES * NACC);
+    for (int64_t s = 0; s < nstamps; s++) {
+        const ngmix_lm_state &state = states[stamp_obj ? stamp_obj[s] : s];
+        if (state.phase == NGMIX_LM_PHASE_DONE) continue;
+        const int band = stamp_band ? stamp_band[s] : 0;
+        double p[NLOC];
+        for (int k = 0; k < NLOC - 1; k++) p[k] = state.xt[k];
+        p[NLOC - 1] = state.xt[NLOC - 1 + band];
+        double *out = sums + s * NSUMS;
+        double *stats = stamp_stats ? stamp_stats + 2 * s : nullptr;
+        const Setup m = setup<MODEL>(p, jac[s], wbar[s], R, C);
+        if (m.bad) {
+            write_refused(NSUMS, out, stats);
+            if (status) status[s] = NGMIX_ERR_G_RANGE;
+            continue;
+        }
+        const double *D = dhat + (size_t)s * nm * 2;
+        const double *P = phat ? phat + (size_t)s * nm * 2 : nullptr;
+        bool notfinite = false;
+        for (int l = 0; l < LANES; l++) {
+            double acc[NACC];
+            for (int k = 0; k < NACC; k++) acc[k] = 0.0;
+            for (int i = l; i < nm; i += LANES) {
+                const int a = i / CH, b = i - a * CH;
+                const double mult = mode_mult(a, b, R, C);
+                if (mult == 0.0) continue;
+                const double dr = D[2 * i], di = D[2 * i + 1];
+                const double pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
+                if (!isfinite(dr + di + pr + pi)) notfinite = true;
+                add_mode<MODEL>(m, a, b, R, mult, dr, di, pr, pi, acc);
+            }
+            for (int k = 0; k < NACC; k++) part[(size_t)k * LANES + l] = acc[k];
+        }
+        double tot[NACC];
+        for (int k = 0; k < NACC; k++) {
+            double *x = part.data() + (size_t)k * LANES;
+            for (int off = LANES / 2; off > 0; off >>= 1)
+                for (int l = 0; l < off; l++) x[l] += x[l + off];
+            tot[k] = x[0];
+        }
+        if (notfinite) {
+            write_refused(NSUMS, out, stats);
+            if (status) status[s] = NGMIX_ERR_NOT_FINITE;
+            continue;
+        }
+        write_sums<MODEL>(tot, m.flux, out, stats);
+        if (status) status[s] = NGMIX_OK;
+    }
+}
+
+}  // namespace kfit
+}  // namespace ngmix

@@ -178,6 +178,15 @@ int launch_lm_advance_team(ngmix_lm_state *states, int64_t nobj, const int64_t *
 int launch_lm_rounds(const ngmix_lm_problem *p, int nrounds, int32_t *counts,
                      int32_t *counts_host, void **events, hipStream_t s);
 
+// kfit.hip
+int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
+                     const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                     const ngmix_lm_state *states, const int32_t *stamp_obj,
+                     const int32_t *stamp_band, double *sums, int32_t *status,
+                     double *stamp_stats, hipStream_t s);
+int launch_kfit_rounds(const ngmix_kfit_problem *p, int nrounds, int32_t *counts,
+                       int32_t *counts_host, void **events, hipStream_t s);
+
 int launch_lm_prior_finish(const ngmix_lm_state *states, int64_t nobj,
                            const ngmix_simple_sep_prior *prior, double *ffx, double *lnp,
                            hipStream_t s);

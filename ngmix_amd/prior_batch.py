@@ -312,6 +312,26 @@ class PriorSimpleSepBatch(PriorSepBatch):
         super().__init__(cen_prior, g_prior, [T_prior] + self.F_priors, rows_from_lnprob=True)
 
 
+class PriorSpergelSepBatch(PriorSepBatch):
+    """
+    The separable joint prior of a Fourier-space Spergel fit (ngmix_amd/kfit.py)
+    over a batch: rows [cen1, cen2, g, r50, nu, F_band...] =
+    sqrt(clip(-2 ln p, 0)), the row order of the reference's Spergel joint
+    prior, and the bounds of the r50, nu and flux terms.  In the device record
+    r50 takes the slot of T and nu is the one middle term.
+    """
+
+    nmid = 1
+
+    def __init__(self, cen_prior, g_prior, r50_prior, nu_prior, F_prior):
+        self.r50_prior = r50_prior
+        self.nu_prior = nu_prior
+        self.F_priors = list(F_prior) if isinstance(F_prior, (list, tuple)) else [F_prior]
+        self.nband = len(self.F_priors)
+        super().__init__(cen_prior, g_prior, [r50_prior, nu_prior] + self.F_priors,
+                         rows_from_lnprob=True)
+
+
 class PriorBatchAdapter(object):
     """
     a reference-style joint prior (fill_fdiff(pars, fdiff) -> nrows,

@@ -1,0 +1,194 @@
+"""
+The cases the host and GPU tests of the Fourier-space fits share: stamps with
+their dense transforms (tests/helpers/kfit_reference.py), trial points, and
+the glue that calls ngmix_kfit_eval_host / _batch on them.  Built once per
+process and left unchanged.
+"""
+import ctypes
+import functools
+
+import numpy as np
+
+from ngmix_amd import _lib
+
+from helpers import kfit_reference as K
+
+SHAPES = [(8, 8), (9, 12), (16, 16)]
+SPECS = [("gauss", None), ("exp", None), ("spergel", -0.6), ("spergel", 0.5), ("spergel", 2.3)]
+EPS = 2.0 ** -52
+# The rounding bound of a sum: C_ROUND * 2^-52 * sum |terms|.  Counted on
+# kfit.hpp's add_mode, in units of 2^-52 (a rounding is half a unit):
+#   a jacobian column alpha_j: k (3 roundings each, two of them), ea / eb (2),
+#     t (2), s (2), Phi (libm, 2 ulp = 4 roundings), Phi' (2), fd (2), the
+#     shear bracket (5), the products (2)                      ~ 30 roundings = 15
+#   two columns per term                                                      30
+#   G: sincos (2 ulp) and the complex product (2), |G|^2 (2), w (2)            6
+#   the sum: ceil(modes / 64) + 6 additions (<= 9 on 16 x 16)                  5
+#   conditioning of Phi in s -- d ln Phi / d ln s = (1 + nu) s / (1 + s) <= 3.3
+#     at nu = 2.3 (the gaussian's s / 2 falls on terms exp(-s / 2) down), s
+#     itself 5 units off, both columns                                        34
+#   conditioning of the phase: |theta| <= pi (|cen1| + |cen2|) / scale < 6 on
+#     these cases, theta 1.5 units off, both columns                          18
+# which is 93; C_ROUND = 96.
+C_ROUND = 96.0
+
+
+def jac_record(cen, deriv):
+    j = np.zeros(1, dtype=_lib.JACOBIAN_DTYPE)
+    j["row0"], j["col0"] = cen
+    j["dvdrow"], j["dvdcol"], j["dudrow"], j["dudcol"] = deriv
+    det = deriv[0] * deriv[3] - deriv[1] * deriv[2]
+    j["det"] = det
+    j["scale"] = np.sqrt(abs(det))
+    return j
+
+
+def _blob(shape, cen, deriv, rng, scale):
+    """a real stamp: a sheared gaussian off the centre plus noise"""
+    pars = (0.3 * scale * rng.uniform(-1, 1), 0.3 * scale * rng.uniform(-1, 1),
+            rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3),
+            2 * (1.6 * scale) ** 2 * rng.uniform(0.8, 1.5), 40.0 * rng.uniform(0.5, 1.5))
+    return np.asarray(K.gauss_image(shape, cen, deriv, pars), dtype=np.float64) \
+        + 0.02 * rng.standard_normal(shape)
+
+
+def _psf(shape, cen, deriv, scale):
+    return np.asarray(K.gauss_image(shape, cen, deriv, (0.0, 0.0, 0.05, -0.03,
+                                                        2 * (0.9 * scale) ** 2, 1.0)),
+                      dtype=np.float64)
+
+
+def make_stamp(shape, jname, spec, psf_shape, seed, gmag=None, band=0, obj=0):
+    """one stamp: the image's transform, the psf's, a trial point"""
+    name, nu = spec
+    rng = np.random.RandomState(seed)
+    deriv = K.JACOBIANS[jname]
+    scale = np.sqrt(abs(deriv[0] * deriv[3] - deriv[1] * deriv[2]))
+    R, C = shape
+    cen = ((R - 1) / 2 + rng.uniform(-0.4, 0.4), (C - 1) / 2 + rng.uniform(-0.4, 0.4))
+    md = K.modes(R, C, deriv)
+    md["cen"] = cen
+    img = _blob(shape, cen, deriv, rng, scale)
+    dhat = K.interleaved(K.dense_transform(img, cen, md))
+    phat = None
+    if psf_shape is not None:
+        pcen = ((psf_shape[0] - 1) / 2 + 0.2, (psf_shape[1] - 1) / 2 - 0.1)
+        pim = _psf(psf_shape, pcen, deriv, scale)
+        phat = K.interleaved(K.dense_transform(pim, pcen, md) / K.LD(pim.sum()))
+    g = rng.uniform(0.05, 0.6) if gmag is None else gmag
+    ang = rng.uniform(0, np.pi)
+    p = [0.7 * scale * rng.uniform(-1, 1), 0.7 * scale * rng.uniform(-1, 1),
+         g * np.cos(2 * ang), g * np.sin(2 * ang), scale * rng.uniform(1.2, 2.5)]
+    if name == "spergel":
+        p.append(nu)
+    p.append(50.0 * rng.uniform(0.5, 1.5))
+    return {"shape": shape, "jname": jname, "model": K.MODEL_ID[name], "deriv": deriv,
+            "cen": cen, "md": md, "image": img, "dhat": dhat, "phat": phat,
+            "wbar": float(rng.uniform(0.5, 30.0)), "p": np.array(p), "band": band, "obj": obj,
+            "jac": jac_record(cen, deriv)}
+
+
+@functools.lru_cache(maxsize=None)
+def sums_cases():
+    """{(model id, shape, with psf): [stamps]}: every shape x jacobian x model
+    spec, with a psf of the stamp's own shape and without one; a 7 x 7 psf in
+    the 9 x 12 stamps; one stamp of each model at |g| = 0.6 exactly"""
+    groups = {}
+    seed = 100
+    for shape in SHAPES:
+        for jname in K.JACOBIANS:
+            for spec in SPECS:
+                for psf_shape in [None, shape] + ([(7, 7)] if shape == (9, 12) else []):
+                    seed += 1
+                    gmag = 0.6 if (jname == "aniso" and psf_shape == shape) else None
+                    st = make_stamp(shape, jname, spec, psf_shape, seed, gmag=gmag)
+                    groups.setdefault((st["model"], shape, psf_shape is not None), []).append(st)
+    return groups
+
+
+@functools.lru_cache(maxsize=None)
+def multiband_case():
+    """one object of 2 bands x 2 epochs ('spergel', 16 x 16, with psf): the
+    stamps and the object's 8 parameters"""
+    stamps = []
+    for band in range(2):
+        for epoch in range(2):
+            stamps.append(make_stamp((16, 16), ("diag", "aniso")[epoch], ("spergel", 1.1),
+                                     (16, 16), 900 + 2 * band + epoch, band=band))
+    pars = np.concatenate([stamps[0]["p"][:6], [55.0, 31.0]])
+    for s in stamps:
+        s["p"] = np.concatenate([pars[:6], [pars[6 + s["band"]]]])
+    return stamps, pars
+
+
+def library_hlr(nu):
+    c, dc = ctypes.c_double(), ctypes.c_double()
+    assert _lib.lib().ngmix_spergel_hlr(float(nu), ctypes.byref(c), ctypes.byref(dc)) == 0
+    return c.value, dc.value
+
+
+def reference(st, p=None):
+    """the helper's sums of a stamp at p (default: its trial point); the
+    Spergel c_nu and c'_nu are the library's table values -- held to the
+    root-finder by tests/test_spergel_hlr_host.py -- so that this comparison
+    is of the kernel's arithmetic alone"""
+    p = st["p"] if p is None else p
+    c = dc = None
+    if st["model"] == K.SPERGEL and K.NU_MIN <= p[5] <= K.NU_MAX:
+        c, dc = library_hlr(p[5])
+    phat = None if st["phat"] is None else K.from_interleaved(st["phat"])
+    return K.stamp_sums(st["model"], p, st["md"], K.from_interleaved(st["dhat"]), phat,
+                        st["wbar"], c, dc)
+
+
+def host_states(x0, mode=0, ftol=1e-10, xtol=1e-10, maxfev=200):
+    """ngmix_lm_state records at the guesses x0 (nobj, npars), host memory"""
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    states = np.zeros(x0.shape[0], dtype=_lib.LM_STATE_DTYPE)
+    assert _lib.lib().ngmix_lm_init(_lib.ptr(states), x0.shape[0], x0.shape[1], _lib.ptr(x0),
+                                    ftol, xtol, 0.0, maxfev, 100.0, mode, None, None) == 0
+    return states
+
+
+def pack_stamps(stamps):
+    """the arrays of one call: dhat, phat or None, wbar, jac"""
+    dhat = np.ascontiguousarray(np.stack([s["dhat"] for s in stamps]))
+    phat = None
+    if stamps[0]["phat"] is not None:
+        phat = np.ascontiguousarray(np.stack([s["phat"] for s in stamps]))
+    wbar = np.array([s["wbar"] for s in stamps])
+    jac = np.concatenate([s["jac"] for s in stamps])
+    return dhat, phat, wbar, jac
+
+
+def eval_host(stamps, states, stamp_obj=None, stamp_band=None, sums=None):
+    """ngmix_kfit_eval_host on stamps of one shape and model: sums, status, stats"""
+    L = _lib.lib()
+    dhat, phat, wbar, jac = pack_stamps(stamps)
+    R, C = stamps[0]["shape"]
+    nloc = K.NLOC[stamps[0]["model"]]
+    n = len(stamps)
+    if sums is None:
+        sums = np.full((n, K.nsums(nloc)), np.nan)
+    status = np.full(n, -7, dtype=np.int32)
+    stats = np.full((n, 2), np.nan)
+    so = None if stamp_obj is None else np.ascontiguousarray(stamp_obj, dtype=np.int32)
+    sb = None if stamp_band is None else np.ascontiguousarray(stamp_band, dtype=np.int32)
+    rc = L.ngmix_kfit_eval_host(_lib.ptr(dhat), None if phat is None else _lib.ptr(phat),
+                                _lib.ptr(wbar), _lib.ptr(jac), R, C, n, stamps[0]["model"],
+                                _lib.ptr(states), None if so is None else _lib.ptr(so),
+                                None if sb is None else _lib.ptr(sb), _lib.ptr(sums),
+                                _lib.ptr(status), _lib.ptr(stats))
+    assert rc == 0, _lib.last_error()
+    return sums, status, stats
+
+
+def worst_ratio(got, ref, absum):
+    """max |got - ref| / (2^-52 sum |terms|); an entry without terms must be 0"""
+    got = np.asarray(got, dtype=K.LD)
+    err = np.abs(got - ref)
+    zero = absum == 0
+    assert np.all(got[zero] == ref[zero])
+    if np.all(zero):
+        return 0.0
+    return float((err[~zero] / (EPS * absum[~zero])).max())

@@ -32,4 +32,5 @@ cd "$ROOT"
   make -C "$ROOT/ngmix_amd/csrc" -j4 asan-metacal-noise > /dev/null 2>&1 && "$ROOT/ngmix_amd/metacal_noise_host_asan"
   make -C "$ROOT/ngmix_amd/csrc" -j4 asan-prepsf-shear > /dev/null 2>&1 && "$ROOT/ngmix_amd/prepsf_shear_host_asan"
   make -C "$ROOT/ngmix_amd/csrc" -j4 asan-prepsf-shear-noise > /dev/null 2>&1 && "$ROOT/ngmix_amd/prepsf_shear_noise_host_asan"
+  make -C "$ROOT/ngmix_amd/csrc" -j4 asan-kfit > /dev/null 2>&1 && "$ROOT/ngmix_amd/kfit_host_asan"
 } | tee "$LOG"
