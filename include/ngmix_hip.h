@@ -1206,12 +1206,20 @@ int ngmix_lm_precise_cov_batch(const ngmix_lm_problem *problem, double *psums,
  *   model   'gauss'   Phi = exp(-s/2),          r0 = r50 / sqrt(2 ln 2)
  *           'exp'     Phi = (1 + s)^(-3/2),     r0 = r50 / 1.6783469900166605
  *           'spergel' Phi = (1 + s)^(-(1 + nu)), r0 = r50 / c_nu
+ *           'moffat'  Phi = 2^(1-nu) / Gamma(nu) x^nu K_nu(x), x = sqrt(s),
+ *                     nu = beta - 1: the untruncated profile
+ *                     (1 + r^2 / r_d^2)^(-beta), r0 = r_d =
+ *                     r50 / sqrt(2^(1/(beta-1)) - 1)      NGMIX_KFIT_MOFFAT
+ *                     fwhm / (2 sqrt(2^(1/beta) - 1))     NGMIX_KFIT_MOFFAT_FWHM
  *   parameters [cen1, cen2, g1, g2, r50, F_band...] (nloc = 6), 'spergel'
- *   [cen1, cen2, g1, g2, r50, nu, F_band...] (nloc = 7)
+ *   [cen1, cen2, g1, g2, r50, nu, F_band...], 'moffat' [cen1, cen2, g1, g2,
+ *   r50 | fwhm, beta, F_band...] (nloc = 7)
  * ---------------------------------------------------------------------- */
 #define NGMIX_KFIT_GAUSS 0
 #define NGMIX_KFIT_EXP 1
 #define NGMIX_KFIT_SPERGEL 2
+#define NGMIX_KFIT_MOFFAT 3
+#define NGMIX_KFIT_MOFFAT_FWHM 4
 #define NGMIX_ERR_NOT_FINITE 8 /* a non-finite transform on a kept mode (per-stamp status) */
 /* HOST: c_nu = r50 / r0 of the Spergel profile and its derivative, from the
    committed Chebyshev table (csrc/spergel_hlr.hpp; 1e-12 relative); returns
@@ -1224,7 +1232,8 @@ int ngmix_spergel_hlr(double nu, double *c, double *dc_dnu);
    wbar (nstamps,): the largest weight of each stamp; jac (nstamps,): only the
    four derivatives are read.  sums: (nstamps, NGMIX_LM_NSUMS(nloc)) in the
    layout of ngmix_lm_eval_batch; status (may be NULL): NGMIX_ERR_G_RANGE where
-   g >= 1, r50 < 1e-4 or nu is outside [-0.85, 4], NGMIX_ERR_NOT_FINITE where
+   g >= 1, the size < 1e-4, nu is outside [-0.85, 4] or beta outside [1.1, 6],
+   NGMIX_ERR_NOT_FINITE where
    a kept mode of dhat or phat is not finite -- the sums then carry ff = +inf;
    stamp_stats (may be NULL): (nstamps, 2) = sum w Re(M^ D^*), sum w |M^|^2.
    The stamps of a finished fit are skipped and their sums left as they are.
@@ -1243,6 +1252,31 @@ int ngmix_kfit_eval_host(const double *dhat, const double *phat, const double *w
                          int model, const ngmix_lm_state *states,
                          const int32_t *stamp_obj, const int32_t *stamp_band,
                          double *sums, int32_t *status, double *stamp_stats);
+/* HOST: the Moffat transform and its derivatives at n pairs (nu = beta - 1 in
+   [0.1, 5], finite x >= 0; csrc/moffat_phi.hpp): out (n, 3) = Phi,
+   x dPhi/dx, dPhi/dnu.  A large x underflows to zeros.  The range of nu is the
+   caller's to keep (the fit's set-up refuses beta outside [1.1, 6]) */
+int ngmix_moffat_phi_host(const double *nu, const double *x, int64_t n, double *out);
+/* DEVICE: the same text, one thread per pair */
+int ngmix_moffat_phi_batch(const double *nu, const double *x, int64_t n, double *out,
+                           void *stream);
+/* DEVICE: the sums of the linear flux of a FIXED unit-flux template
+   T^ = Phi(s) exp(-i k.cen) P^n per stamp: out (nstamps, 3) = sum w Re(T^* D^),
+   sum w |T^|^2, sum w |D^|^2 over the kept modes, w as in the evaluation.
+   model: one of NGMIX_KFIT_*, or -1 for a point source (Phi = 1: the template
+   is the psf itself).  pars (nstamps, npars): [cen1, cen2, g1, g2, size,
+   (nu | beta)] -- the model's local parameters without a flux, 5 or 6 of them;
+   the point source takes 5 and reads the centre.  dhat, phat, wbar, jac and
+   status as ngmix_kfit_eval_batch; a refused stamp's sums are zeros.  A
+   stamp's sums depend on that stamp alone */
+int ngmix_kfit_flux_batch(const double *dhat, const double *phat, const double *wbar,
+                          const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                          int model, const double *pars, double *out, int32_t *status,
+                          void *stream);
+/* HOST: the same for arrays in host memory, the same order of sums */
+int ngmix_kfit_flux_host(const double *dhat, const double *phat, const double *wbar,
+                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                         int model, const double *pars, double *out, int32_t *status);
 /* DEVICE: ngmix_lm_rounds_batch with the evaluation above in place of the
    pixel pass: per round ngmix_kfit_eval_batch, ngmix_lm_prior_sums_batch (when
    `prior` is set) and ngmix_lm_advance_batch; counts, counts_host and events

@@ -204,6 +204,9 @@ class LMProblem(ctypes.Structure):
 KFIT_GAUSS = 0
 KFIT_EXP = 1
 KFIT_SPERGEL = 2
+KFIT_MOFFAT = 3
+KFIT_MOFFAT_FWHM = 4
+KFIT_POINT = -1    # ngmix_kfit_flux_batch alone: a point source
 ERR_NOT_FINITE = 8
 
 

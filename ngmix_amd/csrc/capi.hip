@@ -1089,10 +1089,53 @@ int ngmix_kfit_eval_host(const double *dhat, const double *phat, const double *w
     else if (model == NGMIX_KFIT_EXP)
         kfit::host_eval<NGMIX_KFIT_EXP>(dhat, phat, wbar, jac, R, C, nstamps, states, stamp_obj,
                                         stamp_band, sums, status, stamp_stats);
-    else
+    else if (model == NGMIX_KFIT_SPERGEL)
         kfit::host_eval<NGMIX_KFIT_SPERGEL>(dhat, phat, wbar, jac, R, C, nstamps, states,
                                             stamp_obj, stamp_band, sums, status, stamp_stats);
+    else if (model == NGMIX_KFIT_MOFFAT)
+        kfit::host_eval<NGMIX_KFIT_MOFFAT>(dhat, phat, wbar, jac, R, C, nstamps, states,
+                                           stamp_obj, stamp_band, sums, status, stamp_stats);
+    else
+        kfit::host_eval<NGMIX_KFIT_MOFFAT_FWHM>(dhat, phat, wbar, jac, R, C, nstamps, states,
+                                                stamp_obj, stamp_band, sums, status,
+                                                stamp_stats);
     return NGMIX_OK;
+}
+
+int ngmix_kfit_flux_batch(const double *dhat, const double *phat, const double *wbar,
+                          const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                          const double *pars, double *out, int32_t *status, void *stream)
+{
+    return launch_kfit_flux(dhat, phat, wbar, jac, R, C, nstamps, model, pars, out, status,
+                            (hipStream_t)stream);
+}
+
+int ngmix_kfit_flux_host(const double *dhat, const double *phat, const double *wbar,
+                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                         const double *pars, double *out, int32_t *status)
+{
+    bool nothing;
+    const int st = kfit::check_flux_args("kfit_flux_host", dhat, wbar, jac, R, C, nstamps, model,
+                                         pars, out, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    kfit::host_flux_for<kfit::MODEL_POINT, NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL,
+                        NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(
+        model, dhat, phat, wbar, jac, R, C, nstamps, pars, out, status);
+    return NGMIX_OK;
+}
+
+int ngmix_moffat_phi_host(const double *nu, const double *x, int64_t n, double *out)
+{
+    if (n < 0 || (n > 0 && (!nu || !x || !out))) return NGMIX_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n; i++)
+        moffat_phi(nu[i], x[i], out + 3 * i, out + 3 * i + 1, out + 3 * i + 2);
+    return NGMIX_OK;
+}
+
+int ngmix_moffat_phi_batch(const double *nu, const double *x, int64_t n, double *out,
+                           void *stream)
+{
+    return launch_moffat_phi(nu, x, n, out, (hipStream_t)stream);
 }
 
 int ngmix_kfit_rounds_batch(const ngmix_kfit_problem *problem, int nrounds, int32_t *counts,

@@ -1,6 +1,7 @@
 // kfit.hip -- Fourier-space profile fits: the evaluation kernel
-// of the lock-step LM driver for 'gauss', 'exp' and 'spergel' fitted to the
-// transform of a stamp's own samples, and the rounds that queue it.
+// of the lock-step LM driver for 'gauss', 'exp', 'spergel' and the Moffat
+// profile fitted to the transform of a stamp's own samples, the
+// rounds that queue it, and the linear flux of a fixed template.
 //
 //   kfit_eval_kernel<MODEL>  one WAVE per stamp, four stamps per block: the
 //       lanes stride over the stored modes of the stamp's rfft2 half plane,
@@ -10,6 +11,13 @@
 //       the host twin) and accumulate the stamp's normal equations; the lanes
 //       are summed in the fixed tree of wave_sum.  No LDS, no atomics, fp64: a
 //       stamp's sums do not depend on the batch around it or on the launch.
+//
+//   kfit_flux_kernel<MODEL>  the same walk for a FIXED unit-flux template T^ --
+//       any of the models at given parameters, or a point source (the psf
+//       itself) --: sum w Re(T^* D^), sum w |T^|^2, sum w |D^|^2.  No LM state.
+//
+//   moffat_phi_kernel  moffat_phi.hpp's function at n pairs, one thread each:
+//       what holds the device's arithmetic to the fixture without a fit.
 //
 // The step that consumes the sums is ngmix_lm_advance_batch as it stands: the
 // layout is that of lm_eval_kernel (lmfit.hip), a finished fit is skipped and
@@ -112,12 +120,120 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
         {NGMIX_KFIT_EXP, kernel(kfit_eval_kernel<NGMIX_KFIT_EXP>, "kfit_eval_kernel<exp>")},
         {NGMIX_KFIT_SPERGEL,
          kernel(kfit_eval_kernel<NGMIX_KFIT_SPERGEL>, "kfit_eval_kernel<spergel>")},
+        {NGMIX_KFIT_MOFFAT,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT>, "kfit_eval_kernel<moffat>")},
+        {NGMIX_KFIT_MOFFAT_FWHM,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT_FWHM>, "kfit_eval_kernel<moffat fwhm>")},
     };
     const auto k = find_kernel(rows, [&](const Row &q) { return q.model == model; });
     const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
     return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
                   (const double2 *)phat, wbar, jac, R, C, nstamps, states, stamp_obj, stamp_band,
                   sums, status, stamp_stats);
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(BLOCK) void kfit_flux_kernel(
+    const double2 *__restrict__ dhat, const double2 *__restrict__ phat,
+    const double *__restrict__ wbar, const ngmix_jacobian *__restrict__ jacs, int R, int C,
+    int64_t nstamps, const double *__restrict__ pars, double *__restrict__ out,
+    int32_t *__restrict__ status)
+{
+    const int64_t s = (int64_t)blockIdx.x * KFIT_STAMPS_PER_BLOCK + wave_id();
+    if (s >= nstamps) return;
+    const int lane = lane_id();
+    double *o = out + 3 * (size_t)s;
+    const kfit::Setup m = kfit::flux_setup<MODEL>(pars + (size_t)s * kfit::flux_npars(MODEL),
+                                                  jacs[s], wbar[s], R, C);
+    if (m.bad) {   // (uniform over the wave)
+        if (lane == 0) {
+            kfit::write_flux_refused(o);
+            if (status) status[s] = NGMIX_ERR_G_RANGE;
+        }
+        return;
+    }
+    const int CH = C / 2 + 1, nm = R * CH;
+    const double2 *D = dhat + (size_t)s * nm;
+    const double2 *P = phat ? phat + (size_t)s * nm : nullptr;
+    double acc[3] = {0.0, 0.0, 0.0};
+    bool notfinite = false;
+    for (int i = lane; i < nm; i += WAVE) {
+        const int a = i / CH, b = i - a * CH;
+        const double mult = kfit::mode_mult(a, b, R, C);
+        if (mult == 0.0) continue;
+        const double2 d = D[i];
+        double2 q = make_double2(1.0, 0.0);
+        if (P) q = P[i];
+        if (!isfinite(d.x + d.y + q.x + q.y)) notfinite = true;
+        kfit::flux_mode<MODEL>(m, a, b, R, mult, d.x, d.y, q.x, q.y, acc);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) acc[k] = wave_sum(acc[k]);
+    const bool any_notfinite = __ballot(notfinite) != 0ull;
+    if (lane == 0) {
+        if (any_notfinite) {
+            kfit::write_flux_refused(o);
+        } else {
+            o[0] = acc[0], o[1] = acc[1], o[2] = acc[2];
+        }
+        if (status) status[s] = any_notfinite ? NGMIX_ERR_NOT_FINITE : NGMIX_OK;
+    }
+}
+
+int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
+                     const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                     const double *pars, double *out, int32_t *status, hipStream_t s)
+{
+    bool nothing;
+    const int st = kfit::check_flux_args("kfit_flux", dhat, wbar, jac, R, C, nstamps, model, pars,
+                                         out, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    if (((uintptr_t)dhat | (uintptr_t)phat) & 15) {
+        set_last_error_msg("kfit_flux: dhat and phat must be 16-byte aligned");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    struct Row {
+        int model;
+        decltype(kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS>, "")) k;
+    };
+    static constexpr Row rows[] = {
+        {kfit::MODEL_POINT, kernel(kfit_flux_kernel<kfit::MODEL_POINT>, "kfit_flux_kernel<point>")},
+        {NGMIX_KFIT_GAUSS, kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS>, "kfit_flux_kernel<gauss>")},
+        {NGMIX_KFIT_EXP, kernel(kfit_flux_kernel<NGMIX_KFIT_EXP>, "kfit_flux_kernel<exp>")},
+        {NGMIX_KFIT_SPERGEL,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_SPERGEL>, "kfit_flux_kernel<spergel>")},
+        {NGMIX_KFIT_MOFFAT,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT>, "kfit_flux_kernel<moffat>")},
+        {NGMIX_KFIT_MOFFAT_FWHM,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT_FWHM>, "kfit_flux_kernel<moffat fwhm>")},
+    };
+    const auto k = find_kernel(rows, [&](const Row &q) { return q.model == model; });
+    const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
+    return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
+                  (const double2 *)phat, wbar, jac, R, C, nstamps, pars, out, status);
+}
+
+__global__ __launch_bounds__(BLOCK) void moffat_phi_kernel(const double *__restrict__ nu,
+                                                           const double *__restrict__ x,
+                                                           int64_t n, double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double phi, dx, dnu;
+    moffat_phi(nu[i], x[i], &phi, &dx, &dnu);
+    out[3 * i] = phi, out[3 * i + 1] = dx, out[3 * i + 2] = dnu;
+}
+
+int launch_moffat_phi(const double *nu, const double *x, int64_t n, double *out, hipStream_t s)
+{
+    if (n < 0 || n > 0x7fffffffll * BLOCK || (n > 0 && (!nu || !x || !out))) {
+        set_last_error_msg("moffat_phi: n >= 0 pairs nu, x and out (n, 3) are required");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (n == 0) return NGMIX_OK;
+    return launch(kernel(moffat_phi_kernel, "moffat_phi_kernel"),
+                  dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, NO_OPTIN, s, nu, x, n,
+                  out);
 }
 
 // launch_lm_rounds (lmfit.hip) with the k-space evaluation in place of the

@@ -8,9 +8,11 @@
 //   (k_v, k_u) = J^-T q,
 //   s = r0^2 [((1 + g1) k_u + g2 k_v)^2 + (g2 k_u + (1 - g1) k_v)^2] / (1 - g^2)
 //
-// and Phi = exp(-s/2) | (1 + s)^-3/2 | (1 + s)^-(1 + nu).  With G = exp(-i theta)
+// and Phi = exp(-s/2) | (1 + s)^-3/2 | (1 + s)^-(1 + nu), or the Moffat transform
+// Phi(sqrt(s); beta - 1) of moffat_phi.hpp, whose index beta
+// stands in nu's slot and whose size is r50 or the fwhm.  With G = exp(-i theta)
 // P^n the model is A G for a REAL A, and so is every derivative with respect to
-// g1, g2, r50, nu and F: column j is alpha_j G.  The two centre columns are
+// g1, g2, r50, nu (beta) and F: column j is alpha_j G.  The two centre columns are
 // -i k_v A G and -i k_u A G, a quarter turn from G: their products with the
 // other columns vanish mode by mode, so
 //
@@ -24,6 +26,9 @@
 // or 36.  The modes of a stamp go to the 64 lanes of a wave in the order of the
 // stored plane, lane l taking modes l, l + 64, ..; the lanes are then summed in
 // the tree of wave_sum.  host_eval below walks the same order.
+//
+// kfit_flux_kernel's three sums of a FIXED unit-flux template T^ = Phi G (or G
+// alone: a point source, the psf itself) are flux_mode's, in the same order.
 #pragma once
 
 #include <math.h>
@@ -32,6 +37,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "moffat_phi.hpp"
 #include "spergel_hlr.hpp"
 
 namespace ngmix {
@@ -43,11 +49,20 @@ constexpr double TWO_PI = 6.283185307179586;
 // r50 / r0: sqrt(2 ln 2) for the gaussian, c_0.5 for the exponential
 constexpr double HLR_GAUSS = 1.1774100225154747;
 constexpr double HLR_EXP = 1.6783469900166605;
+constexpr double LN2 = 0.6931471805599453;
+constexpr double MOFFAT_BETA_MIN = 1.1, MOFFAT_BETA_MAX = 6.0;
+// kfit_flux_kernel alone: Phi = 1
+constexpr int MODEL_POINT = -1;
+
+constexpr bool is_moffat(int model)
+{
+    return model == NGMIX_KFIT_MOFFAT || model == NGMIX_KFIT_MOFFAT_FWHM;
+}
 
 template <int MODEL>
 struct Traits {
-    static constexpr int NLOC = MODEL == NGMIX_KFIT_SPERGEL ? 7 : 6;
-    static constexpr int NA = NLOC - 2;                       // g1, g2, r50, (nu,) F
+    static constexpr int NLOC = MODEL == NGMIX_KFIT_SPERGEL || is_moffat(MODEL) ? 7 : 6;
+    static constexpr int NA = NLOC - 2;                       // g1, g2, r50, (nu | beta,) F
     static constexpr int NTRI = NA * (NA + 1) / 2;
     // cen-cen (3) | alpha alpha triangle | cen J^T f (2) | alpha J^T f | f.f
     static constexpr int NACC = 3 + NTRI + 2 + NA + 1;
@@ -63,14 +78,26 @@ struct Setup {
     double r0sq;                 // r0^2
     double ds_scale;             // 2 r0^2 / (1 - g^2)
     double dlns_dr50;            // 2 / r50
-    double dlns_dnu;             // -2 c'_nu / c_nu
+    double dlns_dnu;             // -2 c'_nu / c_nu (Moffat: -2 c'_beta / c_beta)
     double onepnu;               // 1 + nu
     double wscale;               // wbar / (R C)
     double qr_unit, qc_unit;     // 2 pi / R, 2 pi / C
     bool bad;                    // out of range at the trial point
+    MoffatNu mof;                // Moffat alone: what depends on beta
 };
 
-// p: the stamp's nloc local parameters [cen1, cen2, g1, g2, r50, (nu,) F]
+// the Moffat size in units of r_d and its logarithmic derivative with respect
+// to beta: r50 / r_d = sqrt(2^(1/(beta-1)) - 1), fwhm / r_d = 2 sqrt(2^(1/beta) - 1)
+template <int MODEL>
+NGMIX_HD void moffat_size(double beta, double &c, double &dlnc)
+{
+    const double b = MODEL == NGMIX_KFIT_MOFFAT ? beta - 1.0 : beta;
+    const double em = expm1(LN2 / b);               // 2^(1/b) - 1
+    c = (MODEL == NGMIX_KFIT_MOFFAT ? 1.0 : 2.0) * sqrt(em);
+    dlnc = -0.5 * LN2 * (1.0 + em) / (b * b * em);
+}
+
+// p: the stamp's nloc local parameters [cen1, cen2, g1, g2, r50, (nu | beta,) F]
 template <int MODEL>
 NGMIX_HD Setup setup(const double *p, const ngmix_jacobian &jac, double wbar, int R, int C)
 {
@@ -86,13 +113,22 @@ NGMIX_HD Setup setup(const double *p, const ngmix_jacobian &jac, double wbar, in
     m.g1 = p[2];
     m.g2 = p[3];
     const double r50 = p[4];
-    m.nu = MODEL == NGMIX_KFIT_SPERGEL ? p[5] : 0.5;
+    m.nu = Traits<MODEL>::NLOC == 7 ? p[5] : 0.5;
     m.flux = p[Traits<MODEL>::NLOC - 1];
     const double gsq = m.g1 * m.g1 + m.g2 * m.g2;
     // (negated tests: a NaN parameter is out of range)
     m.bad = !(gsq < 1.0) || !(r50 >= R50_MIN) || !(fabs(det) > 0.0);
     double c = MODEL == NGMIX_KFIT_GAUSS ? HLR_GAUSS : HLR_EXP, dc = 0.0;
     if (MODEL == NGMIX_KFIT_SPERGEL && !spergel_hlr(m.nu, c, dc)) m.bad = true;
+    if (is_moffat(MODEL)) {
+        if (!(m.nu >= MOFFAT_BETA_MIN && m.nu <= MOFFAT_BETA_MAX)) {
+            m.bad = true;
+        } else {
+            moffat_size<MODEL>(m.nu, c, dc);
+            dc *= c;
+            m.mof = moffat_nu(m.nu - 1.0);
+        }
+    }
     m.opg1 = 1.0 + m.g1;
     m.omg1 = 1.0 - m.g1;
     m.iD = 1.0 / (1.0 - gsq);
@@ -139,11 +175,16 @@ NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double mult, double 
         const double u = 1.0 + s;
         phi = 1.0 / (u * sqrt(u));
         dphi = -1.5 * phi / u;
-    } else {
+    } else if (MODEL == NGMIX_KFIT_SPERGEL) {
         const double u = 1.0 + s;
         lnu = log1p(s);
         phi = exp(-m.onepnu * lnu);
         dphi = -m.onepnu * phi / u;
+    } else {
+        // D_x = 2 s dPhi/ds; at the DC mode every column but the flux's is zero
+        double dx;
+        moffat_phi_at(m.mof, sqrt(s), phi, dx, lnu);       // lnu: dPhi/dbeta
+        dphi = s > 0.0 ? 0.5 * dx / s : 0.0;
     }
     // G = exp(-i theta) P^n
     const double theta = fma(kv, m.cen1, ku * m.cen2);
@@ -160,6 +201,7 @@ NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double mult, double 
     al[2] = fd * (s * m.dlns_dr50);
     if (MODEL == NGMIX_KFIT_SPERGEL)
         al[3] = fma(fd, s * m.dlns_dnu, -(m.flux * (lnu * phi)));
+    if (is_moffat(MODEL)) al[3] = fma(fd, s * m.dlns_dnu, m.flux * lnu);
     al[NA - 1] = phi;
     const double A = m.flux * al[NA - 1];
     const double fr = fma(A, gr, -dr), fi = fma(A, gi, -di);
@@ -226,10 +268,10 @@ NGMIX_HD void write_refused(int nsums, double *out, double *stats)
     }
 }
 
-inline int model_nloc(int model)
+constexpr int model_nloc(int model)
 {
     return model == NGMIX_KFIT_GAUSS || model == NGMIX_KFIT_EXP ? 6
-           : model == NGMIX_KFIT_SPERGEL                        ? 7
+           : model == NGMIX_KFIT_SPERGEL || is_moffat(model)    ? 7
                                                                 : 0;
 }
 
@@ -242,7 +284,7 @@ inline int check_args(const char *who, const double *dhat, const double *wbar,
     nothing = false;
     const char *why = nullptr;
     if (nstamps < 0) why = "nstamps must not be negative";
-    else if (model_nloc(model) == 0) why = "model must be NGMIX_KFIT_GAUSS, _EXP or _SPERGEL";
+    else if (model_nloc(model) == 0) why = "model must be NGMIX_KFIT_GAUSS, _EXP, _SPERGEL, _MOFFAT or _MOFFAT_FWHM";
     else if (R < 1 || C < 1 || R > 0x7fff || C > 0x7fff) why = "the stamp shape must be 1..32767";
     else if (nstamps == 0) nothing = true;
     else if (!dhat || !wbar || !jac || !states || !sums)
@@ -314,6 +356,143 @@ inline void host_eval(const double *dhat, const double *phat, const double *wbar
         write_sums<MODEL>(tot, m.flux, out, stats);
         if (status) status[s] = NGMIX_OK;
     }
+}
+
+// ---- the linear flux of a fixed template ---------------------------
+
+// the parameters a template of `model` takes, without a flux: [cen1, cen2, g1,
+// g2, size, (nu | beta)]; the point source reads the centre of its five
+constexpr int flux_npars(int model)
+{
+    return model == MODEL_POINT ? 5 : model_nloc(model) - (model_nloc(model) > 0);
+}
+
+// one kept mode's terms of A = sum w Re(T^* D^), B = sum w |T^|^2, E = sum w |D^|^2
+template <int MODEL>
+NGMIX_HD void flux_mode(const Setup &m, int a, int b, int R, double mult, double dr, double di,
+                        double pr, double pi, double (&acc)[3])
+{
+    const double qr = m.qr_unit * (double)(2 * a < R ? a : a - R);   // fftfreq
+    const double qc = m.qc_unit * (double)b;
+    const double kv = fma(m.kvr, qr, m.kvc * qc);
+    const double ku = fma(m.kur, qr, m.kuc * qc);
+    double phi = 1.0;
+    if (MODEL != MODEL_POINT) {
+        const double ea = fma(m.opg1, ku, m.g2 * kv);
+        const double eb = fma(m.g2, ku, m.omg1 * kv);
+        const double s = m.r0sq * (fma(ea, ea, eb * eb) * m.iD);
+        if (MODEL == NGMIX_KFIT_GAUSS) {
+            phi = exp(-0.5 * s);
+        } else if (MODEL == NGMIX_KFIT_EXP) {
+            const double u = 1.0 + s;
+            phi = 1.0 / (u * sqrt(u));
+        } else if (MODEL == NGMIX_KFIT_SPERGEL) {
+            phi = exp(-m.onepnu * log1p(s));
+        } else {
+            double dx, dnu;
+            moffat_phi_at(m.mof, sqrt(s), phi, dx, dnu);
+        }
+    }
+    const double theta = fma(kv, m.cen1, ku * m.cen2);
+    double sn, cs;
+    sincos(theta, &sn, &cs);
+    const double tr = phi * fma(cs, pr, sn * pi);
+    const double ti = phi * fma(cs, pi, -(sn * pr));
+    const double w = m.wscale * mult;
+    acc[0] = fma(w, fma(tr, dr, ti * di), acc[0]);
+    acc[1] = fma(w, fma(tr, tr, ti * ti), acc[1]);
+    acc[2] = fma(w, fma(dr, dr, di * di), acc[2]);
+}
+
+// the set-up of a template: the evaluation's, at unit flux
+template <int MODEL>
+NGMIX_HD Setup flux_setup(const double *pars, const ngmix_jacobian &jac, double wbar, int R, int C)
+{
+    constexpr int EVAL = MODEL == MODEL_POINT ? NGMIX_KFIT_GAUSS : MODEL;
+    constexpr int NLOC = Traits<EVAL>::NLOC;
+    double p[NLOC];
+    if (MODEL == MODEL_POINT) {
+        p[0] = pars[0], p[1] = pars[1], p[2] = 0.0, p[3] = 0.0, p[4] = 1.0;
+    } else {
+        for (int k = 0; k < NLOC - 1; k++) p[k] = pars[k];
+    }
+    p[NLOC - 1] = 1.0;
+    return setup<EVAL>(p, jac, wbar, R, C);
+}
+
+NGMIX_HD void write_flux_refused(double *out)
+{
+    out[0] = 0.0, out[1] = 0.0, out[2] = 0.0;
+}
+
+inline int check_flux_args(const char *who, const double *dhat, const double *wbar,
+                           const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                           const double *pars, const double *out, bool &nothing)
+{
+    nothing = false;
+    const char *why = nullptr;
+    if (nstamps < 0) why = "nstamps must not be negative";
+    else if (flux_npars(model) == 0)
+        why = "model must be -1 (a point source) or one of NGMIX_KFIT_*";
+    else if (R < 1 || C < 1 || R > 0x7fff || C > 0x7fff) why = "the stamp shape must be 1..32767";
+    else if (nstamps == 0) nothing = true;
+    else if (!dhat || !wbar || !jac || !pars || !out)
+        why = "dhat, wbar, jac, pars and out are required";
+    else if (nstamps > 0x7fffffffll) why = "too many stamps for one launch";
+    if (!why) return NGMIX_OK;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    set_last_error_msg(msg);
+    return NGMIX_ERR_BAD_ARG;
+}
+
+// the host twin of kfit_flux_kernel
+template <int MODEL>
+inline void host_flux(const double *dhat, const double *phat, const double *wbar,
+                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                      const double *pars, double *out, int32_t *status)
+{
+    const int CH = C / 2 + 1, nm = R * CH, np = flux_npars(MODEL);
+    std::vector<double> part((size_t)LANES * 3);
+    for (int64_t s = 0; s < nstamps; s++) {
+        const Setup m = flux_setup<MODEL>(pars + s * np, jac[s], wbar[s], R, C);
+        if (m.bad) {
+            write_flux_refused(out + 3 * s);
+            if (status) status[s] = NGMIX_ERR_G_RANGE;
+            continue;
+        }
+        const double *D = dhat + (size_t)s * nm * 2;
+        const double *P = phat ? phat + (size_t)s * nm * 2 : nullptr;
+        bool notfinite = false;
+        for (int l = 0; l < LANES; l++) {
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int i = l; i < nm; i += LANES) {
+                const int a = i / CH, b = i - a * CH;
+                const double mult = mode_mult(a, b, R, C);
+                if (mult == 0.0) continue;
+                const double dr = D[2 * i], di = D[2 * i + 1];
+                const double pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
+                if (!isfinite(dr + di + pr + pi)) notfinite = true;
+                flux_mode<MODEL>(m, a, b, R, mult, dr, di, pr, pi, acc);
+            }
+            for (int k = 0; k < 3; k++) part[(size_t)k * LANES + l] = acc[k];
+        }
+        for (int k = 0; k < 3; k++) {
+            double *x = part.data() + (size_t)k * LANES;
+            for (int off = LANES / 2; off > 0; off >>= 1)
+                for (int l = 0; l < off; l++) x[l] += x[l + off];
+            out[3 * s + k] = x[0];
+        }
+        if (notfinite) write_flux_refused(out + 3 * s);
+        if (status) status[s] = notfinite ? NGMIX_ERR_NOT_FINITE : NGMIX_OK;
+    }
+}
+
+// host_flux<M> for the M of the list that equals model
+template <int... MS, typename... A>
+inline void host_flux_for(int model, A... args)
+{
+    (void)((model == MS ? (host_flux<MS>(args...), true) : false) || ...);
 }
 
 }  // namespace kfit

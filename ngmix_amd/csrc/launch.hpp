@@ -186,6 +186,10 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
                      double *stamp_stats, hipStream_t s);
 int launch_kfit_rounds(const ngmix_kfit_problem *p, int nrounds, int32_t *counts,
                        int32_t *counts_host, void **events, hipStream_t s);
+int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
+                     const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                     const double *pars, double *out, int32_t *status, hipStream_t s);
+int launch_moffat_phi(const double *nu, const double *x, int64_t n, double *out, hipStream_t s);
 
 int launch_lm_prior_finish(const ngmix_lm_state *states, int64_t nobj,
                            const ngmix_simple_sep_prior *prior, double *ffx, double *lnp,

@@ -1,9 +1,11 @@
 """
-Fourier-space profile fits: 'gauss', 'exp' and 'spergel'
-fitted to the transform of a stamp's own samples.
+Fourier-space profile fits: 'gauss', 'exp', 'spergel'
+and 'moffat' fitted to the transform of a stamp's own samples, and the linear
+flux of a fixed profile or of the psf in the same definition.
 
-The reference's GalsimFitter / GalsimSpergelFitter fit the exact profile to a
-k-space observation that galsim draws.  Here the observation is the rfft2 half
+The reference's GalsimFitter / GalsimSpergelFitter / GalsimMoffatFitter fit the
+exact profile to a k-space observation that galsim draws, and its
+GalsimPSFFluxFitter the flux of the psf there.  Here the observation is the rfft2 half
 plane of the stamp itself times the centre phase, the psf enters as the
 transform of its own stamp (no psf model is fitted), and the lock-step LM
 driver of ngmix_amd/lm_batch.py runs with kfit_eval_kernel in place of the
@@ -14,14 +16,21 @@ pixel pass:
     KSpaceFitter             Observation / ObsList / MultiBandObsList in, one
                              batch per call
     kmodel_images            the model's real-space image, for residuals
+    KSpaceFluxBatch          the linear flux of a fixed unit-flux template (a
+                             model at given parameters, or the psf itself) per
+                             object: kfit_flux_kernel, no LM
+    KSpaceFluxFitter         the same for Observation / ObsList
 
 What this is NOT: the pixel values of a KStampBatch are not galsim's (no
 interpolant, no stepk / getGoodImageSize grid), the weight is the Parseval
 weight (twice the reference's), aliases of the profile are not summed (galsim's
-k-space fit does not sum them either), and 'dev' and Moffat are not offered.
+k-space fit does not sum them either), the Moffat profile is not truncated,
+and 'dev' is not offered (it has no closed-form transform).
 
 Parameters: [cen1, cen2, g1, g2, r50, F_band...]; 'spergel':
-[cen1, cen2, g1, g2, r50, nu, F_band...].
+[cen1, cen2, g1, g2, r50, nu, F_band...]; 'moffat': [cen1, cen2, g1, g2, size,
+beta, F_band...], the size r50 (size_type 'r50', the default, or its aliases
+'hlr' / 'half_light_radius') or the fwhm (size_type 'fwhm').
 """
 import ctypes
 import math
@@ -34,20 +43,42 @@ from .defaults import PDEF, CDEF, DEFAULT_LM_PARS
 from .fitting import STEP_PRIOR
 from .prior_batch import as_batch_prior, bounds_arrays
 
-__all__ = ["KStampBatch", "KSpaceBatchFitter", "KSpaceFitter", "kmodel_images"]
+__all__ = ["KStampBatch", "KSpaceBatchFitter", "KSpaceFitter", "kmodel_images",
+           "KSpaceFluxBatch", "KSpaceFluxFitter"]
 
-MODELS = {"gauss": _lib.KFIT_GAUSS, "exp": _lib.KFIT_EXP, "spergel": _lib.KFIT_SPERGEL}
-MODEL_NLOC = {"gauss": 6, "exp": 6, "spergel": 7}
+MODELS = {"gauss": _lib.KFIT_GAUSS, "exp": _lib.KFIT_EXP, "spergel": _lib.KFIT_SPERGEL,
+          "moffat": _lib.KFIT_MOFFAT}
+MODEL_NLOC = {"gauss": 6, "exp": 6, "spergel": 7, "moffat": 7}
+SIZE_TYPES = ("r50", "hlr", "half_light_radius", "fwhm")
 HLR_GAUSS = math.sqrt(2.0 * math.log(2.0))
 HLR_EXP = 1.6783469900166605
 ROUNDS_FIRST = 12      # rounds queued blind before the first look at the counts
 
 
-def _model_id(model):
+def _model_id(model, size_type=None):
     if model not in MODELS:
         raise ValueError("k-space fits offer %s, got %r ('dev' has no closed-form transform)"
                          % (tuple(MODELS), model))
+    if size_type is not None:
+        if size_type not in SIZE_TYPES:
+            raise ValueError("size_type must be one of %s, got %r" % (SIZE_TYPES, size_type))
+        if model != "moffat" and size_type == "fwhm":
+            raise ValueError("size_type 'fwhm' is the Moffat fit's; '%s' takes r50" % model)
+        if model == "moffat" and size_type == "fwhm":
+            return _lib.KFIT_MOFFAT_FWHM
     return MODELS[model]
+
+
+def _moffat_phi(nu, x):
+    """Phi of the Moffat transform at the pairs (nu, x), device tensors of one
+    shape, by ngmix_moffat_phi_batch"""
+    torch = _torch()
+    nu, x = nu.contiguous(), x.contiguous()
+    out = torch.empty(x.shape + (3,), dtype=torch.float64, device=x.device)
+    with _on_device(x.device):
+        _lib.check(_lib.lib().ngmix_moffat_phi_batch(_dptr(nu), _dptr(x), x.numel(), _dptr(out),
+                                                     _stream()), "ngmix_moffat_phi_batch")
+    return out[..., 0]
 
 
 def _mode_grid(R, C, dev):
@@ -141,7 +172,7 @@ def _spergel_hlr(nu):
     return c.value
 
 
-def kmodel_images(kb, pars, model):
+def kmodel_images(kb, pars, model, size_type=None):
     """
     The real-space images (N, R, C) of the band-limited, periodic model at
     pars (N, nloc) -- each stamp's LOCAL parameters, one flux -- by irfft2 of
@@ -149,7 +180,7 @@ def kmodel_images(kb, pars, model):
     Nyquist modes included here, dropped there).  torch ops; not a hot path.
     """
     torch = _torch()
-    _model_id(model)
+    model_id = _model_id(model, size_type)
     nloc = MODEL_NLOC[model]
     p = _as_device_f64(np.asarray(pars) if not hasattr(pars, "device") else pars, kb.device)
     if p.shape != (kb.n, nloc):
@@ -165,6 +196,10 @@ def kmodel_images(kb, pars, model):
     if model == "spergel":
         c = torch.tensor([_spergel_hlr(v) for v in p[:, 5].cpu().numpy()],
                          dtype=torch.float64, device=kb.device)
+    elif model_id == _lib.KFIT_MOFFAT:
+        c = torch.sqrt(torch.expm1(math.log(2.0) / (p[:, 5] - 1.0)))
+    elif model_id == _lib.KFIT_MOFFAT_FWHM:
+        c = 2.0 * torch.sqrt(torch.expm1(math.log(2.0) / p[:, 5]))
     else:
         c = torch.full((kb.n,), HLR_GAUSS if model == "gauss" else HLR_EXP,
                        dtype=torch.float64, device=kb.device)
@@ -176,6 +211,8 @@ def kmodel_images(kb, pars, model):
         phi = torch.exp(-0.5 * s)
     elif model == "exp":
         phi = (1.0 + s) ** -1.5
+    elif model == "moffat":
+        phi = _moffat_phi((col(p[:, 5]) - 1.0).expand_as(s), torch.sqrt(s))
     else:
         phi = torch.exp(-(1.0 + col(p[:, 5])) * torch.log1p(s))
     theta = kv * col(p[:, 0]) + ku * col(p[:, 1])
@@ -196,13 +233,20 @@ class KSpaceBatchFitter(object):
 
     prior: a batch prior whose descriptor() the device prior kernel serves
     (PriorSimpleSepBatch for 'gauss' / 'exp', PriorSpergelSepBatch for
-    'spergel', or a joint_prior object as_batch_prior converts), up to
+    'spergel' and for 'moffat', whose beta it serves as the one middle term, or
+    a joint_prior object as_batch_prior converts), up to
     NGMIX_PRIOR_MAXBAND bands; bounds: [(lo, hi)] * npars (None: the prior's),
-    run through leastsqbound's transform by ngmix_lm_init_batch.
+    run through leastsqbound's transform by ngmix_lm_init_batch.  size_type
+    ('moffat'): what parameter 4 is, 'r50' (or 'hlr', 'half_light_radius') or
+    'fwhm'.  round_s2n: one more evaluation at the fitted parameters with g = 0
+    adds 's2n_r' = sqrt(sum over stamps of sum w |M^|^2) to the result.
     """
 
-    def __init__(self, model, prior=None, fit_pars=None, bounds=None):
-        self.model_id = _model_id(model)
+    def __init__(self, model, prior=None, fit_pars=None, bounds=None, size_type=None,
+                 round_s2n=False):
+        self.model_id = _model_id(model, size_type)
+        self.size_type = size_type
+        self.round_s2n = bool(round_s2n)
         self.model = model
         self.nloc = MODEL_NLOC[model]
         self.prior = as_batch_prior(prior)
@@ -339,8 +383,36 @@ class KSpaceBatchFitter(object):
             flat = d_flat.cpu().numpy()
             tri = d_tri.cpu().numpy()
             self.stamp_status = d_status.cpu().numpy()
+            s2n_r = self._round_s2n(kb, P, d_states, d_sobj, nobj, n) if self.round_s2n else None
         self._d_states = d_states
-        return self._package(flat, tri, nobj, n)
+        res = self._package(flat, tri, nobj, n)
+        if s2n_r is not None:
+            res["s2n_r"] = s2n_r
+        return res
+
+    def _round_s2n(self, kb, P, d_states, d_sobj, nobj, n):
+        """sqrt(sum w |M^|^2) over each object's stamps at its fitted parameters
+        with g = 0: one evaluation on a copy of the states (xt = x, g zeroed,
+        every fit running again), read from the stamp_stats column"""
+        torch = _torch()
+        L = _lib.lib()
+        dev = kb.device
+        rec = _lib.LM_STATE_DTYPE
+        states = np.frombuffer(d_states.cpu().numpy().tobytes(), dtype=rec).copy()
+        states["xt"] = states["x"]
+        states["xt"][:, 2:4] = 0.0
+        states["phase"] = 0
+        d_copy = torch.from_numpy(states.view(np.uint8)).to(dev)
+        d_sums = torch.empty((kb.n, _lib.LM_NSUM if self.nloc == 6 else 36), dtype=torch.float64,
+                             device=dev)
+        d_stats = torch.zeros((kb.n, 2), dtype=torch.float64, device=dev)
+        _lib.check(L.ngmix_kfit_eval_batch(
+            P.dhat, P.phat, P.wbar, P.jac, kb.nrow, kb.ncol, kb.n, self.model_id,
+            _dptr(d_copy), P.stamp_obj, P.stamp_band, _dptr(d_sums), None, _dptr(d_stats),
+            _stream()), "ngmix_kfit_eval_batch")
+        mm = torch.zeros(nobj, dtype=torch.float64, device=dev)
+        mm.index_add_(0, d_sobj.long(), d_stats[:, 1])
+        return torch.sqrt(mm).cpu().numpy()
 
     def states(self):
         """the raw ngmix_lm_state records of the last go() (debugging, tests)"""
@@ -366,7 +438,39 @@ class KSpaceBatchFitter(object):
         }
         if self.model == "spergel":
             res["nu"] = pars[:, 5].copy()
+        if self.model == "moffat":
+            res["beta"] = pars[:, 5].copy()
         return res
+
+
+def _flatten_to_kbatch(list_of_obs):
+    """the stamps of a list of Observation / ObsList / MultiBandObsList as one
+    KStampBatch, with the object and the band of each stamp"""
+    from .observation import get_mb_obs
+    images, weights, jacs, pimages, pjacs, sobj, sband = [], [], [], [], [], [], []
+    for i, obs in enumerate(list_of_obs):
+        for band, olist in enumerate(get_mb_obs(obs)):
+            for o in olist:
+                images.append(o.image)
+                weights.append(o.weight)
+                jacs.append(o.jacobian._data)
+                if o.has_psf():
+                    pimages.append(o.psf.image)
+                    pjacs.append(o.psf.jacobian._data)
+                sobj.append(i)
+                sband.append(band)
+    if pimages and len(pimages) != len(images):
+        raise ValueError("either every observation carries a psf or none does")
+    shapes = {im.shape for im in images} | {("psf",) + im.shape for im in pimages}
+    if len({s for s in shapes if s[0] != "psf"}) != 1 or \
+            len({s for s in shapes if s[0] == "psf"}) > 1:
+        raise ValueError("a k-space batch holds stamps of one shape")
+    kb = KStampBatch.from_images(
+        np.stack(images), np.stack(weights), np.concatenate(jacs).view(np.float64).reshape(-1, 8),
+        psf_images=np.stack(pimages) if pimages else None,
+        psf_jacobians=np.concatenate(pjacs).view(np.float64).reshape(-1, 8)
+        if pimages else None)
+    return kb, sobj, sband
 
 
 class KSpaceFitter(object):
@@ -377,41 +481,132 @@ class KSpaceFitter(object):
     either all of them carry a psf observation or none does.
     """
 
-    def __init__(self, model, prior=None, fit_pars=None):
-        self._batch = KSpaceBatchFitter(model, prior=prior, fit_pars=fit_pars)
+    def __init__(self, model, prior=None, fit_pars=None, size_type=None, round_s2n=False):
+        self._batch = KSpaceBatchFitter(model, prior=prior, fit_pars=fit_pars,
+                                        size_type=size_type, round_s2n=round_s2n)
         self.model = model
 
     def go(self, obs, guess):
         return self.go_many([obs], [guess])[0]
 
     def go_many(self, list_of_obs, guesses):
-        from .observation import get_mb_obs
-        images, weights, jacs, pimages, pjacs, sobj, sband = [], [], [], [], [], [], []
-        for i, obs in enumerate(list_of_obs):
-            for band, olist in enumerate(get_mb_obs(obs)):
-                for o in olist:
-                    images.append(o.image)
-                    weights.append(o.weight)
-                    jacs.append(o.jacobian._data)
-                    if o.has_psf():
-                        pimages.append(o.psf.image)
-                        pjacs.append(o.psf.jacobian._data)
-                    sobj.append(i)
-                    sband.append(band)
-        if pimages and len(pimages) != len(images):
-            raise ValueError("either every observation carries a psf or none does")
-        shapes = {im.shape for im in images} | {("psf",) + im.shape for im in pimages}
-        if len({s for s in shapes if s[0] != "psf"}) != 1 or \
-                len({s for s in shapes if s[0] == "psf"}) > 1:
-            raise ValueError("a k-space batch holds stamps of one shape")
-        kb = KStampBatch.from_images(
-            np.stack(images), np.stack(weights), np.concatenate(jacs).view(np.float64).reshape(-1, 8),
-            psf_images=np.stack(pimages) if pimages else None,
-            psf_jacobians=np.concatenate(pjacs).view(np.float64).reshape(-1, 8)
-            if pimages else None)
+        kb, sobj, sband = _flatten_to_kbatch(list_of_obs)
         res = self._batch.go(kb, np.atleast_2d(np.asarray(guesses, dtype=np.float64)),
                              stamp_obj=sobj, stamp_band=sband)
         out = []
         for i in range(len(list_of_obs)):
             out.append({k: (v if isinstance(v, str) else v[i]) for k, v in res.items()})
         return out
+
+
+class KSpaceFluxBatch(object):
+    """
+    The linear flux of a FIXED unit-flux template in the k-space definition of
+    the fits, per object over its stamps of one band (kfit_flux_kernel: three
+    sums per stamp, no LM):
+
+        res = KSpaceFluxBatch().go(kb)                       # the psf's flux
+        res = KSpaceFluxBatch("exp", pars).go(kb)            # a profile's
+
+    model None: a point source at the stamp's centre, so the template is the
+    psf itself (the reference's GalsimPSFFluxFitter); pars is then None, or
+    (nstamps, 2) centres.  Otherwise pars (nstamps, nloc - 1): each stamp's
+    [cen1, cen2, g1, g2, size, (nu | beta)].  res: (nobj,) arrays flags, flux,
+    flux_err, chi2per, dof, as PSFFluxBatch gives them: where the template's
+    sum is not positive or a sum is not finite, DIV_ZERO with flux = PDEF,
+    flux_err = CDEF and chi2per = 0.
+    """
+
+    def __init__(self, model=None, pars=None, size_type=None):
+        self.model = model
+        self.model_id = _lib.KFIT_POINT if model is None else _model_id(model, size_type)
+        self.npars = 5 if model is None else MODEL_NLOC[model] - 1
+        self.pars = pars
+
+    def sums(self, kb):
+        """the per-stamp sums (nstamps, 3) and status, device tensors"""
+        torch = _torch()
+        dev = kb.device
+        if self.pars is None:
+            if self.model is not None:
+                raise ValueError("a '%s' template needs its parameters" % self.model)
+            p = np.zeros((kb.n, 5))
+        else:
+            p = self.pars
+        d_p = _as_device_f64(np.asarray(p) if not hasattr(p, "device") else p, dev)
+        if self.model is None and d_p.shape == (kb.n, 2):
+            d_p = torch.cat([d_p, torch.zeros((kb.n, 3), dtype=torch.float64, device=dev)], dim=1)
+        if d_p.shape != (kb.n, self.npars):
+            raise ValueError("pars must be (%d, %d)" % (kb.n, self.npars))
+        d_p = d_p.contiguous()
+        with _on_device(dev):
+            d_out = torch.empty((kb.n, 3), dtype=torch.float64, device=dev)
+            d_status = torch.zeros(kb.n, dtype=torch.int32, device=dev)
+            _lib.check(_lib.lib().ngmix_kfit_flux_batch(
+                _dptr(kb.dhat), _dptr(kb.phat) if kb.phat is not None else None, _dptr(kb.wbar),
+                ctypes.c_void_p(kb.jac.data_ptr()), kb.nrow, kb.ncol, kb.n, self.model_id,
+                _dptr(d_p), _dptr(d_out), _dptr(d_status), _stream()), "ngmix_kfit_flux_batch")
+        return d_out, d_status
+
+    def go(self, kb, stamp_obj=None, stamp_band=None):
+        from .flags import DIV_ZERO
+        ns = kb.n
+        sobj = np.arange(ns, dtype=np.int64) if stamp_obj is None else \
+            np.ascontiguousarray(stamp_obj, dtype=np.int64)
+        if sobj.shape != (ns,) or (ns and sobj.min() < 0):
+            raise ValueError("stamp_obj must be (nstamps,) object indices")
+        if stamp_band is not None:
+            sband = np.asarray(stamp_band)
+            if sband.shape != (ns,):
+                raise ValueError("stamp_band has one entry per stamp")
+            for o in np.unique(sobj):
+                if np.unique(sband[sobj == o]).size != 1:
+                    raise ValueError("the stamps of an object must be of one band")
+        d_out, d_status = self.sums(kb)
+        out = d_out.cpu().numpy()
+        self.stamp_status = d_status.cpu().numpy()
+        nobj = int(sobj.max()) + 1 if ns else 0
+        A, B, E = (np.bincount(sobj, weights=out[:, k], minlength=nobj) for k in range(3))
+        nstamp = np.bincount(sobj, minlength=nobj)
+        bad_stamp = np.bincount(sobj, weights=self.stamp_status != 0, minlength=nobj) > 0
+        with np.errstate(all="ignore"):
+            bad = ~(B > 0) | ~np.isfinite(A + B + E) | bad_stamp
+            Bs = np.where(bad, 1.0, B)
+            flux = np.where(bad, PDEF, A / Bs)
+            flux_err = np.where(bad, CDEF, 1.0 / np.sqrt(Bs))
+            chi2 = np.where(bad, 0.0, E - A * A / Bs)
+        dof = (nstamp * kb.npix_eff - 1).astype("f8")
+        dof = np.where(dof <= 0, 1.0e-6, dof)
+        flags = np.where(bad, DIV_ZERO, 0).astype(np.int64)
+        return {"flags": flags, "flux": flux, "flux_err": flux_err, "chi2per": chi2 / dof,
+                "dof": dof}
+
+
+class KSpaceFluxFitter(object):
+    """
+    KSpaceFluxBatch for Observation / ObsList, the two the reference's
+    GalsimPSFFluxFitter takes: go(obs) one dict, go_many(list) a dict of
+    (nobj,) arrays.  model None: the psf's flux (every observation carries a
+    psf); a model name with pars [cen1, cen2, g1, g2, size, (nu | beta)] per
+    object: that profile's.
+    """
+
+    def __init__(self, model=None, size_type=None):
+        self.model = model
+        self.size_type = size_type
+
+    def go(self, obs, pars=None):
+        res = self.go_many([obs], None if pars is None else [pars])
+        return {k: v[0] for k, v in res.items()}
+
+    def go_many(self, list_of_obs, pars=None):
+        from .observation import Observation, ObsList
+        for obs in list_of_obs:
+            if not isinstance(obs, (Observation, ObsList)):
+                raise ValueError("obs should be Observation or ObsList")
+        kb, sobj, _ = _flatten_to_kbatch(list_of_obs)
+        if self.model is None and kb.phat is None:
+            raise ValueError("the psf flux needs the observations' psf images")
+        if pars is not None:
+            pars = np.atleast_2d(np.asarray(pars, dtype=np.float64))[np.asarray(sobj)]
+        return KSpaceFluxBatch(self.model, pars, size_type=self.size_type).go(kb, stamp_obj=sobj)

@@ -38,7 +38,8 @@ GUARDS = {
 # register-heavy on purpose (the stamp or the accumulators live in VGPRs):
 # only memory spills are an error
 NO_SPILL_ONLY = ("admom_grid_kernel", "em_wave_kernel", "wsums_wave_kernel",
-                 "lm_eval_kernel", "lm_eval_fd_kernel", "kfit_eval_kernel")
+                 "lm_eval_kernel", "lm_eval_fd_kernel", "kfit_eval_kernel", "kfit_flux_kernel",
+                 "moffat_phi_kernel")
 
 
 def code_objects(lib):

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """
-Timing of the Fourier-space fits on one GPU: kfit_eval_kernel
-per launch (device events, the median of 7 after 2 warm-ups) and whole fits per
-second through KSpaceBatchFitter, for N 32x32 and 48x48 stamps, 'exp' and
-'spergel', each stamp with a psf transform.
+Timing of the Fourier-space fits on one GPU:
+kfit_eval_kernel per launch (device events, the median of 7 after 2 warm-ups)
+and whole fits per second through KSpaceBatchFitter, for N 32x32 and 48x48
+stamps, 'exp' and 'spergel', each stamp with a psf transform.
 
-    python tools/time_kfit.py [--n 100000] [--json out.json]
+    python tools/time_kfit.py [--n 100000] [--json out.json] [--model moffat] [--flux]
+
+--model moffat times 'spergel' and 'moffat' side by side (the ratio says
+whether K_nu or the sums dominate); --flux adds kfit_flux_kernel per launch for
+the point source and for each timed model.
 
 The real-space LMBatchFitter is a different model (a gaussian mixture against
 a fitted psf mixture) and is not timed here; nothing gates on these figures.
@@ -25,7 +29,8 @@ import torch  # noqa: E402
 
 from ngmix_amd import _lib  # noqa: E402
 from ngmix_amd.batch import _stream  # noqa: E402
-from ngmix_amd.kfit import KSpaceBatchFitter, KStampBatch, kmodel_images, MODEL_NLOC  # noqa: E402
+from ngmix_amd.kfit import (KSpaceBatchFitter, KStampBatch, kmodel_images, MODEL_NLOC,  # noqa: E402
+                            MODELS)
 
 
 def make_batch(n, dim, model, seed):
@@ -46,6 +51,8 @@ def make_batch(n, dim, model, seed):
             rng.uniform(-0.2, 0.2, n), rng.uniform(-0.2, 0.2, n), scale * rng.uniform(1.5, 2.5, n)]
     if model == "spergel":
         cols.append(rng.uniform(0.0, 1.5, n))
+    if model == "moffat":
+        cols.append(rng.uniform(2.0, 4.5, n))
     cols.append(rng.uniform(50.0, 150.0, n))
     truth = np.stack(cols, axis=1)
     # the data: the model's own image plus noise
@@ -78,9 +85,34 @@ def time_eval(kb, guess, model):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         _lib.check(L.ngmix_kfit_eval_batch(p(kb.dhat), p(kb.phat), p(kb.wbar), p(kb.jac), kb.nrow,
-                                           kb.ncol, n, _lib.KFIT_EXP if model == "exp"
-                                           else _lib.KFIT_SPERGEL, p(d_states), None, None, p(sums),
-                                           p(status), p(stats), _stream()), "ngmix_kfit_eval_batch")
+                                           kb.ncol, n, MODELS[model], p(d_states), None, None,
+                                           p(sums), p(status), p(stats), _stream()),
+                   "ngmix_kfit_eval_batch")
+        b.record()
+        b.synchronize()
+        if it >= 2:
+            ms.append(a.elapsed_time(b))
+    assert int((status != 0).sum()) == 0
+    return float(np.median(ms))
+
+
+def time_flux(kb, guess, model):
+    """kfit_flux_kernel per launch; model None: the point source"""
+    L = _lib.lib()
+    n = guess.shape[0]
+    npars = 5 if model is None else MODEL_NLOC[model] - 1
+    d_pars = torch.from_numpy(np.ascontiguousarray(guess[:, :npars])).cuda()
+    out = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    ms = []
+    for it in range(9):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        _lib.check(L.ngmix_kfit_flux_batch(p(kb.dhat), p(kb.phat), p(kb.wbar), p(kb.jac), kb.nrow,
+                                           kb.ncol, n, _lib.KFIT_POINT if model is None
+                                           else MODELS[model], p(d_pars), p(out), p(status),
+                                           _stream()), "ngmix_kfit_flux_batch")
         b.record()
         b.synchronize()
         if it >= 2:
@@ -106,16 +138,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=100000)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--model", default=None, choices=["moffat"])
+    ap.add_argument("--flux", action="store_true")
     args = ap.parse_args()
     out = []
     for dim in (32, 48):
-        for model in ("exp", "spergel"):
+        for model in ("spergel", "moffat") if args.model == "moffat" else ("exp", "spergel"):
             kb, guess = make_batch(args.n, dim, model, 5)
             ev = time_eval(kb, guess, model)
             sec, ok, rounds = time_fit(kb, guess, model)
             row = {"model": model, "dim": dim, "n": args.n, "eval_ms": ev,
                    "modes_per_stamp": dim * (dim // 2 + 1), "fit_s": sec,
                    "fits_per_s": args.n / sec, "flags_ok": ok, "rounds": rounds}
+            if args.flux:
+                row["flux_ms"] = time_flux(kb, guess, model)
+                row["flux_point_ms"] = time_flux(kb, guess, None)
             print(json.dumps(row), flush=True)
             out.append(row)
             del kb
