@@ -469,6 +469,33 @@ int ngmix_metacal_dilate_psf_spectrum_batch(const double *psf, const ngmix_jacob
                                             int64_t nstamps, int ntypes, int psf_nrow,
                                             int psf_ncol, double *spec, int32_t *flags,
                                             void *stream);
+/* DEVICE: the metacal spectra in the layout of the Fourier-space fits (DESIGN.md
+   3.26): the operation of ngmix_metacal_spectrum_batch (sigma given: the round
+   gaussian target; dil, kind and their host copies are not read) or of
+   ngmix_metacal_dilate_spectrum_batch (sigma NULL), without a noise plane,
+   written for ngmix_kfit_eval_batch instead of an inverse FFT.  TYPE-major
+   outputs, stamp t nstamps + n:
+     dhat (ntypes nstamps, nrow, ncol/2+1, 2)  O^(q) about the jacobian centre
+         (no centre phase);
+     phat the same shape: T^(q) / psf_flux, the target psf the fit's model is
+         multiplied with (psf_flux (nstamps,): the psf stamps' sums, required
+         under either target);
+     aux the same shape, real pairs: 1 where the mode is kept and 0 where the
+         band limit dropped it; rho^2 = |T^(q)|^2 / |P^(q')|^2, the factor by
+         which the operation scales the variance of white pixel noise there.
+   A dropped mode is zeros in all three; so are the Nyquist row and column of
+   an even axis, which the fits drop (no partner items are evaluated).  flags
+   (ntypes, nstamps): 1 where a kept mode was not finite.  The other arguments
+   and the refusals as the two entry points above */
+int ngmix_metacal_kfit_spectrum_batch(const double *images, const double *psf,
+                                      const ngmix_jacobian *jac, const double *psf_cen,
+                                      const double *psf_flux, const double *sigma,
+                                      const double *g, const double *dil, const int32_t *kind,
+                                      const double *g_host, const double *dil_host,
+                                      const int32_t *kind_host, int per_stamp_g,
+                                      int64_t nstamps, int ntypes, int nrow, int ncol,
+                                      int psf_nrow, int psf_ncol, double *dhat, double *phat,
+                                      double *aux, int32_t *flags, void *stream);
 /* DEVICE: the noise planes of metacalibration's fixnoise as a pure function of
    (seed, object id, pixel).  Philox4x32-10 with the standard round constants
    and Weyl key increments, key = (seed & 0xffffffff, seed >> 32), counter =
@@ -1305,6 +1332,46 @@ typedef struct {
 int ngmix_kfit_rounds_batch(const ngmix_kfit_problem *problem, int nrounds,
                             int32_t *counts, int32_t *counts_host, void **events,
                             void *stream);
+/* DEVICE: the MODEW form of ngmix_kfit_eval_batch: one more
+   real plane mode_weight (nstamps, R, C/2+1), u >= 0 per stored mode, and
+   omega u wherever the evaluation has the Parseval weight omega -- the residual
+   rows, J^T J, J^T f, f.f and both stamp_stats.  A mode with u = 0 is not read:
+   a non-finite dhat there is no error.  A u that is negative or not finite on
+   a mode with omega > 0 gives NGMIX_ERR_NOT_FINITE and the refused sums.  ncomp
+   (nstamps,), may be NULL: the residual components with omega u > 0, what dof
+   counts (written for a refused stamp too, left alone for a finished fit's).
+   The order of the sums is the unweighted kernel's: with u = 1 everywhere the
+   sums are its sums bit for bit */
+int ngmix_kfit_eval_w_batch(const double *dhat, const double *phat, const double *mode_weight,
+                            const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                            int64_t nstamps, int model, const ngmix_lm_state *states,
+                            const int32_t *stamp_obj, const int32_t *stamp_band,
+                            double *sums, int32_t *status, double *stamp_stats,
+                            int32_t *ncomp, void *stream);
+/* HOST: the same for arrays in host memory, the same text and order of sums */
+int ngmix_kfit_eval_w_host(const double *dhat, const double *phat, const double *mode_weight,
+                           const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                           int64_t nstamps, int model, const ngmix_lm_state *states,
+                           const int32_t *stamp_obj, const int32_t *stamp_band,
+                           double *sums, int32_t *status, double *stamp_stats,
+                           int32_t *ncomp);
+/* DEVICE: the MODEW form of ngmix_kfit_flux_batch: mode_weight and ncomp as
+   ngmix_kfit_eval_w_batch takes them, omega u in all three sums */
+int ngmix_kfit_flux_w_batch(const double *dhat, const double *phat, const double *mode_weight,
+                            const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                            int64_t nstamps, int model, const double *pars, double *out,
+                            int32_t *status, int32_t *ncomp, void *stream);
+/* HOST: the same for arrays in host memory, the same order of sums */
+int ngmix_kfit_flux_w_host(const double *dhat, const double *phat, const double *mode_weight,
+                           const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                           int64_t nstamps, int model, const double *pars, double *out,
+                           int32_t *status, int32_t *ncomp);
+/* DEVICE: ngmix_kfit_rounds_batch with ngmix_kfit_eval_w_batch as the
+   evaluation: the record as it is, mode_weight (problem->nstamps, nrow,
+   ncol/2+1) and ncomp (problem->nstamps,) or NULL beside it */
+int ngmix_kfit_rounds_w_batch(const ngmix_kfit_problem *problem, const double *mode_weight,
+                              int32_t *ncomp, int nrounds, int32_t *counts,
+                              int32_t *counts_host, void **events, void *stream);
 /* HOST: n timing events (hipEvent_t) for ngmix_lm_rounds_batch / to record
    on a stream; elapsed milliseconds between two recorded events (both must
    have completed: synchronise the stream or the later event first) */

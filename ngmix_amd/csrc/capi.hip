@@ -582,6 +582,30 @@ int ngmix_metacal_dilate_psf_spectrum_batch(const double *psf, const ngmix_jacob
                                           (hipStream_t)stream);
 }
 
+int ngmix_metacal_kfit_spectrum_batch(const double *images, const double *psf,
+                                      const ngmix_jacobian *jac, const double *psf_cen,
+                                      const double *psf_flux, const double *sigma,
+                                      const double *g, const double *dil, const int32_t *kind,
+                                      const double *g_host, const double *dil_host,
+                                      const int32_t *kind_host, int per_stamp_g,
+                                      int64_t nstamps, int ntypes, int nrow, int ncol,
+                                      int psf_nrow, int psf_ncol, double *dhat, double *phat,
+                                      double *aux, int32_t *flags, void *stream)
+{
+    if (nstamps > 0 && (!phat || !aux)) {
+        set_last_error_msg("metacal_kfit_spectrum: phat and aux are required");
+        return NGMIX_ERR_BAD_ARG;
+    }
+    if (sigma)
+        return launch_metacal_spectrum(images, nullptr, psf, jac, psf_cen, psf_flux, sigma, g,
+                                       g_host, per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow,
+                                       psf_ncol, dhat, flags, (hipStream_t)stream, phat, aux);
+    return launch_metacal_dilate_spectrum(images, nullptr, psf, jac, psf_cen, g, dil, kind, g_host,
+                                          dil_host, kind_host, per_stamp_g, nstamps, ntypes, nrow,
+                                          ncol, psf_nrow, psf_ncol, dhat, flags, false,
+                                          (hipStream_t)stream, psf_flux, phat, aux);
+}
+
 int ngmix_metacal_noise_batch(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                               int nrow, int ncol, int rot_k, double *out, void *stream)
 {
@@ -1122,6 +1146,84 @@ int ngmix_kfit_flux_host(const double *dhat, const double *phat, const double *w
                         NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(
         model, dhat, phat, wbar, jac, R, C, nstamps, pars, out, status);
     return NGMIX_OK;
+}
+
+// the MODEW entries need their plane (a call with no stamps aside)
+static int need_modew(const char *who, const double *modew, int64_t nstamps)
+{
+    if (modew || nstamps <= 0) return NGMIX_OK;
+    set_last_error_msg((std::string(who) + ": mode_weight is required").c_str());
+    return NGMIX_ERR_BAD_ARG;
+}
+
+int ngmix_kfit_eval_w_batch(const double *dhat, const double *phat, const double *mode_weight,
+                            const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                            int64_t nstamps, int model, const ngmix_lm_state *states,
+                            const int32_t *stamp_obj, const int32_t *stamp_band, double *sums,
+                            int32_t *status, double *stamp_stats, int32_t *ncomp, void *stream)
+{
+    const int st = need_modew("kfit_eval_w", mode_weight, nstamps);
+    if (st != NGMIX_OK) return st;
+    return launch_kfit_eval(dhat, phat, wbar, jac, R, C, nstamps, model, states, stamp_obj,
+                            stamp_band, sums, status, stamp_stats, (hipStream_t)stream,
+                            mode_weight, ncomp);
+}
+
+int ngmix_kfit_eval_w_host(const double *dhat, const double *phat, const double *mode_weight,
+                           const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                           int64_t nstamps, int model, const ngmix_lm_state *states,
+                           const int32_t *stamp_obj, const int32_t *stamp_band, double *sums,
+                           int32_t *status, double *stamp_stats, int32_t *ncomp)
+{
+    bool nothing;
+    int st = kfit::check_args("kfit_eval_w_host", dhat, wbar, jac, R, C, nstamps, model, states,
+                              sums, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    st = need_modew("kfit_eval_w_host", mode_weight, nstamps);
+    if (st != NGMIX_OK) return st;
+    kfit::host_eval_w_for<NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL, NGMIX_KFIT_MOFFAT,
+                          NGMIX_KFIT_MOFFAT_FWHM>(model, dhat, phat, wbar, jac, R, C, nstamps,
+                                                  states, stamp_obj, stamp_band, sums, status,
+                                                  stamp_stats, mode_weight, ncomp);
+    return NGMIX_OK;
+}
+
+int ngmix_kfit_flux_w_batch(const double *dhat, const double *phat, const double *mode_weight,
+                            const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                            int64_t nstamps, int model, const double *pars, double *out,
+                            int32_t *status, int32_t *ncomp, void *stream)
+{
+    const int st = need_modew("kfit_flux_w", mode_weight, nstamps);
+    if (st != NGMIX_OK) return st;
+    return launch_kfit_flux(dhat, phat, wbar, jac, R, C, nstamps, model, pars, out, status,
+                            (hipStream_t)stream, mode_weight, ncomp);
+}
+
+int ngmix_kfit_flux_w_host(const double *dhat, const double *phat, const double *mode_weight,
+                           const double *wbar, const ngmix_jacobian *jac, int R, int C,
+                           int64_t nstamps, int model, const double *pars, double *out,
+                           int32_t *status, int32_t *ncomp)
+{
+    bool nothing;
+    int st = kfit::check_flux_args("kfit_flux_w_host", dhat, wbar, jac, R, C, nstamps, model,
+                                   pars, out, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    st = need_modew("kfit_flux_w_host", mode_weight, nstamps);
+    if (st != NGMIX_OK) return st;
+    kfit::host_flux_w_for<kfit::MODEL_POINT, NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL,
+                          NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(
+        model, dhat, phat, wbar, jac, R, C, nstamps, pars, out, status, mode_weight, ncomp);
+    return NGMIX_OK;
+}
+
+int ngmix_kfit_rounds_w_batch(const ngmix_kfit_problem *problem, const double *mode_weight,
+                              int32_t *ncomp, int nrounds, int32_t *counts,
+                              int32_t *counts_host, void **events, void *stream)
+{
+    const int st = need_modew("kfit_rounds_w", mode_weight, problem ? problem->nstamps : 0);
+    if (st != NGMIX_OK) return st;
+    return launch_kfit_rounds(problem, nrounds, counts, counts_host, events,
+                              (hipStream_t)stream, mode_weight, ncomp);
 }
 
 int ngmix_moffat_phi_host(const double *nu, const double *x, int64_t n, double *out)

@@ -16,6 +16,12 @@
 //       any of the models at given parameters, or a point source (the psf
 //       itself) --: sum w Re(T^* D^), sum w |T^|^2, sum w |D^|^2.  No LM state.
 //
+//   <MODEL, MODEW = true>  both kernels with one more real plane u >= 0 per
+//       stored mode: omega u for the Parseval weight omega, a
+//       mode with u = 0 skipped unread, the components with omega u > 0
+//       counted for dof.  The walk and the order of the sums are the same:
+//       u = 1 everywhere gives the unweighted kernel's sums bit for bit.
+//
 //   moffat_phi_kernel  moffat_phi.hpp's function at n pairs, one thread each:
 //       what holds the device's arithmetic to the fixture without a fit.
 //
@@ -33,13 +39,14 @@ namespace {
 constexpr int KFIT_STAMPS_PER_BLOCK = BLOCK / WAVE;
 }
 
-template <int MODEL>
+template <int MODEL, bool MODEW = false>
 __global__ __launch_bounds__(BLOCK) void kfit_eval_kernel(
     const double2 *__restrict__ dhat, const double2 *__restrict__ phat,
     const double *__restrict__ wbar, const ngmix_jacobian *__restrict__ jacs, int R, int C,
     int64_t nstamps, const ngmix_lm_state *__restrict__ states,
     const int32_t *__restrict__ stamp_obj, const int32_t *__restrict__ stamp_band,
-    double *__restrict__ sums, int32_t *__restrict__ status, double *__restrict__ stamp_stats)
+    double *__restrict__ sums, int32_t *__restrict__ status, double *__restrict__ stamp_stats,
+    const double *__restrict__ modew, int32_t *__restrict__ ncomp)
 {
     using T = kfit::Traits<MODEL>;
     static_assert(kfit::LANES == WAVE, "kfit.hpp mirrors device_utils.hpp");
@@ -58,15 +65,19 @@ __global__ __launch_bounds__(BLOCK) void kfit_eval_kernel(
     double *stats = stamp_stats ? stamp_stats + 2 * (size_t)s : nullptr;
 
     const kfit::Setup m = kfit::setup<MODEL>(p, jacs[s], wbar[s], R, C);
+    const int CH = C / 2 + 1, nm = R * CH;
+    const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
+    int nc = 0;
     if (m.bad) {   // (uniform over the wave)
+        if (MODEW && ncomp) nc = wave_sum_int(kfit::lane_components(m.wscale, U, lane, R, C));
         if (lane == 0) {
             kfit::write_refused(T::NSUMS, out, stats);
             if (status) status[s] = NGMIX_ERR_G_RANGE;
+            if (MODEW && ncomp) ncomp[s] = nc;
         }
         return;
     }
 
-    const int CH = C / 2 + 1, nm = R * CH;
     const double2 *D = dhat + (size_t)s * nm;
     const double2 *P = phat ? phat + (size_t)s * nm : nullptr;
     double acc[T::NACC];
@@ -77,16 +88,20 @@ __global__ __launch_bounds__(BLOCK) void kfit_eval_kernel(
         const int a = i / CH, b = i - a * CH;
         const double mult = kfit::mode_mult(a, b, R, C);
         if (mult == 0.0) continue;
+        double w;
+        if (!kfit::mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
         const double2 d = D[i];
         double2 q = make_double2(1.0, 0.0);
         if (P) q = P[i];
         if (!isfinite(d.x + d.y + q.x + q.y)) notfinite = true;
-        kfit::add_mode<MODEL>(m, a, b, R, mult, d.x, d.y, q.x, q.y, acc);
+        kfit::add_mode<MODEL>(m, a, b, R, w, d.x, d.y, q.x, q.y, acc);
     }
 #pragma unroll
     for (int k = 0; k < T::NACC; k++) acc[k] = wave_sum(acc[k]);
+    if (MODEW && ncomp) nc = wave_sum_int(nc);
     const bool any_notfinite = __ballot(notfinite) != 0ull;
     if (lane == 0) {
+        if (MODEW && ncomp) ncomp[s] = nc;
         if (any_notfinite) {
             kfit::write_refused(T::NSUMS, out, stats);
             if (status) status[s] = NGMIX_ERR_NOT_FINITE;
@@ -101,7 +116,7 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
                      const ngmix_lm_state *states, const int32_t *stamp_obj,
                      const int32_t *stamp_band, double *sums, int32_t *status,
-                     double *stamp_stats, hipStream_t s)
+                     double *stamp_stats, hipStream_t s, const double *modew, int32_t *ncomp)
 {
     bool nothing;
     const int st = kfit::check_args("kfit_eval", dhat, wbar, jac, R, C, nstamps, model, states,
@@ -115,6 +130,19 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
         int model;
         decltype(kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS>, "")) k;
     };
+    // the MODEW form: its own instantiations, the plane of mode weights read
+    static constexpr Row wrows[] = {
+        {NGMIX_KFIT_GAUSS,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS, true>, "kfit_eval_kernel<gauss, modew>")},
+        {NGMIX_KFIT_EXP,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_EXP, true>, "kfit_eval_kernel<exp, modew>")},
+        {NGMIX_KFIT_SPERGEL,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_SPERGEL, true>, "kfit_eval_kernel<spergel, modew>")},
+        {NGMIX_KFIT_MOFFAT,
+         kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT, true>, "kfit_eval_kernel<moffat, modew>")},
+        {NGMIX_KFIT_MOFFAT_FWHM, kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT_FWHM, true>,
+                                        "kfit_eval_kernel<moffat fwhm, modew>")},
+    };
     static constexpr Row rows[] = {
         {NGMIX_KFIT_GAUSS, kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS>, "kfit_eval_kernel<gauss>")},
         {NGMIX_KFIT_EXP, kernel(kfit_eval_kernel<NGMIX_KFIT_EXP>, "kfit_eval_kernel<exp>")},
@@ -125,19 +153,20 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
         {NGMIX_KFIT_MOFFAT_FWHM,
          kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT_FWHM>, "kfit_eval_kernel<moffat fwhm>")},
     };
-    const auto k = find_kernel(rows, [&](const Row &q) { return q.model == model; });
+    const auto pick = [&](const Row &q) { return q.model == model; };
+    const auto k = modew ? find_kernel(wrows, pick) : find_kernel(rows, pick);
     const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
     return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
                   (const double2 *)phat, wbar, jac, R, C, nstamps, states, stamp_obj, stamp_band,
-                  sums, status, stamp_stats);
+                  sums, status, stamp_stats, modew, ncomp);
 }
 
-template <int MODEL>
+template <int MODEL, bool MODEW = false>
 __global__ __launch_bounds__(BLOCK) void kfit_flux_kernel(
     const double2 *__restrict__ dhat, const double2 *__restrict__ phat,
     const double *__restrict__ wbar, const ngmix_jacobian *__restrict__ jacs, int R, int C,
     int64_t nstamps, const double *__restrict__ pars, double *__restrict__ out,
-    int32_t *__restrict__ status)
+    int32_t *__restrict__ status, const double *__restrict__ modew, int32_t *__restrict__ ncomp)
 {
     const int64_t s = (int64_t)blockIdx.x * KFIT_STAMPS_PER_BLOCK + wave_id();
     if (s >= nstamps) return;
@@ -145,14 +174,18 @@ __global__ __launch_bounds__(BLOCK) void kfit_flux_kernel(
     double *o = out + 3 * (size_t)s;
     const kfit::Setup m = kfit::flux_setup<MODEL>(pars + (size_t)s * kfit::flux_npars(MODEL),
                                                   jacs[s], wbar[s], R, C);
+    const int CH = C / 2 + 1, nm = R * CH;
+    const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
+    int nc = 0;
     if (m.bad) {   // (uniform over the wave)
+        if (MODEW && ncomp) nc = wave_sum_int(kfit::lane_components(m.wscale, U, lane, R, C));
         if (lane == 0) {
             kfit::write_flux_refused(o);
             if (status) status[s] = NGMIX_ERR_G_RANGE;
+            if (MODEW && ncomp) ncomp[s] = nc;
         }
         return;
     }
-    const int CH = C / 2 + 1, nm = R * CH;
     const double2 *D = dhat + (size_t)s * nm;
     const double2 *P = phat ? phat + (size_t)s * nm : nullptr;
     double acc[3] = {0.0, 0.0, 0.0};
@@ -161,16 +194,20 @@ __global__ __launch_bounds__(BLOCK) void kfit_flux_kernel(
         const int a = i / CH, b = i - a * CH;
         const double mult = kfit::mode_mult(a, b, R, C);
         if (mult == 0.0) continue;
+        double w;
+        if (!kfit::mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
         const double2 d = D[i];
         double2 q = make_double2(1.0, 0.0);
         if (P) q = P[i];
         if (!isfinite(d.x + d.y + q.x + q.y)) notfinite = true;
-        kfit::flux_mode<MODEL>(m, a, b, R, mult, d.x, d.y, q.x, q.y, acc);
+        kfit::flux_mode<MODEL>(m, a, b, R, w, d.x, d.y, q.x, q.y, acc);
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) acc[k] = wave_sum(acc[k]);
+    if (MODEW && ncomp) nc = wave_sum_int(nc);
     const bool any_notfinite = __ballot(notfinite) != 0ull;
     if (lane == 0) {
+        if (MODEW && ncomp) ncomp[s] = nc;
         if (any_notfinite) {
             kfit::write_flux_refused(o);
         } else {
@@ -182,7 +219,8 @@ __global__ __launch_bounds__(BLOCK) void kfit_flux_kernel(
 
 int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                     const double *pars, double *out, int32_t *status, hipStream_t s)
+                     const double *pars, double *out, int32_t *status, hipStream_t s,
+                     const double *modew, int32_t *ncomp)
 {
     bool nothing;
     const int st = kfit::check_flux_args("kfit_flux", dhat, wbar, jac, R, C, nstamps, model, pars,
@@ -196,6 +234,20 @@ int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
         int model;
         decltype(kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS>, "")) k;
     };
+    static constexpr Row wrows[] = {
+        {kfit::MODEL_POINT,
+         kernel(kfit_flux_kernel<kfit::MODEL_POINT, true>, "kfit_flux_kernel<point, modew>")},
+        {NGMIX_KFIT_GAUSS,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS, true>, "kfit_flux_kernel<gauss, modew>")},
+        {NGMIX_KFIT_EXP,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_EXP, true>, "kfit_flux_kernel<exp, modew>")},
+        {NGMIX_KFIT_SPERGEL,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_SPERGEL, true>, "kfit_flux_kernel<spergel, modew>")},
+        {NGMIX_KFIT_MOFFAT,
+         kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT, true>, "kfit_flux_kernel<moffat, modew>")},
+        {NGMIX_KFIT_MOFFAT_FWHM, kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT_FWHM, true>,
+                                        "kfit_flux_kernel<moffat fwhm, modew>")},
+    };
     static constexpr Row rows[] = {
         {kfit::MODEL_POINT, kernel(kfit_flux_kernel<kfit::MODEL_POINT>, "kfit_flux_kernel<point>")},
         {NGMIX_KFIT_GAUSS, kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS>, "kfit_flux_kernel<gauss>")},
@@ -207,10 +259,12 @@ int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
         {NGMIX_KFIT_MOFFAT_FWHM,
          kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT_FWHM>, "kfit_flux_kernel<moffat fwhm>")},
     };
-    const auto k = find_kernel(rows, [&](const Row &q) { return q.model == model; });
+    const auto pick = [&](const Row &q) { return q.model == model; };
+    const auto k = modew ? find_kernel(wrows, pick) : find_kernel(rows, pick);
     const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
     return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
-                  (const double2 *)phat, wbar, jac, R, C, nstamps, pars, out, status);
+                  (const double2 *)phat, wbar, jac, R, C, nstamps, pars, out, status, modew,
+                  ncomp);
 }
 
 __global__ __launch_bounds__(BLOCK) void moffat_phi_kernel(const double *__restrict__ nu,
@@ -240,7 +294,8 @@ int launch_moffat_phi(const double *nu, const double *x, int64_t n, double *out,
 // pixel pass: nrounds x {kfit eval, prior rows, lmder step} queued by one host
 // call, the same counts / counts_host / events contract
 int launch_kfit_rounds(const ngmix_kfit_problem *p, int nrounds, int32_t *counts,
-                       int32_t *counts_host, void **events, hipStream_t s)
+                       int32_t *counts_host, void **events, hipStream_t s, const double *modew,
+                       int32_t *ncomp)
 {
     if (!p || !p->states || !p->sums || nrounds < 0) {
         set_last_error_msg("kfit_rounds: problem, states and sums are required");
@@ -266,7 +321,7 @@ int launch_kfit_rounds(const ngmix_kfit_problem *p, int nrounds, int32_t *counts
         if (events) NGMIX_HIP_CHECK(hipEventRecord((hipEvent_t)events[3 * r], s));
         int rc = launch_kfit_eval(p->dhat, p->phat, p->wbar, p->jac, p->nrow, p->ncol,
                                   p->nstamps, p->model, p->states, p->stamp_obj, p->stamp_band,
-                                  p->sums, p->status, p->stamp_stats, s);
+                                  p->sums, p->status, p->stamp_stats, s, modew, ncomp);
         if (rc != NGMIX_OK) return rc;
         if (events) NGMIX_HIP_CHECK(hipEventRecord((hipEvent_t)events[3 * r + 1], s));
         if (p->prior) {

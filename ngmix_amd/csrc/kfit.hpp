@@ -152,9 +152,43 @@ NGMIX_HD double mode_mult(int a, int b, int R, int C)
     return b == 0 ? 1.0 : 2.0;
 }
 
-// one kept mode's terms of the running sums; (dr, di) = D^, (pr, pi) = P^n
+// The weight of stored mode i of multiplicity mult > 0: omega = wscale mult, or,
+// MODEW, omega u[i] with the mode's own u >= 0.  false: u = 0,
+// the mode is masked and nothing of it is read.  A u that is negative or not
+// finite where omega > 0 sets notfinite; ncomp counts the residual components
+// of the modes with omega u > 0.
+template <bool MODEW>
+NGMIX_HD bool mode_weight(const Setup &m, double mult, const double *u, int i, double &w,
+                          bool &notfinite, int &ncomp)
+{
+    w = m.wscale * mult;
+    if (!MODEW) return true;
+    const double ui = u[i];
+    if (ui == 0.0) return false;
+    if (w > 0.0 && (!(ui > 0.0) || !isfinite(ui))) notfinite = true;
+    w *= ui;
+    if (w > 0.0) ncomp += (int)mult;
+    return true;
+}
+
+// lane's share of ncomp alone: what a stamp refused before its modes are walked
+// still reports
+NGMIX_HD int lane_components(double wscale, const double *u, int lane, int R, int C)
+{
+    const int CH = C / 2 + 1, nm = R * CH;
+    int n = 0;
+    for (int i = lane; i < nm; i += LANES) {
+        const int a = i / CH, b = i - a * CH;
+        const double mult = mode_mult(a, b, R, C);
+        if (wscale * mult * u[i] > 0.0) n += (int)mult;
+    }
+    return n;
+}
+
+// one kept mode's terms of the running sums; w its weight, (dr, di) = D^,
+// (pr, pi) = P^n
 template <int MODEL>
-NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double mult, double dr, double di,
+NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double w, double dr, double di,
                        double pr, double pi, double (&acc)[Traits<MODEL>::NACC])
 {
     constexpr int NA = Traits<MODEL>::NA, NTRI = Traits<MODEL>::NTRI;
@@ -205,7 +239,6 @@ NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double mult, double 
     al[NA - 1] = phi;
     const double A = m.flux * al[NA - 1];
     const double fr = fma(A, gr, -dr), fi = fma(A, gi, -di);
-    const double w = m.wscale * mult;
     const double gg = w * fma(gr, gr, gi * gi);
     const double gf = w * fma(gr, fr, gi * fi);
     const double cf = (w * A) * fma(gi, fr, -(gr * fi));
@@ -297,13 +330,15 @@ inline int check_args(const char *who, const double *dhat, const double *wbar,
     return NGMIX_ERR_BAD_ARG;
 }
 
-// the host twin of kfit_eval_kernel: the same text, the same order of sums
-template <int MODEL>
+// the host twin of kfit_eval_kernel: the same text, the same order of sums;
+// MODEW: modew (nstamps, R, C/2+1), ncomp (nstamps,) or NULL
+template <int MODEL, bool MODEW = false>
 inline void host_eval(const double *dhat, const double *phat, const double *wbar,
                       const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
                       const ngmix_lm_state *states, const int32_t *stamp_obj,
                       const int32_t *stamp_band, double *sums, int32_t *status,
-                      double *stamp_stats)
+                      double *stamp_stats, const double *modew = nullptr,
+                      int32_t *ncomp = nullptr)
 {
     constexpr int NLOC = Traits<MODEL>::NLOC, NACC = Traits<MODEL>::NACC,
                   NSUMS = Traits<MODEL>::NSUMS;
@@ -319,9 +354,15 @@ inline void host_eval(const double *dhat, const double *phat, const double *wbar
         double *out = sums + s * NSUMS;
         double *stats = stamp_stats ? stamp_stats + 2 * s : nullptr;
         const Setup m = setup<MODEL>(p, jac[s], wbar[s], R, C);
+        const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
+        int nc = 0;
         if (m.bad) {
             write_refused(NSUMS, out, stats);
             if (status) status[s] = NGMIX_ERR_G_RANGE;
+            if (MODEW && ncomp) {
+                for (int l = 0; l < LANES; l++) nc += lane_components(m.wscale, U, l, R, C);
+                ncomp[s] = nc;
+            }
             continue;
         }
         const double *D = dhat + (size_t)s * nm * 2;
@@ -334,13 +375,16 @@ inline void host_eval(const double *dhat, const double *phat, const double *wbar
                 const int a = i / CH, b = i - a * CH;
                 const double mult = mode_mult(a, b, R, C);
                 if (mult == 0.0) continue;
+                double w;
+                if (!mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
                 const double dr = D[2 * i], di = D[2 * i + 1];
                 const double pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
                 if (!isfinite(dr + di + pr + pi)) notfinite = true;
-                add_mode<MODEL>(m, a, b, R, mult, dr, di, pr, pi, acc);
+                add_mode<MODEL>(m, a, b, R, w, dr, di, pr, pi, acc);
             }
             for (int k = 0; k < NACC; k++) part[(size_t)k * LANES + l] = acc[k];
         }
+        if (MODEW && ncomp) ncomp[s] = nc;
         double tot[NACC];
         for (int k = 0; k < NACC; k++) {
             double *x = part.data() + (size_t)k * LANES;
@@ -369,7 +413,7 @@ constexpr int flux_npars(int model)
 
 // one kept mode's terms of A = sum w Re(T^* D^), B = sum w |T^|^2, E = sum w |D^|^2
 template <int MODEL>
-NGMIX_HD void flux_mode(const Setup &m, int a, int b, int R, double mult, double dr, double di,
+NGMIX_HD void flux_mode(const Setup &m, int a, int b, int R, double w, double dr, double di,
                         double pr, double pi, double (&acc)[3])
 {
     const double qr = m.qr_unit * (double)(2 * a < R ? a : a - R);   // fftfreq
@@ -398,7 +442,6 @@ NGMIX_HD void flux_mode(const Setup &m, int a, int b, int R, double mult, double
     sincos(theta, &sn, &cs);
     const double tr = phi * fma(cs, pr, sn * pi);
     const double ti = phi * fma(cs, pi, -(sn * pr));
-    const double w = m.wscale * mult;
     acc[0] = fma(w, fma(tr, dr, ti * di), acc[0]);
     acc[1] = fma(w, fma(tr, tr, ti * ti), acc[1]);
     acc[2] = fma(w, fma(dr, dr, di * di), acc[2]);
@@ -446,19 +489,26 @@ inline int check_flux_args(const char *who, const double *dhat, const double *wb
     return NGMIX_ERR_BAD_ARG;
 }
 
-// the host twin of kfit_flux_kernel
-template <int MODEL>
+// the host twin of kfit_flux_kernel; modew, ncomp as host_eval's
+template <int MODEL, bool MODEW = false>
 inline void host_flux(const double *dhat, const double *phat, const double *wbar,
                       const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
-                      const double *pars, double *out, int32_t *status)
+                      const double *pars, double *out, int32_t *status,
+                      const double *modew = nullptr, int32_t *ncomp = nullptr)
 {
     const int CH = C / 2 + 1, nm = R * CH, np = flux_npars(MODEL);
     std::vector<double> part((size_t)LANES * 3);
     for (int64_t s = 0; s < nstamps; s++) {
         const Setup m = flux_setup<MODEL>(pars + s * np, jac[s], wbar[s], R, C);
+        const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
+        int nc = 0;
         if (m.bad) {
             write_flux_refused(out + 3 * s);
             if (status) status[s] = NGMIX_ERR_G_RANGE;
+            if (MODEW && ncomp) {
+                for (int l = 0; l < LANES; l++) nc += lane_components(m.wscale, U, l, R, C);
+                ncomp[s] = nc;
+            }
             continue;
         }
         const double *D = dhat + (size_t)s * nm * 2;
@@ -470,13 +520,16 @@ inline void host_flux(const double *dhat, const double *phat, const double *wbar
                 const int a = i / CH, b = i - a * CH;
                 const double mult = mode_mult(a, b, R, C);
                 if (mult == 0.0) continue;
+                double w;
+                if (!mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
                 const double dr = D[2 * i], di = D[2 * i + 1];
                 const double pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
                 if (!isfinite(dr + di + pr + pi)) notfinite = true;
-                flux_mode<MODEL>(m, a, b, R, mult, dr, di, pr, pi, acc);
+                flux_mode<MODEL>(m, a, b, R, w, dr, di, pr, pi, acc);
             }
             for (int k = 0; k < 3; k++) part[(size_t)k * LANES + l] = acc[k];
         }
+        if (MODEW && ncomp) ncomp[s] = nc;
         for (int k = 0; k < 3; k++) {
             double *x = part.data() + (size_t)k * LANES;
             for (int off = LANES / 2; off > 0; off >>= 1)
@@ -493,6 +546,16 @@ template <int... MS, typename... A>
 inline void host_flux_for(int model, A... args)
 {
     (void)((model == MS ? (host_flux<MS>(args...), true) : false) || ...);
+}
+template <int... MS, typename... A>
+inline void host_flux_w_for(int model, A... args)
+{
+    (void)((model == MS ? (host_flux<MS, true>(args...), true) : false) || ...);
+}
+template <int... MS, typename... A>
+inline void host_eval_w_for(int model, A... args)
+{
+    (void)((model == MS ? (host_eval<MS, true>(args...), true) : false) || ...);
 }
 
 }  // namespace kfit

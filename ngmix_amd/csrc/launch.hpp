@@ -42,14 +42,17 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
                             const double *psf_flux, const double *sigma, const double *g,
                             const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
                             int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
-                            int32_t *flags, hipStream_t s);
+                            int32_t *flags, hipStream_t s, double *kfit_phat = nullptr,
+                            double *kfit_aux = nullptr);
 int launch_metacal_dilate_spectrum(const double *images, const double *noise, const double *psf,
                                    const ngmix_jacobian *jac, const double *psf_cen,
                                    const double *g, const double *dil, const int32_t *kind,
                                    const double *g_host, const double *dil_host,
                                    const int32_t *kind_host, int per_stamp_g, int64_t nstamps,
                                    int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
-                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s);
+                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s,
+                                   const double *psf_flux = nullptr,
+                                   double *kfit_phat = nullptr, double *kfit_aux = nullptr);
 // metacal_noise.hip
 int launch_metacal_noise(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                          int nrow, int ncol, int rot_k, double *out, hipStream_t s);
@@ -183,12 +186,15 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
                      const ngmix_lm_state *states, const int32_t *stamp_obj,
                      const int32_t *stamp_band, double *sums, int32_t *status,
-                     double *stamp_stats, hipStream_t s);
+                     double *stamp_stats, hipStream_t s, const double *modew = nullptr,
+                     int32_t *ncomp = nullptr);
 int launch_kfit_rounds(const ngmix_kfit_problem *p, int nrounds, int32_t *counts,
-                       int32_t *counts_host, void **events, hipStream_t s);
+                       int32_t *counts_host, void **events, hipStream_t s,
+                       const double *modew = nullptr, int32_t *ncomp = nullptr);
 int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                     const double *pars, double *out, int32_t *status, hipStream_t s);
+                     const double *pars, double *out, int32_t *status, hipStream_t s,
+                     const double *modew = nullptr, int32_t *ncomp = nullptr);
 int launch_moffat_phi(const double *nu, const double *x, int64_t n, double *out, hipStream_t s);
 
 int launch_lm_prior_finish(const ngmix_lm_state *states, int64_t nobj,

@@ -104,6 +104,21 @@ NGMIX_HD ModeSetup mode_setup(const ngmix_jacobian &jac, double pr0, double pc0,
     return m;
 }
 
+// The KFIT form writes for kfit_eval_kernel, not for an inverse
+// FFT: O^ about the centre is D^, and beside it go P^n = T^ / sum P and, per
+// mode, the keep flag and rho^2 = |T^(q)|^2 / |P^(q')|^2, the factor by which
+// the operation scales the variance of white pixel noise there.
+struct KfitOut {
+    double *phat;   // (T N, R, C/2+1, 2) complex
+    double *aux;    // (T N, R, C/2+1, 2): keep, rho^2
+};
+
+// what a mode gives beside O^ in the KFIT form; all zero where it is dropped
+struct KfitMode {
+    cplx pn;
+    double keep, rho2;
+};
+
 // sinc(x) = sin x / x
 NGMIX_HD double sinc(double x) { return x == 0.0 ? 1.0 : sin(x) / x; }
 
@@ -118,10 +133,12 @@ NGMIX_HD double pixel_ft(double qr, double qc) { return sinc(0.5 * qr) * sinc(0.
 // T^(q) = P^(q_t) / Pi(q_t) Pi(q), O^(q) = I^(q') / P^(q') T^(q); a mode is
 // kept only where q' and q_t are strictly inside the band (|Pi(q_t)| >= (2 /
 // pi)^2 there).  PSF_ONLY: T^(q) exp(-i q . psf centre) alone, q a mode of the
-// psf stamp's grid, kept where q_t is inside the band.
-template <bool NOISE, bool PSF_ONLY>
+// psf stamp's grid, kept where q_t is inside the band.  KFIT: O^ about the
+// centre (no shift), m.flux the psf stamp's sum.
+template <bool NOISE, bool PSF_ONLY, bool KFIT>
 NGMIX_HD void dilate_mode_value(const Planes &p, const ModeSetup &m, const DilateSetup &ds,
-                                double qa, double qb, cplx &oi, cplx &on, bool &bad)
+                                double qa, double qb, cplx &oi, cplx &on, bool &bad,
+                                KfitMode &km)
 {
     const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
     const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
@@ -144,12 +161,21 @@ NGMIX_HD void dilate_mode_value(const Planes &p, const ModeSetup &m, const Dilat
     cplx si, sn, sp;
     transforms<NOISE>(p, m.r0, m.c0, qr, qc, si, sn, sp);
     sp = cmul(sp, cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
-    const cplx shift = cexpi(-(qa * m.r0 + qb * m.c0));
-    oi = cmul(cmul(cdiv(si, sp), target), shift);
-    bool ok = isfinite(oi.x) && isfinite(oi.y);
-    if (NOISE) {
-        on = cmul(cmul(cdiv(sn, sp), target), shift);
-        ok = ok && isfinite(on.x) && isfinite(on.y);
+    bool ok;
+    if constexpr (KFIT) {
+        oi = cmul(cdiv(si, sp), target);
+        km.pn = {target.x / m.flux, target.y / m.flux};
+        km.keep = 1.0;
+        km.rho2 = (target.x * target.x + target.y * target.y) / (sp.x * sp.x + sp.y * sp.y);
+        ok = isfinite(oi.x) && isfinite(oi.y);
+    } else {
+        const cplx shift = cexpi(-(qa * m.r0 + qb * m.c0));
+        oi = cmul(cmul(cdiv(si, sp), target), shift);
+        ok = isfinite(oi.x) && isfinite(oi.y);
+        if (NOISE) {
+            on = cmul(cmul(cdiv(sn, sp), target), shift);
+            ok = ok && isfinite(on.x) && isfinite(on.y);
+        }
     }
     if (!ok) {
         bad = true;
@@ -160,13 +186,15 @@ NGMIX_HD void dilate_mode_value(const Planes &p, const ModeSetup &m, const Dilat
 // O^(q) exp(-i q . centre) of the image (and of the noise plane) at the grid
 // frequency q = (qa, qb): zero outside the band; bad is set when a kept mode
 // is not finite (its value is NaN then, never an infinity)
-template <bool NOISE, int TARGET>
+template <bool NOISE, int TARGET, bool KFIT>
 NGMIX_HD void mode_value(const Planes &p, const ModeSetup &m, const DilateSetup &ds, double qa,
-                         double qb, cplx &oi, cplx &on, bool &bad)
+                         double qb, cplx &oi, cplx &on, bool &bad, KfitMode &km)
 {
     oi = on = {0.0, 0.0};
+    km = {{0.0, 0.0}, 0.0, 0.0};
     if constexpr (TARGET != TARGET_GAUSS) {
-        dilate_mode_value<NOISE, TARGET == TARGET_DILATE_PSF>(p, m, ds, qa, qb, oi, on, bad);
+        dilate_mode_value<NOISE, TARGET == TARGET_DILATE_PSF, KFIT>(p, m, ds, qa, qb, oi, on,
+                                                                    bad, km);
         return;
     }
     // world frequency (v, u), the sheared one, and back to pixel axes:
@@ -179,15 +207,25 @@ NGMIX_HD void mode_value(const Planes &p, const ModeSetup &m, const DilateSetup 
     transforms<NOISE>(p, m.r0, m.c0, qr, qc, si, sn, sp);
     // the psf about its own centre
     sp = cmul(sp, cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
-    const double target = m.flux * exp(-m.half_sig2 * (kv * kv + ku * ku));
-    const cplx shift = cexpi(-(qa * m.r0 + qb * m.c0));
+    const double tn = exp(-m.half_sig2 * (kv * kv + ku * ku));
+    const double target = m.flux * tn;
     cplx o = cdiv(si, sp);
-    oi = cmul(cplx{o.x * target, o.y * target}, shift);
-    bool ok = isfinite(oi.x) && isfinite(oi.y);
-    if (NOISE) {
-        o = cdiv(sn, sp);
-        on = cmul(cplx{o.x * target, o.y * target}, shift);
-        ok = ok && isfinite(on.x) && isfinite(on.y);
+    bool ok;
+    if constexpr (KFIT) {
+        oi = {o.x * target, o.y * target};
+        km.pn = {tn, 0.0};
+        km.keep = 1.0;
+        km.rho2 = target * target / (sp.x * sp.x + sp.y * sp.y);
+        ok = isfinite(oi.x) && isfinite(oi.y);
+    } else {
+        const cplx shift = cexpi(-(qa * m.r0 + qb * m.c0));
+        oi = cmul(cplx{o.x * target, o.y * target}, shift);
+        ok = isfinite(oi.x) && isfinite(oi.y);
+        if (NOISE) {
+            o = cdiv(sn, sp);
+            on = cmul(cplx{o.x * target, o.y * target}, shift);
+            ok = ok && isfinite(on.x) && isfinite(on.y);
+        }
     }
     if (!ok) {
         bad = true;
@@ -229,10 +267,10 @@ NGMIX_HD int nyq_item_of(int a, int b, int R, int C)
 
 }  // namespace
 
-size_t metacal_lds_bytes(int R, int C, int Rp, int Cp, bool noise)
+size_t metacal_lds_bytes(int R, int C, int Rp, int Cp, bool noise, bool kfit = false)
 {
     const size_t planes = (size_t)R * C * (noise ? 2 : 1) + (size_t)Rp * Cp;
-    const size_t items = (size_t)(nyq_row_items(R, C) + nyq_col_items(R, C));
+    const size_t items = kfit ? 0 : (size_t)(nyq_row_items(R, C) + nyq_col_items(R, C));
     return (planes + items * 4 * (noise ? 2 : 1)) * sizeof(double);
 }
 
@@ -251,15 +289,21 @@ size_t metacal_psf_lds_bytes(int Rp, int Cp)
 // noise plane's; flags (N, T): 1 where a kept mode was not finite.
 // TARGET_DILATE_PSF: no image and no noise plane, (R, C) = (Rp, Cp) is the psf
 // stamp's grid and spec the target psf's spectrum on it.
-template <bool NOISE, int TARGET>
+// KFIT (no noise plane): spec is D^ (T, N, R, C/2 + 1) complex, TYPE-major as
+// are kf.phat, kf.aux and flags (T, N); no centre phase, no Nyquist partner
+// items -- the Nyquist row and column, which kfit drops, are written as
+// zeros -- and flux_or_norm[n] the psf stamp's sum under either target.
+template <bool NOISE, int TARGET, bool KFIT = false>
 __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
     const double *__restrict__ images, const double *__restrict__ noise,
     const double *__restrict__ psf, const ngmix_jacobian *__restrict__ jac,
     const double *__restrict__ psf_cen, const double *__restrict__ flux_or_dil,
     const typename SecondArg<TARGET>::type *__restrict__ sigma_or_kind,
     const double *__restrict__ g, int per_stamp_g, int T,
-    int R, int C, int Rp, int Cp, double *__restrict__ spec, int32_t *__restrict__ flags)
+    int R, int C, int Rp, int Cp, double *__restrict__ spec, int32_t *__restrict__ flags,
+    const double *__restrict__ norm, KfitOut kf)
 {
+    static_assert(!KFIT || (!NOISE && TARGET != TARGET_DILATE_PSF), "KFIT: an image, no noise");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t n = blockIdx.x / T;
     const int t = blockIdx.x % T;
@@ -270,7 +314,7 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
     double *s_noise = s_img + npix;
     double *s_psf = s_img + (size_t)npix * NPL;
     cplx *s_own = (cplx *)(s_psf + nppix);         // the Nyquist modes' own values
-    const int nitems = nyq_row_items(R, C) + nyq_col_items(R, C);
+    const int nitems = KFIT ? 0 : nyq_row_items(R, C) + nyq_col_items(R, C);
     cplx *s_partner = s_own + (size_t)nitems * NPL;
 
     for (int i = threadIdx.x; i < npix; i += blockDim.x) {
@@ -289,21 +333,36 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
         m = mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], sigma_or_kind[n],
                        flux_or_dil[n]);
     } else {
-        m = mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], 0.0, 0.0);
+        m = mode_setup(jac[n], psf_cen[2 * n], psf_cen[2 * n + 1], gt[0], gt[1], 0.0,
+                       KFIT ? norm[n] : 0.0);
         ds = {flux_or_dil[gi], sigma_or_kind[gi] != 0};
     }
 
     const int Ch = C / 2 + 1;
     const int nmodes = R * Ch;
-    cplx *out = (cplx *)spec + ((n * T + t) * NPL) * (int64_t)nmodes;
+    // (stamp, type) in the order of the outputs
+    const int64_t slot = KFIT ? (int64_t)t * (gridDim.x / T) + n : n * T + t;
+    cplx *out = (cplx *)spec + (slot * NPL) * (int64_t)nmodes;
     bool bad = false;
     for (int w = threadIdx.x; w < nmodes + nitems; w += blockDim.x) {
         cplx oi, on;
+        KfitMode km;
         if (w < nmodes) {
             const int a = w / Ch, b = w % Ch;
-            mode_value<NOISE, TARGET>(planes, m, ds, grid_freq(a, R), grid_freq(b, C), oi, on,
-                                      bad);
             const int s = nyq_item_of(a, b, R, C);
+            if constexpr (KFIT) {
+                oi = {0.0, 0.0};
+                km = {{0.0, 0.0}, 0.0, 0.0};
+                if (s < 0)
+                    mode_value<NOISE, TARGET, KFIT>(planes, m, ds, grid_freq(a, R),
+                                                    grid_freq(b, C), oi, on, bad, km);
+                out[w] = oi;
+                ((cplx *)kf.phat)[slot * nmodes + w] = km.pn;
+                ((cplx *)kf.aux)[slot * nmodes + w] = {km.keep, km.rho2};
+                continue;
+            }
+            mode_value<NOISE, TARGET, KFIT>(planes, m, ds, grid_freq(a, R), grid_freq(b, C), oi,
+                                            on, bad, km);
             if (s < 0) {
                 out[w] = oi;
                 if (NOISE) out[nmodes + w] = on;
@@ -315,8 +374,8 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
             const int s = w - nmodes;
             int a, b;
             nyq_item_mode(s, R, C, a, b);
-            mode_value<NOISE, TARGET>(planes, m, ds, grid_freq((R - a) % R, R),
-                                      grid_freq((C - b) % C, C), oi, on, bad);
+            mode_value<NOISE, TARGET, KFIT>(planes, m, ds, grid_freq((R - a) % R, R),
+                                            grid_freq((C - b) % C, C), oi, on, bad, km);
             s_partner[s] = oi;
             if (NOISE) s_partner[nitems + s] = on;
         }
@@ -330,7 +389,7 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
             out[(int64_t)pl * nmodes + a * Ch + b] = {0.5 * (u.x + v.x), 0.5 * (u.y - v.y)};
         }
     }
-    if (threadIdx.x == 0) flags[n * T + t] = any_bad;
+    if (threadIdx.x == 0) flags[slot] = any_bad;
 }
 
 // the block size that leaves the fewest idle work-item slots (the larger on a tie)
@@ -355,9 +414,15 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
                             const double *psf_flux, const double *sigma, const double *g,
                             const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
                             int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
-                            int32_t *flags, hipStream_t s)
+                            int32_t *flags, hipStream_t s, double *kfit_phat, double *kfit_aux)
 {
     if (nstamps <= 0) return NGMIX_OK;
+    const bool kfit = kfit_phat || kfit_aux;
+    if (kfit && (noise || !kfit_phat || !kfit_aux)) {
+        set_last_error_msg("metacal_spectrum: the kfit form takes phat and aux and no noise "
+                           "plane");
+        return NGMIX_ERR_BAD_ARG;
+    }
     if (!images || !psf || !jac || !psf_cen || !psf_flux || !sigma || !g || !g_host || !spec ||
         !flags) {
         set_last_error_msg("metacal_spectrum: images, psf, jac, psf_cen, psf_flux, sigma, g, "
@@ -373,7 +438,7 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
         set_last_error_msg("metacal_spectrum: too many (stamp, type) pairs for one launch");
         return NGMIX_ERR_BAD_ARG;
     }
-    const size_t lds = metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr);
+    const size_t lds = metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr, kfit);
     if (lds > 160 * 1024 || (int64_t)nrow * ncol > 0x7fffff || (int64_t)psf_nrow * psf_ncol > 0x7fffff) {
         set_last_error_msg("metacal_spectrum: the stamp, its psf stamp and its noise plane do "
                            "not fit the 160 KB of LDS");
@@ -388,13 +453,16 @@ int launch_metacal_spectrum(const double *images, const double *noise, const dou
             return NGMIX_ERR_BAD_ARG;
         }
     }
-    const auto k = noise ? kernel(metacal_spectrum_kernel<true, TARGET_GAUSS>,
-                                  "metacal_spectrum_kernel<noise>")
-                         : kernel(metacal_spectrum_kernel<false, TARGET_GAUSS>,
-                                  "metacal_spectrum_kernel");
+    const auto k = kfit    ? kernel(metacal_spectrum_kernel<false, TARGET_GAUSS, true>,
+                                    "metacal_spectrum_kernel<kfit>")
+                   : noise ? kernel(metacal_spectrum_kernel<true, TARGET_GAUSS>,
+                                    "metacal_spectrum_kernel<noise>")
+                           : kernel(metacal_spectrum_kernel<false, TARGET_GAUSS>,
+                                    "metacal_spectrum_kernel");
     return launch(k, dim3((unsigned)(nstamps * ntypes)), dim3(spectrum_block(nrow, ncol)), lds,
                   48 * 1024, s, images, noise, psf, jac, psf_cen, psf_flux, sigma, g,
-                  per_stamp_g ? 1 : 0, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags);
+                  per_stamp_g ? 1 : 0, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags,
+                  psf_flux, KfitOut{kfit_phat, kfit_aux});
 }
 
 // The dilated psf as the target (psf_only: its own spectrum on the psf stamp's
@@ -407,7 +475,8 @@ int launch_metacal_dilate_spectrum(const double *images, const double *noise, co
                                    const double *g_host, const double *dil_host,
                                    const int32_t *kind_host, int per_stamp_g, int64_t nstamps,
                                    int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
-                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s)
+                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s,
+                                   const double *psf_flux, double *kfit_phat, double *kfit_aux)
 {
     const std::string who = psf_only ? "metacal_dilate_psf_spectrum" : "metacal_dilate_spectrum";
     const auto refuse = [&who](const std::string &what) {
@@ -415,6 +484,9 @@ int launch_metacal_dilate_spectrum(const double *images, const double *noise, co
         return NGMIX_ERR_BAD_ARG;
     };
     if (nstamps <= 0) return NGMIX_OK;
+    const bool kfit = kfit_phat || kfit_aux;
+    if (kfit && (psf_only || noise || !kfit_phat || !kfit_aux || !psf_flux))
+        return refuse("the kfit form takes psf_flux, phat and aux and no noise plane");
     if (psf_only) {
         images = noise = nullptr;
         nrow = psf_nrow;
@@ -430,7 +502,8 @@ int launch_metacal_dilate_spectrum(const double *images, const double *noise, co
         return refuse("the number of types and the stamp shapes must be positive");
     if (nstamps * ntypes > 0x7fffffffll) return refuse("too many (stamp, type) pairs for one launch");
     const size_t lds = psf_only ? metacal_psf_lds_bytes(psf_nrow, psf_ncol)
-                                : metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr);
+                                : metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr,
+                                                    kfit);
     if (lds > 160 * 1024 || (int64_t)nrow * ncol > 0x7fffff ||
         (int64_t)psf_nrow * psf_ncol > 0x7fffff)
         return refuse("the stamp, its psf stamp and its noise plane do not fit the 160 KB of LDS");
@@ -450,13 +523,17 @@ int launch_metacal_dilate_spectrum(const double *images, const double *noise, co
         return launch(kernel(metacal_spectrum_kernel<false, TARGET_DILATE_PSF>,
                              "metacal_spectrum_kernel<dilate psf>"),
                       grid, block, lds, 48 * 1024, s, images, noise, psf, jac, psf_cen, dil, kind, g,
-                      per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags);
-    const auto k = noise ? kernel(metacal_spectrum_kernel<true, TARGET_DILATE>,
-                                  "metacal_spectrum_kernel<noise, dilate>")
-                         : kernel(metacal_spectrum_kernel<false, TARGET_DILATE>,
-                                  "metacal_spectrum_kernel<dilate>");
+                      per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags, psf_flux,
+                      KfitOut{nullptr, nullptr});
+    const auto k = kfit    ? kernel(metacal_spectrum_kernel<false, TARGET_DILATE, true>,
+                                    "metacal_spectrum_kernel<dilate, kfit>")
+                   : noise ? kernel(metacal_spectrum_kernel<true, TARGET_DILATE>,
+                                    "metacal_spectrum_kernel<noise, dilate>")
+                           : kernel(metacal_spectrum_kernel<false, TARGET_DILATE>,
+                                    "metacal_spectrum_kernel<dilate>");
     return launch(k, grid, block, lds, 48 * 1024, s, images, noise, psf, jac, psf_cen, dil, kind, g,
-                  per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags);
+                  per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags, psf_flux,
+                  KfitOut{kfit_phat, kfit_aux});
 }
 
 }  // namespace ngmix

@@ -44,7 +44,7 @@ from .fitting import STEP_PRIOR
 from .prior_batch import as_batch_prior, bounds_arrays
 
 __all__ = ["KStampBatch", "KSpaceBatchFitter", "KSpaceFitter", "kmodel_images",
-           "KSpaceFluxBatch", "KSpaceFluxFitter"]
+           "KSpaceFluxBatch", "KSpaceFluxFitter", "metacal_mode_weights"]
 
 MODELS = {"gauss": _lib.KFIT_GAUSS, "exp": _lib.KFIT_EXP, "spergel": _lib.KFIT_SPERGEL,
           "moffat": _lib.KFIT_MOFFAT}
@@ -112,14 +112,27 @@ class KStampBatch(object):
       jac       (N, 8) the jacobian records
       npix_eff  the residual components of a stamp that enter dof:
                 (R - [R even]) (C - [C even]), the Nyquist row and column dropped
+      mode_weight  None, or (N, R, C//2+1) float64 u >= 0 (DESIGN.md 3.26): the
+                weight of a mode is its Parseval weight times u, a mode with
+                u = 0 is not read, and dof counts the components with a
+                positive weight in place of npix_eff.  None: the kernels
+                without the plane, untouched
     """
 
-    def __init__(self, dhat, phat, wbar, jac, nrow, ncol):
+    def __init__(self, dhat, phat, wbar, jac, nrow, ncol, mode_weight=None):
         self.dhat, self.phat, self.wbar, self.jac = dhat, phat, wbar, jac
         self.nrow, self.ncol = int(nrow), int(ncol)
         self.n = int(dhat.shape[0])
         self.device = dhat.device
         self.npix_eff = (self.nrow - (self.nrow % 2 == 0)) * (self.ncol - (self.ncol % 2 == 0))
+        if mode_weight is not None:
+            if tuple(mode_weight.shape) != (self.n, self.nrow, self.ncol // 2 + 1) or \
+                    mode_weight.dtype != dhat.dtype or mode_weight.device != dhat.device:
+                raise ValueError("mode_weight must be (%d, %d, %d) float64 on the batch's device"
+                                 % (self.n, self.nrow, self.ncol // 2 + 1))
+            mode_weight = mode_weight.contiguous()
+        self.mode_weight = mode_weight
+        self.mcal_flags = None
 
     @staticmethod
     def _planes(sb, what):
@@ -163,6 +176,83 @@ class KStampBatch(object):
         if psf_images is not None:
             psf_sb = StampBatch.from_images(psf_images, None, psf_jacobians, device=device)
         return cls.from_stamps(sb, psf_sb)
+
+    @classmethod
+    def from_metacal(cls, stamps, psf_stamps, types=None, step=0.01, psf="fitgauss",
+                     target_sigma=None, weight="flat", fixnoise=False, rng=None):
+        """
+        The metacal types of a stamp batch as ONE k-space batch of ntypes * N
+        stamps, type-major as MetacalBatch.get_all orders them, without leaving
+        Fourier space: D^ is the sheared, reconvolved spectrum
+        about the jacobian centre, P^n the target psf over the psf stamp's sum,
+        both from the KFIT form of metacal_spectrum_kernel.  stamps, psf_stamps,
+        psf, target_sigma, types, step: as MetacalBatch and get_all take them.
+
+        mode_weight: a mode's u is zero unless EVERY requested type of the
+        object keeps the mode, so an object's types are fitted on the same
+        modes.  weight='flat': u is that 0/1 mask.  weight='noise': u = mask
+        rho_min^2 / rho^2(q) with rho = |T^(q)| / |P^(q')|, the factor by which
+        the operation scales white pixel noise at the mode -- the
+        maximum-likelihood weight of stationary noise; rho_min over the type's
+        masked-in modes of the object; modes with rho^2 < 1e-24 rho_max^2 in any
+        type are masked out.
+
+        mcal_flags (ntypes, N) int32 stays on the batch; a flagged stamp's D^ is
+        NaN, so its fit is refused.  fixnoise is not served here.
+        """
+        if fixnoise:
+            raise NotImplementedError("from_metacal: fixnoise is not served in Fourier space; "
+                                      "MetacalBatch.get_all(fixnoise=True) serves it")
+        if weight not in ("flat", "noise"):
+            raise ValueError("weight must be 'flat' or 'noise', got %r" % (weight,))
+        from . import metacal as mc
+        torch = _torch()
+        mb = mc.MetacalBatch(stamps, psf_stamps, psf=psf, target_sigma=target_sigma, rng=rng)
+        types = mc._check_types(types, mc.DILATE_EXACT if mb.dilate else "fitgauss")
+        g = mc._type_shears(types, float(step))
+        dil = kind = None
+        if mb.dilate:
+            dil = np.full(len(types), 1.0 + 2.0 * abs(float(step)))
+            kind = mc._type_kinds(types)
+        dhat, phat, aux, flags = mb.kfit_spectra(g, False, dil, kind)
+        nt, n = len(types), mb.n
+        R, C = mb.shape
+        with _on_device(mb.device):
+            u = metacal_mode_weights(aux.view(nt, n, R, C // 2 + 1, 2), flags, weight)
+            nan = torch.full((), float("nan"), dtype=torch.float64, device=mb.device)
+            dhat = torch.where(flags.reshape(-1)[:, None, None, None] != 0, nan, dhat)
+            ierr = stamps.ierr.reshape(n, -1)
+            wbar = (ierr * ierr).max(dim=1).values.repeat(nt).contiguous()
+            jac = stamps.jac.repeat(nt, 1).contiguous()
+        kb = cls(dhat, phat, wbar, jac, R, C, mode_weight=u.view(nt * n, R, C // 2 + 1))
+        kb.mcal_flags = flags.cpu().numpy()
+        kb.types = types
+        return kb
+
+
+RHO2_FLOOR = 1.0e-24    # below this of rho_max^2 a mode is under double round-off of the DC mode
+
+
+def metacal_mode_weights(aux, flags, weight):
+    """
+    The mode weights (T, N, R, C//2+1) of from_metacal from the kernel's aux
+    planes (T, N, R, C//2+1, 2) = keep, rho^2 and the flags (T, N): the common
+    mask of an object's types and, weight='noise', rho_min^2 / rho^2 on it.  A
+    flagged (type, object) takes no part in the others' mask.
+    """
+    torch = _torch()
+    bad = (flags != 0)[:, :, None, None]
+    keep = torch.where(bad, torch.ones_like(aux[..., 0]), aux[..., 0])
+    mask = keep.amin(dim=0, keepdim=True) > 0
+    if weight == "flat":
+        return mask.expand_as(keep).to(torch.float64).contiguous()
+    rho2 = torch.where(bad, torch.ones_like(keep), aux[..., 1])
+    zero = torch.zeros_like(rho2)
+    rmax = torch.where(mask, rho2, zero).amax(dim=(2, 3), keepdim=True)
+    mask = mask & (rho2 >= RHO2_FLOOR * rmax).all(dim=0, keepdim=True)
+    inf = torch.full_like(rho2, float("inf"))
+    rmin = torch.where(mask, rho2, inf).amin(dim=(2, 3), keepdim=True)
+    return torch.where(mask, rmin / rho2, zero).contiguous()
 
 
 def _spergel_hlr(nu):
@@ -318,6 +408,10 @@ class KSpaceBatchFitter(object):
                                    device=dev)
             d_sobj, d_sband, d_start = up(sobj), up(sband), up(start)
             d_npix = up(np.diff(start) * np.int64(kb.npix_eff))
+            # with mode weights the kernel counts the components that enter dof
+            d_mw = kb.mode_weight
+            d_ncomp = torch.zeros(kb.n, dtype=torch.int32, device=dev) if d_mw is not None \
+                else None
             d_sums = torch.zeros((kb.n, nsum), dtype=torch.float64, device=dev)
             d_status = torch.zeros(kb.n, dtype=torch.int32, device=dev)
             d_sstats = torch.zeros((kb.n, 2), dtype=torch.float64, device=dev)
@@ -350,9 +444,16 @@ class KSpaceBatchFitter(object):
                 nr = min(grow, 2 * maxfev + 5 - total)
                 d_counts = torch.empty(nr, dtype=torch.int32, device=dev)
                 h_counts = torch.empty(nr, dtype=torch.int32, pin_memory=True)
-                _lib.check(L.ngmix_kfit_rounds_batch(
-                    ctypes.byref(P), nr, _dptr(d_counts), ctypes.c_void_p(h_counts.data_ptr()),
-                    None, stream), "ngmix_kfit_rounds_batch")
+                if d_mw is None:
+                    _lib.check(L.ngmix_kfit_rounds_batch(
+                        ctypes.byref(P), nr, _dptr(d_counts),
+                        ctypes.c_void_p(h_counts.data_ptr()), None, stream),
+                        "ngmix_kfit_rounds_batch")
+                else:
+                    _lib.check(L.ngmix_kfit_rounds_w_batch(
+                        ctypes.byref(P), _dptr(d_mw), _dptr(d_ncomp), nr, _dptr(d_counts),
+                        ctypes.c_void_p(h_counts.data_ptr()), None, stream),
+                        "ngmix_kfit_rounds_w_batch")
                 torch.cuda.current_stream(dev).synchronize()
                 chunks.append((d_counts, h_counts))
                 total += nr
@@ -362,6 +463,9 @@ class KSpaceBatchFitter(object):
                     raise RuntimeError("batched LM did not terminate")
                 grow = min(2 * grow, 64)
             self.rounds_launched = total
+            if d_mw is not None:
+                d_npix = torch.zeros(nobj, dtype=torch.int64, device=dev)
+                d_npix.index_add_(0, d_sobj.long(), d_ncomp.long())
 
             d_ffx = None
             if desc is not None:
@@ -406,10 +510,16 @@ class KSpaceBatchFitter(object):
         d_sums = torch.empty((kb.n, _lib.LM_NSUM if self.nloc == 6 else 36), dtype=torch.float64,
                              device=dev)
         d_stats = torch.zeros((kb.n, 2), dtype=torch.float64, device=dev)
-        _lib.check(L.ngmix_kfit_eval_batch(
-            P.dhat, P.phat, P.wbar, P.jac, kb.nrow, kb.ncol, kb.n, self.model_id,
-            _dptr(d_copy), P.stamp_obj, P.stamp_band, _dptr(d_sums), None, _dptr(d_stats),
-            _stream()), "ngmix_kfit_eval_batch")
+        if kb.mode_weight is None:
+            _lib.check(L.ngmix_kfit_eval_batch(
+                P.dhat, P.phat, P.wbar, P.jac, kb.nrow, kb.ncol, kb.n, self.model_id,
+                _dptr(d_copy), P.stamp_obj, P.stamp_band, _dptr(d_sums), None, _dptr(d_stats),
+                _stream()), "ngmix_kfit_eval_batch")
+        else:
+            _lib.check(L.ngmix_kfit_eval_w_batch(
+                P.dhat, P.phat, _dptr(kb.mode_weight), P.wbar, P.jac, kb.nrow, kb.ncol, kb.n,
+                self.model_id, _dptr(d_copy), P.stamp_obj, P.stamp_band, _dptr(d_sums), None,
+                _dptr(d_stats), None, _stream()), "ngmix_kfit_eval_w_batch")
         mm = torch.zeros(nobj, dtype=torch.float64, device=dev)
         mm.index_add_(0, d_sobj.long(), d_stats[:, 1])
         return torch.sqrt(mm).cpu().numpy()
@@ -542,10 +652,21 @@ class KSpaceFluxBatch(object):
         with _on_device(dev):
             d_out = torch.empty((kb.n, 3), dtype=torch.float64, device=dev)
             d_status = torch.zeros(kb.n, dtype=torch.int32, device=dev)
-            _lib.check(_lib.lib().ngmix_kfit_flux_batch(
-                _dptr(kb.dhat), _dptr(kb.phat) if kb.phat is not None else None, _dptr(kb.wbar),
-                ctypes.c_void_p(kb.jac.data_ptr()), kb.nrow, kb.ncol, kb.n, self.model_id,
-                _dptr(d_p), _dptr(d_out), _dptr(d_status), _stream()), "ngmix_kfit_flux_batch")
+            self._ncomp = None
+            if kb.mode_weight is None:
+                _lib.check(_lib.lib().ngmix_kfit_flux_batch(
+                    _dptr(kb.dhat), _dptr(kb.phat) if kb.phat is not None else None,
+                    _dptr(kb.wbar), ctypes.c_void_p(kb.jac.data_ptr()), kb.nrow, kb.ncol, kb.n,
+                    self.model_id, _dptr(d_p), _dptr(d_out), _dptr(d_status), _stream()),
+                    "ngmix_kfit_flux_batch")
+            else:
+                d_ncomp = torch.zeros(kb.n, dtype=torch.int32, device=dev)
+                _lib.check(_lib.lib().ngmix_kfit_flux_w_batch(
+                    _dptr(kb.dhat), _dptr(kb.phat) if kb.phat is not None else None,
+                    _dptr(kb.mode_weight), _dptr(kb.wbar), ctypes.c_void_p(kb.jac.data_ptr()),
+                    kb.nrow, kb.ncol, kb.n, self.model_id, _dptr(d_p), _dptr(d_out),
+                    _dptr(d_status), _dptr(d_ncomp), _stream()), "ngmix_kfit_flux_w_batch")
+                self._ncomp = d_ncomp.cpu().numpy()
         return d_out, d_status
 
     def go(self, kb, stamp_obj=None, stamp_band=None):
@@ -575,7 +696,11 @@ class KSpaceFluxBatch(object):
             flux = np.where(bad, PDEF, A / Bs)
             flux_err = np.where(bad, CDEF, 1.0 / np.sqrt(Bs))
             chi2 = np.where(bad, 0.0, E - A * A / Bs)
-        dof = (nstamp * kb.npix_eff - 1).astype("f8")
+        if self._ncomp is None:
+            dof = (nstamp * kb.npix_eff - 1).astype("f8")
+        else:
+            # (mode weights: the components with a positive weight)
+            dof = np.bincount(sobj, weights=self._ncomp, minlength=nobj) - 1.0
         dof = np.where(dof <= 0, 1.0e-6, dof)
         flags = np.where(bad, DIV_ZERO, 0).astype(np.int64)
         return {"flags": flags, "flux": flux, "flux_err": flux_err, "chi2per": chi2 / dof,

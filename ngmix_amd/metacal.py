@@ -41,6 +41,13 @@ the images ("metacal pre-psf moments"; csrc/prepsf_shear.hip):
     metacal_moments_many(list_of_obs, measure, step=0.01, types=None, fixnoise=False,
                          noise_seed=None, ids=None, use_noise_image=False) -> [resdict_i]
 
+and the fit of an exact profile in Fourier space to every type, without the
+images either ("metacal shear from Fourier-space fits"):
+
+    metacal_kfit_batch(stamps, psf_stamps, model='gauss', step=0.01, types=None,
+                       psf='fitgauss', target_sigma=None, weight='flat', ...) -> resdict
+    MetacalBatch.kfit_spectra(g, per_stamp=False, dil=None, kind=None)
+
 Moments of noisy stamps carry the noise response; fixnoise=True with noise_seed
 (or noise) sums the cancelling term of the turned, deconvolved, sheared noise
 field with them (DESIGN.md, "fixnoise for the pre-psf moments").
@@ -78,7 +85,7 @@ __all__ = ["MetacalBatch", "get_all_metacal", "METACAL_TYPES", "METACAL_MINIMAL_
            "METACAL_PSF_FIT_FAILURE", "METACAL_NONFINITE", "DeviceNoise",
            "metacal_bootstrap_batch", "shear_response", "mean_shear", "metacal_bootstrap",
            "MetacalBootstrapper", "metacal_bootstrap_many", "METACAL_BAND_LIMIT",
-           "metacal_moments_batch", "metacal_moments_many"]
+           "metacal_moments_batch", "metacal_moments_many", "metacal_kfit_batch"]
 
 METACAL_MINIMAL_TYPES = ["noshear", "1p", "1m", "2p", "2m"]
 METACAL_PSF_TYPES = ["1p_psf", "1m_psf", "2p_psf", "2m_psf"]
@@ -439,6 +446,50 @@ class MetacalBatch(object):
         psf_images = torch.where(flags[:, :, None, None] != 0, nan, psf_images)
         return out, psf_images, flags
 
+    def kfit_spectra(self, g, per_stamp=False, dil=None, kind=None):
+        """
+        The operation of _run without a noise plane, written for the
+        Fourier-space fits (the KFIT form of
+        metacal_spectrum_kernel): g, dil, kind as _run takes them.  Returns
+        dhat, phat, aux, all (T N, R, C//2+1, 2) and type-major -- O^ about the
+        jacobian centre, the target psf over the psf stamp's sum, and (keep,
+        rho^2) per mode -- and the flags (T, N) int32 as _run's, on the device.
+        """
+        torch = _torch()
+        from .batch import _dptr, _stream, _on_device
+        n, (nrow, ncol), (prow, pcol) = self.n, self.shape, self.psf_shape
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        ntypes = g.shape[-2]
+        if g.shape != ((n, ntypes, 2) if per_stamp else (ntypes, 2)):
+            raise ValueError("g must be (T, 2), or (N, T, 2) with per_stamp")
+        _check_shears(g)
+        d_g = torch.from_numpy(g).to(self.device)
+        d_dil = d_kind = None
+        if self.dilate:
+            dil = np.ascontiguousarray(dil, dtype=np.float64)
+            kind = np.ascontiguousarray(kind, dtype=np.int32)
+            if dil.shape != g.shape[:-1] or kind.shape != g.shape[:-1]:
+                raise ValueError("one dilation and one kind per shear")
+            d_dil, d_kind = torch.from_numpy(dil).to(self.device), \
+                torch.from_numpy(kind).to(self.device)
+        shape = (ntypes * n, nrow, ncol // 2 + 1, 2)
+        dhat, phat, aux = (torch.empty(shape, dtype=torch.float64, device=self.device)
+                           for _ in range(3))
+        kflags = torch.empty((ntypes, n), dtype=torch.int32, device=self.device)
+        images = self.stamps.val.reshape(n, nrow, ncol).contiguous()
+        with _on_device(self.device):
+            st = _lib.lib().ngmix_metacal_kfit_spectrum_batch(
+                _dptr(images), _dptr(self.psf_stamps.val), _dptr(self.stamps.jac),
+                _dptr(self._psf_cen), _dptr(self._psf_flux),
+                None if self.dilate else _dptr(self._sigma), _dptr(d_g), _dptr(d_dil),
+                _dptr(d_kind), _lib.ptr(g), _lib.ptr(dil) if self.dilate else None,
+                _lib.ptr(kind) if self.dilate else None, int(per_stamp), n, ntypes, nrow, ncol,
+                prow, pcol, _dptr(dhat), _dptr(phat), _dptr(aux), _dptr(kflags), _stream())
+        _lib.check(st, "ngmix_metacal_kfit_spectrum_batch")
+        flags = torch.where(kflags != 0, METACAL_NONFINITE, 0).to(torch.int32) | \
+            torch.from_numpy(self.fit_flags).to(self.device)[None, :]
+        return dhat, phat, aux, flags
+
     def _psf_jacobians(self):
         """the psf stamps' jacobians with the centre at the stamp's exact centre"""
         jac = self.psf_stamps.jac.clone()
@@ -730,6 +781,81 @@ def metacal_bootstrap_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP
         res["mcal_flags"] = d["flags"]
         resdict[t] = res
     return resdict, batchdict
+
+
+def _flat_moment_r50(stamps, psf_stamps):
+    """a starting r50 per stamp from the flat-weight second moments about the
+    jacobian centres: T = sum I (v^2 + u^2) / sum I of the image less the psf
+    stamp's, as a round gaussian's r50 = sqrt(2 ln 2) sqrt(T / 2); where that
+    is not positive, half the image's own T, and at least half a pixel"""
+    torch = _torch()
+
+    def flat_T(sb):
+        nrow, ncol = _one_shape(sb, "stamps")
+        val = sb.val.reshape(sb.n, nrow, ncol)
+        r = torch.arange(nrow, dtype=torch.float64, device=sb.device)[None, :, None] \
+            - sb.jac[:, 0, None, None]
+        c = torch.arange(ncol, dtype=torch.float64, device=sb.device)[None, None, :] \
+            - sb.jac[:, 1, None, None]
+        col = lambda k: sb.jac[:, k, None, None]
+        v, u = col(2) * r + col(3) * c, col(4) * r + col(5) * c
+        return (val * (v * v + u * u)).sum(dim=(1, 2)) / val.sum(dim=(1, 2))
+
+    T, Tp = flat_T(stamps), flat_T(psf_stamps)
+    floor = (0.5 * stamps.jac[:, 7]) ** 2
+    Tobj = torch.where(T - Tp > 0, T - Tp, 0.5 * T)
+    Tobj = torch.where(torch.isfinite(Tobj) & (Tobj > 2.0 * floor), Tobj, 2.0 * floor)
+    return np.sqrt(2.0 * np.log(2.0)) * torch.sqrt(0.5 * Tobj)
+
+
+def metacal_kfit_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP, types=None,
+                       psf="fitgauss", target_sigma=None, weight="flat", prior=None, guess=None,
+                       size_type=None, fit_pars=None, fixnoise=False, rng=None):
+    """
+    Metacal shear from Fourier-space fits of an exact profile:
+    KStampBatch.from_metacal(stamps, psf_stamps, types, step, psf, target_sigma,
+    weight) -- the types' spectra straight in the fit's layout, the target psf
+    analytic, a weight per mode -- then ONE KSpaceBatchFitter(model, prior,
+    fit_pars, size_type=size_type).go over all types' stamps.
+
+    guess: (N, npars) used for every type, or (ntypes N, npars) type-major;
+        None: centre 0, g = 0, r50 from the stamp's flat-weight second moments
+        (less the psf stamp's), nu = 0.5 | beta = 2.5, flux D^(0)
+    weight: 'flat' or 'noise', as from_metacal
+    psf='dilate-exact' serves the `*_psf` types too; fixnoise is not served.
+
+    Returns {type: KSpaceBatchFitter.go's dict of the type's N objects, with
+    'mcal_flags' (N,) added}: what shear_response and mean_shear take.
+    """
+    from .kfit import KStampBatch, KSpaceBatchFitter, MODEL_NLOC
+    torch = _torch()
+    kb = KStampBatch.from_metacal(stamps, psf_stamps, types=types, step=step, psf=psf,
+                                  target_sigma=target_sigma, weight=weight, fixnoise=fixnoise,
+                                  rng=rng)
+    ntypes, n = len(kb.types), stamps.n
+    fitter = KSpaceBatchFitter(model, prior=prior, fit_pars=fit_pars, size_type=size_type)
+    npars = MODEL_NLOC[model]
+    if guess is None:
+        d_guess = torch.zeros((ntypes * n, npars), dtype=torch.float64, device=kb.device)
+        d_guess[:, 4] = _flat_moment_r50(stamps, psf_stamps).repeat(ntypes)
+        if npars == 7:
+            d_guess[:, 5] = 0.5 if model == "spergel" else 2.5
+        flux = kb.dhat[:, 0, 0, 0]
+        d_guess[:, npars - 1] = torch.where(torch.isfinite(flux), flux, torch.ones_like(flux))
+        guess = d_guess
+    else:
+        guess = np.asarray(guess, dtype=np.float64)
+        if guess.shape == (n, npars):
+            guess = np.tile(guess, (ntypes, 1))
+        if guess.shape != (ntypes * n, npars):
+            raise ValueError("guess must be (%d, %d) or (%d, %d)" % (n, npars, ntypes * n, npars))
+    res = fitter.go(kb, guess)
+    out = {}
+    for i, t in enumerate(kb.types):
+        sl = slice(i * n, (i + 1) * n)
+        out[t] = {k: (v if isinstance(v, str) else v[sl]) for k, v in res.items()}
+        out[t]["mcal_flags"] = kb.mcal_flags[i]
+    return out
 
 
 def _response_column(res, key):

@@ -39,7 +39,15 @@ GUARDS = {
 # only memory spills are an error
 NO_SPILL_ONLY = ("admom_grid_kernel", "em_wave_kernel", "wsums_wave_kernel",
                  "lm_eval_kernel", "lm_eval_fd_kernel", "kfit_eval_kernel", "kfit_flux_kernel",
-                 "moffat_phi_kernel")
+                 "moffat_phi_kernel", "metacal_spectrum_kernel")
+# instantiations that must be there and free of scratch under their own names:
+# the mode-weight forms of the k-space kernels (five models, and the point
+# source of the flux kernel) and the two spectrum kernels that write for them
+REQUIRED = {
+    r"kfit_eval_kernel<-?\d+, true>": 5,
+    r"kfit_flux_kernel<-?\d+, true>": 6,
+    r"metacal_spectrum_kernel<false, [01], true>": 2,
+}
 
 
 def code_objects(lib):
@@ -121,6 +129,13 @@ def check(lib, verbose=False):
     for k in list(GUARDS) + list(NO_SPILL_ONLY):
         if k not in seen:
             problems.append("guarded kernel %s not found in %s" % (k, lib))
+    for pat, count in REQUIRED.items():
+        hits = [n for n in table if re.search(pat, n)]
+        if len(hits) != count:
+            problems.append("%d kernels match %s, %d expected" % (len(hits), pat, count))
+        for n in hits:
+            if table[n].get("private_segment_fixed_size", 0):
+                problems.append("%s: scratch" % n)
     return table, problems
 
 

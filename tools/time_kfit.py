@@ -6,10 +6,18 @@ and whole fits per second through KSpaceBatchFitter, for N 32x32 and 48x48
 stamps, 'exp' and 'spergel', each stamp with a psf transform.
 
     python tools/time_kfit.py [--n 100000] [--json out.json] [--model moffat] [--flux]
+    python tools/time_kfit.py --metacal [--n 100000] [--json out.json]
 
 --model moffat times 'spergel' and 'moffat' side by side (the ratio says
 whether K_nu or the sums dominate); --flux adds kfit_flux_kernel per launch for
 the point source and for each timed model.
+
+--metacal times the metacal shear from Fourier-space fits
+instead: the five types of N stamps, 'gauss', an explicit target width, by
+KStampBatch.from_metacal + one fit (metacal_kfit_batch) against
+MetacalBatch.get_all + KStampBatch.from_stamps + a fit per type on the same
+stamps, both in the same run, each the median of 7 after 2 warm-ups between
+device events, with the parts of either route beside the totals.
 
 The real-space LMBatchFitter is a different model (a gaussian mixture against
 a fitted psf mixture) and is not timed here; nothing gates on these figures.
@@ -134,14 +142,107 @@ def time_fit(kb, guess, model):
     return float(np.median(secs)), int((res["flags"] == 0).sum()), fitter.rounds_launched
 
 
+def _events_ms(fn, reps=9, warm=2):
+    """fn() between two device events: the median of reps - warm after warm"""
+    ms, out = [], None
+    for it in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        if it >= warm:
+            ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), out
+
+
+def time_metacal(n, dim, seed=5):
+    """one row: the direct route against the route through the images"""
+    from ngmix_amd import metacal
+    from ngmix_amd.batch import StampBatch
+    rng = np.random.RandomState(seed)
+    scale = 0.263
+    jac = np.zeros((n, 8))
+    jac[:, 0] = (dim - 1) / 2 + rng.uniform(-0.4, 0.4, n)
+    jac[:, 1] = (dim - 1) / 2 + rng.uniform(-0.4, 0.4, n)
+    jac[:, 2] = jac[:, 5] = scale
+    jac[:, 6], jac[:, 7] = scale * scale, scale
+    pjac = jac.copy()
+    pjac[:, 0] = pjac[:, 1] = (dim - 1) / 2
+    r = torch.arange(dim, dtype=torch.float64, device="cuda")
+    d_jac = torch.from_numpy(jac).cuda()
+
+    def gauss(cen, sig2, flux):
+        dr = r[None, :, None] - cen[:, 0, None, None]
+        dc = r[None, None, :] - cen[:, 1, None, None]
+        return flux[:, None, None] * torch.exp(-0.5 * (dr * dr + dc * dc) / sig2[:, None, None]) \
+            / (2 * np.pi * sig2[:, None, None])
+    one = torch.ones(n, dtype=torch.float64, device="cuda")
+    sig_psf = 1.3
+    sig2 = torch.from_numpy(sig_psf ** 2 + rng.uniform(1.5, 2.5, n) ** 2).cuda()
+    flux = torch.from_numpy(rng.uniform(50.0, 150.0, n)).cuda()
+    imgs = gauss(d_jac[:, 0:2], sig2, flux) + 0.01 * torch.randn(
+        (n, dim, dim), dtype=torch.float64, device="cuda",
+        generator=torch.Generator(device="cuda").manual_seed(seed))
+    psfs = gauss(torch.from_numpy(pjac[:, 0:2]).cuda(), sig_psf ** 2 * one, one)
+    sb = StampBatch.from_images(imgs, torch.full_like(imgs, 1e4), jac)
+    psb = StampBatch.from_images(psfs, None, pjac)
+    sigma = np.full(n, 1.1 * sig_psf * scale)
+    guess = np.zeros((n, 6))
+    guess[:, 4] = 2.0 * scale * 1.1774
+    guess[:, 5] = flux.cpu().numpy()
+    types = metacal.METACAL_MINIMAL_TYPES
+    fit_pars = {"maxfev": 200}
+
+    def direct():
+        return metacal.metacal_kfit_batch(sb, psb, model="gauss", target_sigma=sigma,
+                                          guess=guess, fit_pars=fit_pars)
+
+    def spectra_only():
+        return KStampBatch.from_metacal(sb, psb, target_sigma=sigma)
+
+    def images_only():
+        return metacal.MetacalBatch(sb, psb, target_sigma=sigma).get_all()
+
+    def through_images():
+        res = {}
+        for t, d in images_only().items():
+            kb = KStampBatch.from_stamps(d["stamps"], d["psf_stamps"])
+            res[t] = KSpaceBatchFitter("gauss", fit_pars=fit_pars).go(kb, guess)
+        return res
+
+    direct_ms, a = _events_ms(direct)
+    images_ms, b = _events_ms(through_images)
+    from_metacal_ms, _ = _events_ms(spectra_only)
+    get_all_ms, _ = _events_ms(images_only)
+    ok = lambda res: int(sum((res[t]["flags"] == 0).sum() for t in types))
+    dg = float(np.nanmax(np.abs(a["1p"]["g"] - b["1p"]["g"])))
+    return {"metacal": True, "dim": dim, "n": n, "types": len(types),
+            "direct_ms": direct_ms, "through_images_ms": images_ms,
+            "from_metacal_ms": from_metacal_ms, "get_all_ms": get_all_ms,
+            "direct_flags_ok": ok(a), "through_images_flags_ok": ok(b),
+            "max_abs_dg_1p_between_routes": dg}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=100000)
     ap.add_argument("--json", default=None)
     ap.add_argument("--model", default=None, choices=["moffat"])
     ap.add_argument("--flux", action="store_true")
+    ap.add_argument("--metacal", action="store_true")
     args = ap.parse_args()
     out = []
+    if args.metacal:
+        for dim in (32, 48):
+            row = time_metacal(args.n, dim)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+            torch.cuda.empty_cache()
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     for dim in (32, 48):
         for model in ("spergel", "moffat") if args.model == "moffat" else ("exp", "spergel"):
             kb, guess = make_batch(args.n, dim, model, 5)
