@@ -16,6 +16,7 @@
 #include "lm_core.hpp"
 #include "lm_core_reg.hpp"
 #include "launch_iter.hpp"
+#include "launch_util.hpp"
 #include "metacal_noise.hpp"
 #include "prepsf_shear.hpp"
 #include "kfit.hpp"
@@ -1087,6 +1088,17 @@ int ngmix_spergel_hlr(double nu, double *c, double *dc_dnu)
     return spergel_hlr(nu, *c, *dc_dnu) ? NGMIX_OK : NGMIX_ERR_G_RANGE;
 }
 
+// the MODEW entries need their plane (a call with no stamps aside)
+static int need_modew(const char *who, const double *modew, int64_t nstamps)
+{
+    if (modew || nstamps <= 0) return NGMIX_OK;
+    set_last_error_msg((std::string(who) + ": mode_weight is required").c_str());
+    return NGMIX_ERR_BAD_ARG;
+}
+
+// The kfit entries.  A device entry is its launcher's call: the plain one with
+// no plane and no ncomp, the _w one after need_modew.  The two host entries of
+// a kernel share one body; w: the _w entry, whose plane is required.
 int ngmix_kfit_eval_batch(const double *dhat, const double *phat, const double *wbar,
                           const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
                           const ngmix_lm_state *states, const int32_t *stamp_obj,
@@ -1095,65 +1107,6 @@ int ngmix_kfit_eval_batch(const double *dhat, const double *phat, const double *
 {
     return launch_kfit_eval(dhat, phat, wbar, jac, R, C, nstamps, model, states, stamp_obj,
                             stamp_band, sums, status, stamp_stats, (hipStream_t)stream);
-}
-
-int ngmix_kfit_eval_host(const double *dhat, const double *phat, const double *wbar,
-                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                         const ngmix_lm_state *states, const int32_t *stamp_obj,
-                         const int32_t *stamp_band, double *sums, int32_t *status,
-                         double *stamp_stats)
-{
-    bool nothing;
-    const int st = kfit::check_args("kfit_eval_host", dhat, wbar, jac, R, C, nstamps, model,
-                                    states, sums, nothing);
-    if (st != NGMIX_OK || nothing) return st;
-    if (model == NGMIX_KFIT_GAUSS)
-        kfit::host_eval<NGMIX_KFIT_GAUSS>(dhat, phat, wbar, jac, R, C, nstamps, states, stamp_obj,
-                                          stamp_band, sums, status, stamp_stats);
-    else if (model == NGMIX_KFIT_EXP)
-        kfit::host_eval<NGMIX_KFIT_EXP>(dhat, phat, wbar, jac, R, C, nstamps, states, stamp_obj,
-                                        stamp_band, sums, status, stamp_stats);
-    else if (model == NGMIX_KFIT_SPERGEL)
-        kfit::host_eval<NGMIX_KFIT_SPERGEL>(dhat, phat, wbar, jac, R, C, nstamps, states,
-                                            stamp_obj, stamp_band, sums, status, stamp_stats);
-    else if (model == NGMIX_KFIT_MOFFAT)
-        kfit::host_eval<NGMIX_KFIT_MOFFAT>(dhat, phat, wbar, jac, R, C, nstamps, states,
-                                           stamp_obj, stamp_band, sums, status, stamp_stats);
-    else
-        kfit::host_eval<NGMIX_KFIT_MOFFAT_FWHM>(dhat, phat, wbar, jac, R, C, nstamps, states,
-                                                stamp_obj, stamp_band, sums, status,
-                                                stamp_stats);
-    return NGMIX_OK;
-}
-
-int ngmix_kfit_flux_batch(const double *dhat, const double *phat, const double *wbar,
-                          const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                          const double *pars, double *out, int32_t *status, void *stream)
-{
-    return launch_kfit_flux(dhat, phat, wbar, jac, R, C, nstamps, model, pars, out, status,
-                            (hipStream_t)stream);
-}
-
-int ngmix_kfit_flux_host(const double *dhat, const double *phat, const double *wbar,
-                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                         const double *pars, double *out, int32_t *status)
-{
-    bool nothing;
-    const int st = kfit::check_flux_args("kfit_flux_host", dhat, wbar, jac, R, C, nstamps, model,
-                                         pars, out, nothing);
-    if (st != NGMIX_OK || nothing) return st;
-    kfit::host_flux_for<kfit::MODEL_POINT, NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL,
-                        NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(
-        model, dhat, phat, wbar, jac, R, C, nstamps, pars, out, status);
-    return NGMIX_OK;
-}
-
-// the MODEW entries need their plane (a call with no stamps aside)
-static int need_modew(const char *who, const double *modew, int64_t nstamps)
-{
-    if (modew || nstamps <= 0) return NGMIX_OK;
-    set_last_error_msg((std::string(who) + ": mode_weight is required").c_str());
-    return NGMIX_ERR_BAD_ARG;
 }
 
 int ngmix_kfit_eval_w_batch(const double *dhat, const double *phat, const double *mode_weight,
@@ -1169,23 +1122,53 @@ int ngmix_kfit_eval_w_batch(const double *dhat, const double *phat, const double
                             mode_weight, ncomp);
 }
 
+static int kfit_eval_host(const char *who, bool w, const double *dhat, const double *phat,
+                          const double *modew, const double *wbar, const ngmix_jacobian *jac,
+                          int R, int C, int64_t nstamps, int model, const ngmix_lm_state *states,
+                          const int32_t *stamp_obj, const int32_t *stamp_band, double *sums,
+                          int32_t *status, double *stamp_stats, int32_t *ncomp)
+{
+    bool nothing;
+    int st = kfit::check_args(who, false, R, C, nstamps, kfit::model_nloc(model) != 0,
+                              dhat && wbar && jac && states && sums, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    if (w && (st = need_modew(who, modew, nstamps)) != NGMIX_OK) return st;
+    for_int<NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL, NGMIX_KFIT_MOFFAT,
+            NGMIX_KFIT_MOFFAT_FWHM>(model, [&](auto M) {
+        const kfit::EvalSums<M()> pol{states, stamp_obj, stamp_band, sums, stamp_stats};
+        kfit::host_walk(pol, dhat, phat, wbar, jac, R, C, nstamps, status, modew, ncomp);
+    });
+    return NGMIX_OK;
+}
+
+int ngmix_kfit_eval_host(const double *dhat, const double *phat, const double *wbar,
+                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                         const ngmix_lm_state *states, const int32_t *stamp_obj,
+                         const int32_t *stamp_band, double *sums, int32_t *status,
+                         double *stamp_stats)
+{
+    return kfit_eval_host("kfit_eval_host", false, dhat, phat, nullptr, wbar, jac, R, C, nstamps,
+                          model, states, stamp_obj, stamp_band, sums, status, stamp_stats,
+                          nullptr);
+}
+
 int ngmix_kfit_eval_w_host(const double *dhat, const double *phat, const double *mode_weight,
                            const double *wbar, const ngmix_jacobian *jac, int R, int C,
                            int64_t nstamps, int model, const ngmix_lm_state *states,
                            const int32_t *stamp_obj, const int32_t *stamp_band, double *sums,
                            int32_t *status, double *stamp_stats, int32_t *ncomp)
 {
-    bool nothing;
-    int st = kfit::check_args("kfit_eval_w_host", dhat, wbar, jac, R, C, nstamps, model, states,
-                              sums, nothing);
-    if (st != NGMIX_OK || nothing) return st;
-    st = need_modew("kfit_eval_w_host", mode_weight, nstamps);
-    if (st != NGMIX_OK) return st;
-    kfit::host_eval_w_for<NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL, NGMIX_KFIT_MOFFAT,
-                          NGMIX_KFIT_MOFFAT_FWHM>(model, dhat, phat, wbar, jac, R, C, nstamps,
-                                                  states, stamp_obj, stamp_band, sums, status,
-                                                  stamp_stats, mode_weight, ncomp);
-    return NGMIX_OK;
+    return kfit_eval_host("kfit_eval_w_host", true, dhat, phat, mode_weight, wbar, jac, R, C,
+                          nstamps, model, states, stamp_obj, stamp_band, sums, status,
+                          stamp_stats, ncomp);
+}
+
+int ngmix_kfit_flux_batch(const double *dhat, const double *phat, const double *wbar,
+                          const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                          const double *pars, double *out, int32_t *status, void *stream)
+{
+    return launch_kfit_flux(dhat, phat, wbar, jac, R, C, nstamps, model, pars, out, status,
+                            (hipStream_t)stream);
 }
 
 int ngmix_kfit_flux_w_batch(const double *dhat, const double *phat, const double *mode_weight,
@@ -1199,21 +1182,46 @@ int ngmix_kfit_flux_w_batch(const double *dhat, const double *phat, const double
                             (hipStream_t)stream, mode_weight, ncomp);
 }
 
+static int kfit_flux_host(const char *who, bool w, const double *dhat, const double *phat,
+                          const double *modew, const double *wbar, const ngmix_jacobian *jac,
+                          int R, int C, int64_t nstamps, int model, const double *pars,
+                          double *out, int32_t *status, int32_t *ncomp)
+{
+    bool nothing;
+    int st = kfit::check_args(who, true, R, C, nstamps, kfit::flux_npars(model) != 0,
+                              dhat && wbar && jac && pars && out, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    if (w && (st = need_modew(who, modew, nstamps)) != NGMIX_OK) return st;
+    for_int<kfit::MODEL_POINT, NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL,
+            NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(model, [&](auto M) {
+        const kfit::FluxSums<M()> pol{pars, out};
+        kfit::host_walk(pol, dhat, phat, wbar, jac, R, C, nstamps, status, modew, ncomp);
+    });
+    return NGMIX_OK;
+}
+
+int ngmix_kfit_flux_host(const double *dhat, const double *phat, const double *wbar,
+                         const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
+                         const double *pars, double *out, int32_t *status)
+{
+    return kfit_flux_host("kfit_flux_host", false, dhat, phat, nullptr, wbar, jac, R, C, nstamps,
+                          model, pars, out, status, nullptr);
+}
+
 int ngmix_kfit_flux_w_host(const double *dhat, const double *phat, const double *mode_weight,
                            const double *wbar, const ngmix_jacobian *jac, int R, int C,
                            int64_t nstamps, int model, const double *pars, double *out,
                            int32_t *status, int32_t *ncomp)
 {
-    bool nothing;
-    int st = kfit::check_flux_args("kfit_flux_w_host", dhat, wbar, jac, R, C, nstamps, model,
-                                   pars, out, nothing);
-    if (st != NGMIX_OK || nothing) return st;
-    st = need_modew("kfit_flux_w_host", mode_weight, nstamps);
-    if (st != NGMIX_OK) return st;
-    kfit::host_flux_w_for<kfit::MODEL_POINT, NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL,
-                          NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(
-        model, dhat, phat, wbar, jac, R, C, nstamps, pars, out, status, mode_weight, ncomp);
-    return NGMIX_OK;
+    return kfit_flux_host("kfit_flux_w_host", true, dhat, phat, mode_weight, wbar, jac, R, C,
+                          nstamps, model, pars, out, status, ncomp);
+}
+
+int ngmix_kfit_rounds_batch(const ngmix_kfit_problem *problem, int nrounds, int32_t *counts,
+                            int32_t *counts_host, void **events, void *stream)
+{
+    return launch_kfit_rounds(problem, nrounds, counts, counts_host, events,
+                              (hipStream_t)stream);
 }
 
 int ngmix_kfit_rounds_w_batch(const ngmix_kfit_problem *problem, const double *mode_weight,
@@ -1238,13 +1246,6 @@ int ngmix_moffat_phi_batch(const double *nu, const double *x, int64_t n, double 
                            void *stream)
 {
     return launch_moffat_phi(nu, x, n, out, (hipStream_t)stream);
-}
-
-int ngmix_kfit_rounds_batch(const ngmix_kfit_problem *problem, int nrounds, int32_t *counts,
-                            int32_t *counts_host, void **events, void *stream)
-{
-    return launch_kfit_rounds(problem, nrounds, counts, counts_host, events,
-                              (hipStream_t)stream);
 }
 
 int ngmix_events_create(int n, void **events)

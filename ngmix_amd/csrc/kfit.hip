@@ -7,10 +7,10 @@
 //       lanes stride over the stored modes of the stamp's rfft2 half plane,
 //       load D^ and P^n as 16-byte pairs (consecutive lanes, consecutive
 //       pairs), evaluate the model and its analytic jacobian at the object's
-//       trial point in registers (kfit.hpp has the per-mode text, shared with
-//       the host twin) and accumulate the stamp's normal equations; the lanes
-//       are summed in the fixed tree of wave_sum.  No LDS, no atomics, fp64: a
-//       stamp's sums do not depend on the batch around it or on the launch.
+//       trial point in registers and accumulate the stamp's normal equations;
+//       the lanes are summed in the fixed tree of wave_sum.  No LDS, no
+//       atomics, fp64: a stamp's sums do not depend on the batch around it or
+//       on the launch.
 //
 //   kfit_flux_kernel<MODEL>  the same walk for a FIXED unit-flux template T^ --
 //       any of the models at given parameters, or a point source (the psf
@@ -25,6 +25,12 @@
 //   moffat_phi_kernel  moffat_phi.hpp's function at n pairs, one thread each:
 //       what holds the device's arithmetic to the fixture without a fit.
 //
+// Both kernels are a prologue and stamp_walk<Policy, MODEW> below, with kfit.hpp's
+// EvalSums<MODEL> or FluxSums<MODEL> for what they differ in; the walk over a
+// lane's modes, the per-mode text and the epilogues are kfit.hpp's, shared with
+// the host twins.  A launcher's kernel is the (model, modew != nullptr) entry of
+// its one table of rows, a row a model's <MODEL, false> and <MODEL, true>.
+//
 // The step that consumes the sums is ngmix_lm_advance_batch as it stands: the
 // layout is that of lm_eval_kernel (lmfit.hip), a finished fit is skipped and
 // its sums are left as they are.
@@ -37,7 +43,88 @@ namespace ngmix {
 
 namespace {
 constexpr int KFIT_STAMPS_PER_BLOCK = BLOCK / WAVE;
+
+// the device's load of mode i's D^ and P^n (1 without a psf): 16 bytes each,
+// consecutive lanes, consecutive pairs; the launchers check the alignment
+struct LoadPairs {
+    const double2 *D, *P;
+    NGMIX_HD void operator()(int i, double &dr, double &di, double &pr, double &pi) const
+    {
+        const double2 d = D[i];
+        double2 q = make_double2(1.0, 0.0);
+        if (P) q = P[i];
+        dr = d.x, di = d.y, pr = q.x, pi = q.y;
+    }
+};
+
+// a wave's stamp s, the body of both kernels: the policy's set-up, lane's modes
+// (kfit.hpp: walk_lane), the lanes summed in the tree of wave_sum, lane 0 writes
+template <typename Policy, bool MODEW>
+__device__ __forceinline__ void stamp_walk(const Policy &pol, const double2 *dhat,
+                                           const double2 *phat, const double *wbar,
+                                           const ngmix_jacobian *jacs, int R, int C, int64_t s,
+                                           int lane, int32_t *status, const double *modew,
+                                           int32_t *ncomp)
+{
+    static_assert(kfit::LANES == WAVE, "kfit.hpp mirrors device_utils.hpp");
+    kfit::Setup m;
+    if (!pol.setup(s, jacs, wbar, R, C, m)) return;
+    const int nm = R * (C / 2 + 1);
+    const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
+    int nc = 0;
+    if (m.bad) {   // (uniform over the wave)
+        if (MODEW && ncomp) nc = wave_sum_int(kfit::lane_components(m.wscale, U, lane, R, C));
+        if (lane == 0) kfit::refuse_stamp(pol, s, nc, status, MODEW ? ncomp : nullptr);
+        return;
+    }
+    const LoadPairs load{dhat + (size_t)s * nm, phat ? phat + (size_t)s * nm : nullptr};
+    double acc[Policy::NACC];
+#pragma unroll
+    for (int k = 0; k < Policy::NACC; k++) acc[k] = 0.0;
+    bool notfinite = false;
+    kfit::walk_lane<Policy, MODEW>(m, R, C, load, U, lane, acc, notfinite, nc);
+#pragma unroll
+    for (int k = 0; k < Policy::NACC; k++) acc[k] = wave_sum(acc[k]);
+    if (MODEW && ncomp) nc = wave_sum_int(nc);
+    const bool any_notfinite = __ballot(notfinite) != 0ull;
+    if (lane == 0) {
+        if (MODEW && ncomp) ncomp[s] = nc;
+        pol.finish(s, m, acc, any_notfinite, status);
+    }
 }
+
+// a launcher's row: a model and its kernel without and with a plane of mode
+// weights, each with the name the census counts it under
+template <typename K>
+struct KfitRow {
+    int model;
+    K k[2];
+};
+
+// the kernel of (model, with a plane); no kernel for a model outside the table
+template <typename K, size_t N>
+K kfit_kernel(const KfitRow<K> (&rows)[N], int model, bool w)
+{
+    for (const KfitRow<K> &r : rows)
+        if (r.model == model) return r.k[w];
+    return K{nullptr, nullptr};
+}
+
+// what every kfit launcher refuses after its argument check
+int check_aligned(const char *who, const double *dhat, const double *phat)
+{
+    if ((((uintptr_t)dhat | (uintptr_t)phat) & 15) == 0) return NGMIX_OK;
+    char msg[96];
+    snprintf(msg, sizeof(msg), "%s: dhat and phat must be 16-byte aligned", who);
+    set_last_error_msg(msg);
+    return NGMIX_ERR_BAD_ARG;
+}
+
+dim3 kfit_grid(int64_t nstamps)
+{
+    return dim3((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
+}
+}  // namespace
 
 template <int MODEL, bool MODEW = false>
 __global__ __launch_bounds__(BLOCK) void kfit_eval_kernel(
@@ -48,68 +135,19 @@ __global__ __launch_bounds__(BLOCK) void kfit_eval_kernel(
     double *__restrict__ sums, int32_t *__restrict__ status, double *__restrict__ stamp_stats,
     const double *__restrict__ modew, int32_t *__restrict__ ncomp)
 {
-    using T = kfit::Traits<MODEL>;
-    static_assert(kfit::LANES == WAVE, "kfit.hpp mirrors device_utils.hpp");
     const int64_t s = (int64_t)blockIdx.x * KFIT_STAMPS_PER_BLOCK + wave_id();
     if (s >= nstamps) return;
-    const int lane = lane_id();
-    const int obj = stamp_obj ? stamp_obj[s] : (int)s;
-    const ngmix_lm_state &state = states[obj];
-    if (state.phase == NGMIX_LM_PHASE_DONE) return;   // this object has finished
-    const int band = stamp_band ? stamp_band[s] : 0;
-    double p[T::NLOC];
-#pragma unroll
-    for (int k = 0; k < T::NLOC - 1; k++) p[k] = state.xt[k];
-    p[T::NLOC - 1] = state.xt[T::NLOC - 1 + band];
-    double *out = sums + (size_t)s * T::NSUMS;
-    double *stats = stamp_stats ? stamp_stats + 2 * (size_t)s : nullptr;
+    stamp_walk<kfit::EvalSums<MODEL>, MODEW>({states, stamp_obj, stamp_band, sums, stamp_stats},
+                                             dhat, phat, wbar, jacs, R, C, s, lane_id(), status,
+                                             modew, ncomp);
+}
 
-    const kfit::Setup m = kfit::setup<MODEL>(p, jacs[s], wbar[s], R, C);
-    const int CH = C / 2 + 1, nm = R * CH;
-    const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
-    int nc = 0;
-    if (m.bad) {   // (uniform over the wave)
-        if (MODEW && ncomp) nc = wave_sum_int(kfit::lane_components(m.wscale, U, lane, R, C));
-        if (lane == 0) {
-            kfit::write_refused(T::NSUMS, out, stats);
-            if (status) status[s] = NGMIX_ERR_G_RANGE;
-            if (MODEW && ncomp) ncomp[s] = nc;
-        }
-        return;
-    }
-
-    const double2 *D = dhat + (size_t)s * nm;
-    const double2 *P = phat ? phat + (size_t)s * nm : nullptr;
-    double acc[T::NACC];
-#pragma unroll
-    for (int k = 0; k < T::NACC; k++) acc[k] = 0.0;
-    bool notfinite = false;
-    for (int i = lane; i < nm; i += WAVE) {
-        const int a = i / CH, b = i - a * CH;
-        const double mult = kfit::mode_mult(a, b, R, C);
-        if (mult == 0.0) continue;
-        double w;
-        if (!kfit::mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
-        const double2 d = D[i];
-        double2 q = make_double2(1.0, 0.0);
-        if (P) q = P[i];
-        if (!isfinite(d.x + d.y + q.x + q.y)) notfinite = true;
-        kfit::add_mode<MODEL>(m, a, b, R, w, d.x, d.y, q.x, q.y, acc);
-    }
-#pragma unroll
-    for (int k = 0; k < T::NACC; k++) acc[k] = wave_sum(acc[k]);
-    if (MODEW && ncomp) nc = wave_sum_int(nc);
-    const bool any_notfinite = __ballot(notfinite) != 0ull;
-    if (lane == 0) {
-        if (MODEW && ncomp) ncomp[s] = nc;
-        if (any_notfinite) {
-            kfit::write_refused(T::NSUMS, out, stats);
-            if (status) status[s] = NGMIX_ERR_NOT_FINITE;
-        } else {
-            kfit::write_sums<MODEL>(acc, m.flux, out, stats);
-            if (status) status[s] = NGMIX_OK;
-        }
-    }
+template <int M>
+static constexpr auto eval_row(const char *plain, const char *w)
+{
+    using K = decltype(kernel(kfit_eval_kernel<M>, plain));
+    return KfitRow<K>{M, {kernel(kfit_eval_kernel<M, false>, plain),
+                          kernel(kfit_eval_kernel<M, true>, w)}};
 }
 
 int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
@@ -119,44 +157,22 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
                      double *stamp_stats, hipStream_t s, const double *modew, int32_t *ncomp)
 {
     bool nothing;
-    const int st = kfit::check_args("kfit_eval", dhat, wbar, jac, R, C, nstamps, model, states,
-                                    sums, nothing);
+    int st = kfit::check_args("kfit_eval", false, R, C, nstamps, kfit::model_nloc(model) != 0,
+                              dhat && wbar && jac && states && sums, nothing);
     if (st != NGMIX_OK || nothing) return st;
-    if (((uintptr_t)dhat | (uintptr_t)phat) & 15) {
-        set_last_error_msg("kfit_eval: dhat and phat must be 16-byte aligned");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    struct Row {
-        int model;
-        decltype(kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS>, "")) k;
+    st = check_aligned("kfit_eval", dhat, phat);
+    if (st != NGMIX_OK) return st;
+    static constexpr decltype(eval_row<NGMIX_KFIT_GAUSS>("", "")) rows[] = {
+        eval_row<NGMIX_KFIT_GAUSS>("kfit_eval_kernel<gauss>", "kfit_eval_kernel<gauss, modew>"),
+        eval_row<NGMIX_KFIT_EXP>("kfit_eval_kernel<exp>", "kfit_eval_kernel<exp, modew>"),
+        eval_row<NGMIX_KFIT_SPERGEL>("kfit_eval_kernel<spergel>",
+                                     "kfit_eval_kernel<spergel, modew>"),
+        eval_row<NGMIX_KFIT_MOFFAT>("kfit_eval_kernel<moffat>", "kfit_eval_kernel<moffat, modew>"),
+        eval_row<NGMIX_KFIT_MOFFAT_FWHM>("kfit_eval_kernel<moffat fwhm>",
+                                         "kfit_eval_kernel<moffat fwhm, modew>"),
     };
-    // the MODEW form: its own instantiations, the plane of mode weights read
-    static constexpr Row wrows[] = {
-        {NGMIX_KFIT_GAUSS,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS, true>, "kfit_eval_kernel<gauss, modew>")},
-        {NGMIX_KFIT_EXP,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_EXP, true>, "kfit_eval_kernel<exp, modew>")},
-        {NGMIX_KFIT_SPERGEL,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_SPERGEL, true>, "kfit_eval_kernel<spergel, modew>")},
-        {NGMIX_KFIT_MOFFAT,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT, true>, "kfit_eval_kernel<moffat, modew>")},
-        {NGMIX_KFIT_MOFFAT_FWHM, kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT_FWHM, true>,
-                                        "kfit_eval_kernel<moffat fwhm, modew>")},
-    };
-    static constexpr Row rows[] = {
-        {NGMIX_KFIT_GAUSS, kernel(kfit_eval_kernel<NGMIX_KFIT_GAUSS>, "kfit_eval_kernel<gauss>")},
-        {NGMIX_KFIT_EXP, kernel(kfit_eval_kernel<NGMIX_KFIT_EXP>, "kfit_eval_kernel<exp>")},
-        {NGMIX_KFIT_SPERGEL,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_SPERGEL>, "kfit_eval_kernel<spergel>")},
-        {NGMIX_KFIT_MOFFAT,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT>, "kfit_eval_kernel<moffat>")},
-        {NGMIX_KFIT_MOFFAT_FWHM,
-         kernel(kfit_eval_kernel<NGMIX_KFIT_MOFFAT_FWHM>, "kfit_eval_kernel<moffat fwhm>")},
-    };
-    const auto pick = [&](const Row &q) { return q.model == model; };
-    const auto k = modew ? find_kernel(wrows, pick) : find_kernel(rows, pick);
-    const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
-    return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
+    const auto k = kfit_kernel(rows, model, modew != nullptr);
+    return launch(k, kfit_grid(nstamps), dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
                   (const double2 *)phat, wbar, jac, R, C, nstamps, states, stamp_obj, stamp_band,
                   sums, status, stamp_stats, modew, ncomp);
 }
@@ -170,51 +186,16 @@ __global__ __launch_bounds__(BLOCK) void kfit_flux_kernel(
 {
     const int64_t s = (int64_t)blockIdx.x * KFIT_STAMPS_PER_BLOCK + wave_id();
     if (s >= nstamps) return;
-    const int lane = lane_id();
-    double *o = out + 3 * (size_t)s;
-    const kfit::Setup m = kfit::flux_setup<MODEL>(pars + (size_t)s * kfit::flux_npars(MODEL),
-                                                  jacs[s], wbar[s], R, C);
-    const int CH = C / 2 + 1, nm = R * CH;
-    const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
-    int nc = 0;
-    if (m.bad) {   // (uniform over the wave)
-        if (MODEW && ncomp) nc = wave_sum_int(kfit::lane_components(m.wscale, U, lane, R, C));
-        if (lane == 0) {
-            kfit::write_flux_refused(o);
-            if (status) status[s] = NGMIX_ERR_G_RANGE;
-            if (MODEW && ncomp) ncomp[s] = nc;
-        }
-        return;
-    }
-    const double2 *D = dhat + (size_t)s * nm;
-    const double2 *P = phat ? phat + (size_t)s * nm : nullptr;
-    double acc[3] = {0.0, 0.0, 0.0};
-    bool notfinite = false;
-    for (int i = lane; i < nm; i += WAVE) {
-        const int a = i / CH, b = i - a * CH;
-        const double mult = kfit::mode_mult(a, b, R, C);
-        if (mult == 0.0) continue;
-        double w;
-        if (!kfit::mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
-        const double2 d = D[i];
-        double2 q = make_double2(1.0, 0.0);
-        if (P) q = P[i];
-        if (!isfinite(d.x + d.y + q.x + q.y)) notfinite = true;
-        kfit::flux_mode<MODEL>(m, a, b, R, w, d.x, d.y, q.x, q.y, acc);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) acc[k] = wave_sum(acc[k]);
-    if (MODEW && ncomp) nc = wave_sum_int(nc);
-    const bool any_notfinite = __ballot(notfinite) != 0ull;
-    if (lane == 0) {
-        if (MODEW && ncomp) ncomp[s] = nc;
-        if (any_notfinite) {
-            kfit::write_flux_refused(o);
-        } else {
-            o[0] = acc[0], o[1] = acc[1], o[2] = acc[2];
-        }
-        if (status) status[s] = any_notfinite ? NGMIX_ERR_NOT_FINITE : NGMIX_OK;
-    }
+    stamp_walk<kfit::FluxSums<MODEL>, MODEW>({pars, out}, dhat, phat, wbar, jacs, R, C, s,
+                                             lane_id(), status, modew, ncomp);
+}
+
+template <int M>
+static constexpr auto flux_row(const char *plain, const char *w)
+{
+    using K = decltype(kernel(kfit_flux_kernel<M>, plain));
+    return KfitRow<K>{M, {kernel(kfit_flux_kernel<M, false>, plain),
+                          kernel(kfit_flux_kernel<M, true>, w)}};
 }
 
 int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
@@ -223,46 +204,23 @@ int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
                      const double *modew, int32_t *ncomp)
 {
     bool nothing;
-    const int st = kfit::check_flux_args("kfit_flux", dhat, wbar, jac, R, C, nstamps, model, pars,
-                                         out, nothing);
+    int st = kfit::check_args("kfit_flux", true, R, C, nstamps, kfit::flux_npars(model) != 0,
+                              dhat && wbar && jac && pars && out, nothing);
     if (st != NGMIX_OK || nothing) return st;
-    if (((uintptr_t)dhat | (uintptr_t)phat) & 15) {
-        set_last_error_msg("kfit_flux: dhat and phat must be 16-byte aligned");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    struct Row {
-        int model;
-        decltype(kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS>, "")) k;
+    st = check_aligned("kfit_flux", dhat, phat);
+    if (st != NGMIX_OK) return st;
+    static constexpr decltype(flux_row<NGMIX_KFIT_GAUSS>("", "")) rows[] = {
+        flux_row<kfit::MODEL_POINT>("kfit_flux_kernel<point>", "kfit_flux_kernel<point, modew>"),
+        flux_row<NGMIX_KFIT_GAUSS>("kfit_flux_kernel<gauss>", "kfit_flux_kernel<gauss, modew>"),
+        flux_row<NGMIX_KFIT_EXP>("kfit_flux_kernel<exp>", "kfit_flux_kernel<exp, modew>"),
+        flux_row<NGMIX_KFIT_SPERGEL>("kfit_flux_kernel<spergel>",
+                                     "kfit_flux_kernel<spergel, modew>"),
+        flux_row<NGMIX_KFIT_MOFFAT>("kfit_flux_kernel<moffat>", "kfit_flux_kernel<moffat, modew>"),
+        flux_row<NGMIX_KFIT_MOFFAT_FWHM>("kfit_flux_kernel<moffat fwhm>",
+                                         "kfit_flux_kernel<moffat fwhm, modew>"),
     };
-    static constexpr Row wrows[] = {
-        {kfit::MODEL_POINT,
-         kernel(kfit_flux_kernel<kfit::MODEL_POINT, true>, "kfit_flux_kernel<point, modew>")},
-        {NGMIX_KFIT_GAUSS,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS, true>, "kfit_flux_kernel<gauss, modew>")},
-        {NGMIX_KFIT_EXP,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_EXP, true>, "kfit_flux_kernel<exp, modew>")},
-        {NGMIX_KFIT_SPERGEL,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_SPERGEL, true>, "kfit_flux_kernel<spergel, modew>")},
-        {NGMIX_KFIT_MOFFAT,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT, true>, "kfit_flux_kernel<moffat, modew>")},
-        {NGMIX_KFIT_MOFFAT_FWHM, kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT_FWHM, true>,
-                                        "kfit_flux_kernel<moffat fwhm, modew>")},
-    };
-    static constexpr Row rows[] = {
-        {kfit::MODEL_POINT, kernel(kfit_flux_kernel<kfit::MODEL_POINT>, "kfit_flux_kernel<point>")},
-        {NGMIX_KFIT_GAUSS, kernel(kfit_flux_kernel<NGMIX_KFIT_GAUSS>, "kfit_flux_kernel<gauss>")},
-        {NGMIX_KFIT_EXP, kernel(kfit_flux_kernel<NGMIX_KFIT_EXP>, "kfit_flux_kernel<exp>")},
-        {NGMIX_KFIT_SPERGEL,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_SPERGEL>, "kfit_flux_kernel<spergel>")},
-        {NGMIX_KFIT_MOFFAT,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT>, "kfit_flux_kernel<moffat>")},
-        {NGMIX_KFIT_MOFFAT_FWHM,
-         kernel(kfit_flux_kernel<NGMIX_KFIT_MOFFAT_FWHM>, "kfit_flux_kernel<moffat fwhm>")},
-    };
-    const auto pick = [&](const Row &q) { return q.model == model; };
-    const auto k = modew ? find_kernel(wrows, pick) : find_kernel(rows, pick);
-    const dim3 grid((unsigned)((nstamps + KFIT_STAMPS_PER_BLOCK - 1) / KFIT_STAMPS_PER_BLOCK));
-    return launch(k, grid, dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
+    const auto k = kfit_kernel(rows, model, modew != nullptr);
+    return launch(k, kfit_grid(nstamps), dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
                   (const double2 *)phat, wbar, jac, R, C, nstamps, pars, out, status, modew,
                   ncomp);
 }

@@ -1,5 +1,6 @@
-// kfit.hpp -- Fourier-space profile fits: the per-stamp set-up
-// and the per-mode text of kfit_eval_kernel, shared with its host twin.
+// kfit.hpp -- Fourier-space profile fits: the per-stamp set-up,
+// the per-mode text and the ONE walk over a stamp's stored modes that
+// kfit_eval_kernel, kfit_flux_kernel and their host twins all run.
 //
 // A stamp's residual rows are sqrt(w) Re (M^ - D^) and sqrt(w) Im (M^ - D^) of
 // every stored mode of its rfft2 half plane, with
@@ -23,12 +24,14 @@
 //   (J^T f)[j]            = sum w alpha_j (Re G Re f + Im G Im f)
 //
 // which are 20 (nloc = 6) or 26 (nloc = 7) running sums per lane instead of 28
-// or 36.  The modes of a stamp go to the 64 lanes of a wave in the order of the
-// stored plane, lane l taking modes l, l + 64, ..; the lanes are then summed in
-// the tree of wave_sum.  host_eval below walks the same order.
+// or 36.  kfit_flux_kernel's three sums of a FIXED unit-flux template T^ = Phi G
+// (or G alone: a point source, the psf itself) are FluxSums<MODEL>::add's.
 //
-// kfit_flux_kernel's three sums of a FIXED unit-flux template T^ = Phi G (or G
-// alone: a point source, the psf itself) are flux_mode's, in the same order.
+// The walk: walk_lane<Policy, MODEW> is a lane's modes (lane l takes l, l + 64,
+// .. in the order of the stored plane) with EvalSums<MODEL> or FluxSums<MODEL> for
+// what the two kernels differ in.  The kernels call it with lane_id() (kfit.hip:
+// stamp_walk), host_walk once per lane, adding the lanes as wave_sum does
+// (tree_sum); only the load of a pair differs.
 #pragma once
 
 #include <math.h>
@@ -185,119 +188,60 @@ NGMIX_HD int lane_components(double wscale, const double *u, int lane, int R, in
     return n;
 }
 
-// one kept mode's terms of the running sums; w its weight, (dr, di) = D^,
-// (pr, pi) = P^n
-template <int MODEL>
-NGMIX_HD void add_mode(const Setup &m, int a, int b, int R, double w, double dr, double di,
-                       double pr, double pi, double (&acc)[Traits<MODEL>::NACC])
+// stored mode (a, b) at a set-up: (k_v, k_u) = J^-T q, the sheared pair
+// ea = (1 + g1) k_u + g2 k_v, eb = g2 k_u + (1 - g1) k_v, t = ea^2 + eb^2 and
+// s = r0^2 t / (1 - g^2)
+// (SHEARED false: the point source, which reads k_v and k_u alone)
+template <bool SHEARED = true>
+struct Mode {
+    double kv, ku, ea, eb, t, s;
+    NGMIX_HD Mode(const Setup &m, int a, int b, int R)
+    {
+        const double qr = m.qr_unit * (double)(2 * a < R ? a : a - R);   // fftfreq
+        const double qc = m.qc_unit * (double)b;
+        kv = fma(m.kvr, qr, m.kvc * qc);
+        ku = fma(m.kur, qr, m.kuc * qc);
+        ea = eb = t = s = 0.0;
+        if (!SHEARED) return;
+        ea = fma(m.opg1, ku, m.g2 * kv);
+        eb = fma(m.g2, ku, m.omg1 * kv);
+        t = fma(ea, ea, eb * eb);
+        s = m.r0sq * (t * m.iD);
+    }
+    // G = exp(-i theta) P^n, (pr, pi) = P^n
+    NGMIX_HD void G(const Setup &m, double pr, double pi, double &gr, double &gi) const
+    {
+        const double theta = fma(kv, m.cen1, ku * m.cen2);
+        double sn, cs;
+        sincos(theta, &sn, &cs);
+        gr = fma(cs, pr, sn * pi);
+        gi = fma(cs, pi, -(sn * pr));
+    }
+};
+
+// Phi(s) of MODEL (the point source: 1) and, DERIV, dphi = dPhi/ds and the term
+// of the nu (beta) column: lnu = ln(1 + s) for Spergel, dPhi/dbeta for Moffat
+template <int MODEL, bool DERIV>
+NGMIX_HD void profile(const Setup &m, double s, double &phi, double &dphi, double &lnu)
 {
-    constexpr int NA = Traits<MODEL>::NA, NTRI = Traits<MODEL>::NTRI;
-    const double qr = m.qr_unit * (double)(2 * a < R ? a : a - R);   // fftfreq
-    const double qc = m.qc_unit * (double)b;
-    const double kv = fma(m.kvr, qr, m.kvc * qc);
-    const double ku = fma(m.kur, qr, m.kuc * qc);
-    const double ea = fma(m.opg1, ku, m.g2 * kv);
-    const double eb = fma(m.g2, ku, m.omg1 * kv);
-    const double t = fma(ea, ea, eb * eb);          // s = r0^2 t / (1 - g^2)
-    const double s = m.r0sq * (t * m.iD);
-    // Phi and dPhi/ds
-    double phi, dphi, lnu = 0.0;
-    if (MODEL == NGMIX_KFIT_GAUSS) {
+    if (MODEL == MODEL_POINT) {
+        phi = 1.0;
+    } else if (MODEL == NGMIX_KFIT_GAUSS) {
         phi = exp(-0.5 * s);
-        dphi = -0.5 * phi;
+        if (DERIV) dphi = -0.5 * phi;
     } else if (MODEL == NGMIX_KFIT_EXP) {
         const double u = 1.0 + s;
         phi = 1.0 / (u * sqrt(u));
-        dphi = -1.5 * phi / u;
+        if (DERIV) dphi = -1.5 * phi / u;
     } else if (MODEL == NGMIX_KFIT_SPERGEL) {
-        const double u = 1.0 + s;
         lnu = log1p(s);
         phi = exp(-m.onepnu * lnu);
-        dphi = -m.onepnu * phi / u;
+        if (DERIV) dphi = -m.onepnu * phi / (1.0 + s);
     } else {
         // D_x = 2 s dPhi/ds; at the DC mode every column but the flux's is zero
         double dx;
-        moffat_phi_at(m.mof, sqrt(s), phi, dx, lnu);       // lnu: dPhi/dbeta
-        dphi = s > 0.0 ? 0.5 * dx / s : 0.0;
-    }
-    // G = exp(-i theta) P^n
-    const double theta = fma(kv, m.cen1, ku * m.cen2);
-    double sn, cs;
-    sincos(theta, &sn, &cs);
-    const double gr = fma(cs, pr, sn * pi);
-    const double gi = fma(cs, pi, -(sn * pr));
-    // alpha_j: g1, g2, r50, (nu,) F
-    double al[NA];
-    const double fd = m.flux * dphi;       // d A / d s
-    const double tD = t * m.iD;
-    al[0] = fd * (m.ds_scale * (fma(ea, ku, -(eb * kv)) + m.g1 * tD));
-    al[1] = fd * (m.ds_scale * (fma(ea, kv, eb * ku) + m.g2 * tD));
-    al[2] = fd * (s * m.dlns_dr50);
-    if (MODEL == NGMIX_KFIT_SPERGEL)
-        al[3] = fma(fd, s * m.dlns_dnu, -(m.flux * (lnu * phi)));
-    if (is_moffat(MODEL)) al[3] = fma(fd, s * m.dlns_dnu, m.flux * lnu);
-    al[NA - 1] = phi;
-    const double A = m.flux * al[NA - 1];
-    const double fr = fma(A, gr, -dr), fi = fma(A, gi, -di);
-    const double gg = w * fma(gr, gr, gi * gi);
-    const double gf = w * fma(gr, fr, gi * fi);
-    const double cf = (w * A) * fma(gi, fr, -(gr * fi));
-    const double aa = (A * A) * gg;
-    acc[0] = fma(kv * kv, aa, acc[0]);
-    acc[1] = fma(kv * ku, aa, acc[1]);
-    acc[2] = fma(ku * ku, aa, acc[2]);
-    int k = 3;
-#pragma unroll
-    for (int i = 0; i < NA; i++) {
-        const double ai = al[i] * gg;
-#pragma unroll
-        for (int j = i; j < NA; j++) {
-            acc[k] = fma(ai, al[j], acc[k]);
-            k++;
-        }
-    }
-    acc[3 + NTRI] = fma(kv, cf, acc[3 + NTRI]);
-    acc[4 + NTRI] = fma(ku, cf, acc[4 + NTRI]);
-#pragma unroll
-    for (int i = 0; i < NA; i++) acc[5 + NTRI + i] = fma(al[i], gf, acc[5 + NTRI + i]);
-    acc[5 + NTRI + NA] = fma(w, fma(fr, fr, fi * fi), acc[5 + NTRI + NA]);
-}
-
-// the stamp's sums in the layout ngmix_lm_advance_batch reads -- J^T J upper
-// triangle | J^T f | f.f over the nloc local parameters -- from the reduced
-// running sums, and the two statistics: sum w Re(M^ D^*) = sum w |M^|^2 -
-// sum w Re(M^ f*) and sum w |M^|^2, both from the flux column (M^ = F alpha_F G)
-template <int MODEL>
-NGMIX_HD void write_sums(const double (&acc)[Traits<MODEL>::NACC], double flux, double *out,
-                         double *stats)
-{
-    constexpr int NLOC = Traits<MODEL>::NLOC, NA = Traits<MODEL>::NA,
-                  NTRI = Traits<MODEL>::NTRI;
-    int k = 0, ka = 3;
-    for (int i = 0; i < NLOC; i++)
-        for (int j = i; j < NLOC; j++) {
-            double v = 0.0;
-            if (j < 2) v = acc[i + j];            // (0,0) (0,1) (1,1)
-            else if (i >= 2) v = acc[ka++];
-            out[k++] = v;
-        }
-    for (int i = 0; i < NLOC; i++) out[k++] = acc[3 + NTRI + i];
-    out[k] = acc[5 + NTRI + NA];
-    if (stats) {
-        const double mm = flux * flux * acc[3 + NTRI - 1];          // (F, F)
-        stats[0] = mm - flux * acc[5 + NTRI + NA - 1];
-        stats[1] = mm;
-    }
-}
-
-// a stamp that cannot be evaluated: the reference's LOWVAL residuals
-NGMIX_HD void write_refused(int nsums, double *out, double *stats)
-{
-    for (int k = 0; k < nsums - 1; k++) out[k] = 0.0;
-    out[nsums - 1] = INFINITY;
-    if (stats) {
-        stats[0] = 0.0;
-        stats[1] = 0.0;
+        moffat_phi_at(m.mof, sqrt(s), phi, dx, lnu);
+        if (DERIV) dphi = s > 0.0 ? 0.5 * dx / s : 0.0;
     }
 }
 
@@ -308,102 +252,6 @@ constexpr int model_nloc(int model)
                                                                 : 0;
 }
 
-// the argument checks of ngmix_kfit_eval_batch and its host twin; nothing: a
-// legal call with no stamps
-inline int check_args(const char *who, const double *dhat, const double *wbar,
-                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                      const ngmix_lm_state *states, const double *sums, bool &nothing)
-{
-    nothing = false;
-    const char *why = nullptr;
-    if (nstamps < 0) why = "nstamps must not be negative";
-    else if (model_nloc(model) == 0) why = "model must be NGMIX_KFIT_GAUSS, _EXP, _SPERGEL, _MOFFAT or _MOFFAT_FWHM";
-    else if (R < 1 || C < 1 || R > 0x7fff || C > 0x7fff) why = "the stamp shape must be 1..32767";
-    else if (nstamps == 0) nothing = true;
-    else if (!dhat || !wbar || !jac || !states || !sums)
-        why = "dhat, wbar, jac, states and sums are required";
-    else if (nstamps > 0x7fffffffll) why = "too many stamps for one launch";
-    if (!why) return NGMIX_OK;
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, why);
-    set_last_error_msg(msg);
-    return NGMIX_ERR_BAD_ARG;
-}
-
-// the host twin of kfit_eval_kernel: the same text, the same order of sums;
-// MODEW: modew (nstamps, R, C/2+1), ncomp (nstamps,) or NULL
-template <int MODEL, bool MODEW = false>
-inline void host_eval(const double *dhat, const double *phat, const double *wbar,
-                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
-                      const ngmix_lm_state *states, const int32_t *stamp_obj,
-                      const int32_t *stamp_band, double *sums, int32_t *status,
-                      double *stamp_stats, const double *modew = nullptr,
-                      int32_t *ncomp = nullptr)
-{
-    constexpr int NLOC = Traits<MODEL>::NLOC, NACC = Traits<MODEL>::NACC,
-                  NSUMS = Traits<MODEL>::NSUMS;
-    const int CH = C / 2 + 1, nm = R * CH;
-    std::vector<double> part((size_t)LANES * NACC);
-    for (int64_t s = 0; s < nstamps; s++) {
-        const ngmix_lm_state &state = states[stamp_obj ? stamp_obj[s] : s];
-        if (state.phase == NGMIX_LM_PHASE_DONE) continue;
-        const int band = stamp_band ? stamp_band[s] : 0;
-        double p[NLOC];
-        for (int k = 0; k < NLOC - 1; k++) p[k] = state.xt[k];
-        p[NLOC - 1] = state.xt[NLOC - 1 + band];
-        double *out = sums + s * NSUMS;
-        double *stats = stamp_stats ? stamp_stats + 2 * s : nullptr;
-        const Setup m = setup<MODEL>(p, jac[s], wbar[s], R, C);
-        const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
-        int nc = 0;
-        if (m.bad) {
-            write_refused(NSUMS, out, stats);
-            if (status) status[s] = NGMIX_ERR_G_RANGE;
-            if (MODEW && ncomp) {
-                for (int l = 0; l < LANES; l++) nc += lane_components(m.wscale, U, l, R, C);
-                ncomp[s] = nc;
-            }
-            continue;
-        }
-        const double *D = dhat + (size_t)s * nm * 2;
-        const double *P = phat ? phat + (size_t)s * nm * 2 : nullptr;
-        bool notfinite = false;
-        for (int l = 0; l < LANES; l++) {
-            double acc[NACC];
-            for (int k = 0; k < NACC; k++) acc[k] = 0.0;
-            for (int i = l; i < nm; i += LANES) {
-                const int a = i / CH, b = i - a * CH;
-                const double mult = mode_mult(a, b, R, C);
-                if (mult == 0.0) continue;
-                double w;
-                if (!mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
-                const double dr = D[2 * i], di = D[2 * i + 1];
-                const double pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
-                if (!isfinite(dr + di + pr + pi)) notfinite = true;
-                add_mode<MODEL>(m, a, b, R, w, dr, di, pr, pi, acc);
-            }
-            for (int k = 0; k < NACC; k++) part[(size_t)k * LANES + l] = acc[k];
-        }
-        if (MODEW && ncomp) ncomp[s] = nc;
-        double tot[NACC];
-        for (int k = 0; k < NACC; k++) {
-            double *x = part.data() + (size_t)k * LANES;
-            for (int off = LANES / 2; off > 0; off >>= 1)
-                for (int l = 0; l < off; l++) x[l] += x[l + off];
-            tot[k] = x[0];
-        }
-        if (notfinite) {
-            write_refused(NSUMS, out, stats);
-            if (status) status[s] = NGMIX_ERR_NOT_FINITE;
-            continue;
-        }
-        write_sums<MODEL>(tot, m.flux, out, stats);
-        if (status) status[s] = NGMIX_OK;
-    }
-}
-
-// ---- the linear flux of a fixed template ---------------------------
-
 // the parameters a template of `model` takes, without a flux: [cen1, cen2, g1,
 // g2, size, (nu | beta)]; the point source reads the centre of its five
 constexpr int flux_npars(int model)
@@ -411,151 +259,289 @@ constexpr int flux_npars(int model)
     return model == MODEL_POINT ? 5 : model_nloc(model) - (model_nloc(model) > 0);
 }
 
-// one kept mode's terms of A = sum w Re(T^* D^), B = sum w |T^|^2, E = sum w |D^|^2
+// ---- what the two kernels differ in ------------------------------------------------
+// A policy carries the call's own arguments and NACC, add() (a kept mode's terms
+// of the running sums), setup() (the stamp's Setup; false: the stamp is skipped
+// and nothing of it is written), finish() (the record and status of a walked
+// stamp) and write_refused().
+
+// kfit_eval_kernel: the normal equations of the stamp's object at its LM state's
+// trial point, in the layout ngmix_lm_advance_batch reads
 template <int MODEL>
-NGMIX_HD void flux_mode(const Setup &m, int a, int b, int R, double w, double dr, double di,
-                        double pr, double pi, double (&acc)[3])
-{
-    const double qr = m.qr_unit * (double)(2 * a < R ? a : a - R);   // fftfreq
-    const double qc = m.qc_unit * (double)b;
-    const double kv = fma(m.kvr, qr, m.kvc * qc);
-    const double ku = fma(m.kur, qr, m.kuc * qc);
-    double phi = 1.0;
-    if (MODEL != MODEL_POINT) {
-        const double ea = fma(m.opg1, ku, m.g2 * kv);
-        const double eb = fma(m.g2, ku, m.omg1 * kv);
-        const double s = m.r0sq * (fma(ea, ea, eb * eb) * m.iD);
-        if (MODEL == NGMIX_KFIT_GAUSS) {
-            phi = exp(-0.5 * s);
-        } else if (MODEL == NGMIX_KFIT_EXP) {
-            const double u = 1.0 + s;
-            phi = 1.0 / (u * sqrt(u));
-        } else if (MODEL == NGMIX_KFIT_SPERGEL) {
-            phi = exp(-m.onepnu * log1p(s));
-        } else {
-            double dx, dnu;
-            moffat_phi_at(m.mof, sqrt(s), phi, dx, dnu);
+struct EvalSums {
+    using T = Traits<MODEL>;
+    static constexpr int NACC = T::NACC;
+    const ngmix_lm_state *states;
+    const int32_t *stamp_obj, *stamp_band;
+    double *sums, *stamp_stats;
+
+    // one kept mode's terms of the running sums; w its weight, (dr, di) = D^,
+    // (pr, pi) = P^n
+    static NGMIX_HD void add(const Setup &m, int a, int b, int R, double w, double dr, double di,
+                             double pr, double pi, double (&acc)[NACC])
+    {
+        constexpr int NA = T::NA, NTRI = T::NTRI;
+        const Mode<> q(m, a, b, R);
+        double phi, dphi = 0.0, lnu = 0.0, gr, gi;
+        profile<MODEL, true>(m, q.s, phi, dphi, lnu);
+        q.G(m, pr, pi, gr, gi);
+        // alpha_j: g1, g2, r50, (nu,) F
+        double al[NA];
+        const double fd = m.flux * dphi;       // d A / d s
+        const double tD = q.t * m.iD;
+        al[0] = fd * (m.ds_scale * (fma(q.ea, q.ku, -(q.eb * q.kv)) + m.g1 * tD));
+        al[1] = fd * (m.ds_scale * (fma(q.ea, q.kv, q.eb * q.ku) + m.g2 * tD));
+        al[2] = fd * (q.s * m.dlns_dr50);
+        if (MODEL == NGMIX_KFIT_SPERGEL)
+            al[3] = fma(fd, q.s * m.dlns_dnu, -(m.flux * (lnu * phi)));
+        if (is_moffat(MODEL)) al[3] = fma(fd, q.s * m.dlns_dnu, m.flux * lnu);
+        al[NA - 1] = phi;
+        const double A = m.flux * al[NA - 1];
+        const double fr = fma(A, gr, -dr), fi = fma(A, gi, -di);
+        const double gg = w * fma(gr, gr, gi * gi);
+        const double gf = w * fma(gr, fr, gi * fi);
+        const double cf = (w * A) * fma(gi, fr, -(gr * fi));
+        const double aa = (A * A) * gg;
+        acc[0] = fma(q.kv * q.kv, aa, acc[0]);
+        acc[1] = fma(q.kv * q.ku, aa, acc[1]);
+        acc[2] = fma(q.ku * q.ku, aa, acc[2]);
+        int k = 3;
+#pragma unroll
+        for (int i = 0; i < NA; i++) {
+            const double ai = al[i] * gg;
+#pragma unroll
+            for (int j = i; j < NA; j++) {
+                acc[k] = fma(ai, al[j], acc[k]);
+                k++;
+            }
         }
+        acc[3 + NTRI] = fma(q.kv, cf, acc[3 + NTRI]);
+        acc[4 + NTRI] = fma(q.ku, cf, acc[4 + NTRI]);
+#pragma unroll
+        for (int i = 0; i < NA; i++) acc[5 + NTRI + i] = fma(al[i], gf, acc[5 + NTRI + i]);
+        acc[5 + NTRI + NA] = fma(w, fma(fr, fr, fi * fi), acc[5 + NTRI + NA]);
     }
-    const double theta = fma(kv, m.cen1, ku * m.cen2);
-    double sn, cs;
-    sincos(theta, &sn, &cs);
-    const double tr = phi * fma(cs, pr, sn * pi);
-    const double ti = phi * fma(cs, pi, -(sn * pr));
-    acc[0] = fma(w, fma(tr, dr, ti * di), acc[0]);
-    acc[1] = fma(w, fma(tr, tr, ti * ti), acc[1]);
-    acc[2] = fma(w, fma(dr, dr, di * di), acc[2]);
-}
+    // a finished fit is skipped and its sums are left as they are
+    NGMIX_HD bool setup(int64_t s, const ngmix_jacobian *jacs, const double *wbar, int R, int C,
+                        Setup &m) const
+    {
+        const ngmix_lm_state &state = states[stamp_obj ? stamp_obj[s] : (int)s];
+        if (state.phase == NGMIX_LM_PHASE_DONE) return false;
+        const int band = stamp_band ? stamp_band[s] : 0;
+        double p[T::NLOC];
+#pragma unroll
+        for (int k = 0; k < T::NLOC - 1; k++) p[k] = state.xt[k];
+        p[T::NLOC - 1] = state.xt[T::NLOC - 1 + band];
+        m = kfit::setup<MODEL>(p, jacs[s], wbar[s], R, C);
+        return true;
+    }
+    // a stamp that cannot be evaluated: the reference's LOWVAL residuals
+    NGMIX_HD void write_refused(int64_t s) const
+    {
+        double *out = sums + (size_t)s * T::NSUMS;
+        for (int k = 0; k < T::NSUMS - 1; k++) out[k] = 0.0;
+        out[T::NSUMS - 1] = INFINITY;
+        if (stamp_stats) stamp_stats[2 * (size_t)s] = 0.0, stamp_stats[2 * (size_t)s + 1] = 0.0;
+    }
+    // J^T J upper triangle | J^T f | f.f over the nloc local parameters, from the
+    // reduced running sums, and the two statistics: sum w Re(M^ D^*) = sum w |M^|^2
+    // - sum w Re(M^ f*) and sum w |M^|^2, both from the flux column (M^ = F alpha_F G)
+    NGMIX_HD void finish(int64_t s, const Setup &m, const double (&acc)[NACC], bool notfinite,
+                         int32_t *status) const
+    {
+        constexpr int NLOC = T::NLOC, NA = T::NA, NTRI = T::NTRI;
+        if (notfinite) {
+            write_refused(s);
+            if (status) status[s] = NGMIX_ERR_NOT_FINITE;
+            return;
+        }
+        double *out = sums + (size_t)s * T::NSUMS;
+        int k = 0, ka = 3;
+        for (int i = 0; i < NLOC; i++)
+            for (int j = i; j < NLOC; j++) {
+                double v = 0.0;
+                if (j < 2) v = acc[i + j];            // (0,0) (0,1) (1,1)
+                else if (i >= 2) v = acc[ka++];
+                out[k++] = v;
+            }
+        for (int i = 0; i < NLOC; i++) out[k++] = acc[3 + NTRI + i];
+        out[k] = acc[5 + NTRI + NA];
+        if (stamp_stats) {
+            const double mm = m.flux * m.flux * acc[3 + NTRI - 1];          // (F, F)
+            stamp_stats[2 * (size_t)s] = mm - m.flux * acc[5 + NTRI + NA - 1];
+            stamp_stats[2 * (size_t)s + 1] = mm;
+        }
+        if (status) status[s] = NGMIX_OK;
+    }
+};
 
-// the set-up of a template: the evaluation's, at unit flux
+// kfit_flux_kernel: the three sums of a fixed template, whose
+// set-up is the evaluation's at pars and unit flux
 template <int MODEL>
-NGMIX_HD Setup flux_setup(const double *pars, const ngmix_jacobian &jac, double wbar, int R, int C)
-{
-    constexpr int EVAL = MODEL == MODEL_POINT ? NGMIX_KFIT_GAUSS : MODEL;
-    constexpr int NLOC = Traits<EVAL>::NLOC;
-    double p[NLOC];
-    if (MODEL == MODEL_POINT) {
-        p[0] = pars[0], p[1] = pars[1], p[2] = 0.0, p[3] = 0.0, p[4] = 1.0;
-    } else {
-        for (int k = 0; k < NLOC - 1; k++) p[k] = pars[k];
+struct FluxSums {
+    static constexpr int NACC = 3;
+    const double *pars;
+    double *out;
+
+    // one kept mode's terms of A = sum w Re(T^* D^), B = sum w |T^|^2, E = sum w |D^|^2
+    static NGMIX_HD void add(const Setup &m, int a, int b, int R, double w, double dr, double di,
+                             double pr, double pi, double (&acc)[NACC])
+    {
+        const Mode<MODEL != MODEL_POINT> q(m, a, b, R);
+        double phi, dphi = 0.0, lnu = 0.0, gr, gi;
+        profile<MODEL, false>(m, q.s, phi, dphi, lnu);
+        q.G(m, pr, pi, gr, gi);
+        const double tr = phi * gr;
+        const double ti = phi * gi;
+        acc[0] = fma(w, fma(tr, dr, ti * di), acc[0]);
+        acc[1] = fma(w, fma(tr, tr, ti * ti), acc[1]);
+        acc[2] = fma(w, fma(dr, dr, di * di), acc[2]);
     }
-    p[NLOC - 1] = 1.0;
-    return setup<EVAL>(p, jac, wbar, R, C);
-}
+    NGMIX_HD bool setup(int64_t s, const ngmix_jacobian *jacs, const double *wbar, int R, int C,
+                        Setup &m) const
+    {
+        constexpr int EVAL = MODEL == MODEL_POINT ? NGMIX_KFIT_GAUSS : MODEL;
+        constexpr int NLOC = Traits<EVAL>::NLOC;
+        const double *q = pars + (size_t)s * flux_npars(MODEL);
+        double p[NLOC];
+        if (MODEL == MODEL_POINT) {
+            p[0] = q[0], p[1] = q[1], p[2] = 0.0, p[3] = 0.0, p[4] = 1.0;
+        } else {
+            for (int k = 0; k < NLOC - 1; k++) p[k] = q[k];
+        }
+        p[NLOC - 1] = 1.0;
+        m = kfit::setup<EVAL>(p, jacs[s], wbar[s], R, C);
+        return true;
+    }
+    NGMIX_HD void write_refused(int64_t s) const
+    {
+        double *o = out + 3 * (size_t)s;
+        o[0] = 0.0, o[1] = 0.0, o[2] = 0.0;
+    }
+    NGMIX_HD void finish(int64_t s, const Setup &, const double (&acc)[NACC], bool notfinite,
+                         int32_t *status) const
+    {
+        double *o = out + 3 * (size_t)s;
+        if (notfinite) write_refused(s);
+        else o[0] = acc[0], o[1] = acc[1], o[2] = acc[2];
+        if (status) status[s] = notfinite ? NGMIX_ERR_NOT_FINITE : NGMIX_OK;
+    }
+};
 
-NGMIX_HD void write_flux_refused(double *out)
+// ---- the walk ------------------------------------------------------------------------
+
+// the host's load of mode i's D^ and P^n (1 without a psf): two doubles each, for
+// callers that promise 8-byte alignment only; kfit.hip has the 16-byte form
+struct LoadDoubles {
+    const double *D, *P;
+    void operator()(int i, double &dr, double &di, double &pr, double &pi) const
+    {
+        dr = D[2 * i], di = D[2 * i + 1];
+        pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
+    }
+};
+
+// lane's modes of one stamp: the kept ones are loaded, tested and added to acc;
+// U: the stamp's plane of mode weights (MODEW), nc: lane's count of components
+template <typename Policy, bool MODEW, typename Load>
+NGMIX_HD void walk_lane(const Setup &m, int R, int C, const Load &load, const double *U, int lane,
+                        double (&acc)[Policy::NACC], bool &notfinite, int &nc)
 {
-    out[0] = 0.0, out[1] = 0.0, out[2] = 0.0;
+    const int CH = C / 2 + 1, nm = R * CH;
+    for (int i = lane; i < nm; i += LANES) {
+        const int a = i / CH, b = i - a * CH;
+        const double mult = mode_mult(a, b, R, C);
+        if (mult == 0.0) continue;
+        double w;
+        if (!mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
+        double dr, di, pr, pi;
+        load(i, dr, di, pr, pi);
+        if (!isfinite(dr + di + pr + pi)) notfinite = true;
+        Policy::add(m, a, b, R, w, dr, di, pr, pi, acc);
+    }
 }
 
-inline int check_flux_args(const char *who, const double *dhat, const double *wbar,
-                           const ngmix_jacobian *jac, int R, int C, int64_t nstamps, int model,
-                           const double *pars, const double *out, bool &nothing)
+// a stamp out of range at its trial point; nc: its components, counted without
+// a walk, for ncomp (NULL: not asked for)
+template <typename Policy>
+NGMIX_HD void refuse_stamp(const Policy &pol, int64_t s, int nc, int32_t *status, int32_t *ncomp)
+{
+    pol.write_refused(s);
+    if (status) status[s] = NGMIX_ERR_G_RANGE;
+    if (ncomp) ncomp[s] = nc;
+}
+
+// the 64 lanes' values in the order of wave_sum; x is consumed
+inline double tree_sum(double *x)
+{
+    for (int off = LANES / 2; off > 0; off >>= 1)
+        for (int l = 0; l < off; l++) x[l] += x[l + off];
+    return x[0];
+}
+
+// the host twin of stamp_walk (kfit.hip) over a batch: the same text, the same
+// order of sums; modew (nstamps, R, C/2+1) or NULL (a plain entry: MODEW false),
+// with it ncomp (nstamps,) or NULL
+template <typename Policy>
+inline void host_walk(const Policy &pol, const double *dhat, const double *phat,
+                      const double *wbar, const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
+                      int32_t *status, const double *modew, int32_t *ncomp)
+{
+    constexpr int NACC = Policy::NACC;
+    const int nm = R * (C / 2 + 1);
+    if (!modew) ncomp = nullptr;
+    std::vector<double> part((size_t)LANES * NACC);
+    for (int64_t s = 0; s < nstamps; s++) {
+        Setup m;
+        if (!pol.setup(s, jac, wbar, R, C, m)) continue;
+        const double *U = modew ? modew + (size_t)s * nm : nullptr;
+        int nc = 0;
+        if (m.bad) {
+            if (ncomp)
+                for (int l = 0; l < LANES; l++) nc += lane_components(m.wscale, U, l, R, C);
+            refuse_stamp(pol, s, nc, status, ncomp);
+            continue;
+        }
+        const LoadDoubles load{dhat + (size_t)s * nm * 2,
+                               phat ? phat + (size_t)s * nm * 2 : nullptr};
+        bool notfinite = false;
+        for (int l = 0; l < LANES; l++) {
+            double acc[NACC];
+            for (int k = 0; k < NACC; k++) acc[k] = 0.0;
+            if (U) walk_lane<Policy, true>(m, R, C, load, U, l, acc, notfinite, nc);
+            else walk_lane<Policy, false>(m, R, C, load, U, l, acc, notfinite, nc);
+            for (int k = 0; k < NACC; k++) part[(size_t)k * LANES + l] = acc[k];
+        }
+        double tot[NACC];
+        for (int k = 0; k < NACC; k++) tot[k] = tree_sum(part.data() + (size_t)k * LANES);
+        if (ncomp) ncomp[s] = nc;
+        pol.finish(s, m, tot, notfinite, status);
+    }
+}
+
+// The argument check of every kfit entry, device and host (flux: the words of
+// the flux entries); its caller gives the model test's result and whether the
+// required pointers are there.  nothing: a legal call with no stamps.
+inline int check_args(const char *who, bool flux, int R, int C, int64_t nstamps, bool model_ok,
+                      bool have, bool &nothing)
 {
     nothing = false;
     const char *why = nullptr;
     if (nstamps < 0) why = "nstamps must not be negative";
-    else if (flux_npars(model) == 0)
-        why = "model must be -1 (a point source) or one of NGMIX_KFIT_*";
+    else if (!model_ok)
+        why = flux ? "model must be -1 (a point source) or one of NGMIX_KFIT_*"
+                   : "model must be NGMIX_KFIT_GAUSS, _EXP, _SPERGEL, _MOFFAT or _MOFFAT_FWHM";
     else if (R < 1 || C < 1 || R > 0x7fff || C > 0x7fff) why = "the stamp shape must be 1..32767";
     else if (nstamps == 0) nothing = true;
-    else if (!dhat || !wbar || !jac || !pars || !out)
-        why = "dhat, wbar, jac, pars and out are required";
+    else if (!have)
+        why = flux ? "dhat, wbar, jac, pars and out are required"
+                   : "dhat, wbar, jac, states and sums are required";
     else if (nstamps > 0x7fffffffll) why = "too many stamps for one launch";
     if (!why) return NGMIX_OK;
     char msg[160];
     snprintf(msg, sizeof(msg), "%s: %s", who, why);
     set_last_error_msg(msg);
     return NGMIX_ERR_BAD_ARG;
-}
-
-// the host twin of kfit_flux_kernel; modew, ncomp as host_eval's
-template <int MODEL, bool MODEW = false>
-inline void host_flux(const double *dhat, const double *phat, const double *wbar,
-                      const ngmix_jacobian *jac, int R, int C, int64_t nstamps,
-                      const double *pars, double *out, int32_t *status,
-                      const double *modew = nullptr, int32_t *ncomp = nullptr)
-{
-    const int CH = C / 2 + 1, nm = R * CH, np = flux_npars(MODEL);
-    std::vector<double> part((size_t)LANES * 3);
-    for (int64_t s = 0; s < nstamps; s++) {
-        const Setup m = flux_setup<MODEL>(pars + s * np, jac[s], wbar[s], R, C);
-        const double *U = MODEW ? modew + (size_t)s * nm : nullptr;
-        int nc = 0;
-        if (m.bad) {
-            write_flux_refused(out + 3 * s);
-            if (status) status[s] = NGMIX_ERR_G_RANGE;
-            if (MODEW && ncomp) {
-                for (int l = 0; l < LANES; l++) nc += lane_components(m.wscale, U, l, R, C);
-                ncomp[s] = nc;
-            }
-            continue;
-        }
-        const double *D = dhat + (size_t)s * nm * 2;
-        const double *P = phat ? phat + (size_t)s * nm * 2 : nullptr;
-        bool notfinite = false;
-        for (int l = 0; l < LANES; l++) {
-            double acc[3] = {0.0, 0.0, 0.0};
-            for (int i = l; i < nm; i += LANES) {
-                const int a = i / CH, b = i - a * CH;
-                const double mult = mode_mult(a, b, R, C);
-                if (mult == 0.0) continue;
-                double w;
-                if (!mode_weight<MODEW>(m, mult, U, i, w, notfinite, nc)) continue;
-                const double dr = D[2 * i], di = D[2 * i + 1];
-                const double pr = P ? P[2 * i] : 1.0, pi = P ? P[2 * i + 1] : 0.0;
-                if (!isfinite(dr + di + pr + pi)) notfinite = true;
-                flux_mode<MODEL>(m, a, b, R, w, dr, di, pr, pi, acc);
-            }
-            for (int k = 0; k < 3; k++) part[(size_t)k * LANES + l] = acc[k];
-        }
-        if (MODEW && ncomp) ncomp[s] = nc;
-        for (int k = 0; k < 3; k++) {
-            double *x = part.data() + (size_t)k * LANES;
-            for (int off = LANES / 2; off > 0; off >>= 1)
-                for (int l = 0; l < off; l++) x[l] += x[l + off];
-            out[3 * s + k] = x[0];
-        }
-        if (notfinite) write_flux_refused(out + 3 * s);
-        if (status) status[s] = notfinite ? NGMIX_ERR_NOT_FINITE : NGMIX_OK;
-    }
-}
-
-// host_flux<M> for the M of the list that equals model
-template <int... MS, typename... A>
-inline void host_flux_for(int model, A... args)
-{
-    (void)((model == MS ? (host_flux<MS>(args...), true) : false) || ...);
-}
-template <int... MS, typename... A>
-inline void host_flux_w_for(int model, A... args)
-{
-    (void)((model == MS ? (host_flux<MS, true>(args...), true) : false) || ...);
-}
-template <int... MS, typename... A>
-inline void host_eval_w_for(int model, A... args)
-{
-    (void)((model == MS ? (host_eval<MS, true>(args...), true) : false) || ...);
 }
 
 }  // namespace kfit

@@ -17,7 +17,7 @@ SHAPES = [(8, 8), (9, 12), (16, 16)]
 SPECS = [("gauss", None), ("exp", None), ("spergel", -0.6), ("spergel", 0.5), ("spergel", 2.3)]
 EPS = 2.0 ** -52
 # The rounding bound of a sum: C_ROUND * 2^-52 * sum |terms|.  Counted on
-# kfit.hpp's add_mode, in units of 2^-52 (a rounding is half a unit):
+# kfit.hpp's EvalSums::add, in units of 2^-52 (a rounding is half a unit):
 #   a jacobian column alpha_j: k (3 roundings each, two of them), ea / eb (2),
 #     t (2), s (2), Phi (libm, 2 ulp = 4 roundings), Phi' (2), fd (2), the
 #     shear bracket (5), the products (2)                      ~ 30 roundings = 15
