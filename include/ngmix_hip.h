@@ -1238,15 +1238,28 @@ int ngmix_lm_precise_cov_batch(const ngmix_lm_problem *problem, double *psums,
  *                     (1 + r^2 / r_d^2)^(-beta), r0 = r_d =
  *                     r50 / sqrt(2^(1/(beta-1)) - 1)      NGMIX_KFIT_MOFFAT
  *                     fwhm / (2 sqrt(2^(1/beta) - 1))     NGMIX_KFIT_MOFFAT_FWHM
+ *           'dev10'   Phi = sum_j p_j exp(-f_j s / 2) over the ten gaussians of
+ *                     the pixel-space 'dev' mixture, with
+ *                     s = T t / (2 (1 + g^2)): the size is ngmix's T, not r50.
+ *                     The exact de Vaucouleurs profile is not offered
+ *           'bdf'     Phi = sum_i a_i exp(-f_i tau s / 2) over the six 'exp' and
+ *                     ten 'dev' gaussians, a_i = (1 - fracdev) p_i | fracdev p_j,
+ *                     tau = ngmix_get_cm_Tfactor(fracdev, 1): the transform of
+ *                     the pixel-space 'bdf' mixture at the same parameters
  *   parameters [cen1, cen2, g1, g2, r50, F_band...] (nloc = 6), 'spergel'
  *   [cen1, cen2, g1, g2, r50, nu, F_band...], 'moffat' [cen1, cen2, g1, g2,
- *   r50 | fwhm, beta, F_band...] (nloc = 7)
+ *   r50 | fwhm, beta, F_band...] (nloc = 7), 'dev10' [cen1, cen2, g1, g2, T,
+ *   F_band...] (nloc = 6), 'bdf' [cen1, cen2, g1, g2, T, fracdev, F_band...]
+ *   (nloc = 7)
  * ---------------------------------------------------------------------- */
 #define NGMIX_KFIT_GAUSS 0
 #define NGMIX_KFIT_EXP 1
 #define NGMIX_KFIT_SPERGEL 2
 #define NGMIX_KFIT_MOFFAT 3
 #define NGMIX_KFIT_MOFFAT_FWHM 4
+/* (5, 6 and 7 are no models: callers were promised NGMIX_ERR_BAD_ARG for them) */
+#define NGMIX_KFIT_DEV10 8
+#define NGMIX_KFIT_BDF 9
 #define NGMIX_ERR_NOT_FINITE 8 /* a non-finite transform on a kept mode (per-stamp status) */
 /* HOST: c_nu = r50 / r0 of the Spergel profile and its derivative, from the
    committed Chebyshev table (csrc/spergel_hlr.hpp; 1e-12 relative); returns
@@ -1259,7 +1272,9 @@ int ngmix_spergel_hlr(double nu, double *c, double *dc_dnu);
    wbar (nstamps,): the largest weight of each stamp; jac (nstamps,): only the
    four derivatives are read.  sums: (nstamps, NGMIX_LM_NSUMS(nloc)) in the
    layout of ngmix_lm_eval_batch; status (may be NULL): NGMIX_ERR_G_RANGE where
-   g >= 1, the size < 1e-4, nu is outside [-0.85, 4] or beta outside [1.1, 6],
+   g >= 1, the size < 1e-4, nu is outside [-0.85, 4] or beta outside [1.1, 6]
+   ('dev10', 'bdf': g >= 1, T not > 0, a parameter that is not finite, or a
+   fracdev at which the T factor's denominator is zero),
    NGMIX_ERR_NOT_FINITE where
    a kept mode of dhat or phat is not finite -- the sums then carry ff = +inf;
    stamp_stats (may be NULL): (nstamps, 2) = sum w Re(M^ D^*), sum w |M^|^2.
@@ -1292,7 +1307,8 @@ int ngmix_moffat_phi_batch(const double *nu, const double *x, int64_t n, double 
    sum w |T^|^2, sum w |D^|^2 over the kept modes, w as in the evaluation.
    model: one of NGMIX_KFIT_*, or -1 for a point source (Phi = 1: the template
    is the psf itself).  pars (nstamps, npars): [cen1, cen2, g1, g2, size,
-   (nu | beta)] -- the model's local parameters without a flux, 5 or 6 of them;
+   (nu | beta | fracdev)] -- the model's local parameters without a flux, 5 or 6
+   of them;
    the point source takes 5 and reads the centre.  dhat, phat, wbar, jac and
    status as ngmix_kfit_eval_batch; a refused stamp's sums are zeros.  A
    stamp's sums depend on that stamp alone */

@@ -206,6 +206,8 @@ KFIT_EXP = 1
 KFIT_SPERGEL = 2
 KFIT_MOFFAT = 3
 KFIT_MOFFAT_FWHM = 4
+KFIT_DEV10 = 8
+KFIT_BDF = 9
 KFIT_POINT = -1    # ngmix_kfit_flux_batch alone: a point source
 ERR_NOT_FINITE = 8
 

@@ -1134,7 +1134,7 @@ static int kfit_eval_host(const char *who, bool w, const double *dhat, const dou
     if (st != NGMIX_OK || nothing) return st;
     if (w && (st = need_modew(who, modew, nstamps)) != NGMIX_OK) return st;
     for_int<NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL, NGMIX_KFIT_MOFFAT,
-            NGMIX_KFIT_MOFFAT_FWHM>(model, [&](auto M) {
+            NGMIX_KFIT_MOFFAT_FWHM, NGMIX_KFIT_DEV10, NGMIX_KFIT_BDF>(model, [&](auto M) {
         const kfit::EvalSums<M()> pol{states, stamp_obj, stamp_band, sums, stamp_stats};
         kfit::host_walk(pol, dhat, phat, wbar, jac, R, C, nstamps, status, modew, ncomp);
     });
@@ -1193,7 +1193,8 @@ static int kfit_flux_host(const char *who, bool w, const double *dhat, const dou
     if (st != NGMIX_OK || nothing) return st;
     if (w && (st = need_modew(who, modew, nstamps)) != NGMIX_OK) return st;
     for_int<kfit::MODEL_POINT, NGMIX_KFIT_GAUSS, NGMIX_KFIT_EXP, NGMIX_KFIT_SPERGEL,
-            NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM>(model, [&](auto M) {
+            NGMIX_KFIT_MOFFAT, NGMIX_KFIT_MOFFAT_FWHM, NGMIX_KFIT_DEV10, NGMIX_KFIT_BDF>(
+        model, [&](auto M) {
         const kfit::FluxSums<M()> pol{pars, out};
         kfit::host_walk(pol, dhat, phat, wbar, jac, R, C, nstamps, status, modew, ncomp);
     });

@@ -1,7 +1,8 @@
 // kfit.hip -- Fourier-space profile fits: the evaluation kernel
-// of the lock-step LM driver for 'gauss', 'exp', 'spergel' and the Moffat
-// profile fitted to the transform of a stamp's own samples, the
-// rounds that queue it, and the linear flux of a fixed template.
+// of the lock-step LM driver for 'gauss', 'exp', 'spergel', the Moffat profile
+//  and the gaussian mixtures 'dev10' and 'bdf' 
+// fitted to the transform of a stamp's own samples, the rounds that queue it,
+// and the linear flux of a fixed template.
 //
 //   kfit_eval_kernel<MODEL>  one WAVE per stamp, four stamps per block: the
 //       lanes stride over the stored modes of the stamp's rfft2 half plane,
@@ -170,6 +171,8 @@ int launch_kfit_eval(const double *dhat, const double *phat, const double *wbar,
         eval_row<NGMIX_KFIT_MOFFAT>("kfit_eval_kernel<moffat>", "kfit_eval_kernel<moffat, modew>"),
         eval_row<NGMIX_KFIT_MOFFAT_FWHM>("kfit_eval_kernel<moffat fwhm>",
                                          "kfit_eval_kernel<moffat fwhm, modew>"),
+        eval_row<NGMIX_KFIT_DEV10>("kfit_eval_kernel<dev10>", "kfit_eval_kernel<dev10, modew>"),
+        eval_row<NGMIX_KFIT_BDF>("kfit_eval_kernel<bdf>", "kfit_eval_kernel<bdf, modew>"),
     };
     const auto k = kfit_kernel(rows, model, modew != nullptr);
     return launch(k, kfit_grid(nstamps), dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,
@@ -218,6 +221,8 @@ int launch_kfit_flux(const double *dhat, const double *phat, const double *wbar,
         flux_row<NGMIX_KFIT_MOFFAT>("kfit_flux_kernel<moffat>", "kfit_flux_kernel<moffat, modew>"),
         flux_row<NGMIX_KFIT_MOFFAT_FWHM>("kfit_flux_kernel<moffat fwhm>",
                                          "kfit_flux_kernel<moffat fwhm, modew>"),
+        flux_row<NGMIX_KFIT_DEV10>("kfit_flux_kernel<dev10>", "kfit_flux_kernel<dev10, modew>"),
+        flux_row<NGMIX_KFIT_BDF>("kfit_flux_kernel<bdf>", "kfit_flux_kernel<bdf, modew>"),
     };
     const auto k = kfit_kernel(rows, model, modew != nullptr);
     return launch(k, kfit_grid(nstamps), dim3(BLOCK), 0, NO_OPTIN, s, (const double2 *)dhat,

@@ -11,7 +11,10 @@
 //
 // and Phi = exp(-s/2) | (1 + s)^-3/2 | (1 + s)^-(1 + nu), or the Moffat transform
 // Phi(sqrt(s); beta - 1) of moffat_phi.hpp, whose index beta
-// stands in nu's slot and whose size is r50 or the fwhm.  With G = exp(-i theta)
+// stands in nu's slot and whose size is r50 or the fwhm.  'dev10' and 'bdf'
+//  are the transforms of the pixel-space gaussian mixtures of
+// those names: Phi = sum a_i exp(-f_i tau s / 2) with s = T t / (2 (1 + g^2)),
+// the size ngmix's T and fracdev in nu's slot.  With G = exp(-i theta)
 // P^n the model is A G for a REAL A, and so is every derivative with respect to
 // g1, g2, r50, nu (beta) and F: column j is alpha_j G.  The two centre columns are
 // -i k_v A G and -i k_u A G, a quarter turn from G: their products with the
@@ -62,10 +65,20 @@ constexpr bool is_moffat(int model)
     return model == NGMIX_KFIT_MOFFAT || model == NGMIX_KFIT_MOFFAT_FWHM;
 }
 
+// the gaussian mixtures of common.hpp's tables: 'dev10' is components 6..15,
+// 'bdf' all of 0..15
+constexpr bool is_mix(int model)
+{
+    return model == NGMIX_KFIT_DEV10 || model == NGMIX_KFIT_BDF;
+}
+constexpr int MIX_NEXP = 6, MIX_N = 16;
+constexpr int mix_first(int model) { return model == NGMIX_KFIT_BDF ? 0 : MIX_NEXP; }
+
 template <int MODEL>
 struct Traits {
-    static constexpr int NLOC = MODEL == NGMIX_KFIT_SPERGEL || is_moffat(MODEL) ? 7 : 6;
-    static constexpr int NA = NLOC - 2;                       // g1, g2, r50, (nu | beta,) F
+    static constexpr int NLOC =
+        MODEL == NGMIX_KFIT_SPERGEL || is_moffat(MODEL) || MODEL == NGMIX_KFIT_BDF ? 7 : 6;
+    static constexpr int NA = NLOC - 2;          // g1, g2, r50 | T, (nu | beta | fracdev,) F
     static constexpr int NTRI = NA * (NA + 1) / 2;
     // cen-cen (3) | alpha alpha triangle | cen J^T f (2) | alpha J^T f | f.f
     static constexpr int NACC = 3 + NTRI + 2 + NA + 1;
@@ -87,6 +100,9 @@ struct Setup {
     double qr_unit, qc_unit;     // 2 pi / R, 2 pi / C
     bool bad;                    // out of range at the trial point
     MoffatNu mof;                // Moffat alone: what depends on beta
+    // the mixtures alone (set_mix): h_i = -f_i tau / 2 and a_i h_i of component i
+    double mh[MIX_N], mc[MIX_N];
+    double ifd;                  // 1 - fracdev
 };
 
 // the Moffat size in units of r_d and its logarithmic derivative with respect
@@ -100,7 +116,43 @@ NGMIX_HD void moffat_size(double beta, double &c, double &dlnc)
     dlnc = -0.5 * LN2 * (1.0 + em) / (b * b * em);
 }
 
-// p: the stamp's nloc local parameters [cen1, cen2, g1, g2, r50, (nu | beta,) F]
+// What a mixture's Setup holds in place of the r0^2 convention:
+// with r0sq = T / 2 and iD = 1 / (1 + g^2), Mode's s is T t / (2 (1 + g^2)), the
+// quadratic form of a gaussian of trace T at shear g; a component's exponent is
+// h_i s.  tau = 1 / ((1 - fd) sum_exp p f + fd sum_dev p f) is cm_Tfactor at
+// TdByTe = 1, d ln tau / d fd = -(sum_dev p f - sum_exp p f) tau.  Out of range:
+// T not > 0, g^2 not < 1, a parameter that is not finite, tau's denominator zero.
+template <int MODEL>
+NGMIX_HD void set_mix(Setup &m, double T, double gsq)
+{
+    constexpr ModelTables tab = NGMIX_MODEL_TABLES;
+    const double fd = MODEL == NGMIX_KFIT_BDF ? m.nu : 1.0;
+    m.ifd = 1.0 - fd;
+    double tau = 1.0;
+    m.dlns_dnu = 0.0;
+    if (MODEL == NGMIX_KFIT_BDF) {
+        double se = 0.0, sd = 0.0;
+        for (int i = 0; i < MIX_NEXP; i++) se += tab.pvals[i] * tab.fvals[i];
+        for (int i = MIX_NEXP; i < MIX_N; i++) sd += tab.pvals[i] * tab.fvals[i];
+        const double den = fma(m.ifd, se, fd * sd);
+        if (den == 0.0) m.bad = true;
+        tau = 1.0 / den;
+        m.dlns_dnu = -(sd - se) * tau;
+    }
+    if (!(T > 0.0) || !isfinite(m.cen1 + m.cen2 + T + fd + m.flux)) m.bad = true;
+    for (int i = mix_first(MODEL); i < MIX_N; i++) {
+        m.mh[i] = -0.5 * tab.fvals[i] * tau;
+        m.mc[i] = (tab.pvals[i] * (MODEL == NGMIX_KFIT_BDF ? (i < MIX_NEXP ? m.ifd : fd) : 1.0)) *
+                  m.mh[i];
+    }
+    m.iD = 1.0 / (1.0 + gsq);
+    m.r0sq = 0.5 * T;
+    m.ds_scale = T * m.iD;
+    m.dlns_dr50 = 1.0 / T;
+}
+
+// p: the stamp's nloc local parameters [cen1, cen2, g1, g2, r50 | T,
+// (nu | beta | fracdev,) F]
 template <int MODEL>
 NGMIX_HD Setup setup(const double *p, const ngmix_jacobian &jac, double wbar, int R, int C)
 {
@@ -134,12 +186,17 @@ NGMIX_HD Setup setup(const double *p, const ngmix_jacobian &jac, double wbar, in
     }
     m.opg1 = 1.0 + m.g1;
     m.omg1 = 1.0 - m.g1;
-    m.iD = 1.0 / (1.0 - gsq);
-    const double r0 = r50 / c;
-    m.r0sq = r0 * r0;
-    m.ds_scale = 2.0 * m.r0sq * m.iD;
-    m.dlns_dr50 = 2.0 / r50;
-    m.dlns_dnu = -2.0 * dc / c;
+    if (is_mix(MODEL)) {
+        m.bad = !(gsq < 1.0) || !(fabs(det) > 0.0);
+        set_mix<MODEL>(m, r50, gsq);
+    } else {
+        m.iD = 1.0 / (1.0 - gsq);
+        const double r0 = r50 / c;
+        m.r0sq = r0 * r0;
+        m.ds_scale = 2.0 * m.r0sq * m.iD;
+        m.dlns_dr50 = 2.0 / r50;
+        m.dlns_dnu = -2.0 * dc / c;
+    }
     m.onepnu = 1.0 + m.nu;
     m.wscale = wbar / ((double)R * (double)C);
     m.qr_unit = TWO_PI / (double)R;
@@ -190,7 +247,7 @@ NGMIX_HD int lane_components(double wscale, const double *u, int lane, int R, in
 
 // stored mode (a, b) at a set-up: (k_v, k_u) = J^-T q, the sheared pair
 // ea = (1 + g1) k_u + g2 k_v, eb = g2 k_u + (1 - g1) k_v, t = ea^2 + eb^2 and
-// s = r0^2 t / (1 - g^2)
+// s = r0^2 t / (1 - g^2) (a mixture: T t / (2 (1 + g^2)), by its set-up)
 // (SHEARED false: the point source, which reads k_v and k_u alone)
 template <bool SHEARED = true>
 struct Mode {
@@ -220,7 +277,10 @@ struct Mode {
 };
 
 // Phi(s) of MODEL (the point source: 1) and, DERIV, dphi = dPhi/ds and the term
-// of the nu (beta) column: lnu = ln(1 + s) for Spergel, dPhi/dbeta for Moffat
+// of the nu (beta, fracdev) column: lnu = ln(1 + s) for Spergel, dPhi/dbeta for
+// Moffat, for 'bdf' sum_dev p_j e_j - sum_exp p_i e_i, dPhi/dfracdev at fixed tau.
+// A mixture's exponentials e_i = exp(h_i s) are each made once and go straight
+// into the sums of Phi, dPhi/ds and that term.
 template <int MODEL, bool DERIV>
 NGMIX_HD void profile(const Setup &m, double s, double &phi, double &dphi, double &lnu)
 {
@@ -237,6 +297,18 @@ NGMIX_HD void profile(const Setup &m, double s, double &phi, double &dphi, doubl
         lnu = log1p(s);
         phi = exp(-m.onepnu * lnu);
         if (DERIV) dphi = -m.onepnu * phi / (1.0 + s);
+    } else if (is_mix(MODEL)) {
+        constexpr ModelTables tab = NGMIX_MODEL_TABLES;
+        double pe = 0.0, pd = 0.0, dp = 0.0;
+#pragma unroll
+        for (int i = mix_first(MODEL); i < MIX_N; i++) {
+            const double e = exp(m.mh[i] * s);
+            if (i < MIX_NEXP) pe = fma(tab.pvals[i], e, pe);
+            else pd = fma(tab.pvals[i], e, pd);
+            if (DERIV) dp = fma(m.mc[i], e, dp);
+        }
+        phi = MODEL == NGMIX_KFIT_BDF ? fma(m.ifd, pe, m.nu * pd) : pd;
+        if (DERIV) dphi = dp, lnu = pd - pe;
     } else {
         // D_x = 2 s dPhi/ds; at the DC mode every column but the flux's is zero
         double dx;
@@ -247,13 +319,13 @@ NGMIX_HD void profile(const Setup &m, double s, double &phi, double &dphi, doubl
 
 constexpr int model_nloc(int model)
 {
-    return model == NGMIX_KFIT_GAUSS || model == NGMIX_KFIT_EXP ? 6
-           : model == NGMIX_KFIT_SPERGEL || is_moffat(model)    ? 7
-                                                                : 0;
+    return model == NGMIX_KFIT_GAUSS || model == NGMIX_KFIT_EXP || model == NGMIX_KFIT_DEV10 ? 6
+           : model == NGMIX_KFIT_SPERGEL || is_moffat(model) || model == NGMIX_KFIT_BDF  ? 7
+                                                                                         : 0;
 }
 
 // the parameters a template of `model` takes, without a flux: [cen1, cen2, g1,
-// g2, size, (nu | beta)]; the point source reads the centre of its five
+// g2, size, (nu | beta | fracdev)]; the point source reads the centre of its five
 constexpr int flux_npars(int model)
 {
     return model == MODEL_POINT ? 5 : model_nloc(model) - (model_nloc(model) > 0);
@@ -285,16 +357,18 @@ struct EvalSums {
         double phi, dphi = 0.0, lnu = 0.0, gr, gi;
         profile<MODEL, true>(m, q.s, phi, dphi, lnu);
         q.G(m, pr, pi, gr, gi);
-        // alpha_j: g1, g2, r50, (nu,) F
+        // alpha_j: g1, g2, r50 | T, (nu | beta | fracdev,) F
         double al[NA];
         const double fd = m.flux * dphi;       // d A / d s
-        const double tD = q.t * m.iD;
+        // (a mixture's s carries 1 / (1 + g^2): the sign of its g-term is the other)
+        const double tD = is_mix(MODEL) ? -(q.t * m.iD) : q.t * m.iD;
         al[0] = fd * (m.ds_scale * (fma(q.ea, q.ku, -(q.eb * q.kv)) + m.g1 * tD));
         al[1] = fd * (m.ds_scale * (fma(q.ea, q.kv, q.eb * q.ku) + m.g2 * tD));
         al[2] = fd * (q.s * m.dlns_dr50);
         if (MODEL == NGMIX_KFIT_SPERGEL)
             al[3] = fma(fd, q.s * m.dlns_dnu, -(m.flux * (lnu * phi)));
-        if (is_moffat(MODEL)) al[3] = fma(fd, q.s * m.dlns_dnu, m.flux * lnu);
+        if (is_moffat(MODEL) || MODEL == NGMIX_KFIT_BDF)
+            al[3] = fma(fd, q.s * m.dlns_dnu, m.flux * lnu);
         al[NA - 1] = phi;
         const double A = m.flux * al[NA - 1];
         const double fr = fma(A, gr, -dr), fi = fma(A, gi, -di);
@@ -530,7 +604,8 @@ inline int check_args(const char *who, bool flux, int R, int C, int64_t nstamps,
     if (nstamps < 0) why = "nstamps must not be negative";
     else if (!model_ok)
         why = flux ? "model must be -1 (a point source) or one of NGMIX_KFIT_*"
-                   : "model must be NGMIX_KFIT_GAUSS, _EXP, _SPERGEL, _MOFFAT or _MOFFAT_FWHM";
+                   : "model must be NGMIX_KFIT_GAUSS, _EXP, _SPERGEL, _MOFFAT, _MOFFAT_FWHM, "
+                     "_DEV10 or _BDF";
     else if (R < 1 || C < 1 || R > 0x7fff || C > 0x7fff) why = "the stamp shape must be 1..32767";
     else if (nstamps == 0) nothing = true;
     else if (!have)

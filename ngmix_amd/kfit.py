@@ -1,7 +1,8 @@
 """
-Fourier-space profile fits: 'gauss', 'exp', 'spergel'
-and 'moffat' fitted to the transform of a stamp's own samples, and the linear
-flux of a fixed profile or of the psf in the same definition.
+Fourier-space profile fits: 'gauss', 'exp',
+'spergel', 'moffat' and the gaussian mixtures 'dev10' and 'bdf' fitted to the
+transform of a stamp's own samples, and the linear flux of a fixed profile or
+of the psf in the same definition.
 
 The reference's GalsimFitter / GalsimSpergelFitter / GalsimMoffatFitter fit the
 exact profile to a k-space observation that galsim draws, and its
@@ -25,12 +26,19 @@ What this is NOT: the pixel values of a KStampBatch are not galsim's (no
 interpolant, no stepk / getGoodImageSize grid), the weight is the Parseval
 weight (twice the reference's), aliases of the profile are not summed (galsim's
 k-space fit does not sum them either), the Moffat profile is not truncated,
-and 'dev' is not offered (it has no closed-form transform).
+and 'dev', the exact de Vaucouleurs profile, is not offered (it has no
+closed-form transform).  'dev10' is the transform of ngmix's ten-gaussian
+approximation of it, the mixture GMixModel(pars, 'dev') builds, and 'bdf' that
+of GMixModel(pars, 'bdf') (bulge + disk, TdByTe = 1): the pixel-space models
+themselves, fitted in Fourier space with the pixel-space fitters' parameters.
 
 Parameters: [cen1, cen2, g1, g2, r50, F_band...]; 'spergel':
 [cen1, cen2, g1, g2, r50, nu, F_band...]; 'moffat': [cen1, cen2, g1, g2, size,
 beta, F_band...], the size r50 (size_type 'r50', the default, or its aliases
-'hlr' / 'half_light_radius') or the fwhm (size_type 'fwhm').
+'hlr' / 'half_light_radius') or the fwhm (size_type 'fwhm'); 'dev10':
+[cen1, cen2, g1, g2, T, F_band...]; 'bdf': [cen1, cen2, g1, g2, T, fracdev,
+F_band...] -- the size of these two is ngmix's T, not r50, and they take no
+size_type.
 """
 import ctypes
 import math
@@ -47,8 +55,9 @@ __all__ = ["KStampBatch", "KSpaceBatchFitter", "KSpaceFitter", "kmodel_images",
            "KSpaceFluxBatch", "KSpaceFluxFitter", "metacal_mode_weights"]
 
 MODELS = {"gauss": _lib.KFIT_GAUSS, "exp": _lib.KFIT_EXP, "spergel": _lib.KFIT_SPERGEL,
-          "moffat": _lib.KFIT_MOFFAT}
-MODEL_NLOC = {"gauss": 6, "exp": 6, "spergel": 7, "moffat": 7}
+          "moffat": _lib.KFIT_MOFFAT, "dev10": _lib.KFIT_DEV10, "bdf": _lib.KFIT_BDF}
+MODEL_NLOC = {"gauss": 6, "exp": 6, "spergel": 7, "moffat": 7, "dev10": 6, "bdf": 7}
+MIX_MODELS = ("dev10", "bdf")     # the size parameter is T
 SIZE_TYPES = ("r50", "hlr", "half_light_radius", "fwhm")
 HLR_GAUSS = math.sqrt(2.0 * math.log(2.0))
 HLR_EXP = 1.6783469900166605
@@ -57,9 +66,12 @@ ROUNDS_FIRST = 12      # rounds queued blind before the first look at the counts
 
 def _model_id(model, size_type=None):
     if model not in MODELS:
-        raise ValueError("k-space fits offer %s, got %r ('dev' has no closed-form transform)"
+        raise ValueError("k-space fits offer %s, got %r ('dev', the exact profile, has no "
+                         "closed-form transform; 'dev10' is its ten-gaussian mixture)"
                          % (tuple(MODELS), model))
     if size_type is not None:
+        if model in MIX_MODELS:
+            raise ValueError("'%s' takes T and no size_type, got %r" % (model, size_type))
         if size_type not in SIZE_TYPES:
             raise ValueError("size_type must be one of %s, got %r" % (SIZE_TYPES, size_type))
         if model != "moffat" and size_type == "fwhm":
@@ -255,6 +267,22 @@ def metacal_mode_weights(aux, flags, weight):
     return torch.where(mask, rmin / rho2, zero).contiguous()
 
 
+def _mix_table(model, fracdev):
+    """amplitudes a_i (N, ncomp) and T_i / T = f_i tau (N, ncomp) of the
+    mixture of 'dev10' (fracdev None) or 'bdf' at fracdev (N, 1, 1), from
+    autodiff's copy of the model tables and its T factor"""
+    torch = _torch()
+    from .autodiff import _PVALS, _FVALS, _tfactor
+    lo = 6 if model == "dev10" else 0
+    dt = dict(dtype=torch.float64, device=fracdev.device)
+    pv, fv = torch.tensor(_PVALS[lo:16], **dt), torch.tensor(_FVALS[lo:16], **dt)
+    if model == "dev10":
+        return pv.expand(fracdev.shape[0], -1), fv.expand(fracdev.shape[0], -1)
+    fd = fracdev.reshape(-1, 1)
+    amp = torch.cat([(1.0 - fd) * pv[:6], fd * pv[6:]], dim=1)
+    return amp, fv[None, :] / _tfactor(1.0 - fd, fd, 1.0)
+
+
 def _spergel_hlr(nu):
     c, dc = ctypes.c_double(), ctypes.c_double()
     _lib.check(_lib.lib().ngmix_spergel_hlr(float(nu), ctypes.byref(c), ctypes.byref(dc)),
@@ -283,6 +311,18 @@ def kmodel_images(kb, pars, model, size_type=None):
     kv = (col(j[:, 5]) * qr[None] - col(j[:, 4]) * qc[None]) / det
     ku = (-col(j[:, 3]) * qr[None] + col(j[:, 2]) * qc[None]) / det
     g1, g2, r50, F = col(p[:, 2]), col(p[:, 3]), col(p[:, 4]), col(p[:, nloc - 1])
+    a = (1.0 + g1) * ku + g2 * kv
+    b = g2 * ku + (1.0 - g1) * kv
+    theta = kv * col(p[:, 0]) + ku * col(p[:, 1])
+    if model in MIX_MODELS:
+        # (parameter 4 is T: a gaussian of trace T_i at shear g has k^T C_i k =
+        # T_i (a^2 + b^2) / (2 (1 + g^2)))
+        amp, frac = _mix_table(model, p[:, 5] if model == "bdf" else p[:, 4])
+        s = r50 * (a * a + b * b) / (2.0 * (1.0 + g1 * g1 + g2 * g2))
+        phi = torch.zeros_like(s)
+        for i in range(amp.shape[1]):
+            phi = phi + col(amp[:, i]) * torch.exp(-0.5 * col(frac[:, i]) * s)
+        return _model_image(kb, F * phi, theta)
     if model == "spergel":
         c = torch.tensor([_spergel_hlr(v) for v in p[:, 5].cpu().numpy()],
                          dtype=torch.float64, device=kb.device)
@@ -294,8 +334,6 @@ def kmodel_images(kb, pars, model, size_type=None):
         c = torch.full((kb.n,), HLR_GAUSS if model == "gauss" else HLR_EXP,
                        dtype=torch.float64, device=kb.device)
     r0 = r50 / col(c)
-    a = (1.0 + g1) * ku + g2 * kv
-    b = g2 * ku + (1.0 - g1) * kv
     s = r0 * r0 * (a * a + b * b) / (1.0 - g1 * g1 - g2 * g2)
     if model == "gauss":
         phi = torch.exp(-0.5 * s)
@@ -305,10 +343,18 @@ def kmodel_images(kb, pars, model, size_type=None):
         phi = _moffat_phi((col(p[:, 5]) - 1.0).expand_as(s), torch.sqrt(s))
     else:
         phi = torch.exp(-(1.0 + col(p[:, 5])) * torch.log1p(s))
-    theta = kv * col(p[:, 0]) + ku * col(p[:, 1])
-    # M^ and the phase that takes the origin back from the centre to pixel (0, 0)
-    ang = -theta - (qr[None] * col(j[:, 0]) + qc[None] * col(j[:, 1]))
-    M = torch.polar(F * phi, ang)
+    return _model_image(kb, F * phi, theta)
+
+
+def _model_image(kb, amp, theta):
+    """irfft2 of M^ = amp exp(-i theta) P^n with the phase that takes the origin
+    back from the centre to pixel (0, 0)"""
+    torch = _torch()
+    R, C = kb.nrow, kb.ncol
+    qr, qc = _mode_grid(R, C, kb.device)
+    col = lambda t: t[:, None, None]
+    ang = -theta - (qr[None] * col(kb.jac[:, 0]) + qc[None] * col(kb.jac[:, 1]))
+    M = torch.polar(amp, ang)
     if kb.phat is not None:
         M = M * torch.view_as_complex(kb.phat)
     return torch.fft.irfft2(M, s=(R, C))
@@ -322,13 +368,15 @@ class KSpaceBatchFitter(object):
         res = fitter.go(kb, guess)          # guess (nobj, nloc - 1 + nband)
 
     prior: a batch prior whose descriptor() the device prior kernel serves
-    (PriorSimpleSepBatch for 'gauss' / 'exp', PriorSpergelSepBatch for
-    'spergel' and for 'moffat', whose beta it serves as the one middle term, or
-    a joint_prior object as_batch_prior converts), up to
+    (PriorSimpleSepBatch for 'gauss' / 'exp' / 'dev10', whose size term is then
+    a T prior, PriorSpergelSepBatch for 'spergel' and for 'moffat', whose beta it
+    serves as the one middle term, for 'bdf' a joint_prior.PriorBDFSep or the
+    PriorSepBatch of one middle term as_batch_prior makes of it, or any
+    joint_prior object as_batch_prior converts), up to
     NGMIX_PRIOR_MAXBAND bands; bounds: [(lo, hi)] * npars (None: the prior's),
     run through leastsqbound's transform by ngmix_lm_init_batch.  size_type
     ('moffat'): what parameter 4 is, 'r50' (or 'hlr', 'half_light_radius') or
-    'fwhm'.  round_s2n: one more evaluation at the fitted parameters with g = 0
+    'fwhm'; 'dev10' and 'bdf' take T there and no size_type.  round_s2n: one more evaluation at the fitted parameters with g = 0
     adds 's2n_r' = sqrt(sum over stamps of sum w |M^|^2) to the result.
     """
 
@@ -544,8 +592,15 @@ class KSpaceBatchFitter(object):
             "dof": cols[9].astype(np.int64), "lnprob": cols[5].copy(),
             "chi2per": cols[10].copy(), "s2n": cols[11].copy(),
             "g": pars[:, 2:4].copy(), "g_cov": cov[:, 2:4, 2:4].copy(),
-            "r50": pars[:, 4].copy(), "flux": pars[:, self.nloc - 1:].copy(),
+            "flux": pars[:, self.nloc - 1:].copy(),
         }
+        size = "T" if self.model in MIX_MODELS else "r50"
+        res[size] = pars[:, 4].copy()
+        if size == "T":
+            res["T_err"] = res["pars_err"][:, 4].copy()
+        if self.model == "bdf":
+            res["fracdev"] = pars[:, 5].copy()
+            res["fracdev_err"] = res["pars_err"][:, 5].copy()
         if self.model == "spergel":
             res["nu"] = pars[:, 5].copy()
         if self.model == "moffat":
@@ -621,7 +676,8 @@ class KSpaceFluxBatch(object):
     model None: a point source at the stamp's centre, so the template is the
     psf itself (the reference's GalsimPSFFluxFitter); pars is then None, or
     (nstamps, 2) centres.  Otherwise pars (nstamps, nloc - 1): each stamp's
-    [cen1, cen2, g1, g2, size, (nu | beta)].  res: (nobj,) arrays flags, flux,
+    [cen1, cen2, g1, g2, size, (nu | beta | fracdev)], the size T for 'dev10'
+    and 'bdf'.  res: (nobj,) arrays flags, flux,
     flux_err, chi2per, dof, as PSFFluxBatch gives them: where the template's
     sum is not positive or a sum is not finite, DIV_ZERO with flux = PDEF,
     flux_err = CDEF and chi2per = 0.
@@ -712,8 +768,8 @@ class KSpaceFluxFitter(object):
     KSpaceFluxBatch for Observation / ObsList, the two the reference's
     GalsimPSFFluxFitter takes: go(obs) one dict, go_many(list) a dict of
     (nobj,) arrays.  model None: the psf's flux (every observation carries a
-    psf); a model name with pars [cen1, cen2, g1, g2, size, (nu | beta)] per
-    object: that profile's.
+    psf); a model name with pars [cen1, cen2, g1, g2, size, (nu | beta |
+    fracdev)] per object: that profile's.
     """
 
     def __init__(self, model=None, size_type=None):

@@ -783,11 +783,11 @@ def metacal_bootstrap_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP
     return resdict, batchdict
 
 
-def _flat_moment_r50(stamps, psf_stamps):
-    """a starting r50 per stamp from the flat-weight second moments about the
+def _flat_moment_T(stamps, psf_stamps):
+    """a starting T per stamp from the flat-weight second moments about the
     jacobian centres: T = sum I (v^2 + u^2) / sum I of the image less the psf
-    stamp's, as a round gaussian's r50 = sqrt(2 ln 2) sqrt(T / 2); where that
-    is not positive, half the image's own T, and at least half a pixel"""
+    stamp's; where that is not positive, half the image's own T, and at least
+    that of a round gaussian of half a pixel's sigma"""
     torch = _torch()
 
     def flat_T(sb):
@@ -804,8 +804,13 @@ def _flat_moment_r50(stamps, psf_stamps):
     T, Tp = flat_T(stamps), flat_T(psf_stamps)
     floor = (0.5 * stamps.jac[:, 7]) ** 2
     Tobj = torch.where(T - Tp > 0, T - Tp, 0.5 * T)
-    Tobj = torch.where(torch.isfinite(Tobj) & (Tobj > 2.0 * floor), Tobj, 2.0 * floor)
-    return np.sqrt(2.0 * np.log(2.0)) * torch.sqrt(0.5 * Tobj)
+    return torch.where(torch.isfinite(Tobj) & (Tobj > 2.0 * floor), Tobj, 2.0 * floor)
+
+
+def _flat_moment_r50(stamps, psf_stamps):
+    """_flat_moment_T as a round gaussian's r50 = sqrt(2 ln 2) sqrt(T / 2)"""
+    torch = _torch()
+    return np.sqrt(2.0 * np.log(2.0)) * torch.sqrt(0.5 * _flat_moment_T(stamps, psf_stamps))
 
 
 def metacal_kfit_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP, types=None,
@@ -820,14 +825,15 @@ def metacal_kfit_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP, typ
 
     guess: (N, npars) used for every type, or (ntypes N, npars) type-major;
         None: centre 0, g = 0, r50 from the stamp's flat-weight second moments
-        (less the psf stamp's), nu = 0.5 | beta = 2.5, flux D^(0)
+        (less the psf stamp's) -- for 'dev10' and 'bdf' that T itself --,
+        nu = 0.5 | beta = 2.5 | fracdev = 0.5, flux D^(0)
     weight: 'flat' or 'noise', as from_metacal
     psf='dilate-exact' serves the `*_psf` types too; fixnoise is not served.
 
     Returns {type: KSpaceBatchFitter.go's dict of the type's N objects, with
     'mcal_flags' (N,) added}: what shear_response and mean_shear take.
     """
-    from .kfit import KStampBatch, KSpaceBatchFitter, MODEL_NLOC
+    from .kfit import KStampBatch, KSpaceBatchFitter, MODEL_NLOC, MIX_MODELS
     torch = _torch()
     kb = KStampBatch.from_metacal(stamps, psf_stamps, types=types, step=step, psf=psf,
                                   target_sigma=target_sigma, weight=weight, fixnoise=fixnoise,
@@ -837,9 +843,10 @@ def metacal_kfit_batch(stamps, psf_stamps, model="gauss", step=DEFAULT_STEP, typ
     npars = MODEL_NLOC[model]
     if guess is None:
         d_guess = torch.zeros((ntypes * n, npars), dtype=torch.float64, device=kb.device)
-        d_guess[:, 4] = _flat_moment_r50(stamps, psf_stamps).repeat(ntypes)
+        size = _flat_moment_T if model in MIX_MODELS else _flat_moment_r50
+        d_guess[:, 4] = size(stamps, psf_stamps).repeat(ntypes)
         if npars == 7:
-            d_guess[:, 5] = 0.5 if model == "spergel" else 2.5
+            d_guess[:, 5] = 2.5 if model == "moffat" else 0.5
         flux = kb.dhat[:, 0, 0, 0]
         d_guess[:, npars - 1] = torch.where(torch.isfinite(flux), flux, torch.ones_like(flux))
         guess = d_guess

@@ -41,11 +41,11 @@ NO_SPILL_ONLY = ("admom_grid_kernel", "em_wave_kernel", "wsums_wave_kernel",
                  "lm_eval_kernel", "lm_eval_fd_kernel", "kfit_eval_kernel", "kfit_flux_kernel",
                  "moffat_phi_kernel", "metacal_spectrum_kernel")
 # instantiations that must be there and free of scratch under their own names:
-# the mode-weight forms of the k-space kernels (five models, and the point
+# the mode-weight forms of the k-space kernels (seven models, and the point
 # source of the flux kernel) and the two spectrum kernels that write for them
 REQUIRED = {
-    r"kfit_eval_kernel<-?\d+, true>": 5,
-    r"kfit_flux_kernel<-?\d+, true>": 6,
+    r"kfit_eval_kernel<-?\d+, true>": 7,
+    r"kfit_flux_kernel<-?\d+, true>": 8,
     r"metacal_spectrum_kernel<false, [01], true>": 2,
 }
 
