@@ -590,6 +590,62 @@ int ngmix_prepsf_shear_fixnoise_sums_host(
     const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags);
+/* DEVICE: ngmix_prepsf_shear_sums_batch with the noise power of every mode from
+   a noise image of the stamp (PrePSFMom's use_noise_image) instead of the
+   weight map.  noise_power (n, dim, dim): one independent noise realisation per
+   stamp, NOT tapered and not turned; N^ its discrete-time Fourier transform
+   (only |N^|^2 is used: the centre does not matter).  The covariance weight of
+   mode k becomes w (fft_dim / dim)^2 |N^(k')|^2 / |P^(k')|^2 with k' the sheared
+   frequency the stamp and the psf are read at.  The four moment sums are those
+   of ngmix_prepsf_shear_sums_batch to the bit.  weights is not read and may be
+   NULL.  flags: 1, all fourteen sums NaN, also where a pixel of noise_power is
+   not finite.  Every other argument, the order of summation and the refusals
+   are those of ngmix_prepsf_shear_sums_batch; refused too: NULL noise_power
+   with n > 0, and the three planes not fitting the 160 KB of LDS.  n == 0 is a
+   no-op */
+int ngmix_prepsf_shear_power_sums_batch(
+    const double *images, const double *weights, const double *psf, const double *noise_power,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags, void *stream);
+/* HOST twin of ngmix_prepsf_shear_power_sums_batch: the same arguments on host
+   pointers, the same code in the kernel's summation order */
+int ngmix_prepsf_shear_power_sums_host(
+    const double *images, const double *weights, const double *psf, const double *noise_power,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags);
+/* DEVICE: ngmix_prepsf_shear_fixnoise_sums_batch with the noise power from
+   noise_power, as ngmix_prepsf_shear_power_sums_batch takes it.  The variance
+   of the fixnoise term of mode k is estimated from the same plane at the
+   frequency its turned copy would be read at: with q' = (q'_r, q'_c) the
+   sheared image of q = (-k_c, k_r), |DTFT[rot90(N, 1)](q'_r, q'_c)| = |N^(q'_c,
+   -q'_r)|, so the covariance sums are fk_a fk_b w (fft_dim / dim)^2 (|N^(k')|^2
+   / |P^(k')|^2 + |N^(q'_c, -q'_r)|^2 / |P^(q')|^2) and no turned copy is held.
+   The four moment sums are those of ngmix_prepsf_shear_fixnoise_sums_batch to
+   the bit.  noise_turned (tapered, turned: the fixnoise FIELD) and noise_power
+   (neither: the power ESTIMATE) may come from the same noise image.  Refused
+   too: the four planes not fitting the 160 KB of LDS */
+int ngmix_prepsf_shear_fixnoise_power_sums_batch(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
+    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
+    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
+    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
+    double *sums, int32_t *flags, void *stream);
+/* HOST twin of ngmix_prepsf_shear_fixnoise_power_sums_batch: the same arguments
+   on host pointers, the same code in the kernel's summation order */
+int ngmix_prepsf_shear_fixnoise_power_sums_host(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
+    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
+    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
+    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
+    double *sums, int32_t *flags);
 /* HOST: the generator alone: out (n, 4) = Philox4x32-10 of counters (n, 4)
    under keys (n, 2) */
 int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,

@@ -694,6 +694,74 @@ int ngmix_prepsf_shear_fixnoise_sums_host(
                             flags);
 }
 
+int ngmix_prepsf_shear_power_sums_batch(
+    const double *images, const double *weights, const double *psf, const double *noise_power,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags, void *stream)
+{
+    return launch_prepsf_shear_power_sums(images, weights, psf, noise_power, cen, psf_cen, edge, g,
+                                          g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
+                                          nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
+                                          dudcol, sums, flags, (hipStream_t)stream);
+}
+
+int ngmix_prepsf_shear_power_sums_host(
+    const double *images, const double *weights, const double *psf, const double *noise_power,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags)
+{
+    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
+    bool nothing;
+    const int st = pshear::check_args("prepsf_shear_power_sums_host", images, weights, psf, cen,
+                                      psf_cen, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n,
+                                      ntypes, nmodes, dim, pdim, fft_dim, deriv, sums, flags,
+                                      nothing, false, nullptr, true, noise_power);
+    if (st != NGMIX_OK || nothing) return st;
+    return pshear::run_host<true>(images, weights, psf, nullptr, cen, psf_cen, edge, g,
+                                  per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
+                                  fft_dim, deriv, sums, flags, noise_power);
+}
+
+int ngmix_prepsf_shear_fixnoise_power_sums_batch(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
+    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
+    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
+    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
+    double *sums, int32_t *flags, void *stream)
+{
+    return launch_prepsf_shear_fixnoise_power_sums(
+        images, weights, psf, noise_turned, noise_power, cen, psf_cen, edge, g, g_host, per_stamp_g,
+        mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol,
+        sums, flags, (hipStream_t)stream);
+}
+
+int ngmix_prepsf_shear_fixnoise_power_sums_host(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
+    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
+    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
+    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
+    double *sums, int32_t *flags)
+{
+    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
+    bool nothing;
+    const int st = pshear::check_args("prepsf_shear_fixnoise_power_sums_host", images, weights, psf,
+                                      cen, psf_cen, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n,
+                                      ntypes, nmodes, dim, pdim, fft_dim, deriv, sums, flags,
+                                      nothing, true, noise_turned, true, noise_power);
+    if (st != NGMIX_OK || nothing) return st;
+    return pshear::run_host<true>(images, weights, psf, noise_turned, cen, psf_cen, edge, g,
+                                  per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
+                                  fft_dim, deriv, sums, flags, noise_power);
+}
+
 int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,
                              uint32_t *out)
 {

@@ -21,6 +21,11 @@
 // NOISE (fixnoise): a third plane in LDS, the noise plane in its
 // turned layout, tapered while staged; after the image term every mode takes
 // add_noise_mode's term from it at the turned, sheared frequency.
+//
+// POWER (use_noise_image): one more plane in LDS, the stamp's
+// noise image, UN-tapered; the noise power of every term is that plane's at
+// the frequency the term is read at (prepsf_shear.hpp), not the weight map's,
+// and the weights are not read.
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "launch.hpp"
@@ -70,7 +75,10 @@ __device__ __forceinline__ void block_total(double (&vals)[NV], double *scratch)
 // segment, and the scalar loads and registers of the NOISE = false form stay
 // those of the kernel before the noise form existed (the scalar file is full:
 // with the pointer among the first arguments that form ran 3 to 6 % slower).
-template <bool NOISE>
+// POWER: noise_power (N, dim, dim), the un-tapered noise images, behind it for
+// the same reason; else unread, and the POWER = false forms are the code they
+// were before the axis existed.
+template <bool NOISE, bool POWER>
 __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const double *__restrict__ images, const double *__restrict__ weights,
     const double *__restrict__ psf, const double *__restrict__ cen,
@@ -79,7 +87,7 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const int32_t *__restrict__ mcol, const double *__restrict__ wgt,
     const double *__restrict__ fk, int T, int nmodes, int dim, int pdim, int fft_dim, double j00,
     double j01, double j10, double j11, double *__restrict__ sums, int32_t *__restrict__ flags,
-    const double *__restrict__ noise_turned)
+    const double *__restrict__ noise_turned, const double *__restrict__ noise_power)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ double s_plane[2];      // the psf's sum, the stamp's total variance
@@ -89,7 +97,8 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
 
     double *s_img = (double *)smem;
     double *s_noise = s_img + npix;
-    double *s_psf = s_noise + (NOISE ? npix : 0);
+    double *s_power = s_noise + (NOISE ? npix : 0);
+    double *s_psf = s_power + (POWER ? npix : 0);
     double *s_red = s_psf + nppix;
 
     // staging; on the way the two plane sums, strided as the host twin takes them
@@ -97,13 +106,15 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     for (int i = threadIdx.x; i < npix; i += blockDim.x) {
         const double v = images[n * npix + i];
         s_img[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
-        plane[1] += pixel_var(weights[n * npix + i]);
+        if (!POWER) plane[1] += pixel_var(weights[n * npix + i]);
     }
     if (NOISE)
         for (int i = threadIdx.x; i < npix; i += blockDim.x) {
             const double v = noise_turned[n * npix + i];
             s_noise[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
         }
+    if (POWER)
+        for (int i = threadIdx.x; i < npix; i += blockDim.x) s_power[i] = noise_power[n * npix + i];
     for (int i = threadIdx.x; i < nppix; i += blockDim.x) {
         const double v = psf[n * nppix + i];
         s_psf[i] = v;
@@ -120,20 +131,22 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     const double deriv[4] = {j00, j01, j10, j11};
     const double *gt = g + ((per_stamp_g ? n * T : 0) + t) * 2;
     const Setup m = setup(cen + 2 * n, psf_cen + 2 * n, deriv, gt[0], gt[1], s_plane[0],
-                          s_plane[1] * noise_scale);
-    const dtft::Planes planes = {s_img, nullptr, s_psf, dim, dim, pdim, pdim};
-    const dtft::Planes nplanes = {s_noise, nullptr, s_psf, dim, dim, pdim, pdim};
+                          POWER ? noise_scale : s_plane[1] * noise_scale);
+    const double *pw = POWER ? s_power : nullptr;
+    const dtft::Planes planes = {s_img, pw, s_psf, dim, dim, pdim, pdim};
+    const dtft::Planes nplanes = {s_noise, pw, s_psf, dim, dim, pdim, pdim};
 
     double acc[NSUMS];
 #pragma unroll
     for (int i = 0; i < NSUMS; i++) acc[i] = 0.0;
     bool out_of_band = false;
     for (int k = threadIdx.x; k < nmodes; k += blockDim.x) {
-        if (!add_mode(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k], fk[nmodes + k],
-                      fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
+        if (!add_mode<POWER>(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k], fk[nmodes + k],
+                             fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
             out_of_band = true;
-        if (NOISE && !add_noise_mode(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k], fk[k],
-                                     fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
+        if (NOISE && !add_noise_mode<POWER>(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k],
+                                            fk[k], fk[nmodes + k], fk[2 * nmodes + k],
+                                            fk[3 * nmodes + k], acc))
             out_of_band = true;
     }
     const int any_out = __syncthreads_or(out_of_band ? 1 : 0);
@@ -144,9 +157,10 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
 
 namespace {
 
-// both entries: each launches its own instantiation
-int launch_sums(const char *who, bool with_noise, const double *images, const double *weights,
-                const double *psf, const double *noise_turned, const double *cen,
+// all four entries: each launches its own instantiation
+int launch_sums(const char *who, bool with_noise, bool with_power, const double *images,
+                const double *weights, const double *psf, const double *noise_turned,
+                const double *noise_power, const double *cen,
                 const double *psf_cen, const double *edge, const double *g, const double *g_host,
                 int per_stamp_g, const int32_t *mrow, const int32_t *mcol, const double *wgt,
                 const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
@@ -157,15 +171,22 @@ int launch_sums(const char *who, bool with_noise, const double *images, const do
     bool nothing;
     const int st = check_args(who, images, weights, psf, cen, psf_cen, g, g_host, per_stamp_g,
                               mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, deriv,
-                              sums, flags, nothing, with_noise, noise_turned);
+                              sums, flags, nothing, with_noise, noise_turned, with_power,
+                              noise_power);
     if (st != NGMIX_OK || nothing) return st;
     static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "prepsf_shear.hpp mirrors device_utils.hpp");
-    const auto k = with_noise ? kernel(prepsf_shear_sums_kernel<true>, "prepsf_shear_sums_kernel<1>")
-                              : kernel(prepsf_shear_sums_kernel<false>, "prepsf_shear_sums_kernel");
+    const auto k =
+        with_power
+            ? (with_noise
+                   ? kernel(prepsf_shear_sums_kernel<true, true>, "prepsf_shear_sums_kernel<1, 1>")
+                   : kernel(prepsf_shear_sums_kernel<false, true>, "prepsf_shear_sums_kernel<0, 1>"))
+            : (with_noise ? kernel(prepsf_shear_sums_kernel<true, false>, "prepsf_shear_sums_kernel<1>")
+                          : kernel(prepsf_shear_sums_kernel<false, false>, "prepsf_shear_sums_kernel"));
     return launch(k, dim3((unsigned)(n * ntypes)), dim3(block_size(nmodes)),
-                  lds_bytes(dim, pdim, with_noise), 48 * 1024, s, images, weights, psf, cen, psf_cen,
-                  edge, g, per_stamp_g ? 1 : 0, mrow, mcol, wgt, fk, ntypes, nmodes, dim, pdim,
-                  fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, noise_turned);
+                  lds_bytes(dim, pdim, with_noise, with_power), 48 * 1024, s, images, weights, psf,
+                  cen, psf_cen, edge, g, per_stamp_g ? 1 : 0, mrow, mcol, wgt, fk, ntypes, nmodes,
+                  dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, noise_turned,
+                  noise_power);
 }
 
 }  // namespace
@@ -178,8 +199,8 @@ int launch_prepsf_shear_sums(const double *images, const double *weights, const 
                              int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow,
                              double dudcol, double *sums, int32_t *flags, hipStream_t s)
 {
-    return launch_sums("prepsf_shear_sums", false, images, weights, psf, nullptr, cen, psf_cen,
-                       edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim,
+    return launch_sums("prepsf_shear_sums", false, false, images, weights, psf, nullptr, nullptr,
+                       cen, psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim,
                        pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, s);
 }
 
@@ -191,9 +212,37 @@ int launch_prepsf_shear_fixnoise_sums(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags, hipStream_t s)
 {
-    return launch_sums("prepsf_shear_fixnoise_sums", true, images, weights, psf, noise_turned, cen,
-                       psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
+    return launch_sums("prepsf_shear_fixnoise_sums", true, false, images, weights, psf,
+                       noise_turned, nullptr, cen, psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
                        nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, s);
+}
+
+int launch_prepsf_shear_power_sums(
+    const double *images, const double *weights, const double *psf, const double *noise_power,
+    const double *cen, const double *psf_cen, const double *edge, const double *g,
+    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
+    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
+    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
+    int32_t *flags, hipStream_t s)
+{
+    return launch_sums("prepsf_shear_power_sums", false, true, images, weights, psf, nullptr,
+                       noise_power, cen, psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk,
+                       n, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums,
+                       flags, s);
+}
+
+int launch_prepsf_shear_fixnoise_power_sums(
+    const double *images, const double *weights, const double *psf, const double *noise_turned,
+    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
+    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
+    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
+    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
+    double *sums, int32_t *flags, hipStream_t s)
+{
+    return launch_sums("prepsf_shear_fixnoise_power_sums", true, true, images, weights, psf,
+                       noise_turned, noise_power, cen, psf_cen, edge, g, g_host, per_stamp_g, mrow,
+                       mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
+                       dudcol, sums, flags, s);
 }
 
 }  // namespace ngmix

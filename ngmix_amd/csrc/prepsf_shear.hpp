@@ -18,6 +18,21 @@
 //   F^(k) = N'^(q') / P^(q') exp(-i (q_r (r0 + c0 - (n - 1)) + q_c (c0 - r0)))
 //
 // (add_noise_mode); no target psf enters.
+//
+// POWER (ngmix_prepsf_shear_*power_sums_*): the noise power of a
+// mode is not the stamp's one scalar but that of a noise image N of the stamp,
+// UN-tapered, at the frequency the mode is read at: the covariance weight of the
+// image term is w eff^2 |N^(k')|^2 / |P^(k')|^2 (N rides the image's phase
+// recurrence as the third plane of dtft::transforms), that of the fixnoise term
+// w eff^2 |N^(q'_c, -q'_r)|^2 / |P^(q')|^2 -- the power the turned plane rot90(N)
+// has at q', since with N'[i, j] = N[j, n - 1 - i]
+//
+//   DTFT[N'](q_r, q_c) = exp(-i q_r (n - 1)) N^(q_c, -q_r),   so
+//   |DTFT[rot90(N, 1)](q_r, q_c)| = |N^(q_c, -q_r)|
+//
+// and no turned copy is held (one dtft::transform_one of the same plane).  Only
+// the modulus is used: the centre the plane is transformed about does not matter.
+// The four moment sums are those of the forms without POWER, to the bit.
 #pragma once
 #include <string>
 #include <vector>
@@ -46,6 +61,7 @@ struct Setup {
     double i00, i01, i10, i11;     // J^-T
     double d00, d01, d11;          // A - 1 (symmetric), exactly 0 at g = 0
     double min_amp, pnoise;        // 1e-5 |sum of the psf|, the noise power per mode
+                                   // (POWER: eff^2, what scales the plane's |N^|^2)
 };
 
 NGMIX_HD Setup setup(const double *cen, const double *psf_cen, const double *deriv, double g1,
@@ -81,6 +97,9 @@ NGMIX_HD double pixel_var(double w) { return w > 0.0 ? 1.0 / w : 0.0; }
 // fkr, fkf), added to acc: the four moments, then the upper triangle of their
 // covariance (pp, pc, pr, pf, cc, cr, cf, rr, rf, ff).  p: the TAPERED image and
 // the psf.  false, and nothing added, when the sheared frequency leaves the band.
+// POWER: p.noise is the UN-tapered noise image whose |N^(k')|^2 m.pnoise is the
+// mode's noise power, in place of m.pnoise alone.
+template <bool POWER = false>
 NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int D, double wgt,
                        double fp, double fc, double fr, double ff, double (&acc)[NSUMS])
 {
@@ -91,7 +110,8 @@ NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int 
     const double qr = qa + (m.j00 * dv + m.j10 * du), qc = qb + (m.j01 * dv + m.j11 * du);
     if (!(fabs(qr) < dtft::PI && fabs(qc) < dtft::PI)) return false;
     cplx si, sn, sp;
-    dtft::transforms<false>(p, m.r0, m.c0, qr, qc, si, sn, sp);
+    dtft::transforms<POWER>(p, m.r0, m.c0, qr, qc, si, sn, sp);
+    const double pnoise = POWER ? (sn.x * sn.x + sn.y * sn.y) * m.pnoise : m.pnoise;
     // the psf about its own centre
     sp = dtft::cmul(sp, dtft::cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
     const double amp = hypot(sp.x, sp.y);
@@ -103,7 +123,7 @@ NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int 
         }
     }
     const cplx k = dtft::cdiv(si, sp);
-    const double w = wgt * m.pnoise / (sp.x * sp.x + sp.y * sp.y);
+    const double w = wgt * pnoise / (sp.x * sp.x + sp.y * sp.y);
     const double kr = wgt * k.x;
     acc[0] += kr * fp;
     acc[1] += kr * fc;
@@ -129,6 +149,10 @@ NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int 
 // sheared image q' of the turned frequency q = (-k_c, k_r), about the image's
 // centre; turning back by rot90(k=3) moves that centre to (n - 1 - c0, r0),
 // which is the closing phase.  false, and nothing added, when q' leaves the band.
+// POWER: p.noise is the UN-tapered, UN-turned noise image; the variance of the
+// term takes its power at (q'_c, -q'_r), the frequency the turned plane would
+// be read at (the identity at the top), times m.pnoise.
+template <bool POWER = false>
 NGMIX_HD bool add_noise_mode(const dtft::Planes &p, const Setup &m, int a, int b, int D, int n,
                              double wgt, double fp, double fc, double fr, double ff,
                              double (&acc)[NSUMS])
@@ -152,7 +176,12 @@ NGMIX_HD bool add_noise_mode(const dtft::Planes &p, const Setup &m, int a, int b
     const cplx back =
         dtft::cexpi(-(qa * (m.r0 + m.c0 - (double)(n - 1)) + qb * (m.c0 - m.r0)));
     const cplx k = dtft::cmul(dtft::cdiv(sn, sp), back);
-    const double w = wgt * m.pnoise / (sp.x * sp.x + sp.y * sp.y);
+    double pnoise = m.pnoise;
+    if (POWER) {
+        const cplx pw = dtft::transform_one(p.noise, p.R, p.C, m.r0, m.c0, qc, -qr);
+        pnoise = (pw.x * pw.x + pw.y * pw.y) * m.pnoise;
+    }
+    const double w = wgt * pnoise / (sp.x * sp.x + sp.y * sp.y);
     const double kr = wgt * k.x;
     acc[0] += kr * fp;
     acc[1] += kr * fc;
@@ -187,10 +216,10 @@ NGMIX_HD bool finish(const double (&tot)[NSUMS], bool out_of_band, int D, double
 }
 
 // bytes of LDS of one block: the tapered image, with fixnoise the tapered noise
-// plane, the psf, one row of sums per wave
-inline size_t lds_bytes(int dim, int pdim, bool noise = false)
+// plane, with power the un-tapered noise image, the psf, one row of sums per wave
+inline size_t lds_bytes(int dim, int pdim, bool noise = false, bool power = false)
 {
-    return ((size_t)dim * dim * (noise ? 2 : 1) + (size_t)pdim * pdim +
+    return ((size_t)dim * dim * (1 + (noise ? 1 : 0) + (power ? 1 : 0)) + (size_t)pdim * pdim +
             (MAX_BLOCK / LANES) * NSUMS) * sizeof(double);
 }
 
@@ -209,7 +238,9 @@ inline int block_size(int nmodes)
 }
 
 // the refusals shared by the launchers and the host twins; nothing: n == 0.
-// with_noise: the fixnoise entries, which need noise_turned and its room in LDS
+// with_noise: the fixnoise entries, which need noise_turned and its room in LDS;
+// with_power: the power entries, which need noise_power and its room, and do
+// not read the weights
 inline int check_args(const char *who, const double *images, const double *weights,
                       const double *psf, const double *cen, const double *psf_cen,
                       const double *g, const double *g_host, int per_stamp_g,
@@ -217,7 +248,8 @@ inline int check_args(const char *who, const double *images, const double *weigh
                       const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
                       int fft_dim, const double *deriv, const double *sums, const int32_t *flags,
                       bool &nothing, bool with_noise = false,
-                      const double *noise_turned = nullptr)
+                      const double *noise_turned = nullptr, bool with_power = false,
+                      const double *noise_power = nullptr)
 {
     nothing = false;
     std::string why;
@@ -228,14 +260,22 @@ inline int check_args(const char *who, const double *images, const double *weigh
     else if (!(fabs(det) > 0.0) || !isfinite(det))
         why = "the jacobian's derivatives have no inverse";
     else if (n == 0) nothing = true;
-    else if (!images || !weights || !psf || !cen || !psf_cen || !g || !g_host || !mrow || !mcol ||
+    else if (!images || (!weights && !with_power) || !psf || !cen || !psf_cen || !g || !g_host || !mrow || !mcol ||
              !wgt || !fk || !sums || !flags)
         why = "images, weights, psf, cen, psf_cen, g, g_host, mrow, mcol, wgt, fk, sums and "
               "flags are required";
     else if (with_noise && !noise_turned) why = "noise_turned is required";
-    else if (dim > 0x7fff || pdim > 0x7fff || lds_bytes(dim, pdim, with_noise) > LDS_LIMIT)
-        why = with_noise ? "the stamp, its noise plane and its psf stamp do not fit the 160 KB of LDS"
-                         : "the stamp and its psf stamp do not fit the 160 KB of LDS";
+    else if (with_power && !noise_power) why = "noise_power is required";
+    else if (dim > 0x7fff || pdim > 0x7fff ||
+             lds_bytes(dim, pdim, with_noise, with_power) > LDS_LIMIT)
+        why = with_noise && with_power
+                  ? "the stamp, its noise plane, its noise-power plane and its psf stamp do not "
+                    "fit the 160 KB of LDS"
+              : with_power
+                  ? "the stamp, its noise-power plane and its psf stamp do not fit the 160 KB of LDS"
+              : with_noise
+                  ? "the stamp, its noise plane and its psf stamp do not fit the 160 KB of LDS"
+                  : "the stamp and its psf stamp do not fit the 160 KB of LDS";
     else if (n * ntypes > 0x7fffffffll) why = "too many (stamp, type) pairs for one launch";
     else {
         const int64_t ng = (per_stamp_g ? n : 1) * ntypes;
@@ -281,14 +321,16 @@ inline double host_plane_sum(const double *plane, int count, int block, double *
     return host_block_sum(part, block);
 }
 
-// noise_turned: null (the sums of the stamps alone), or the planes of fixnoise
+// noise_turned: null (the sums of the stamps alone), or the planes of fixnoise;
+// POWER: noise_power, the un-tapered noise images (the weights are not read)
+template <bool POWER = false>
 inline int run_host(const double *images, const double *weights, const double *psf,
                     const double *noise_turned, const double *cen, const double *psf_cen,
                     const double *edge,
                     const double *g, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
                     const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
                     int dim, int pdim, int fft_dim, const double *deriv, double *sums,
-                    int32_t *flags)
+                    int32_t *flags, const double *noise_power = nullptr)
 {
     const int npix = dim * dim, nppix = pdim * pdim, block = block_size(nmodes);
     const double noise_scale = ((double)fft_dim / (double)dim) * ((double)fft_dim / (double)dim);
@@ -306,9 +348,11 @@ inline int run_host(const double *images, const double *weights, const double *p
         }
         const double psf_sum =
             host_plane_sum(ps, nppix, block, part, [](double v) { return v; });
-        const double var = host_plane_sum(weights + i * npix, npix, block, part, pixel_var);
-        const dtft::Planes planes = {tapered, nullptr, ps, dim, dim, pdim, pdim};
-        const dtft::Planes nplanes = {tnoise, nullptr, ps, dim, dim, pdim, pdim};
+        const double var =
+            POWER ? 1.0 : host_plane_sum(weights + i * npix, npix, block, part, pixel_var);
+        const double *pw = POWER ? noise_power + i * npix : nullptr;
+        const dtft::Planes planes = {tapered, pw, ps, dim, dim, pdim, pdim};
+        const dtft::Planes nplanes = {tnoise, pw, ps, dim, dim, pdim, pdim};
         for (int t = 0; t < ntypes; t++) {
             const double *gt = g + ((per_stamp_g ? i * ntypes : 0) + t) * 2;
             const Setup m =
@@ -317,13 +361,14 @@ inline int run_host(const double *images, const double *weights, const double *p
             for (int th = 0; th < block; th++) {
                 double acc[NSUMS] = {0.0};
                 for (int k = th; k < nmodes; k += block) {
-                    if (!add_mode(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k],
-                                  fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k], acc))
+                    if (!add_mode<POWER>(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k],
+                                         fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k],
+                                         acc))
                         out_of_band = true;
                     if (noise_turned &&
-                        !add_noise_mode(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k], fk[k],
-                                        fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k],
-                                        acc))
+                        !add_noise_mode<POWER>(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k],
+                                               fk[k], fk[nmodes + k], fk[2 * nmodes + k],
+                                               fk[3 * nmodes + k], acc))
                         out_of_band = true;
                 }
                 for (int s = 0; s < NSUMS; s++) part[(size_t)s * block + th] = acc[s];

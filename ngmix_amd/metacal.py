@@ -1020,6 +1020,12 @@ def metacal_moments_batch(stamps, psf_stamps, measure, step=DEFAULT_STEP, types=
     fixnoise=True with neither raises NotImplementedError (the host draw from
     an rng is not served); a noise source with fixnoise=False, or both, is a
     ValueError.
+
+    A `measure` made with use_noise_image=True needs the stamps' noise images
+    (DESIGN.md 3.28), which a StampBatch does not hold and this function has
+    no argument for: it raises the reference's ValueError for a missing
+    obs.noise.  Send them to measure.go_metacal_batch(..., noise_images=) with
+    the batch's arrays, or measure observations with metacal_moments_many.
     """
     from .batch import StampBatch
     from .prepsfmom import _fixnoise_source
@@ -1064,6 +1070,15 @@ def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fi
         sqrt(weight) where weight > 0 (ids: one per observation, default the
         positions in the list), or
     use_noise_image: each observation's own ob.noise, as get_all_metacal takes it.
+
+    A `measure` made with use_noise_image=True takes the noise power of every
+    mode of every object from that object's ob.noise (ValueError if one has
+    none), whatever this function's own use_noise_image= says: the keyword
+    chooses the fixnoise FIELD, the measure's switch the power ESTIMATE of the
+    covariance.  Both may name ob.noise; then the one plane serves as field
+    (turned, tapered) and as power estimate (neither), as in the reference's
+    metacal, where the noise image that is sheared and added is the one the
+    moments' errors are then taken from.
     """
     from .moments import make_mom_result
     from .prepsfmom import _check_obs_and_get_psf_obs, _fixnoise_source
@@ -1079,6 +1094,8 @@ def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fi
         for o in list_of_obs:
             if not o.has_noise():
                 raise ValueError("use_noise_image=True: every observation needs a noise image")
+    if measure.use_noise_image and not all(o.has_noise() for o in list_of_obs):
+        raise ValueError('obs.noise must be set when use_noise_image=True')
     psfs = [_check_obs_and_get_psf_obs(o, False) for o in list_of_obs]
     groups = {}
     for i, (o, p) in enumerate(zip(list_of_obs, psfs)):
@@ -1099,7 +1116,8 @@ def metacal_moments_many(list_of_obs, measure, step=DEFAULT_STEP, types=None, fi
             np.stack([o.image for o in sub]), np.stack([o.weight for o in sub]),
             np.array([[o.jacobian.row0, o.jacobian.col0] for o in sub]), key[2:],
             np.stack([p.image for p in psub]),
-            np.array([[p.jacobian.row0, p.jacobian.col0] for p in psub]), g, noise=noise)
+            np.array([[p.jacobian.row0, p.jacobian.col0] for p in psub]), g, noise=noise,
+            noise_images=np.stack([o.noise for o in sub]) if measure.use_noise_image else None)
         for k, i in enumerate(idx):
             out[i] = {}
             for it, t in enumerate(types):

@@ -67,6 +67,14 @@ def _torch():
     return torch
 
 
+class NoiseImageRequired(ValueError, NotImplementedError):
+    """use_noise_image=True on the sheared route without noise images.  The
+    reference's error for a missing obs.noise is a ValueError, and this is one,
+    with the reference's message; before the route served use_noise_image the
+    same call raised NotImplementedError, and code that catches that to fall
+    back to the weight map's white level keeps working: it is both."""
+
+
 # ---------------------------------------------------------------------------
 # k-space kernels (host, float64)
 
@@ -556,7 +564,7 @@ class PrePSFMom(object):
 
     # ---- the moments of the object as sheared before the psf
     def measure_arrays_sheared(self, images, weights, cen, deriv, psf_images, psf_cen, g,
-                               noise=None, noise_ierr=None):
+                               noise=None, noise_ierr=None, noise_images=None):
         """
         The sums of measure_arrays for every stamp as sheared BEFORE its psf by
         each of T shears, without making an image: the transforms of the stamp
@@ -582,6 +590,18 @@ class PrePSFMom(object):
         variance; a kept mode whose turned, sheared frequency leaves the band,
         or a noise pixel that is not finite, flags its (stamp, type) as well.
 
+        noise_images: with use_noise_image, (N, dim, dim) one independent noise
+        realisation per stamp (obs.noise), numpy or device tensor, required
+        (without it the reference's ValueError, as NoiseImageRequired;
+        ValueError too when it is sent without use_noise_image).  The noise power of every mode is
+        then |N^|^2 (padded size / dim)^2 of that plane, NOT tapered, at the
+        sheared frequency the mode is read at, in place of the weight map's
+        white level -- and for the fixnoise term at the frequency the turned
+        plane would be read at.  Only the ten covariance sums
+        change; the moment sums are those without it, to the bit.  `noise` (the
+        fixnoise FIELD) and noise_images (the power ESTIMATE) may be the same
+        planes.  A pixel that is not finite flags its stamp, all types.
+
         Returns (sums (N, T, 6) = [nan, nan, M+, Mx, Mr, Mf], their covariance
         (N, T, 6, 6), flags (N, T), the kernels, the padded size).  flags is
         flags.METACAL_BAND_LIMIT where a kept mode's sheared frequency leaves
@@ -593,10 +613,10 @@ class PrePSFMom(object):
             raise NotImplementedError(
                 "sheared pre-psf moments deconvolve the psf at the sheared frequency: "
                 "no_psf (a pixel in real space) is not served")
-        if self.use_noise_image:
-            raise NotImplementedError(
-                "sheared pre-psf moments take the noise power from the weight map: "
-                "use_noise_image=True is not served")
+        if self.use_noise_image and noise_images is None:
+            raise NoiseImageRequired('obs.noise must be set when use_noise_image=True')
+        if noise_images is not None and not self.use_noise_image:
+            raise ValueError("noise_images were sent to a measurement with use_noise_image=False")
         g = np.ascontiguousarray(g, dtype=np.float64)
         if g.ndim not in (2, 3) or g.shape[-1] != 2 or g.shape[-2] == 0:
             raise ValueError("g must be (T, 2) or (N, T, 2), got %s" % (g.shape,))
@@ -611,6 +631,9 @@ class PrePSFMom(object):
         if psf_images.shape[0] != n:
             raise ValueError("one psf stamp per stamp: %d stamps, %d psf stamps"
                              % (n, psf_images.shape[0]))
+        if noise_images is not None and tuple(noise_images.shape) != (n, dim, dim):
+            raise ValueError("noise_images must hold one %d x %d plane per stamp, got %s"
+                             % (dim, dim, tuple(noise_images.shape)))
         deriv = tuple(float(d) for d in deriv)
         target_dim = int(max(dim, pdim) * self.pad_factor)
         mom = np.full((n, ntypes, 6), np.nan)
@@ -649,14 +672,19 @@ class PrePSFMom(object):
                     _dptr(d_plan[1]), _dptr(d_plan[2]), _dptr(d_plan[3]), n, ntypes, int(mrow.size),
                     int(dim), int(pdim), target_dim, deriv[0], deriv[1], deriv[2], deriv[3],
                     _dptr(d_sums), _dptr(d_flags), _stream())
-            if noise is None:
-                entry = "ngmix_prepsf_shear_sums_batch"
-                st = _lib.lib().ngmix_prepsf_shear_sums_batch(*(head + rest))
-            else:
-                entry = "ngmix_prepsf_shear_fixnoise_sums_batch"
+            planes = ()
+            if noise is not None:
                 d_noise = _turned_noise(noise, noise_ierr, d_w, n, dim, dev)
-                st = _lib.lib().ngmix_prepsf_shear_fixnoise_sums_batch(
-                    *(head + (_dptr(d_noise),) + rest))
+                planes += (_dptr(d_noise),)
+            if noise_images is not None:
+                d_power = _to_device(noise_images, dev).contiguous()
+                planes += (_dptr(d_power),)
+            entry = {(False, False): "ngmix_prepsf_shear_sums_batch",
+                     (True, False): "ngmix_prepsf_shear_fixnoise_sums_batch",
+                     (False, True): "ngmix_prepsf_shear_power_sums_batch",
+                     (True, True): "ngmix_prepsf_shear_fixnoise_power_sums_batch",
+                     }[noise is not None, noise_images is not None]
+            st = getattr(_lib.lib(), entry)(*(head + planes + rest))
         _lib.check(st, entry)
         # one download: a flagged (stamp, type) is the one whose sums are NaN, all
         # fourteen (d_flags says the same to callers that stay on the device)
@@ -672,7 +700,7 @@ class PrePSFMom(object):
 
     def go_metacal_batch(self, images, weights, cen, deriv, psf_images, psf_cen, step=0.01,
                          types=None, fixnoise=False, noise=None, noise_seed=None, ids=None,
-                         noise_ierr=None):
+                         noise_ierr=None, noise_images=None):
         """
         The pre-psf moments of metacalibration's types from the stamps alone
         (measure_arrays_sheared at the types' shears, no metacal image is
@@ -690,6 +718,11 @@ class PrePSFMom(object):
         (default sqrt(weight) where weight > 0; ids default to the positions).
         Without either, fixnoise=True is not served (NotImplementedError): the
         host draw from an rng is not made here.
+
+        noise_images: with use_noise_image, the (N, dim, dim) noise images the
+        covariance takes the noise power of every mode from (required then; see
+        measure_arrays_sheared): sums_cov, e_err, T_err, flux_err and s2n are
+        those of the stamps' correlated noise, the moments themselves unchanged.
         """
         from .metacal import _check_types, _type_shears
         from .moments import make_mom_result_batch
@@ -698,7 +731,7 @@ class PrePSFMom(object):
         g = _type_shears(types, float(step))
         mom, cov, flags, kernels, _ = self.measure_arrays_sheared(
             images, weights, cen, deriv, psf_images, psf_cen, g, noise=noise,
-            noise_ierr=noise_ierr)
+            noise_ierr=noise_ierr, noise_images=noise_images)
         out = {}
         for i, t in enumerate(types):
             res = make_mom_result_batch(mom[:, i], cov[:, i], sums_norm=kernels["fk00"])
