@@ -627,6 +627,19 @@ int ngmix_metacal_noise_host(const double *ierr, const int64_t *ids, uint64_t se
     return NGMIX_OK;
 }
 
+// The sheared pre-psf moments (prepsf_shear.hpp): every entry fills the record
+// of its form -- the planes it takes, null for the others, and the form, so
+// that a null plane the form requires is refused -- and makes one call.
+
+// a host twin: the refusals of the launcher, then the sums
+static int prepsf_shear_host(const char *who, const pshear::Args &a)
+{
+    bool nothing;
+    const int st = pshear::check_args(who, a, nothing);
+    if (st != NGMIX_OK || nothing) return st;
+    return pshear::run_host(a);
+}
+
 int ngmix_prepsf_shear_sums_batch(
     const double *images, const double *weights, const double *psf,
     const double *cen, const double *psf_cen, const double *edge, const double *g,
@@ -635,10 +648,11 @@ int ngmix_prepsf_shear_sums_batch(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags, void *stream)
 {
-    return launch_prepsf_shear_sums(images, weights, psf, cen, psf_cen, edge, g, g_host,
-                                    per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
-                                    fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags,
-                                    (hipStream_t)stream);
+    const pshear::Args a = {
+        images, weights, psf, nullptr, nullptr, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, false, false};
+    return launch_prepsf_shear_sums("prepsf_shear_sums", a, (hipStream_t)stream);
 }
 
 int ngmix_prepsf_shear_sums_host(
@@ -649,15 +663,11 @@ int ngmix_prepsf_shear_sums_host(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags)
 {
-    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
-    bool nothing;
-    const int st = pshear::check_args("prepsf_shear_sums_host", images, weights, psf, cen, psf_cen,
-                                      g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
-                                      nmodes, dim, pdim, fft_dim, deriv, sums, flags, nothing);
-    if (st != NGMIX_OK || nothing) return st;
-    return pshear::run_host(images, weights, psf, nullptr, cen, psf_cen, edge, g, per_stamp_g, mrow,
-                            mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, deriv, sums,
-                            flags);
+    const pshear::Args a = {
+        images, weights, psf, nullptr, nullptr, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, false, false};
+    return prepsf_shear_host("prepsf_shear_sums_host", a);
 }
 
 int ngmix_prepsf_shear_fixnoise_sums_batch(
@@ -668,10 +678,11 @@ int ngmix_prepsf_shear_fixnoise_sums_batch(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags, void *stream)
 {
-    return launch_prepsf_shear_fixnoise_sums(images, weights, psf, noise_turned, cen, psf_cen, edge,
-                                             g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
-                                             nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
-                                             dudcol, sums, flags, (hipStream_t)stream);
+    const pshear::Args a = {
+        images, weights, psf, noise_turned, nullptr, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, true, false};
+    return launch_prepsf_shear_sums("prepsf_shear_fixnoise_sums", a, (hipStream_t)stream);
 }
 
 int ngmix_prepsf_shear_fixnoise_sums_host(
@@ -682,16 +693,11 @@ int ngmix_prepsf_shear_fixnoise_sums_host(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags)
 {
-    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
-    bool nothing;
-    const int st = pshear::check_args("prepsf_shear_fixnoise_sums_host", images, weights, psf, cen,
-                                      psf_cen, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n,
-                                      ntypes, nmodes, dim, pdim, fft_dim, deriv, sums, flags,
-                                      nothing, true, noise_turned);
-    if (st != NGMIX_OK || nothing) return st;
-    return pshear::run_host(images, weights, psf, noise_turned, cen, psf_cen, edge, g, per_stamp_g,
-                            mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, deriv, sums,
-                            flags);
+    const pshear::Args a = {
+        images, weights, psf, noise_turned, nullptr, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, true, false};
+    return prepsf_shear_host("prepsf_shear_fixnoise_sums_host", a);
 }
 
 int ngmix_prepsf_shear_power_sums_batch(
@@ -702,10 +708,11 @@ int ngmix_prepsf_shear_power_sums_batch(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags, void *stream)
 {
-    return launch_prepsf_shear_power_sums(images, weights, psf, noise_power, cen, psf_cen, edge, g,
-                                          g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
-                                          nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
-                                          dudcol, sums, flags, (hipStream_t)stream);
+    const pshear::Args a = {
+        images, weights, psf, nullptr, noise_power, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, false, true};
+    return launch_prepsf_shear_sums("prepsf_shear_power_sums", a, (hipStream_t)stream);
 }
 
 int ngmix_prepsf_shear_power_sums_host(
@@ -716,16 +723,11 @@ int ngmix_prepsf_shear_power_sums_host(
     int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
     int32_t *flags)
 {
-    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
-    bool nothing;
-    const int st = pshear::check_args("prepsf_shear_power_sums_host", images, weights, psf, cen,
-                                      psf_cen, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n,
-                                      ntypes, nmodes, dim, pdim, fft_dim, deriv, sums, flags,
-                                      nothing, false, nullptr, true, noise_power);
-    if (st != NGMIX_OK || nothing) return st;
-    return pshear::run_host<true>(images, weights, psf, nullptr, cen, psf_cen, edge, g,
-                                  per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
-                                  fft_dim, deriv, sums, flags, noise_power);
+    const pshear::Args a = {
+        images, weights, psf, nullptr, noise_power, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, false, true};
+    return prepsf_shear_host("prepsf_shear_power_sums_host", a);
 }
 
 int ngmix_prepsf_shear_fixnoise_power_sums_batch(
@@ -736,10 +738,11 @@ int ngmix_prepsf_shear_fixnoise_power_sums_batch(
     int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
     double *sums, int32_t *flags, void *stream)
 {
-    return launch_prepsf_shear_fixnoise_power_sums(
-        images, weights, psf, noise_turned, noise_power, cen, psf_cen, edge, g, g_host, per_stamp_g,
-        mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol,
-        sums, flags, (hipStream_t)stream);
+    const pshear::Args a = {
+        images, weights, psf, noise_turned, noise_power, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, true, true};
+    return launch_prepsf_shear_sums("prepsf_shear_fixnoise_power_sums", a, (hipStream_t)stream);
 }
 
 int ngmix_prepsf_shear_fixnoise_power_sums_host(
@@ -750,16 +753,11 @@ int ngmix_prepsf_shear_fixnoise_power_sums_host(
     int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
     double *sums, int32_t *flags)
 {
-    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
-    bool nothing;
-    const int st = pshear::check_args("prepsf_shear_fixnoise_power_sums_host", images, weights, psf,
-                                      cen, psf_cen, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n,
-                                      ntypes, nmodes, dim, pdim, fft_dim, deriv, sums, flags,
-                                      nothing, true, noise_turned, true, noise_power);
-    if (st != NGMIX_OK || nothing) return st;
-    return pshear::run_host<true>(images, weights, psf, noise_turned, cen, psf_cen, edge, g,
-                                  per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim,
-                                  fft_dim, deriv, sums, flags, noise_power);
+    const pshear::Args a = {
+        images, weights, psf, noise_turned, noise_power, cen, psf_cen, edge, g, g_host,
+        per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim,
+        {dvdrow, dvdcol, dudrow, dudcol}, sums, flags, true, true};
+    return prepsf_shear_host("prepsf_shear_fixnoise_power_sums_host", a);
 }
 
 int ngmix_philox4x32_10_host(const uint32_t *counters, const uint32_t *keys, int64_t n,

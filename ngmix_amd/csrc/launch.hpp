@@ -5,6 +5,10 @@
 
 namespace ngmix {
 
+namespace pshear {
+struct Args;       // prepsf_shear.hpp
+}
+
 // pixpass.hip
 int launch_loglike_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
                         int32_t *status, void *stream);
@@ -57,34 +61,7 @@ int launch_metacal_dilate_spectrum(const double *images, const double *noise, co
 int launch_metacal_noise(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                          int nrow, int ncol, int rot_k, double *out, hipStream_t s);
 // prepsf_shear.hip
-int launch_prepsf_shear_sums(
-    const double *images, const double *weights, const double *psf,
-    const double *cen, const double *psf_cen, const double *edge, const double *g,
-    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
-    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
-    int32_t *flags, hipStream_t s);
-int launch_prepsf_shear_fixnoise_sums(
-    const double *images, const double *weights, const double *psf, const double *noise_turned,
-    const double *cen, const double *psf_cen, const double *edge, const double *g,
-    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
-    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
-    int32_t *flags, hipStream_t s);
-int launch_prepsf_shear_power_sums(
-    const double *images, const double *weights, const double *psf, const double *noise_power,
-    const double *cen, const double *psf_cen, const double *edge, const double *g,
-    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
-    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
-    int32_t *flags, hipStream_t s);
-int launch_prepsf_shear_fixnoise_power_sums(
-    const double *images, const double *weights, const double *psf, const double *noise_turned,
-    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
-    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
-    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
-    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
-    double *sums, int32_t *flags, hipStream_t s);
+int launch_prepsf_shear_sums(const char *who, const pshear::Args &a, hipStream_t s);
 // loglike_grad.hip
 int launch_loglike_grad(const ngmix_batch *b, const ngmix_gauss2d *gmix, double *out,
                         double *grad, int32_t *status, hipStream_t s);

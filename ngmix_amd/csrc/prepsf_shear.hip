@@ -5,7 +5,8 @@
 //
 //   M_t = sum_k w(k) K(k) I^(k'_t) / P^(k'_t),   k'_t = k + J^T (A_t - 1) J^-T k
 //
-// (prepsf_shear.hpp has the per-mode text, shared with the host twin).  Under a
+// (prepsf_shear.hpp has the argument record of every form, the per-mode text
+// and the refusals, shared with the host twin).  Under a
 // shear k' is not a product grid, so the separable products of the unsheared
 // measurement do not apply: the transforms are dense sums of modes x pixels
 // terms, as in metacal.hip, over the kernel's modes alone.
@@ -26,6 +27,9 @@
 // noise image, UN-tapered; the noise power of every term is that plane's at
 // the frequency the term is read at (prepsf_shear.hpp), not the weight map's,
 // and the weights are not read.
+//
+// One kernel text with two template axes, and one launcher for the four forms:
+// the C entries differ in the planes they put into the record.
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "launch.hpp"
@@ -61,6 +65,22 @@ __device__ __forceinline__ void block_total(double (&vals)[NV], double *scratch)
             for (int k = 1; k < nw; k++) s += scratch[k * NV + i];
             vals[i] = s;
         }
+    }
+}
+
+// Plane n of src (count = dim * dim values) into LDS, strided over the block;
+// with edge, tapered on the way.  VAR: the image's loop, which adds up the
+// variances of the plane's pixels (pixel_var of weights) as it goes; else
+// weights and var are not touched.
+template <bool VAR>
+__device__ __forceinline__ void stage_plane(double *dst, const double *src, int64_t n,
+                                            int count, const double *edge, int dim,
+                                            const double *weights, double &var)
+{
+    for (int i = threadIdx.x; i < count; i += blockDim.x) {
+        const double v = src[n * count + i];
+        dst[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
+        if (VAR) var += pixel_var(weights[n * count + i]);
     }
 }
 
@@ -102,19 +122,11 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
     double *s_red = s_psf + nppix;
 
     // staging; on the way the two plane sums, strided as the host twin takes them
+    // (the psf's loop is its own: another count, no taper, the sum of the values)
     double plane[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < npix; i += blockDim.x) {
-        const double v = images[n * npix + i];
-        s_img[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
-        if (!POWER) plane[1] += pixel_var(weights[n * npix + i]);
-    }
-    if (NOISE)
-        for (int i = threadIdx.x; i < npix; i += blockDim.x) {
-            const double v = noise_turned[n * npix + i];
-            s_noise[i] = edge ? edge[i / dim] * edge[i % dim] * v : v;
-        }
-    if (POWER)
-        for (int i = threadIdx.x; i < npix; i += blockDim.x) s_power[i] = noise_power[n * npix + i];
+    stage_plane<!POWER>(s_img, images, n, npix, edge, dim, weights, plane[1]);
+    if (NOISE) stage_plane<false>(s_noise, noise_turned, n, npix, edge, dim, nullptr, plane[1]);
+    if (POWER) stage_plane<false>(s_power, noise_power, n, npix, nullptr, dim, nullptr, plane[1]);
     for (int i = threadIdx.x; i < nppix; i += blockDim.x) {
         const double v = psf[n * nppix + i];
         s_psf[i] = v;
@@ -155,94 +167,25 @@ __global__ __launch_bounds__(BLOCK) void prepsf_shear_sums_kernel(
         flags[n * T + t] = finish(acc, any_out != 0, fft_dim, sums + (n * T + t) * NSUMS) ? 1 : 0;
 }
 
-namespace {
-
-// all four entries: each launches its own instantiation
-int launch_sums(const char *who, bool with_noise, bool with_power, const double *images,
-                const double *weights, const double *psf, const double *noise_turned,
-                const double *noise_power, const double *cen,
-                const double *psf_cen, const double *edge, const double *g, const double *g_host,
-                int per_stamp_g, const int32_t *mrow, const int32_t *mcol, const double *wgt,
-                const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-                int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
-                double *sums, int32_t *flags, hipStream_t s)
+// every form: the refusals, then the instantiation of (a.with_noise, a.with_power)
+int launch_prepsf_shear_sums(const char *who, const Args &a, hipStream_t s)
 {
-    const double deriv[4] = {dvdrow, dvdcol, dudrow, dudcol};
     bool nothing;
-    const int st = check_args(who, images, weights, psf, cen, psf_cen, g, g_host, per_stamp_g,
-                              mrow, mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, deriv,
-                              sums, flags, nothing, with_noise, noise_turned, with_power,
-                              noise_power);
+    const int st = check_args(who, a, nothing);
     if (st != NGMIX_OK || nothing) return st;
     static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "prepsf_shear.hpp mirrors device_utils.hpp");
-    const auto k =
-        with_power
-            ? (with_noise
-                   ? kernel(prepsf_shear_sums_kernel<true, true>, "prepsf_shear_sums_kernel<1, 1>")
-                   : kernel(prepsf_shear_sums_kernel<false, true>, "prepsf_shear_sums_kernel<0, 1>"))
-            : (with_noise ? kernel(prepsf_shear_sums_kernel<true, false>, "prepsf_shear_sums_kernel<1>")
-                          : kernel(prepsf_shear_sums_kernel<false, false>, "prepsf_shear_sums_kernel"));
-    return launch(k, dim3((unsigned)(n * ntypes)), dim3(block_size(nmodes)),
-                  lds_bytes(dim, pdim, with_noise, with_power), 48 * 1024, s, images, weights, psf,
-                  cen, psf_cen, edge, g, per_stamp_g ? 1 : 0, mrow, mcol, wgt, fk, ntypes, nmodes,
-                  dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, noise_turned,
-                  noise_power);
-}
-
-}  // namespace
-
-int launch_prepsf_shear_sums(const double *images, const double *weights, const double *psf,
-                             const double *cen, const double *psf_cen, const double *edge,
-                             const double *g, const double *g_host, int per_stamp_g,
-                             const int32_t *mrow, const int32_t *mcol, const double *wgt,
-                             const double *fk, int64_t n, int ntypes, int nmodes, int dim,
-                             int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow,
-                             double dudcol, double *sums, int32_t *flags, hipStream_t s)
-{
-    return launch_sums("prepsf_shear_sums", false, false, images, weights, psf, nullptr, nullptr,
-                       cen, psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes, nmodes, dim,
-                       pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, s);
-}
-
-int launch_prepsf_shear_fixnoise_sums(
-    const double *images, const double *weights, const double *psf, const double *noise_turned,
-    const double *cen, const double *psf_cen, const double *edge, const double *g,
-    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
-    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
-    int32_t *flags, hipStream_t s)
-{
-    return launch_sums("prepsf_shear_fixnoise_sums", true, false, images, weights, psf,
-                       noise_turned, nullptr, cen, psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk, n, ntypes,
-                       nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums, flags, s);
-}
-
-int launch_prepsf_shear_power_sums(
-    const double *images, const double *weights, const double *psf, const double *noise_power,
-    const double *cen, const double *psf_cen, const double *edge, const double *g,
-    const double *g_host, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
-    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-    int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol, double *sums,
-    int32_t *flags, hipStream_t s)
-{
-    return launch_sums("prepsf_shear_power_sums", false, true, images, weights, psf, nullptr,
-                       noise_power, cen, psf_cen, edge, g, g_host, per_stamp_g, mrow, mcol, wgt, fk,
-                       n, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow, dudcol, sums,
-                       flags, s);
-}
-
-int launch_prepsf_shear_fixnoise_power_sums(
-    const double *images, const double *weights, const double *psf, const double *noise_turned,
-    const double *noise_power, const double *cen, const double *psf_cen, const double *edge,
-    const double *g, const double *g_host, int per_stamp_g, const int32_t *mrow,
-    const int32_t *mcol, const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
-    int dim, int pdim, int fft_dim, double dvdrow, double dvdcol, double dudrow, double dudcol,
-    double *sums, int32_t *flags, hipStream_t s)
-{
-    return launch_sums("prepsf_shear_fixnoise_power_sums", true, true, images, weights, psf,
-                       noise_turned, noise_power, cen, psf_cen, edge, g, g_host, per_stamp_g, mrow,
-                       mcol, wgt, fk, n, ntypes, nmodes, dim, pdim, fft_dim, dvdrow, dvdcol, dudrow,
-                       dudcol, sums, flags, s);
+    static constexpr decltype(kernel(prepsf_shear_sums_kernel<false, false>, "")) kernels[2][2] = {
+        {kernel(prepsf_shear_sums_kernel<false, false>, "prepsf_shear_sums_kernel"),
+         kernel(prepsf_shear_sums_kernel<false, true>, "prepsf_shear_sums_kernel<0, 1>")},
+        {kernel(prepsf_shear_sums_kernel<true, false>, "prepsf_shear_sums_kernel<1>"),
+         kernel(prepsf_shear_sums_kernel<true, true>, "prepsf_shear_sums_kernel<1, 1>")},
+    };
+    return launch(kernels[a.with_noise][a.with_power], dim3((unsigned)(a.n * a.ntypes)),
+                  dim3(block_size(a.nmodes)), lds_bytes(a.dim, a.pdim, a.with_noise, a.with_power),
+                  48 * 1024, s, a.images, a.weights, a.psf, a.cen, a.psf_cen, a.edge, a.g,
+                  a.per_stamp_g ? 1 : 0, a.mrow, a.mcol, a.wgt, a.fk, a.ntypes, a.nmodes, a.dim,
+                  a.pdim, a.fft_dim, a.deriv[0], a.deriv[1], a.deriv[2], a.deriv[3], a.sums,
+                  a.flags, a.noise_turned, a.noise_power);
 }
 
 }  // namespace ngmix

@@ -1,8 +1,9 @@
 // prepsf_shear.hpp -- the pre-psf Fourier moments of a stamp as sheared before
-// its psf: what one kept mode of the weight kernel adds to the
-// fourteen sums, the refusals and the order of the reduction.  One text for the
-// kernel (prepsf_shear.hip) and its host twin (capi.hip,
-// ngmix_prepsf_shear_sums_host).
+// its psf: the argument record of every form (Args), what
+// one kept mode of the weight kernel adds to the fourteen sums, the refusals and
+// the order of the reduction.  One text for the kernel (prepsf_shear.hip) and
+// its host twin (run_host, behind the ngmix_prepsf_shear_*_host entries of
+// capi.hip).
 //
 //   M = sum_k w(k) K(k) I^(k') / P^(k'),   k' = k + J^T (A - 1) J^-T k
 //
@@ -17,7 +18,11 @@
 //
 //   F^(k) = N'^(q') / P^(q') exp(-i (q_r (r0 + c0 - (n - 1)) + q_c (c0 - r0)))
 //
-// (add_noise_mode); no target psf enters.
+// (add_noise_mode); no target psf enters.  Both terms are one text: the sheared
+// frequency (sheared_freq), the psf about its own centre and floored
+// (psf_about_centre), the fourteen accumulations (accumulate); add_mode
+// and add_noise_mode differ in the frequency they start from, the plane they
+// read, the closing phase and where the noise power comes from.
 //
 // POWER (ngmix_prepsf_shear_*power_sums_*): the noise power of a
 // mode is not the stamp's one scalar but that of a noise image N of the stamp,
@@ -48,6 +53,32 @@ using dtft::cplx;
 constexpr int NSUMS = 14;
 constexpr int MAX_BLOCK = 256, LANES = 64;       // = BLOCK, WAVE of device_utils.hpp
 constexpr size_t LDS_LIMIT = 160 * 1024;
+
+// What every form takes: the C entries fill one and hand it on.  images,
+// weights, noise_turned, noise_power (N, dim, dim), psf (N, pdim, pdim), cen,
+// psf_cen (N, 2), edge (dim,) or null, g (ng, T, 2) with ng = 1 or N and g_host
+// its copy on the host (the same pointer in the host twin); the plan: mrow,
+// mcol, wgt (nmodes,), fk (4, nmodes); deriv = (dvdrow, dvdcol, dudrow, dudcol);
+// sums (N, T, 14), flags (N, T).
+struct Args {
+    const double *images, *weights, *psf;
+    const double *noise_turned;    // rot90(k=1) of the noise planes; null without fixnoise
+    const double *noise_power;     // the un-tapered noise images; null without power
+    const double *cen, *psf_cen, *edge, *g, *g_host;
+    int per_stamp_g;
+    const int32_t *mrow, *mcol;
+    const double *wgt, *fk;
+    int64_t n;
+    int ntypes, nmodes, dim, pdim, fft_dim;
+    double deriv[4];
+    double *sums;
+    int32_t *flags;
+    // the form, set by the entry and not read off the planes: a null plane in a
+    // form that requires it is refused.  with_noise: the fixnoise entries, which
+    // need noise_turned and its room in LDS; with_power: the power entries, which
+    // need noise_power and its room, and do not read the weights
+    bool with_noise, with_power;
+};
 
 // 2 pi fftfreq(D)[a] for the signed mode number a, rounded as numpy rounds it
 // (a times the rounded 1/D, then times the rounded 2 pi): the frequency the
@@ -93,26 +124,22 @@ NGMIX_HD Setup setup(const double *cen, const double *psf_cen, const double *der
 // 1 / w where the weight is positive, 0 elsewhere
 NGMIX_HD double pixel_var(double w) { return w > 0.0 ? 1.0 / w : 0.0; }
 
-// The terms of the kept mode (a, b), of weight wgt and kernels fk = (fkp, fkc,
-// fkr, fkf), added to acc: the four moments, then the upper triangle of their
-// covariance (pp, pc, pr, pf, cc, cr, cf, rr, rf, ff).  p: the TAPERED image and
-// the psf.  false, and nothing added, when the sheared frequency leaves the band.
-// POWER: p.noise is the UN-tapered noise image whose |N^(k')|^2 m.pnoise is the
-// mode's noise power, in place of m.pnoise alone.
-template <bool POWER = false>
-NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int D, double wgt,
-                       double fp, double fc, double fr, double ff, double (&acc)[NSUMS])
+// The sheared frequency (qr, qc) of the pixel-axis frequency (qa, qb): to the
+// world frequency (v, u), the sheared one, and back to pixel axes.  The band
+// test on it stays with the two callers: returned through a helper, its && is
+// compiled to other code than the early return it is.
+NGMIX_HD void sheared_freq(const Setup &m, double qa, double qb, double &qr, double &qc)
 {
-    const double qa = mode_freq(a, D), qb = mode_freq(b, D);
-    // world frequency (v, u), the sheared one, and back to pixel axes
     const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
     const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
-    const double qr = qa + (m.j00 * dv + m.j10 * du), qc = qb + (m.j01 * dv + m.j11 * du);
-    if (!(fabs(qr) < dtft::PI && fabs(qc) < dtft::PI)) return false;
-    cplx si, sn, sp;
-    dtft::transforms<POWER>(p, m.r0, m.c0, qr, qc, si, sn, sp);
-    const double pnoise = POWER ? (sn.x * sn.x + sn.y * sn.y) * m.pnoise : m.pnoise;
-    // the psf about its own centre
+    qr = qa + (m.j00 * dv + m.j10 * du);
+    qc = qb + (m.j01 * dv + m.j11 * du);
+}
+
+// sp, the psf's transform about the IMAGE's centre at (qr, qc), brought about
+// the psf's own centre; an amplitude of m.min_amp or less is raised to it
+NGMIX_HD void psf_about_centre(const Setup &m, double qr, double qc, cplx &sp)
+{
     sp = dtft::cmul(sp, dtft::cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
     const double amp = hypot(sp.x, sp.y);
     if (amp <= m.min_amp) {
@@ -122,9 +149,13 @@ NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int 
             sp = {m.min_amp, 0.0};
         }
     }
-    const cplx k = dtft::cdiv(si, sp);
-    const double w = wgt * pnoise / (sp.x * sp.x + sp.y * sp.y);
-    const double kr = wgt * k.x;
+}
+
+// one term into acc: the four moments kr K, then the upper triangle of their
+// covariance w K K' (pp, pc, pr, pf, cc, cr, cf, rr, rf, ff)
+NGMIX_HD void accumulate(double kr, double w, double fp, double fc, double fr, double ff,
+                         double (&acc)[NSUMS])
+{
     acc[0] += kr * fp;
     acc[1] += kr * fc;
     acc[2] += kr * fr;
@@ -139,6 +170,27 @@ NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int 
     acc[11] += fr * fr * w;
     acc[12] += fr * ff * w;
     acc[13] += ff * ff * w;
+}
+
+// The terms of the kept mode (a, b), of weight wgt and kernels fk = (fkp, fkc,
+// fkr, fkf), added to acc (accumulate).  p: the TAPERED image and the psf.
+// false, and nothing added, when the sheared frequency leaves the band.
+// POWER: p.noise is the UN-tapered noise image whose |N^(k')|^2 m.pnoise is the
+// mode's noise power, in place of m.pnoise alone.
+template <bool POWER = false>
+NGMIX_HD bool add_mode(const dtft::Planes &p, const Setup &m, int a, int b, int D, double wgt,
+                       double fp, double fc, double fr, double ff, double (&acc)[NSUMS])
+{
+    double qr, qc;
+    sheared_freq(m, mode_freq(a, D), mode_freq(b, D), qr, qc);
+    if (!(fabs(qr) < dtft::PI && fabs(qc) < dtft::PI)) return false;
+    cplx si, sn, sp;
+    dtft::transforms<POWER>(p, m.r0, m.c0, qr, qc, si, sn, sp);
+    const double pnoise = POWER ? (sn.x * sn.x + sn.y * sn.y) * m.pnoise : m.pnoise;
+    psf_about_centre(m, qr, qc, sp);
+    const cplx k = dtft::cdiv(si, sp);
+    const double w = wgt * pnoise / (sp.x * sp.x + sp.y * sp.y);
+    accumulate(wgt * k.x, w, fp, fc, fr, ff, acc);
     return true;
 }
 
@@ -158,21 +210,12 @@ NGMIX_HD bool add_noise_mode(const dtft::Planes &p, const Setup &m, int a, int b
                              double (&acc)[NSUMS])
 {
     const double qa = -mode_freq(b, D), qb = mode_freq(a, D);
-    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
-    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
-    const double qr = qa + (m.j00 * dv + m.j10 * du), qc = qb + (m.j01 * dv + m.j11 * du);
+    double qr, qc;
+    sheared_freq(m, qa, qb, qr, qc);
     if (!(fabs(qr) < dtft::PI && fabs(qc) < dtft::PI)) return false;
     cplx sn, unused, sp;
     dtft::transforms<false>(p, m.r0, m.c0, qr, qc, sn, unused, sp);
-    sp = dtft::cmul(sp, dtft::cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
-    const double amp = hypot(sp.x, sp.y);
-    if (amp <= m.min_amp) {
-        if (amp != 0.0) {
-            sp = {sp.x / amp * m.min_amp, sp.y / amp * m.min_amp};
-        } else {
-            sp = {m.min_amp, 0.0};
-        }
-    }
+    psf_about_centre(m, qr, qc, sp);
     const cplx back =
         dtft::cexpi(-(qa * (m.r0 + m.c0 - (double)(n - 1)) + qb * (m.c0 - m.r0)));
     const cplx k = dtft::cmul(dtft::cdiv(sn, sp), back);
@@ -182,21 +225,7 @@ NGMIX_HD bool add_noise_mode(const dtft::Planes &p, const Setup &m, int a, int b
         pnoise = (pw.x * pw.x + pw.y * pw.y) * m.pnoise;
     }
     const double w = wgt * pnoise / (sp.x * sp.x + sp.y * sp.y);
-    const double kr = wgt * k.x;
-    acc[0] += kr * fp;
-    acc[1] += kr * fc;
-    acc[2] += kr * fr;
-    acc[3] += kr * ff;
-    acc[4] += fp * fp * w;
-    acc[5] += fp * fc * w;
-    acc[6] += fp * fr * w;
-    acc[7] += fp * ff * w;
-    acc[8] += fc * fc * w;
-    acc[9] += fc * fr * w;
-    acc[10] += fc * ff * w;
-    acc[11] += fr * fr * w;
-    acc[12] += fr * ff * w;
-    acc[13] += ff * ff * w;
+    accumulate(wgt * k.x, w, fp, fc, fr, ff, acc);
     return true;
 }
 
@@ -217,7 +246,7 @@ NGMIX_HD bool finish(const double (&tot)[NSUMS], bool out_of_band, int D, double
 
 // bytes of LDS of one block: the tapered image, with fixnoise the tapered noise
 // plane, with power the un-tapered noise image, the psf, one row of sums per wave
-inline size_t lds_bytes(int dim, int pdim, bool noise = false, bool power = false)
+inline size_t lds_bytes(int dim, int pdim, bool noise, bool power)
 {
     return ((size_t)dim * dim * (1 + (noise ? 1 : 0) + (power ? 1 : 0)) + (size_t)pdim * pdim +
             (MAX_BLOCK / LANES) * NSUMS) * sizeof(double);
@@ -237,50 +266,39 @@ inline int block_size(int nmodes)
     return block;
 }
 
-// the refusals shared by the launchers and the host twins; nothing: n == 0.
-// with_noise: the fixnoise entries, which need noise_turned and its room in LDS;
-// with_power: the power entries, which need noise_power and its room, and do
-// not read the weights
-inline int check_args(const char *who, const double *images, const double *weights,
-                      const double *psf, const double *cen, const double *psf_cen,
-                      const double *g, const double *g_host, int per_stamp_g,
-                      const int32_t *mrow, const int32_t *mcol, const double *wgt,
-                      const double *fk, int64_t n, int ntypes, int nmodes, int dim, int pdim,
-                      int fft_dim, const double *deriv, const double *sums, const int32_t *flags,
-                      bool &nothing, bool with_noise = false,
-                      const double *noise_turned = nullptr, bool with_power = false,
-                      const double *noise_power = nullptr)
+// the refusals shared by the launcher and the host twins; nothing: n == 0
+inline int check_args(const char *who, const Args &a, bool &nothing)
 {
     nothing = false;
     std::string why;
-    const double det = deriv[0] * deriv[3] - deriv[1] * deriv[2];
-    if (n < 0) why = "n must not be negative";
-    else if (ntypes <= 0 || nmodes <= 0 || dim <= 0 || pdim <= 0 || fft_dim <= 0)
+    const double det = a.deriv[0] * a.deriv[3] - a.deriv[1] * a.deriv[2];
+    if (a.n < 0) why = "n must not be negative";
+    else if (a.ntypes <= 0 || a.nmodes <= 0 || a.dim <= 0 || a.pdim <= 0 || a.fft_dim <= 0)
         why = "the number of types, the number of modes and the sizes must be positive";
     else if (!(fabs(det) > 0.0) || !isfinite(det))
         why = "the jacobian's derivatives have no inverse";
-    else if (n == 0) nothing = true;
-    else if (!images || (!weights && !with_power) || !psf || !cen || !psf_cen || !g || !g_host || !mrow || !mcol ||
-             !wgt || !fk || !sums || !flags)
+    else if (a.n == 0) nothing = true;
+    else if (!a.images || (!a.weights && !a.with_power) || !a.psf || !a.cen || !a.psf_cen ||
+             !a.g || !a.g_host || !a.mrow || !a.mcol || !a.wgt || !a.fk || !a.sums || !a.flags)
         why = "images, weights, psf, cen, psf_cen, g, g_host, mrow, mcol, wgt, fk, sums and "
               "flags are required";
-    else if (with_noise && !noise_turned) why = "noise_turned is required";
-    else if (with_power && !noise_power) why = "noise_power is required";
-    else if (dim > 0x7fff || pdim > 0x7fff ||
-             lds_bytes(dim, pdim, with_noise, with_power) > LDS_LIMIT)
-        why = with_noise && with_power
+    else if (a.with_noise && !a.noise_turned) why = "noise_turned is required";
+    else if (a.with_power && !a.noise_power) why = "noise_power is required";
+    else if (a.dim > 0x7fff || a.pdim > 0x7fff ||
+             lds_bytes(a.dim, a.pdim, a.with_noise, a.with_power) > LDS_LIMIT)
+        why = a.with_noise && a.with_power
                   ? "the stamp, its noise plane, its noise-power plane and its psf stamp do not "
                     "fit the 160 KB of LDS"
-              : with_power
+              : a.with_power
                   ? "the stamp, its noise-power plane and its psf stamp do not fit the 160 KB of LDS"
-              : with_noise
+              : a.with_noise
                   ? "the stamp, its noise plane and its psf stamp do not fit the 160 KB of LDS"
                   : "the stamp and its psf stamp do not fit the 160 KB of LDS";
-    else if (n * ntypes > 0x7fffffffll) why = "too many (stamp, type) pairs for one launch";
+    else if (a.n * a.ntypes > 0x7fffffffll) why = "too many (stamp, type) pairs for one launch";
     else {
-        const int64_t ng = (per_stamp_g ? n : 1) * ntypes;
+        const int64_t ng = (a.per_stamp_g ? a.n : 1) * a.ntypes;
         for (int64_t i = 0; i < ng && why.empty(); i++) {
-            const double g1 = g_host[2 * i], g2 = g_host[2 * i + 1];
+            const double g1 = a.g_host[2 * i], g2 = a.g_host[2 * i + 1];
             if (!(g1 * g1 + g2 * g2 < 1.0))
                 why = "shear " + std::to_string(i) + " is not inside the unit circle";
         }
@@ -321,53 +339,48 @@ inline double host_plane_sum(const double *plane, int count, int block, double *
     return host_block_sum(part, block);
 }
 
-// noise_turned: null (the sums of the stamps alone), or the planes of fixnoise;
-// POWER: noise_power, the un-tapered noise images (the weights are not read)
-template <bool POWER = false>
-inline int run_host(const double *images, const double *weights, const double *psf,
-                    const double *noise_turned, const double *cen, const double *psf_cen,
-                    const double *edge,
-                    const double *g, int per_stamp_g, const int32_t *mrow, const int32_t *mcol,
-                    const double *wgt, const double *fk, int64_t n, int ntypes, int nmodes,
-                    int dim, int pdim, int fft_dim, const double *deriv, double *sums,
-                    int32_t *flags, const double *noise_power = nullptr)
+// the sums of checked arguments; POWER = a.with_power
+template <bool POWER>
+inline void run_host_body(const Args &a)
 {
-    const int npix = dim * dim, nppix = pdim * pdim, block = block_size(nmodes);
-    const double noise_scale = ((double)fft_dim / (double)dim) * ((double)fft_dim / (double)dim);
-    std::vector<double> tapered_v(npix), noise_v(noise_turned ? npix : 0),
+    const int dim = a.dim, nmodes = a.nmodes, ntypes = a.ntypes;
+    const int npix = dim * dim, nppix = a.pdim * a.pdim, block = block_size(nmodes);
+    const double *edge = a.edge, *fk = a.fk;
+    const double noise_scale =
+        ((double)a.fft_dim / (double)dim) * ((double)a.fft_dim / (double)dim);
+    std::vector<double> tapered_v(npix), noise_v(a.with_noise ? npix : 0),
         part_v((size_t)block * NSUMS);
     double *tapered = tapered_v.data(), *tnoise = noise_v.data(), *part = part_v.data();
-    for (int64_t i = 0; i < n; i++) {
-        const double *im = images + i * npix, *ps = psf + i * nppix;
+    const auto taper = [&](double *dst, const double *src) {
         for (int p = 0; p < npix; p++)
-            tapered[p] = edge ? edge[p / dim] * edge[p % dim] * im[p] : im[p];
-        if (noise_turned) {
-            const double *nz = noise_turned + i * npix;
-            for (int p = 0; p < npix; p++)
-                tnoise[p] = edge ? edge[p / dim] * edge[p % dim] * nz[p] : nz[p];
-        }
+            dst[p] = edge ? edge[p / dim] * edge[p % dim] * src[p] : src[p];
+    };
+    for (int64_t i = 0; i < a.n; i++) {
+        const double *ps = a.psf + i * nppix;
+        taper(tapered, a.images + i * npix);
+        if (a.with_noise) taper(tnoise, a.noise_turned + i * npix);
         const double psf_sum =
             host_plane_sum(ps, nppix, block, part, [](double v) { return v; });
         const double var =
-            POWER ? 1.0 : host_plane_sum(weights + i * npix, npix, block, part, pixel_var);
-        const double *pw = POWER ? noise_power + i * npix : nullptr;
-        const dtft::Planes planes = {tapered, pw, ps, dim, dim, pdim, pdim};
-        const dtft::Planes nplanes = {tnoise, pw, ps, dim, dim, pdim, pdim};
+            POWER ? 1.0 : host_plane_sum(a.weights + i * npix, npix, block, part, pixel_var);
+        const double *pw = POWER ? a.noise_power + i * npix : nullptr;
+        const dtft::Planes planes = {tapered, pw, ps, dim, dim, a.pdim, a.pdim};
+        const dtft::Planes nplanes = {tnoise, pw, ps, dim, dim, a.pdim, a.pdim};
         for (int t = 0; t < ntypes; t++) {
-            const double *gt = g + ((per_stamp_g ? i * ntypes : 0) + t) * 2;
-            const Setup m =
-                setup(cen + 2 * i, psf_cen + 2 * i, deriv, gt[0], gt[1], psf_sum, var * noise_scale);
+            const double *gt = a.g + ((a.per_stamp_g ? i * ntypes : 0) + t) * 2;
+            const Setup m = setup(a.cen + 2 * i, a.psf_cen + 2 * i, a.deriv, gt[0], gt[1], psf_sum,
+                                  var * noise_scale);
             bool out_of_band = false;
             for (int th = 0; th < block; th++) {
                 double acc[NSUMS] = {0.0};
                 for (int k = th; k < nmodes; k += block) {
-                    if (!add_mode<POWER>(planes, m, mrow[k], mcol[k], fft_dim, wgt[k], fk[k],
-                                         fk[nmodes + k], fk[2 * nmodes + k], fk[3 * nmodes + k],
-                                         acc))
+                    if (!add_mode<POWER>(planes, m, a.mrow[k], a.mcol[k], a.fft_dim, a.wgt[k],
+                                         fk[k], fk[nmodes + k], fk[2 * nmodes + k],
+                                         fk[3 * nmodes + k], acc))
                         out_of_band = true;
-                    if (noise_turned &&
-                        !add_noise_mode<POWER>(nplanes, m, mrow[k], mcol[k], fft_dim, dim, wgt[k],
-                                               fk[k], fk[nmodes + k], fk[2 * nmodes + k],
+                    if (a.with_noise &&
+                        !add_noise_mode<POWER>(nplanes, m, a.mrow[k], a.mcol[k], a.fft_dim, dim,
+                                               a.wgt[k], fk[k], fk[nmodes + k], fk[2 * nmodes + k],
                                                fk[3 * nmodes + k], acc))
                         out_of_band = true;
                 }
@@ -375,9 +388,17 @@ inline int run_host(const double *images, const double *weights, const double *p
             }
             double tot[NSUMS];
             for (int s = 0; s < NSUMS; s++) tot[s] = host_block_sum(part + (size_t)s * block, block);
-            flags[i * ntypes + t] = finish(tot, out_of_band, fft_dim, sums + (i * ntypes + t) * NSUMS);
+            a.flags[i * ntypes + t] =
+                finish(tot, out_of_band, a.fft_dim, a.sums + (i * ntypes + t) * NSUMS);
         }
     }
+}
+
+// the host twin of every form, for arguments that check_args passed
+inline int run_host(const Args &a)
+{
+    if (a.with_power) run_host_body<true>(a);
+    else run_host_body<false>(a);
     return NGMIX_OK;
 }
 

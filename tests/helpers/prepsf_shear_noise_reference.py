@@ -180,41 +180,10 @@ def reference(dim, pdim, n, kind, ap_rad, dtype=np.longdouble, rows_of=None):
 def call_host(L, ptr, c, nturned, g, rows, cols, kwgt, kfk, D, ap_rad, deriv=DERIV, host=True,
               **over):
     """ngmix_prepsf_shear_fixnoise_sums_host (host=False: _batch with a null
-    stream, for the refusals) on a case's arrays and its TURNED noise planes nturned;
-    returns (status, sums (n, T, 14), flags (n, T)).  `over` replaces arguments
-    by name."""
-    n, dim = c["images"].shape[0], c["images"].shape[1]
-    pdim = c["psfs"].shape[1]
-    g = np.ascontiguousarray(g, dtype=np.float64)
-    nt = g.shape[-2]
-    half = (D + 1) // 2
-    a = dict(
-        images=np.ascontiguousarray(c["images"]), weights=np.ascontiguousarray(c["weights"]),
-        psf=np.ascontiguousarray(c["psfs"]),
-        noise_turned=None if nturned is None else np.ascontiguousarray(nturned),
-        cen=np.ascontiguousarray(c["cen"]), psf_cen=np.ascontiguousarray(c["pcen"]),
-        edge=prepsfmom._apodization_edge(dim, ap_rad) if ap_rad > 0 else None,
-        g=g, g_host=g, per_stamp_g=1 if g.ndim == 3 else 0,
-        mrow=np.where(rows < half, rows, rows - D).astype(np.int32),
-        mcol=np.where(cols < half, cols, cols - D).astype(np.int32),
-        wgt=np.ascontiguousarray(kwgt, dtype=np.float64),
-        fk=np.ascontiguousarray(kfk, dtype=np.float64), n=n, ntypes=nt, nmodes=int(rows.size),
-        dim=dim, pdim=pdim, fft_dim=D, deriv=deriv,
-        sums=np.full((n, nt, 14), -7.0), flags=np.full((n, nt), -7, dtype=np.int32))
-    a.update(over)
-
-    def p(x):
-        return None if x is None else ptr(x)
-    args = [p(a[k]) for k in ("images", "weights", "psf", "noise_turned", "cen", "psf_cen", "edge",
-                              "g", "g_host")]
-    args += [a["per_stamp_g"]] + [p(a[k]) for k in ("mrow", "mcol", "wgt", "fk")]
-    args += [a["n"], a["ntypes"], a["nmodes"], a["dim"], a["pdim"], a["fft_dim"]]
-    args += [float(d) for d in a["deriv"]] + [p(a["sums"]), p(a["flags"])]
-    if host:
-        st = L.ngmix_prepsf_shear_fixnoise_sums_host(*args)
-    else:
-        st = L.ngmix_prepsf_shear_fixnoise_sums_batch(*(args + [None]))
-    return st, a["sums"], a["flags"]
+    stream, for the refusals) on a case's arrays and its TURNED noise planes
+    nturned (ps.call_entry)."""
+    return ps.call_entry(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv, host,
+                         fixnoise=True, nturned=nturned, **over)
 
 
 # ---------------------------------------------------------------------------

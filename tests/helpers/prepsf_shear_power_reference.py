@@ -58,8 +58,8 @@ rounding; a wrong frequency, a tapered plane or a missing eff^2 moves a sum by
 """
 import numpy as np
 
-from ngmix_amd import prepsfmom
 from . import prepsf_shear_noise_reference as pn
+from . import prepsf_shear_reference as ps
 from .prepsf_shear_noise_reference import (  # noqa: F401  (what the tests take from here)
     AP_RADS, DERIV, KINDS, STEP, TYPES, case, gaussian_stamp, host_fexp, measure_of, noise_planes,
     plan_of, turned, type_shears)
@@ -192,42 +192,10 @@ def call_host(L, ptr, c, power, nturned, g, rows, cols, kwgt, kfk, D, ap_rad, de
     """ngmix_prepsf_shear_power_sums_host, or with TURNED fixnoise planes nturned
     ngmix_prepsf_shear_fixnoise_power_sums_host (host=False: the _batch entries
     with a null stream, for the refusals; base=True: the entries without the
-    noise image, on the same arrays); returns (status, sums (n, T, 14), flags
-    (n, T)).  `over` replaces arguments by name."""
-    n, dim = c["images"].shape[0], c["images"].shape[1]
-    pdim = c["psfs"].shape[1]
-    g = np.ascontiguousarray(g, dtype=np.float64)
-    nt = g.shape[-2]
-    half = (D + 1) // 2
-    a = dict(
-        images=np.ascontiguousarray(c["images"]), weights=np.ascontiguousarray(c["weights"]),
-        psf=np.ascontiguousarray(c["psfs"]),
-        noise_turned=None if nturned is None else np.ascontiguousarray(nturned),
-        noise_power=None if power is None else np.ascontiguousarray(power),
-        cen=np.ascontiguousarray(c["cen"]), psf_cen=np.ascontiguousarray(c["pcen"]),
-        edge=prepsfmom._apodization_edge(dim, ap_rad) if ap_rad > 0 else None,
-        g=g, g_host=g, per_stamp_g=1 if g.ndim == 3 else 0,
-        mrow=np.where(rows < half, rows, rows - D).astype(np.int32),
-        mcol=np.where(cols < half, cols, cols - D).astype(np.int32),
-        wgt=np.ascontiguousarray(kwgt, dtype=np.float64),
-        fk=np.ascontiguousarray(kfk, dtype=np.float64), n=n, ntypes=nt, nmodes=int(rows.size),
-        dim=dim, pdim=pdim, fft_dim=D, deriv=deriv,
-        sums=np.full((n, nt, 14), -7.0), flags=np.full((n, nt), -7, dtype=np.int32))
-    fix = nturned is not None or "noise_turned" in over
-    a.update(over)
-
-    def p(x):
-        return None if x is None else ptr(x)
-    names = ["images", "weights", "psf"] + (["noise_turned"] if fix else []) + \
-        ([] if base else ["noise_power"]) + ["cen", "psf_cen", "edge", "g", "g_host"]
-    args = [p(a[k]) for k in names]
-    args += [a["per_stamp_g"]] + [p(a[k]) for k in ("mrow", "mcol", "wgt", "fk")]
-    args += [a["n"], a["ntypes"], a["nmodes"], a["dim"], a["pdim"], a["fft_dim"]]
-    args += [float(d) for d in a["deriv"]] + [p(a["sums"]), p(a["flags"])]
-    entry = "ngmix_prepsf_shear_%s%ssums_%s" % ("fixnoise_" if fix else "", "" if base else "power_",
-                                                "host" if host else "batch")
-    st = getattr(L, entry)(*(args + ([] if host else [None])))
-    return st, a["sums"], a["flags"]
+    noise image, on the same arrays) (ps.call_entry)."""
+    return ps.call_entry(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv, host,
+                         fixnoise=nturned is not None or "noise_turned" in over,
+                         nturned=nturned, with_power=not base, power=power, **over)
 
 
 # ---------------------------------------------------------------------------

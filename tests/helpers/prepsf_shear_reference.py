@@ -300,9 +300,13 @@ def gap(got, ref):
                         ref["scale"][ok].astype(np.longdouble)))
 
 
-def call_host(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv=DERIV, host=True, **over):
-    """ngmix_prepsf_shear_sums_host on a case's arrays; returns (status, sums
-    (n, T, 14), flags (n, T)).  `over` replaces arguments by name (refusals)."""
+def call_entry(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv=DERIV, host=True,
+               fixnoise=False, nturned=None, with_power=False, power=None, **over):
+    """One of the eight ngmix_prepsf_shear_*sums_{host,batch} entries on a case's
+    arrays (host=False: _batch with a null stream, for the refusals).  fixnoise:
+    the entries that take the TURNED noise planes nturned; with_power: those
+    that take the noise images `power`.  Returns (status, sums (n, T, 14), flags
+    (n, T)).  `over` replaces arguments by name (refusals)."""
     n, dim = c["images"].shape[0], c["images"].shape[1]
     pdim = c["psfs"].shape[1]
     g = np.ascontiguousarray(g, dtype=np.float64)
@@ -310,8 +314,10 @@ def call_host(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv=DERIV, host=
     half = (D + 1) // 2
     a = dict(
         images=np.ascontiguousarray(c["images"]), weights=np.ascontiguousarray(c["weights"]),
-        psf=np.ascontiguousarray(c["psfs"]), cen=np.ascontiguousarray(c["cen"]),
-        psf_cen=np.ascontiguousarray(c["pcen"]),
+        psf=np.ascontiguousarray(c["psfs"]),
+        noise_turned=None if nturned is None else np.ascontiguousarray(nturned),
+        noise_power=None if power is None else np.ascontiguousarray(power),
+        cen=np.ascontiguousarray(c["cen"]), psf_cen=np.ascontiguousarray(c["pcen"]),
         edge=prepsfmom._apodization_edge(dim, ap_rad) if ap_rad > 0 else None,
         g=g, g_host=g, per_stamp_g=1 if g.ndim == 3 else 0,
         mrow=np.where(rows < half, rows, rows - D).astype(np.int32),
@@ -324,12 +330,19 @@ def call_host(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv=DERIV, host=
 
     def p(x):
         return None if x is None else ptr(x)
-    args = [p(a[k]) for k in ("images", "weights", "psf", "cen", "psf_cen", "edge", "g", "g_host")]
+    names = ["images", "weights", "psf"] + (["noise_turned"] if fixnoise else []) + \
+        (["noise_power"] if with_power else []) + ["cen", "psf_cen", "edge", "g", "g_host"]
+    args = [p(a[k]) for k in names]
     args += [a["per_stamp_g"]] + [p(a[k]) for k in ("mrow", "mcol", "wgt", "fk")]
     args += [a["n"], a["ntypes"], a["nmodes"], a["dim"], a["pdim"], a["fft_dim"]]
     args += [float(d) for d in a["deriv"]] + [p(a["sums"]), p(a["flags"])]
-    if host:
-        st = L.ngmix_prepsf_shear_sums_host(*args)
-    else:
-        st = L.ngmix_prepsf_shear_sums_batch(*(args + [None]))
+    entry = "ngmix_prepsf_shear_%s%ssums_%s" % ("fixnoise_" if fixnoise else "",
+                                                "power_" if with_power else "",
+                                                "host" if host else "batch")
+    st = getattr(L, entry)(*(args + ([] if host else [None])))
     return st, a["sums"], a["flags"]
+
+
+def call_host(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv=DERIV, host=True, **over):
+    """ngmix_prepsf_shear_sums_host on a case's arrays (call_entry)."""
+    return call_entry(L, ptr, c, g, rows, cols, kwgt, kfk, D, ap_rad, deriv, host, **over)
