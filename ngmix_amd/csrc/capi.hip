@@ -17,6 +17,7 @@
 #include "lm_core_reg.hpp"
 #include "launch_iter.hpp"
 #include "launch_util.hpp"
+#include "metacal.hpp"
 #include "metacal_noise.hpp"
 #include "prepsf_shear.hpp"
 #include "kfit.hpp"
@@ -548,9 +549,11 @@ int ngmix_metacal_spectrum_batch(const double *images, const double *noise, cons
                                  int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
                                  double *spec, int32_t *flags, void *stream)
 {
-    return launch_metacal_spectrum(images, noise, psf, jac, psf_cen, psf_flux, sigma, g, g_host,
-                                   per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow, psf_ncol,
-                                   spec, flags, (hipStream_t)stream);
+    const mcal::Args a = {
+        images, noise, psf, jac, psf_cen, psf_flux, sigma, g, nullptr, nullptr, g_host, nullptr,
+        nullptr, per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags,
+        nullptr, nullptr, mcal::TARGET_GAUSS, noise != nullptr, false};
+    return launch_metacal_spectrum("metacal_spectrum", a, (hipStream_t)stream);
 }
 
 int ngmix_metacal_dilate_spectrum_batch(const double *images, const double *noise,
@@ -562,10 +565,11 @@ int ngmix_metacal_dilate_spectrum_batch(const double *images, const double *nois
                                         int ncol, int psf_nrow, int psf_ncol, double *spec,
                                         int32_t *flags, void *stream)
 {
-    return launch_metacal_dilate_spectrum(images, noise, psf, jac, psf_cen, g, dil, kind, g_host,
-                                          dil_host, kind_host, per_stamp_g, nstamps, ntypes, nrow,
-                                          ncol, psf_nrow, psf_ncol, spec, flags, false,
-                                          (hipStream_t)stream);
+    const mcal::Args a = {
+        images, noise, psf, jac, psf_cen, nullptr, nullptr, g, dil, kind, g_host, dil_host,
+        kind_host, per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags,
+        nullptr, nullptr, mcal::TARGET_DILATE, noise != nullptr, false};
+    return launch_metacal_spectrum("metacal_dilate_spectrum", a, (hipStream_t)stream);
 }
 
 int ngmix_metacal_dilate_psf_spectrum_batch(const double *psf, const ngmix_jacobian *jac,
@@ -577,10 +581,11 @@ int ngmix_metacal_dilate_psf_spectrum_batch(const double *psf, const ngmix_jacob
                                             int psf_ncol, double *spec, int32_t *flags,
                                             void *stream)
 {
-    return launch_metacal_dilate_spectrum(nullptr, nullptr, psf, jac, psf_cen, g, dil, kind, g_host,
-                                          dil_host, kind_host, per_stamp_g, nstamps, ntypes,
-                                          psf_nrow, psf_ncol, psf_nrow, psf_ncol, spec, flags, true,
-                                          (hipStream_t)stream);
+    const mcal::Args a = {
+        nullptr, nullptr, psf, jac, psf_cen, nullptr, nullptr, g, dil, kind, g_host, dil_host,
+        kind_host, per_stamp_g, nstamps, ntypes, psf_nrow, psf_ncol, psf_nrow, psf_ncol, spec,
+        flags, nullptr, nullptr, mcal::TARGET_DILATE_PSF, false, false};
+    return launch_metacal_spectrum("metacal_dilate_psf_spectrum", a, (hipStream_t)stream);
 }
 
 int ngmix_metacal_kfit_spectrum_batch(const double *images, const double *psf,
@@ -593,18 +598,14 @@ int ngmix_metacal_kfit_spectrum_batch(const double *images, const double *psf,
                                       int psf_nrow, int psf_ncol, double *dhat, double *phat,
                                       double *aux, int32_t *flags, void *stream)
 {
-    if (nstamps > 0 && (!phat || !aux)) {
-        set_last_error_msg("metacal_kfit_spectrum: phat and aux are required");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    if (sigma)
-        return launch_metacal_spectrum(images, nullptr, psf, jac, psf_cen, psf_flux, sigma, g,
-                                       g_host, per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow,
-                                       psf_ncol, dhat, flags, (hipStream_t)stream, phat, aux);
-    return launch_metacal_dilate_spectrum(images, nullptr, psf, jac, psf_cen, g, dil, kind, g_host,
-                                          dil_host, kind_host, per_stamp_g, nstamps, ntypes, nrow,
-                                          ncol, psf_nrow, psf_ncol, dhat, flags, false,
-                                          (hipStream_t)stream, psf_flux, phat, aux);
+    // sigma given: the round gaussian as the target, else the dilated psf; a
+    // missing phat or aux is refused under this entry's own name
+    const mcal::Args a = {
+        images, nullptr, psf, jac, psf_cen, psf_flux, sigma, g, dil, kind, g_host, dil_host,
+        kind_host, per_stamp_g, nstamps, ntypes, nrow, ncol, psf_nrow, psf_ncol, dhat, flags,
+        phat, aux, sigma ? mcal::TARGET_GAUSS : mcal::TARGET_DILATE, false, true};
+    return launch_metacal_spectrum(sigma ? "metacal_spectrum" : "metacal_dilate_spectrum", a,
+                                   (hipStream_t)stream);
 }
 
 int ngmix_metacal_noise_batch(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,

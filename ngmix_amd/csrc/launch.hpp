@@ -8,6 +8,9 @@ namespace ngmix {
 namespace pshear {
 struct Args;       // prepsf_shear.hpp
 }
+namespace mcal {
+struct Args;       // metacal.hpp
+}
 
 // pixpass.hip
 int launch_loglike_grid(const ngmix_batch *b, ngmix_gauss2d *gmix, double *out,
@@ -41,22 +44,7 @@ int launch_prepsf_sums(const double *kim_re, const double *kim_im, const double 
                        int64_t stride_r, int R, int C, double df2, double df4, double *out,
                        hipStream_t s);
 // metacal.hip
-int launch_metacal_spectrum(const double *images, const double *noise, const double *psf,
-                            const ngmix_jacobian *jac, const double *psf_cen,
-                            const double *psf_flux, const double *sigma, const double *g,
-                            const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
-                            int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
-                            int32_t *flags, hipStream_t s, double *kfit_phat = nullptr,
-                            double *kfit_aux = nullptr);
-int launch_metacal_dilate_spectrum(const double *images, const double *noise, const double *psf,
-                                   const ngmix_jacobian *jac, const double *psf_cen,
-                                   const double *g, const double *dil, const int32_t *kind,
-                                   const double *g_host, const double *dil_host,
-                                   const int32_t *kind_host, int per_stamp_g, int64_t nstamps,
-                                   int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
-                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s,
-                                   const double *psf_flux = nullptr,
-                                   double *kfit_phat = nullptr, double *kfit_aux = nullptr);
+int launch_metacal_spectrum(const char *who, const mcal::Args &a, hipStream_t s);
 // metacal_noise.hip
 int launch_metacal_noise(const double *ierr, const int64_t *ids, uint64_t seed, int64_t n,
                          int nrow, int ncol, int rot_k, double *out, hipStream_t s);

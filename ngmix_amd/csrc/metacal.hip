@@ -12,9 +12,11 @@
 // plane are staged in LDS once; every thread owns output modes of the half
 // plane b <= C/2 (the image is real) and walks ALL pixels in the same order,
 // so every LDS read is one address for the whole wave.  The phase of a pixel
-// is carried by the recurrence of dtft.hpp (shared with prepsf_shear.hip);
-// image, noise and psf share it (the psf up to one factor per mode for its own
-// centre): 4 FMA per pixel for the phase and 2 per pixel and plane for the sums.
+// is carried by the recurrence of dtft.hpp; image, noise and psf share it (the
+// psf up to one factor per mode for its own centre): 4 FMA per pixel for the
+// phase and 2 per pixel and plane for the sums.  The geometry of a (stamp,
+// shear), the sheared frequency and that factor are shear_geom.hpp's, shared
+// with prepsf_shear.hip.
 //
 // A second target (TARGET_DILATE): the psf stamp's own
 // transform, deconvolved from the pixel, dilated -- and, for the psf-sheared
@@ -23,11 +25,20 @@
 // the psf pixels (dtft.hpp, transform_one): (4 + 2) Rp Cp more FMA per mode.
 // TARGET_DILATE_PSF is the same target alone, at the modes of the PSF stamp's
 // grid: the target psf image.
+//
+// One kernel text, one argument record for every form (metacal.hpp), one check
+// and one launcher.  mode_value and dilate_mode_value share the
+// sheared frequency and the psf's phase through shear_geom.hpp; their tails
+// (deconvolve, times the target, KFIT or shift and noise, NaN fill) stay two
+// texts: one tail over a real or complex target changed the machine code of six
+// of the seven kernels and timed up to 0.6 % slower (3.30).
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "dtft.hpp"
 #include "launch.hpp"
 #include "launch_util.hpp"
+#include "metacal.hpp"
+#include "shear_geom.hpp"
 
 #include <cmath>
 #include <string>
@@ -37,9 +48,7 @@ namespace ngmix {
 namespace {
 
 using namespace dtft;   // cplx, cmul, cexpi, cdiv, Planes, transforms, SEED, PI
-
-// the reconvolution target of a spectrum kernel, and what it reads beside g
-enum { TARGET_GAUSS = 0, TARGET_DILATE = 1, TARGET_DILATE_PSF = 2 };
+using namespace mcal;   // Args, TARGET_GAUSS, TARGET_DILATE, TARGET_DILATE_PSF
 
 // The two arrays a target reads: psf_flux and sigma (N,) of the round gaussian;
 // of the dilated psf the dilation d >= 1 and the kind (0: the image is sheared,
@@ -62,18 +71,16 @@ struct DilateSetup {
 // the integer numerator of fftfreq(n)[i]
 NGMIX_HD int fft_index(int i, int n) { return i < (n + 1) / 2 ? i : i - n; }
 
-// 2 pi fftfreq(n)[i]; the Nyquist entry of an even n is exactly -pi
+// 2 pi fftfreq(n)[i] as 2 pi (i / n), the grid of the inverse FFT the spectra go
+// into; the Nyquist entry of an even n is exactly -pi.  (pshear::mode_freq is
+// the same quantity rounded as numpy rounds it, for kernels built with numpy.)
 NGMIX_HD double grid_freq(int i, int n)
 {
     return (2.0 * PI) * ((double)fft_index(i, n) / (double)n);
 }
 
-// what a mode needs of its stamp and shear
-struct ModeSetup {
-    double r0, c0, pr0, pc0;       // centres of the image and of the psf
-    double j00, j01, j10, j11;     // J = [[dvdrow, dvdcol], [dudrow, dudcol]]
-    double i00, i01, i10, i11;     // J^-T
-    double d00, d01, d11;          // A - 1 (symmetric), exactly 0 at g = 0
+// what a mode needs of its stamp and shear: the geometry, and
+struct ModeSetup : shear::Geom {
     double flux, half_sig2;        // sum of the psf image, (sigma_T (1 + 2|g|))^2 / 2
 };
 
@@ -81,23 +88,8 @@ NGMIX_HD ModeSetup mode_setup(const ngmix_jacobian &jac, double pr0, double pc0,
                               double g2, double sigma, double flux)
 {
     ModeSetup m;
-    m.r0 = jac.row0;
-    m.c0 = jac.col0;
-    m.pr0 = pr0;
-    m.pc0 = pc0;
-    m.j00 = jac.dvdrow;
-    m.j01 = jac.dvdcol;
-    m.j10 = jac.dudrow;
-    m.j11 = jac.dudcol;
-    const double det = m.j00 * m.j11 - m.j01 * m.j10;
-    m.i00 = m.j11 / det;
-    m.i01 = -m.j10 / det;
-    m.i10 = -m.j01 / det;
-    m.i11 = m.j00 / det;
-    const double root = sqrt(1.0 - g1 * g1 - g2 * g2);
-    m.d00 = (1.0 - g1) / root - 1.0;
-    m.d01 = g2 / root;
-    m.d11 = (1.0 + g1) / root - 1.0;
+    shear::set_geom(m, jac.row0, jac.col0, pr0, pc0, jac.dvdrow, jac.dvdcol, jac.dudrow,
+                    jac.dudcol, g1, g2);
     const double sig = sigma * (1.0 + 2.0 * sqrt(g1 * g1 + g2 * g2));
     m.half_sig2 = 0.5 * (sig * sig);
     m.flux = flux;
@@ -140,9 +132,8 @@ NGMIX_HD void dilate_mode_value(const Planes &p, const ModeSetup &m, const Dilat
                                 double qa, double qb, cplx &oi, cplx &on, bool &bad,
                                 KfitMode &km)
 {
-    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
-    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
-    const double sr = qa + (m.j00 * dv + m.j10 * du), sc = qb + (m.j01 * dv + m.j11 * du);
+    double sr, sc;
+    shear::sheared_freq(m, qa, qb, sr, sc);
     const double qr = ds.shear_psf ? qa : sr, qc = ds.shear_psf ? qb : sc;
     const double tr = ds.dil * (ds.shear_psf ? sr : qa), tc = ds.dil * (ds.shear_psf ? sc : qb);
     if (!(fabs(tr) < PI && fabs(tc) < PI)) return;
@@ -160,7 +151,7 @@ NGMIX_HD void dilate_mode_value(const Planes &p, const ModeSetup &m, const Dilat
     }
     cplx si, sn, sp;
     transforms<NOISE>(p, m.r0, m.c0, qr, qc, si, sn, sp);
-    sp = cmul(sp, cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
+    shear::psf_to_own_centre(m, qr, qc, sp);
     bool ok;
     if constexpr (KFIT) {
         oi = cmul(cdiv(si, sp), target);
@@ -199,14 +190,13 @@ NGMIX_HD void mode_value(const Planes &p, const ModeSetup &m, const DilateSetup 
     }
     // world frequency (v, u), the sheared one, and back to pixel axes:
     // q' = q + J^T (A - 1) J^-T q
-    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
-    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
-    const double qr = qa + (m.j00 * dv + m.j10 * du), qc = qb + (m.j01 * dv + m.j11 * du);
+    double kv, ku, qr, qc;
+    shear::sheared_freq(m, qa, qb, kv, ku, qr, qc);
     if (!(fabs(qr) < PI && fabs(qc) < PI)) return;
     cplx si, sn, sp;
     transforms<NOISE>(p, m.r0, m.c0, qr, qc, si, sn, sp);
     // the psf about its own centre
-    sp = cmul(sp, cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
+    shear::psf_to_own_centre(m, qr, qc, sp);
     const double tn = exp(-m.half_sig2 * (kv * kv + ku * ku));
     const double target = m.flux * tn;
     cplx o = cdiv(si, sp);
@@ -265,21 +255,20 @@ NGMIX_HD int nyq_item_of(int a, int b, int R, int C)
     return -1;
 }
 
+// bytes of LDS of one block: the planes, and the own and the partner value of
+// every Nyquist item and plane (TARGET_DILATE_PSF: the psf stamp alone, the
+// items of its own grid, which is (nrow, ncol) then; KFIT: no items)
+size_t lds_bytes(const Args &a)
+{
+    const size_t npl = a.with_noise ? 2 : 1;
+    const size_t planes = (a.target == TARGET_DILATE_PSF ? 0 : (size_t)a.nrow * a.ncol * npl) +
+                          (size_t)a.psf_nrow * a.psf_ncol;
+    const size_t items =
+        a.with_kfit ? 0 : (size_t)(nyq_row_items(a.nrow, a.ncol) + nyq_col_items(a.nrow, a.ncol));
+    return (planes + items * 4 * npl) * sizeof(double);
+}
+
 }  // namespace
-
-size_t metacal_lds_bytes(int R, int C, int Rp, int Cp, bool noise, bool kfit = false)
-{
-    const size_t planes = (size_t)R * C * (noise ? 2 : 1) + (size_t)Rp * Cp;
-    const size_t items = kfit ? 0 : (size_t)(nyq_row_items(R, C) + nyq_col_items(R, C));
-    return (planes + items * 4 * (noise ? 2 : 1)) * sizeof(double);
-}
-
-// TARGET_DILATE_PSF: the psf stamp alone, the Nyquist items of its own grid
-size_t metacal_psf_lds_bytes(int Rp, int Cp)
-{
-    const size_t items = (size_t)(nyq_row_items(Rp, Cp) + nyq_col_items(Rp, Cp));
-    return ((size_t)Rp * Cp + items * 4) * sizeof(double);
-}
 
 // images (N, R, C), noise (N, R, C) with NOISE, psf (N, Rp, Cp); jac (N,): the
 // image's jacobian; psf_cen (N, 2); psf_flux (N,), sigma (N,) of TARGET_GAUSS,
@@ -392,148 +381,98 @@ __global__ __launch_bounds__(BLOCK) void metacal_spectrum_kernel(
     if (threadIdx.x == 0) flags[slot] = any_bad;
 }
 
-// the block size that leaves the fewest idle work-item slots (the larger on a tie)
-static int spectrum_block(int nrow, int ncol)
-{
-    const int nwork = nrow * (ncol / 2 + 1) + nyq_row_items(nrow, ncol) + nyq_col_items(nrow, ncol);
-    int block = BLOCK, waste = (nwork + BLOCK - 1) / BLOCK * BLOCK;
-    for (int b = BLOCK - WAVE; b >= WAVE; b -= WAVE) {
-        const int slots = (nwork + b - 1) / b * b;
-        if (slots < waste) {
-            waste = slots;
-            block = b;
-        }
-    }
-    return block;
-}
+namespace {
 
-// g_host: the caller's host copy of g, checked here (|g| < 1) before anything
-// is launched
-int launch_metacal_spectrum(const double *images, const double *noise, const double *psf,
-                            const ngmix_jacobian *jac, const double *psf_cen,
-                            const double *psf_flux, const double *sigma, const double *g,
-                            const double *g_host, int per_stamp_g, int64_t nstamps, int ntypes,
-                            int nrow, int ncol, int psf_nrow, int psf_ncol, double *spec,
-                            int32_t *flags, hipStream_t s, double *kfit_phat, double *kfit_aux)
+// the refusals of every form, for a.nstamps > 0; the host copies are read here
+int check_args(const char *who, const Args &a)
 {
-    if (nstamps <= 0) return NGMIX_OK;
-    const bool kfit = kfit_phat || kfit_aux;
-    if (kfit && (noise || !kfit_phat || !kfit_aux)) {
-        set_last_error_msg("metacal_spectrum: the kfit form takes phat and aux and no noise "
-                           "plane");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    if (!images || !psf || !jac || !psf_cen || !psf_flux || !sigma || !g || !g_host || !spec ||
-        !flags) {
-        set_last_error_msg("metacal_spectrum: images, psf, jac, psf_cen, psf_flux, sigma, g, "
-                           "g_host, spec and flags are required");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    if (ntypes <= 0 || nrow <= 0 || ncol <= 0 || psf_nrow <= 0 || psf_ncol <= 0) {
-        set_last_error_msg("metacal_spectrum: the number of types and the stamp shapes must be "
-                           "positive");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    if (nstamps * ntypes > 0x7fffffffll) {
-        set_last_error_msg("metacal_spectrum: too many (stamp, type) pairs for one launch");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    const size_t lds = metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr, kfit);
-    if (lds > 160 * 1024 || (int64_t)nrow * ncol > 0x7fffff || (int64_t)psf_nrow * psf_ncol > 0x7fffff) {
-        set_last_error_msg("metacal_spectrum: the stamp, its psf stamp and its noise plane do "
-                           "not fit the 160 KB of LDS");
-        return NGMIX_ERR_BAD_ARG;
-    }
-    const int64_t ng = (per_stamp_g ? nstamps : 1) * ntypes;
-    for (int64_t i = 0; i < ng; i++) {
-        const double g1 = g_host[2 * i], g2 = g_host[2 * i + 1];
-        if (!(g1 * g1 + g2 * g2 < 1.0)) {
-            set_last_error_msg(("metacal_spectrum: shear " + std::to_string(i) +
-                                " is not inside the unit circle").c_str());
-            return NGMIX_ERR_BAD_ARG;
-        }
-    }
-    const auto k = kfit    ? kernel(metacal_spectrum_kernel<false, TARGET_GAUSS, true>,
-                                    "metacal_spectrum_kernel<kfit>")
-                   : noise ? kernel(metacal_spectrum_kernel<true, TARGET_GAUSS>,
-                                    "metacal_spectrum_kernel<noise>")
-                           : kernel(metacal_spectrum_kernel<false, TARGET_GAUSS>,
-                                    "metacal_spectrum_kernel");
-    return launch(k, dim3((unsigned)(nstamps * ntypes)), dim3(spectrum_block(nrow, ncol)), lds,
-                  48 * 1024, s, images, noise, psf, jac, psf_cen, psf_flux, sigma, g,
-                  per_stamp_g ? 1 : 0, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags,
-                  psf_flux, KfitOut{kfit_phat, kfit_aux});
-}
-
-// The dilated psf as the target (psf_only: its own spectrum on the psf stamp's
-// grid; images, noise, nrow and ncol are not looked at then).  g_host, dil_host,
-// kind_host: the caller's host copies, checked here (|g| < 1, d >= 1 and finite,
-// kind 0 or 1) before anything is launched
-int launch_metacal_dilate_spectrum(const double *images, const double *noise, const double *psf,
-                                   const ngmix_jacobian *jac, const double *psf_cen,
-                                   const double *g, const double *dil, const int32_t *kind,
-                                   const double *g_host, const double *dil_host,
-                                   const int32_t *kind_host, int per_stamp_g, int64_t nstamps,
-                                   int ntypes, int nrow, int ncol, int psf_nrow, int psf_ncol,
-                                   double *spec, int32_t *flags, bool psf_only, hipStream_t s,
-                                   const double *psf_flux, double *kfit_phat, double *kfit_aux)
-{
-    const std::string who = psf_only ? "metacal_dilate_psf_spectrum" : "metacal_dilate_spectrum";
-    const auto refuse = [&who](const std::string &what) {
-        set_last_error_msg((who + ": " + what).c_str());
+    const auto refuse = [who](const std::string &what) {
+        set_last_error_msg((std::string(who) + ": " + what).c_str());
         return NGMIX_ERR_BAD_ARG;
     };
-    if (nstamps <= 0) return NGMIX_OK;
-    const bool kfit = kfit_phat || kfit_aux;
-    if (kfit && (psf_only || noise || !kfit_phat || !kfit_aux || !psf_flux))
-        return refuse("the kfit form takes psf_flux, phat and aux and no noise plane");
-    if (psf_only) {
-        images = noise = nullptr;
-        nrow = psf_nrow;
-        ncol = psf_ncol;
-    } else if (!images) {
-        return refuse("images is required");
+    const bool gauss = a.target == TARGET_GAUSS, psf_only = a.target == TARGET_DILATE_PSF;
+    if (a.with_kfit && (!a.kfit_phat || !a.kfit_aux)) {
+        set_last_error_msg("metacal_kfit_spectrum: phat and aux are required");
+        return NGMIX_ERR_BAD_ARG;
     }
-    if (!psf || !jac || !psf_cen || !g || !dil || !kind || !g_host || !dil_host || !kind_host ||
-        !spec || !flags)
-        return refuse("psf, jac, psf_cen, g, dil, kind, g_host, dil_host, kind_host, spec and "
-                      "flags are required");
-    if (ntypes <= 0 || nrow <= 0 || ncol <= 0 || psf_nrow <= 0 || psf_ncol <= 0)
+    if (a.with_kfit && (psf_only || a.with_noise || (!gauss && !a.psf_flux)))
+        return refuse(gauss ? "the kfit form takes phat and aux and no noise plane"
+                            : "the kfit form takes psf_flux, phat and aux and no noise plane");
+    const bool rest = a.psf && a.jac && a.psf_cen && a.g && a.g_host && a.spec && a.flags;
+    if (gauss) {
+        if (!rest || !a.images || !a.psf_flux || !a.sigma)
+            return refuse("images, psf, jac, psf_cen, psf_flux, sigma, g, g_host, spec and flags "
+                          "are required");
+    } else {
+        if (!psf_only && !a.images) return refuse("images is required");
+        if (!rest || !a.dil || !a.kind || !a.dil_host || !a.kind_host)
+            return refuse("psf, jac, psf_cen, g, dil, kind, g_host, dil_host, kind_host, spec and "
+                          "flags are required");
+    }
+    if (a.ntypes <= 0 || a.nrow <= 0 || a.ncol <= 0 || a.psf_nrow <= 0 || a.psf_ncol <= 0)
         return refuse("the number of types and the stamp shapes must be positive");
-    if (nstamps * ntypes > 0x7fffffffll) return refuse("too many (stamp, type) pairs for one launch");
-    const size_t lds = psf_only ? metacal_psf_lds_bytes(psf_nrow, psf_ncol)
-                                : metacal_lds_bytes(nrow, ncol, psf_nrow, psf_ncol, noise != nullptr,
-                                                    kfit);
-    if (lds > 160 * 1024 || (int64_t)nrow * ncol > 0x7fffff ||
-        (int64_t)psf_nrow * psf_ncol > 0x7fffff)
+    if (a.nstamps * a.ntypes > 0x7fffffffll)
+        return refuse("too many (stamp, type) pairs for one launch");
+    if (lds_bytes(a) > shear::LDS_LIMIT || (int64_t)a.nrow * a.ncol > 0x7fffff ||
+        (int64_t)a.psf_nrow * a.psf_ncol > 0x7fffff)
         return refuse("the stamp, its psf stamp and its noise plane do not fit the 160 KB of LDS");
-    const int64_t ng = (per_stamp_g ? nstamps : 1) * ntypes;
+    const int64_t ng = (a.per_stamp_g ? a.nstamps : 1) * a.ntypes;
     for (int64_t i = 0; i < ng; i++) {
-        const double g1 = g_host[2 * i], g2 = g_host[2 * i + 1];
+        const double g1 = a.g_host[2 * i], g2 = a.g_host[2 * i + 1];
         if (!(g1 * g1 + g2 * g2 < 1.0))
             return refuse("shear " + std::to_string(i) + " is not inside the unit circle");
-        if (!(dil_host[i] >= 1.0 && std::isfinite(dil_host[i])))
+        if (gauss) continue;
+        if (!(a.dil_host[i] >= 1.0 && std::isfinite(a.dil_host[i])))
             return refuse("dilation " + std::to_string(i) + " is not a finite number >= 1");
-        if (kind_host[i] != 0 && kind_host[i] != 1)
+        if (a.kind_host[i] != 0 && a.kind_host[i] != 1)
             return refuse("kind " + std::to_string(i) + " is neither 0 (image) nor 1 (psf)");
     }
-    const dim3 grid((unsigned)(nstamps * ntypes)), block(spectrum_block(nrow, ncol));
-    const int per = per_stamp_g ? 1 : 0;
-    if (psf_only)
-        return launch(kernel(metacal_spectrum_kernel<false, TARGET_DILATE_PSF>,
-                             "metacal_spectrum_kernel<dilate psf>"),
-                      grid, block, lds, 48 * 1024, s, images, noise, psf, jac, psf_cen, dil, kind, g,
-                      per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags, psf_flux,
-                      KfitOut{nullptr, nullptr});
-    const auto k = kfit    ? kernel(metacal_spectrum_kernel<false, TARGET_DILATE, true>,
-                                    "metacal_spectrum_kernel<dilate, kfit>")
-                   : noise ? kernel(metacal_spectrum_kernel<true, TARGET_DILATE>,
-                                    "metacal_spectrum_kernel<noise, dilate>")
-                           : kernel(metacal_spectrum_kernel<false, TARGET_DILATE>,
-                                    "metacal_spectrum_kernel<dilate>");
-    return launch(k, grid, block, lds, 48 * 1024, s, images, noise, psf, jac, psf_cen, dil, kind, g,
-                  per, ntypes, nrow, ncol, psf_nrow, psf_ncol, spec, flags, psf_flux,
-                  KfitOut{kfit_phat, kfit_aux});
+    return NGMIX_OK;
+}
+
+}  // namespace
+
+// every form: the refusals, then the instantiation of (a.target, a.with_noise,
+// a.with_kfit).  The two targets' second arrays differ in type, and so do their
+// kernels': a table for each, and one launch call that takes either
+int launch_metacal_spectrum(const char *who, const Args &a, hipStream_t s)
+{
+    if (a.nstamps <= 0) return NGMIX_OK;
+    const int st = check_args(who, a);
+    if (st != NGMIX_OK) return st;
+    static_assert(shear::MAX_BLOCK == BLOCK && shear::LANES == WAVE,
+                  "shear_geom.hpp mirrors device_utils.hpp");
+    using Gauss = decltype(kernel(metacal_spectrum_kernel<false, TARGET_GAUSS>, ""));
+    using Dilate = decltype(kernel(metacal_spectrum_kernel<false, TARGET_DILATE>, ""));
+    // [with_noise][with_kfit]; no kernel takes both (check_args has refused them)
+    static constexpr Gauss gauss[2][2] = {
+        {kernel(metacal_spectrum_kernel<false, TARGET_GAUSS>, "metacal_spectrum_kernel"),
+         kernel(metacal_spectrum_kernel<false, TARGET_GAUSS, true>, "metacal_spectrum_kernel<kfit>")},
+        {kernel(metacal_spectrum_kernel<true, TARGET_GAUSS>, "metacal_spectrum_kernel<noise>"),
+         {nullptr, nullptr}},
+    };
+    static constexpr Dilate dilate[2][2] = {
+        {kernel(metacal_spectrum_kernel<false, TARGET_DILATE>, "metacal_spectrum_kernel<dilate>"),
+         kernel(metacal_spectrum_kernel<false, TARGET_DILATE, true>,
+                "metacal_spectrum_kernel<dilate, kfit>")},
+        {kernel(metacal_spectrum_kernel<true, TARGET_DILATE>,
+                "metacal_spectrum_kernel<noise, dilate>"),
+         {nullptr, nullptr}},
+    };
+    static constexpr Dilate dilate_psf = kernel(metacal_spectrum_kernel<false, TARGET_DILATE_PSF>,
+                                                "metacal_spectrum_kernel<dilate psf>");
+    const int nwork = a.nrow * (a.ncol / 2 + 1) + nyq_row_items(a.nrow, a.ncol) +
+                      nyq_col_items(a.nrow, a.ncol);
+    // first, second: psf_flux and sigma of the gaussian, dil and kind of the dilated psf
+    const auto start = [&](auto k, const double *first, auto *second) {
+        return launch(k, dim3((unsigned)(a.nstamps * a.ntypes)), dim3(shear::block_size(nwork)),
+                      lds_bytes(a), 48 * 1024, s, a.images, a.noise, a.psf, a.jac, a.psf_cen, first,
+                      second, a.g, a.per_stamp_g ? 1 : 0, a.ntypes, a.nrow, a.ncol, a.psf_nrow,
+                      a.psf_ncol, a.spec, a.flags, a.psf_flux, KfitOut{a.kfit_phat, a.kfit_aux});
+    };
+    if (a.target == TARGET_GAUSS) return start(gauss[a.with_noise][a.with_kfit], a.psf_flux, a.sigma);
+    return start(a.target == TARGET_DILATE_PSF ? dilate_psf : dilate[a.with_noise][a.with_kfit], a.dil,
+                 a.kind);
 }
 
 }  // namespace ngmix

@@ -173,7 +173,7 @@ int launch_prepsf_shear_sums(const char *who, const Args &a, hipStream_t s)
     bool nothing;
     const int st = check_args(who, a, nothing);
     if (st != NGMIX_OK || nothing) return st;
-    static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "prepsf_shear.hpp mirrors device_utils.hpp");
+    static_assert(MAX_BLOCK == BLOCK && LANES == WAVE, "shear_geom.hpp mirrors device_utils.hpp");
     static constexpr decltype(kernel(prepsf_shear_sums_kernel<false, false>, "")) kernels[2][2] = {
         {kernel(prepsf_shear_sums_kernel<false, false>, "prepsf_shear_sums_kernel"),
          kernel(prepsf_shear_sums_kernel<false, true>, "prepsf_shear_sums_kernel<0, 1>")},

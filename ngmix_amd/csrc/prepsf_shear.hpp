@@ -19,10 +19,12 @@
 //   F^(k) = N'^(q') / P^(q') exp(-i (q_r (r0 + c0 - (n - 1)) + q_c (c0 - r0)))
 //
 // (add_noise_mode); no target psf enters.  Both terms are one text: the sheared
-// frequency (sheared_freq), the psf about its own centre and floored
-// (psf_about_centre), the fourteen accumulations (accumulate); add_mode
-// and add_noise_mode differ in the frequency they start from, the plane they
-// read, the closing phase and where the noise power comes from.
+// frequency (shear::sheared_freq of shear_geom.hpp, which also has the geometry
+// of a (stamp, type), the block-size chooser and the LDS limit, shared with
+// metacal.hip), the psf about its own centre and floored (psf_about_centre), the
+// fourteen accumulations (accumulate); add_mode and add_noise_mode differ in the
+// frequency they start from, the plane they read, the closing phase and where
+// the noise power comes from.
 //
 // POWER (ngmix_prepsf_shear_*power_sums_*): the noise power of a
 // mode is not the stamp's one scalar but that of a noise image N of the stamp,
@@ -44,15 +46,15 @@
 
 #include "common.hpp"
 #include "dtft.hpp"
+#include "shear_geom.hpp"
 
 namespace ngmix {
 namespace pshear {
 
 using dtft::cplx;
+using namespace shear;   // Geom, sheared_freq, block_size, MAX_BLOCK, LANES, LDS_LIMIT
 
 constexpr int NSUMS = 14;
-constexpr int MAX_BLOCK = 256, LANES = 64;       // = BLOCK, WAVE of device_utils.hpp
-constexpr size_t LDS_LIMIT = 160 * 1024;
 
 // What every form takes: the C entries fill one and hand it on.  images,
 // weights, noise_turned, noise_power (N, dim, dim), psf (N, pdim, pdim), cen,
@@ -82,15 +84,12 @@ struct Args {
 
 // 2 pi fftfreq(D)[a] for the signed mode number a, rounded as numpy rounds it
 // (a times the rounded 1/D, then times the rounded 2 pi): the frequency the
-// plan's kernels were built at
+// plan's kernels were built at (metacal.hip's grid_freq is 2 pi (i / n), the
+// inverse FFT's grid: two roundings of one quantity, both on purpose)
 NGMIX_HD double mode_freq(int a, int D) { return ((double)a * (1.0 / (double)D)) * (2.0 * dtft::PI); }
 
-// what every mode of one (stamp, type) shares
-struct Setup {
-    double r0, c0, pr0, pc0;       // centres of the image and of the psf
-    double j00, j01, j10, j11;     // J = [[dvdrow, dvdcol], [dudrow, dudcol]]
-    double i00, i01, i10, i11;     // J^-T
-    double d00, d01, d11;          // A - 1 (symmetric), exactly 0 at g = 0
+// what every mode of one (stamp, type) shares: the geometry, and
+struct Setup : Geom {
     double min_amp, pnoise;        // 1e-5 |sum of the psf|, the noise power per mode
                                    // (POWER: eff^2, what scales the plane's |N^|^2)
 };
@@ -99,23 +98,8 @@ NGMIX_HD Setup setup(const double *cen, const double *psf_cen, const double *der
                      double g2, double psf_sum, double pnoise)
 {
     Setup m;
-    m.r0 = cen[0];
-    m.c0 = cen[1];
-    m.pr0 = psf_cen[0];
-    m.pc0 = psf_cen[1];
-    m.j00 = deriv[0];
-    m.j01 = deriv[1];
-    m.j10 = deriv[2];
-    m.j11 = deriv[3];
-    const double det = m.j00 * m.j11 - m.j01 * m.j10;
-    m.i00 = m.j11 / det;
-    m.i01 = -m.j10 / det;
-    m.i10 = -m.j01 / det;
-    m.i11 = m.j00 / det;
-    const double root = sqrt(1.0 - g1 * g1 - g2 * g2);
-    m.d00 = (1.0 - g1) / root - 1.0;
-    m.d01 = g2 / root;
-    m.d11 = (1.0 + g1) / root - 1.0;
+    set_geom(m, cen[0], cen[1], psf_cen[0], psf_cen[1], deriv[0], deriv[1], deriv[2], deriv[3], g1,
+             g2);
     m.min_amp = 1.0e-5 * fabs(psf_sum);
     m.pnoise = pnoise;
     return m;
@@ -124,23 +108,11 @@ NGMIX_HD Setup setup(const double *cen, const double *psf_cen, const double *der
 // 1 / w where the weight is positive, 0 elsewhere
 NGMIX_HD double pixel_var(double w) { return w > 0.0 ? 1.0 / w : 0.0; }
 
-// The sheared frequency (qr, qc) of the pixel-axis frequency (qa, qb): to the
-// world frequency (v, u), the sheared one, and back to pixel axes.  The band
-// test on it stays with the two callers: returned through a helper, its && is
-// compiled to other code than the early return it is.
-NGMIX_HD void sheared_freq(const Setup &m, double qa, double qb, double &qr, double &qc)
-{
-    const double kv = m.i00 * qa + m.i01 * qb, ku = m.i10 * qa + m.i11 * qb;
-    const double dv = m.d00 * kv + m.d01 * ku, du = m.d01 * kv + m.d11 * ku;
-    qr = qa + (m.j00 * dv + m.j10 * du);
-    qc = qb + (m.j01 * dv + m.j11 * du);
-}
-
 // sp, the psf's transform about the IMAGE's centre at (qr, qc), brought about
 // the psf's own centre; an amplitude of m.min_amp or less is raised to it
 NGMIX_HD void psf_about_centre(const Setup &m, double qr, double qc, cplx &sp)
 {
-    sp = dtft::cmul(sp, dtft::cexpi(-(qr * (m.r0 - m.pr0) + qc * (m.c0 - m.pc0))));
+    psf_to_own_centre(m, qr, qc, sp);
     const double amp = hypot(sp.x, sp.y);
     if (amp <= m.min_amp) {
         if (amp != 0.0) {
@@ -250,20 +222,6 @@ inline size_t lds_bytes(int dim, int pdim, bool noise, bool power)
 {
     return ((size_t)dim * dim * (1 + (noise ? 1 : 0) + (power ? 1 : 0)) + (size_t)pdim * pdim +
             (MAX_BLOCK / LANES) * NSUMS) * sizeof(double);
-}
-
-// the block size that leaves the fewest idle mode slots (the larger on a tie)
-inline int block_size(int nmodes)
-{
-    int block = MAX_BLOCK, waste = (nmodes + MAX_BLOCK - 1) / MAX_BLOCK * MAX_BLOCK;
-    for (int b = MAX_BLOCK - LANES; b >= LANES; b -= LANES) {
-        const int slots = (nmodes + b - 1) / b * b;
-        if (slots < waste) {
-            waste = slots;
-            block = b;
-        }
-    }
-    return block;
 }
 
 // the refusals shared by the launcher and the host twins; nothing: n == 0
